@@ -25,10 +25,14 @@ The window is resident in HBM in its plan form (compact events binned by source 
 by every solver iteration); its one-off build time is reported as ``plan_build_ms`` and, folded into a single
 evaluation, as ``value_incl_plan_build`` -- it is NOT in the timed region of ``value``.
 
-Timing: W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize() and
-MAX-reduced over the ranks; blocks repeat until >= ``--min-seconds`` of timed work and the MEDIAN block is reported
-(``repeats``).  The dominant kernels are timed by HIP events stamped with their own dispatch (hipExtLaunchKernelGGL on the
-launch stream) during the last two timed blocks (steady-state clocks).
+Timing: W warm-up steps, then ONE block of exactly K timed steps, bracketed by barrier + torch.cuda.synchronize() and
+MAX-reduced over the ranks; ``ms_per_step`` is that block / K.  ``--min-seconds S`` repeats the block until >= S of timed
+work and reports the MEDIAN block (``repeats``).  The dominant kernels are then timed by HIP events stamped with their own
+dispatch (hipExtLaunchKernelGGL on the launch stream) during two more blocks (steady-state clocks), outside ``ms_per_step``.
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the arrays a caller of the timed path receives -- as
+DIR/<name>.npy (float32 / float64; rank<r>_<name>.npy per rank of an N-rank job), right after the timed block.  The inputs
+are seeded: the same arguments give the same inputs on every run, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
@@ -41,11 +45,6 @@ import statistics
 import subprocess
 import sys
 import time
-
-# HIP spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (4 unless told otherwise) and reads the variable when its runtime
-# initialises; the package asks for 16 at import (_hip.hw_queues: the window pipeline keeps a queue per window in flight) -- this
-# process touches the GPU before it imports the package, so it says so itself
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -73,7 +72,10 @@ def parse_args(argv=None):
                          "reduce; ranks may then share a GPU -- a functional test of the N-rank path on a one-GPU box)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous + shard assignment + gather only (gloo, CPU, no kernels)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the K-step block until this much timed work")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until this much timed work (default: one block, exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--max-repeats", type=int, default=100000,
                     help="cap on timed blocks (the default never binds: --min-seconds decides, also under the driver's --steps 20)")
     ap.add_argument("--events", type=int, default=None, help="events per window (default: the config's)")
@@ -423,9 +425,11 @@ class Rank(object):
         self.dist.all_gather_object(parts, obj)
         return parts
 
-    def timed_blocks(self, step, lib, profile_kernel=0, launches_per_step=1, profile_blocks=2):
-        """Warm-up, then blocks of exactly --steps steps (barrier + synchronize on both sides, MAX over ranks) until
-        --min-seconds of timed work; returns (block times [s], per-launch kernel times [ms] of the profiled blocks)."""
+    def timed_blocks(self, step, lib, profile_kernel=0, launches_per_step=1, profile_blocks=2, outputs=None):
+        """Warm-up, then one block of exactly --steps steps (barrier + synchronize on both sides, MAX over ranks), repeated until
+        --min-seconds of timed work; returns (block times [s], per-launch kernel times [ms] of the profiled blocks, which are not
+        among the block times).  ``outputs()`` -> {name: tensor} is what the last timed step computed: written for --dump-outputs
+        before the profiled blocks run."""
         import ctypes
 
         import torch
@@ -451,14 +455,19 @@ class Rank(object):
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             self.sync_all()
-            blocks.append(self.max_over_ranks(dt))
+            dt = self.max_over_ranks(dt)
             if prof:
                 buf = (ctypes.c_float * nrec)()
                 got = lib.ebos_profile_stop(buf, nrec)
                 kernel_ms.extend(buf[i] for i in range(got))
+            else:
+                blocks.append(dt)
 
+        one_block(False)
         while sum(blocks) < a.min_seconds and len(blocks) < a.max_repeats:
             one_block(False)
+        if a.dump_outputs and outputs is not None:
+            dump_outputs(a.dump_outputs, outputs(), self.rank, self.world)
         for _ in range(profile_blocks):  # the profiled blocks come LAST: clocks and caches are in their steady state by then
             one_block(True)
         return blocks, kernel_ms
@@ -536,6 +545,28 @@ def lead_with_binding(roof, issue):
         if k not in lead and k not in ("achieved", "peak", "unit", "frac", "bound"):
             lead[k] = v
     return lead
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy (rank<r>_<name>.npy in an N-rank job), float32 / float64 as computed,
+    at most DUMP_LIMIT_BYTES over all ranks."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        v = np.ascontiguousarray(t.detach().cpu().numpy())
+        if v.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"--dump-outputs: {name} is {v.dtype}, not float32 / float64")
+        host[name] = v
+    total = world * sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes over {world} rank(s) exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(dirname, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), v)
 
 
 def base_line(R, value, ms_per_step, blocks, scaling, workload_cfg):
@@ -636,7 +667,8 @@ def run_config2(R):
         return step
 
     step = make_step(plan, flow, cptrs)
-    blocks, kernel_ms = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE)
+    blocks, kernel_ms = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE,
+                                       outputs=lambda: {"iwe": iwe, "variance": out, "moments": moments})
     elapsed = statistics.median(blocks)
     contrast = float(out.item())
     ranks_seen = R.gather({"rank": rank, "local_rank": R.local_rank, "device": torch.cuda.get_device_name(dev),
@@ -1080,7 +1112,7 @@ def run_config3(R):
         _hip.check(lib.ebos_gradient_magnitude_dense_job_f32(job.ref, P(flow), P(out), None, None, P(d_flow), P(d_iwe), P(partials), n_part, stream),
                    "ebos_gradient_magnitude_dense_job")
 
-    blocks, sobel_ms = R.timed_blocks(step, lib, profile_kernel=_hip.PROFILE_GRADMAG_FUSED)
+    blocks, sobel_ms = R.timed_blocks(step, lib, profile_kernel=_hip.PROFILE_GRADMAG_FUSED, outputs=lambda: {"gradient_magnitude": out})
     elapsed = statistics.median(blocks)
     contrast = float(out.item())
     ranks_seen = R.gather({"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", rank)), "device": str(dev), "units": 1,
@@ -1250,7 +1282,8 @@ def run_config4(R):
         if not torch.equal(first, got):
             raise SystemExit(f"config 4: batched contrasts differ from the per-window calls: {first[:4].tolist()} vs {got[:4].tolist()}")
         step, graphed = batch_step, False
-    blocks, _ = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE, launches_per_step=max(len(mine), 1), profile_blocks=0)
+    blocks, _ = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE, launches_per_step=max(len(mine), 1), profile_blocks=0,
+                               outputs=lambda: {"variance": torch.cat([bt.variances for bt in batches]) if batches else outs[:len(mine)]})
     elapsed = statistics.median(blocks)
     if graphed and not torch.equal(first, outs[:len(mine)]):
         raise SystemExit("config 4: the replayed graph's contrasts differ from the eager pass")
@@ -1337,7 +1370,8 @@ def run_config5(R):
     def step():
         res["v"] = plan.variance_2dof(th, chunk=16, halo=a.halo, n_streams=a.streams)
 
-    blocks, _ = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE, launches_per_step=max(len(mine), 1), profile_blocks=0)
+    blocks, _ = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE, launches_per_step=max(len(mine), 1), profile_blocks=0,
+                               outputs=lambda: {"variance": res["v"]})
     elapsed = statistics.median(blocks)
     v = res["v"].cpu().numpy()
     # roofline leg: the timed sweep keeps three hypotheses in flight on three streams, where a dispatch's begin-to-end time

@@ -43,8 +43,7 @@ from .contrast_maximization import ContrastMaximization, patch_grid_shape
 # in creation order: two streams that land on the same queue run their kernels one after the other -- resident launches of two
 # windows that fit the device side by side then take turns (346 x 260, 100 k events, two windows in flight: 10.5 ms per window
 # instead of 5.6, for every SECOND pipeline object of a process: its fresh streams aliased the first one's).  Streams created once
-# keep the mapping the first pipeline got; where more windows in flight are wanted than queues exist, GPU_MAX_HW_QUEUES=8 in the
-# environment of the process (before its first HIP call) gives every stream a queue of its own.
+# keep the mapping the first pipeline got; the pipeline plans for no more windows in flight than ``_hip.hw_queues()`` leaves room for.
 _STREAM_POOL = {}
 
 
