@@ -207,8 +207,22 @@ SIGNATURES = {
     "ebos_gauss1d_f64": (_I, _GAUSS),
     "ebos_gauss1d_bwd_f32": (_I, _GAUSS),
     "ebos_gauss1d_bwd_f64": (_I, _GAUSS),
+    "ebos_event_filter_scratch_bytes": (_Z, [_L, _I, _I]),
+    "ebos_baf_mask": (_I, [_P, _I, _I, _P, _P, _D, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_hot_mask": (_I, [_P, _I, _I, _P, _P, _D, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_filter_compact": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
+
+
+FILTER_SRC_F32, FILTER_SRC_F64, FILTER_SRC_RAW32, FILTER_SRC_RAW64 = 0, 1, 2, 3
+FILTER_STATUS_OUT_OF_SENSOR, FILTER_STATUS_CLIPPED = 0, 1
+
+
+class EventSource(C.Structure):
+    """``ebos_event_source`` of include/ebos_hip.h (same field order): the window an event filter reads."""
+    _fields_ = [("kind", _I), ("layout", _I)] + [(k, _P) for k in ("events", "col", "row", "t", "pol")] + \
+               [("ticks_per_second", _D), ("n", _L)]
 
 
 class CmaxPatchProblem(C.Structure):

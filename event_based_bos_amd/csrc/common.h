@@ -33,6 +33,11 @@ bool profile_next_pair(hipEvent_t* start, hipEvent_t* stop, int which = 0);
 
 inline hipStream_t as_stream(ebos_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// device-wide exclusive scan of int32 data[n] in place (event_plan.hip); the grand total -> *total (device).
+// block_sums: scan_blocks(n) int32 of scratch.  Three launches on `s`.
+int64_t scan_blocks(int64_t n);
+void scan_exclusive_i32(int32_t* data, int64_t n, int32_t* total, int32_t* block_sums, hipStream_t s);
+
 // grid size for a grid-stride streaming kernel: enough workgroups to fill 256 CUs x 8, no more
 inline int stream_grid(int64_t items, int block, int max_blocks = 256 * 8) {
   int64_t g = (items + block - 1) / block;

@@ -598,9 +598,17 @@ int events_to_soa_impl(const T* events, const T* tminmax, int ref_mode, double r
   return EBOS_OK;
 }
 
-inline int64_t scan_blocks(int64_t n_keys) { return (n_keys + kScanTile - 1) / kScanTile; }
-
 }  // namespace
+
+int64_t scan_blocks(int64_t n_keys) { return (n_keys + kScanTile - 1) / kScanTile; }
+
+void scan_exclusive_i32(int32_t* data, int64_t n, int32_t* total, int32_t* block_sums, hipStream_t s) {
+  const int nblk = (int)scan_blocks(n);
+  scan_tiles_kernel<<<dim3(nblk), dim3(kScanBlock), 0, s>>>(data, n, block_sums);
+  scan_block_sums_kernel<<<dim3(1), dim3(kScanBlock), 0, s>>>(block_sums, nblk, total);
+  scan_add_offsets_kernel<<<dim3(nblk), dim3(kScanBlock), 0, s>>>(data, n, block_sums);
+}
+
 }  // namespace ebos
 
 extern "C" {
@@ -710,7 +718,6 @@ int ebos_bin_events_f32(const float* x, const float* y, const float* dt, const f
   int32_t* cursor = reinterpret_cast<int32_t*>(scratch);
   const size_t a = ((size_t)n_keys * 4 + 255) & ~(size_t)255;
   int32_t* block_sums = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(scratch) + a);
-  const int nblk = (int)scan_blocks(n_keys);
 
   if (hipMemsetAsync(key_offsets, 0, (size_t)(n_keys + 1) * 4, s) != hipSuccess ||
       hipMemsetAsync(cursor, 0, (size_t)n_keys * 4, s) != hipSuccess) {
@@ -727,9 +734,7 @@ int ebos_bin_events_f32(const float* x, const float* y, const float* dt, const f
   if (n > 0)
     bin_hist_kernel<<<dim3(stream_grid(n, 256)), dim3(256), 0, s>>>(x, y, n, H, W, tile_h, tile_w, tiles_x, key_offsets,
                                                                    oob_count, records ? rank : nullptr);
-  scan_tiles_kernel<<<dim3(nblk), dim3(kScanBlock), 0, s>>>(key_offsets, n_keys, block_sums);
-  scan_block_sums_kernel<<<dim3(1), dim3(kScanBlock), 0, s>>>(block_sums, nblk, key_offsets + n_keys);
-  scan_add_offsets_kernel<<<dim3(nblk), dim3(kScanBlock), 0, s>>>(key_offsets, n_keys, block_sums);
+  scan_exclusive_i32(key_offsets, n_keys, key_offsets + n_keys, block_sums, s);
   if (n > 0 && records) {
     bin_scatter_records_kernel<<<dim3(stream_grid(n, 256)), dim3(256), 0, s>>>(x, y, dt, p, n, H, W, tile_h, tile_w, tiles_x,
                                                                               key_offsets, rank, rec, frac_count);

@@ -3,9 +3,10 @@
 Kept from the reference: the constructor signature, ``preprocess(events) -> (events, time_period)``,
 ``estimate(events, *args, **kwargs) -> np.ndarray [2, H, W]`` and the owned helpers ``orig_imager`` /
 ``crop_imager`` / ``orig_warper`` / ``crop_warper`` (always ``normalize_t=True``, :98-100).  Visualisation,
-flow-error bookkeeping and the event-filter zoo of the reference are outside the accelerated path
- -- only the CROP step of the filter pipeline (always prepended by the reference's
-``EventFilter``, src/utils/event_filters.py:182-202) is kept because it defines which events enter the window.
+flow-error bookkeeping are outside the accelerated path.  ``preprocess`` runs the reference's
+filter pipeline (src/solver/base.py:108-139): CROP to the region of interest, then the filters ``solver.filter.filters``
+lists ("BAF", "HOT": ``event_filters.EventFilter`` on the GPU, the BAF time map carried from window to window when
+BAF_continuous_update is set).  A config without a ``filters`` list only crops, exactly as before.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .. import costs, event_image_converter, warp
+from .. import costs, event_filters, event_image_converter, warp
 from .._staging import to_gpu
 
 logger = logging.getLogger(__name__)
@@ -47,7 +48,17 @@ class SolverBase(object):
         self.warp_direction = self.slv_config.get("warp_direction", "first")
         self.motion_model = self.slv_config.get("motion_model", "dense-flow")
         self.roi = self._roi_from_config(self.slv_config)
+        self.filter_set = self._filter_from_config(self.orig_image_shape, self.slv_config)
         self.previous_best = None
+
+    @staticmethod
+    def _filter_from_config(image_shape, cfg: dict) -> Optional[event_filters.EventFilter]:
+        """The reference's ``setup_filter_preprocess`` (src/solver/base.py:108-121): an ``EventFilter`` of the ``solver.filter``
+        section when it lists filters (an unknown name raises KeyError here); None when it lists none -- CROP alone."""
+        section = cfg.get("filter") or {}
+        if not section.get("filters"):
+            return None
+        return event_filters.EventFilter(image_shape, section)
 
     @staticmethod
     def _roi_from_config(cfg: dict) -> Optional[Tuple[int, int, int, int]]:
@@ -58,13 +69,18 @@ class SolverBase(object):
         return tuple(int(p[k]) for k in keys) if all(k in p for k in keys) else None
 
     def preprocess(self, events) -> tuple:
-        """CROP the window to the ROI and report its time period (src/solver/base.py:123-139)."""
+        """CROP the window to the ROI, then the listed BAF / HOT filters, and report its time period -- that of the cropped
+        window (src/solver/base.py:123-139)."""
         ev = to_gpu(events)
+        if self.filter_set is not None and ev.shape[0] < event_filters.MIN_EVENTS:
+            return events, float((ev[:, 2].max() - ev[:, 2].min()).item()) if ev.shape[0] else 0.0  # (EventFilter.process: as it is)
         if self.roi is not None:
             x0, x1, y0, y1 = self.roi
             keep = (ev[:, 0] >= x0) & (ev[:, 0] < x1) & (ev[:, 1] >= y0) & (ev[:, 1] < y1)
             ev = ev[keep]
         period = float((ev[:, 2].max() - ev[:, 2].min()).item()) if ev.shape[0] else 0.0
+        if self.filter_set is not None:
+            ev = self.filter_set.process(ev, skip=("CROP",) if self.roi is not None else ())
         if isinstance(events, np.ndarray):
             return ev.cpu().numpy(), period
         return (ev if events.is_cuda else ev.cpu()), period

@@ -20,6 +20,12 @@ import since round 5; on a small sensor -- 346 x 260 -- eight windows run side b
 
 Only the objective family of ``fused_loop`` is pipelined; ``run`` raises for any other solver configuration (use
 ``solver.estimate`` per window then).  Across ranks, windows are dealt out with ``sharding.shard_units``.
+
+The BAF / HOT event filters the solver's config lists (``solver.filter.filters``, the reference's preprocessing,
+src/solver/base.py:108-139) run on every raw window on the ingest stream before its plan is built (``event_filters``: the
+filters' masks chained on the device, one compaction, one host read-back of the kept count per window); the pipeline adds no
+CROP.  The BAF time map of BAF_continuous_update carries over the windows of one ``run`` call in list order and starts from
+zero at every call.  A window solved again after a resident fallback reuses the events it was filtered to the first time.
 """
 from __future__ import annotations
 
@@ -34,6 +40,7 @@ from .. import _hip, ops
 from .._hip import check, stream_ptr
 from .._staging import to_gpu
 from ..data_loader import RawEventStore
+from ..event_filters import EventFilter
 from ..event_plan import EventPlan
 from . import fused_loop
 from .contrast_maximization import ContrastMaximization, patch_grid_shape
@@ -81,6 +88,11 @@ class WindowPipeline(object):
         self.resident = bool(resident) if resident is not None else os.environ.get("EBOS_RESIDENT", "1") != "0"
         self.resident_fallbacks: List[int] = []
         self.device = torch.device(device)
+        # the configured BAF / HOT filters (no CROP: the pipeline's region of interest is the solver's image), state of its own
+        section = dict(solver.slv_config.get("filter") or {})
+        self.filters = EventFilter(solver.orig_image_shape, dict(section, parameters={
+            k: v for k, v in (section.get("parameters") or {}).items() if k not in ("xmin", "xmax", "ymin", "ymax")})) \
+            if section.get("filters") else None
         self.lib = _hip.require_gpu()
         self.histories: List[List[float]] = []
         # the streams live as long as the process (_pooled_streams): torch's caching allocator pools blocks per stream, so fresh
@@ -121,11 +133,23 @@ class WindowPipeline(object):
             self.ingest_stream, self.streams = _pooled_streams(self.device, self.n_concurrent)
 
     # ------------------------------------------------------------------ stages
-    def _ingest(self, store: RawEventStore, window: Tuple[int, int]) -> EventPlan:
+    def _ingest(self, store: RawEventStore, window: Tuple[int, int], filtered: Optional[tuple] = None) -> Tuple[EventPlan, Optional[tuple]]:
+        """The window's plan, and its filtered raw columns when filters are configured (``filtered``: those of an earlier
+        ingest of the same window, reused as they are -- filtering again would advance a continuous BAF map twice)."""
         s = self.solver
-        plan = store.plan(window[0], window[1], s.orig_image_shape, s.warp_direction, True, tile=self.tile, device=self.device,
-                          deferred=True, emit="compact")  # no host read-back: the host never waits for the GPU until the end;
-        # lean build: the fused loop reads only the compact events and offsets (0.09 ms instead of 0.4 per 2 M-event window)
+        if self.filters is None:
+            plan = store.plan(window[0], window[1], s.orig_image_shape, s.warp_direction, True, tile=self.tile, device=self.device,
+                              deferred=True, emit="compact")  # no host read-back: the host never waits for the GPU until the end;
+            # lean build: the fused loop reads only the compact events and offsets (0.09 ms instead of 0.4 per 2 M-event window)
+        else:
+            if filtered is None:   # (one host read-back: the kept count sizes the plan)
+                filtered = self.filters.filter_raw_window(*store.load_raw(window[0], window[1], self.device), store.TICKS_PER_SECOND)
+            plan = EventPlan.build_raw(*filtered, s.orig_image_shape, s.warp_direction, True, tile=self.tile,
+                                       ticks_per_second=store.TICKS_PER_SECOND, deferred=True, emit="compact")
+        return self._check_plan(plan), filtered
+
+    def _check_plan(self, plan: EventPlan) -> EventPlan:
+        s = self.solver
         if self.two_dof:
             if not s._translation_loop_fused(plan):
                 raise NotImplementedError("this 2-DoF configuration is outside the native loop (variance contrast, optionally blurred, no "
@@ -234,20 +258,24 @@ class WindowPipeline(object):
             groups = [list(windows[i:i + self.n_concurrent]) for i in range(0, len(windows), self.n_concurrent)]
             pending: List[dict] = []
 
-            def ingest_group(group):   # one event per window: a window's stream waits for ITS plan, not for the group's last one
-                plans, ready = [], []
+            def ingest_group(group, filtered=None):   # one event per window: a window's stream waits for ITS plan, not for the group's last one
+                plans, ready, kept = [], [], []
                 with torch.cuda.stream(ingest):
-                    for wnd in group:
-                        plans.append(self._ingest(store, wnd))
+                    for k, wnd in enumerate(group):
+                        plan, f = self._ingest(store, wnd, None if filtered is None else filtered[k])
+                        plans.append(plan)
+                        kept.append(f)
                         ev = torch.cuda.Event()
                         ev.record(ingest)
                         ready.append(ev)
-                return plans, ready
+                return plans, ready, kept
 
+            if self.filters is not None:
+                self.filters.reset()   # (the continuous BAF map runs over this call's windows, in list order)
             nxt = ingest_group(groups[0]) if groups else None
             resident = self.resident
             for g in range(len(groups)):
-                plans, ready = nxt
+                plans, ready, kept = nxt
                 for st, ev in zip(streams, ready):
                     st.wait_event(ev)
                 # A recording whose windows the resident kernel refuses (crowded tiles: status -104, or flows beyond its windows) would
@@ -265,8 +293,8 @@ class WindowPipeline(object):
                         if bool((torch.cat(first) != 0).any().item()):
                             resident = False
                 solved = self._solve_group(plans, streams, resident=resident)   # asynchronous: returns once enqueued
-                for r, wnd in zip(solved, groups[g]):
-                    r["window"] = wnd
+                for r, wnd, f in zip(solved, groups[g], kept):
+                    r["window"], r["filtered"] = wnd, f
                 pending += solved
                 nxt = ingest_group(groups[g + 1]) if g + 1 < len(groups) else None  # ... so this overlaps with it
             for st in streams:
@@ -279,7 +307,7 @@ class WindowPipeline(object):
             self.resident_fallbacks = sorted({owner[i] for i in np.flatnonzero(bad)})
             for i in range(0, len(self.resident_fallbacks), len(streams)):   # (in groups, like the first pass)
                 ks = self.resident_fallbacks[i:i + len(streams)]
-                plans, ready = ingest_group([pending[k]["window"] for k in ks])
+                plans, ready, _ = ingest_group([pending[k]["window"] for k in ks], [pending[k]["filtered"] for k in ks])
                 for st, ev in zip(streams, ready):
                     st.wait_event(ev)
                 for k, redo in zip(ks, self._solve_group(plans, streams, resident=False)):

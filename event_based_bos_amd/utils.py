@@ -4,6 +4,8 @@ Only ``crop_event`` is on the path: it selects the events of a region of interes
 src/utils/event_filters.py:182-202) and of a patch (src/solver/patch_eklt.py:118-124).  The per-patch use -- one pass
 over the whole event array per patch, only to count -- is replaced by ``EventPlan.patch_event_counts``.
 
+The reference's event filters are re-exported from ``event_filters`` under their names, as src/utils/__init__.py:2 does.
+
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
 """
@@ -49,3 +51,7 @@ def crop_event(events: NUMPY_TORCH, x0: int, x1: int, y0: int, y1: int) -> NUMPY
     numpy arrays and torch tensors on any device, order kept.  src/utils/event_utils.py:109-129."""
     mask = (x0 <= events[..., 0]) & (events[..., 0] < x1) & (y0 <= events[..., 1]) & (events[..., 1] < y1)
     return events[mask]
+
+
+from .event_filters import (EventFilter, background_activity_filter, continuous_background_activity_filter,  # noqa: E402,F401
+                            hot_pixel_filter)

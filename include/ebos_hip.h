@@ -905,6 +905,72 @@ int ebos_cmax_resident_status(const void* mailbox, ebos_stream_t stream);
  * (nothing changed). */
 int ebos_cmax_resident_iterations(const void* mailbox, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Event filters (src/utils/event_filters.py), bit-identical to the reference's per-event loops.
+ *
+ * A window is described by an ebos_event_source (host struct, device buffers):
+ *   kind EBOS_FILTER_SRC_F32 / _F64: AoS events [n, 4]; `layout` = ix | iy << 2 | it << 4 names the row, column and
+ *        time columns (index_convention, :21; the default (0, 1, 2) is layout 0x24); pixels are int(x), int(y) of
+ *        the input's own dtype (truncation), times the input's values as float64;
+ *   kind EBOS_FILTER_SRC_RAW32 / _RAW64: raw sensor columns col (= y) / row (= x) int16, t int32 / int64 ticks,
+ *        pol uint8 (compaction only); t in seconds = (double)t / ticks_per_second (data_loader.py:104).
+ * A filter reads the events with mask_in[i] != 0 (mask_in NULL = all n) and writes mask_out[n] (1 = kept, 0 otherwise)
+ * and the kept count *n_out (device int32).  n_in (device int32, nullable) is the number of events in the filter's input:
+ * when it is below 10 the filter is skipped -- mask_out = mask_in, *n_out = *n_in, time map unchanged -- as
+ * EventFilter.process skips the remaining filters (:184-187), so that a chain of filters runs without a host read-back.
+ * status[3] (device int32, accumulates; the caller zeroes it): [EBOS_FILTER_STATUS_OUT_OF_SENSOR] input events whose
+ * pixel lies outside [0, H) x [0, W) (the reference wraps negative indices; callers raise), [EBOS_FILTER_STATUS_CLIPPED]
+ * events whose clipped BAF neighbourhood holds fewer than num_support_event + 1 pixels (the reference raises IndexError
+ * at time_array[-1 - num_support_event], :89).  Outputs are undefined when either is non-zero.
+ * scratch: ebos_event_filter_scratch_bytes(n, H, W) bytes (caller-owned) for any of the three calls.
+ *
+ *   ebos_baf_mask        continuous_background_activity_filter (:46-97): events in array order, time map
+ *                        M = time_map_in ([H, W] float64; NULL = zeros) updated to max(M, t) at the event's pixel, kept iff
+ *                        t - (the (num_support_event + 1)-th largest M over the clipped (2 ksize + 1)^2 neighbourhood) < dt;
+ *                        the final map -> time_map_out (may be time_map_in).  0 <= ksize <= 7 and
+ *                        0 <= num_support_event <= 15, else EBOS_ERR_UNSUPPORTED.  Deterministic: no atomic order
+ *                        reaches any output.
+ *   ebos_hot_mask        hot_pixel_filter (:100-128): drops the events of pixels whose image value is > thresh.  iwe NULL:
+ *                        the value is the pixel's event count (= create_iwe(events, sigma=0) for integer coordinates);
+ *                        else iwe [H, W] float64 of the input events (ebos_splat_f64, bilinear, eps 1e-8: fractional
+ *                        coordinates).
+ *   ebos_filter_compact  the events with mask[i] != 0, in their order, in the source's own format -> events_out [n, 4]
+ *                        (AoS) or col_out / row_out / t_out / pol_out (raw); *n_out = their number (replaces the
+ *                        np.vstack of kept events, :95-97, 128).
+ * ---------------------------------------------------------------------------------------- */
+typedef enum ebos_filter_source_kind {
+  EBOS_FILTER_SRC_F32 = 0,
+  EBOS_FILTER_SRC_F64 = 1,
+  EBOS_FILTER_SRC_RAW32 = 2,
+  EBOS_FILTER_SRC_RAW64 = 3
+} ebos_filter_source_kind;
+
+typedef enum ebos_filter_status_slot {
+  EBOS_FILTER_STATUS_OUT_OF_SENSOR = 0,
+  EBOS_FILTER_STATUS_CLIPPED = 1
+} ebos_filter_status_slot;
+
+typedef struct ebos_event_source {
+  int kind, layout;
+  const void* events;
+  const int16_t* col;
+  const int16_t* row;
+  const void* t;
+  const uint8_t* pol;
+  double ticks_per_second;
+  int64_t n;
+} ebos_event_source;
+
+size_t ebos_event_filter_scratch_bytes(int64_t n, int H, int W);
+int ebos_baf_mask(const ebos_event_source* src, int H, int W, const uint8_t* mask_in, const int32_t* n_in, double dt, int ksize,
+                  int num_support_event, const double* time_map_in, double* time_map_out, uint8_t* mask_out, int32_t* n_out,
+                  int32_t* status, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_hot_mask(const ebos_event_source* src, int H, int W, const uint8_t* mask_in, const int32_t* n_in, double thresh,
+                  const double* iwe, uint8_t* mask_out, int32_t* n_out, int32_t* status, void* scratch, size_t scratch_bytes,
+                  ebos_stream_t stream);
+int ebos_filter_compact(const ebos_event_source* src, const uint8_t* mask, void* events_out, int16_t* col_out, int16_t* row_out,
+                        void* t_out, uint8_t* pol_out, int32_t* n_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
