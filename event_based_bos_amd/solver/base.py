@@ -2,8 +2,9 @@
 
 Kept from the reference: the constructor signature, ``preprocess(events) -> (events, time_period)``,
 ``estimate(events, *args, **kwargs) -> np.ndarray [2, H, W]`` and the owned helpers ``orig_imager`` /
-``crop_imager`` / ``orig_warper`` / ``crop_warper`` (always ``normalize_t=True``, :98-100).  Visualisation,
-flow-error bookkeeping are outside the accelerated path.  ``preprocess`` runs the reference's
+``crop_imager`` / ``orig_warper`` / ``crop_warper`` (always ``normalize_t=True``, :98-100).  Visualisation is outside the
+accelerated path; the driver's evaluation calls ``calculate_flow_error`` / ``save_flow_error_as_text``
+(:289-353) are here, on the GPU metrics of ``flow_error``.  ``preprocess`` runs the reference's
 filter pipeline (src/solver/base.py:108-139): CROP to the region of interest, then the filters ``solver.filter.filters``
 lists ("BAF", "HOT": ``event_filters.EventFilter`` on the GPU, the BAF time map carried from window to window when
 BAF_continuous_update is set).  A config without a ``filters`` list only crops, exactly as before.
@@ -11,12 +12,13 @@ BAF_continuous_update is set).  A config without a ``filters`` list only crops, 
 from __future__ import annotations
 
 import logging
+import os
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from .. import costs, event_filters, event_image_converter, warp
+from .. import costs, event_filters, event_image_converter, flow_error, warp
 from .._staging import to_gpu
 
 logger = logging.getLogger(__name__)
@@ -88,5 +90,52 @@ class SolverBase(object):
     def estimate(self, events, *args, **kwargs) -> np.ndarray:
         raise NotImplementedError
 
+    def calculate_flow_error(self, pred_disp, gt_flow, timescale: float = 1.0, events=None, roi: Optional[dict] = None) -> dict:
+        """Flow error of one window (src/solver/base.py:289-318): ``flow_error.calculate_flow_error_numpy(gt_flow[None],
+        pred_disp[None], event_mask)`` on the GPU.
+
+        Args:
+            pred_disp, gt_flow ... [2, H, W] pixel displacements (numpy or torch; an ROI view is read in place on the device).
+            timescale ... only logged, as in the reference.
+            events ... optional [n, 4] events: the mask is ``orig_imager.create_eventmask`` of them as a float64 device tensor,
+                sliced ``[:, xmin:xmax, ymin:ymax]`` with ``roi``; it never leaves the device.  (The reference hands numpy
+                events to create_eventmask, whose bilinear weights drop contributions below 1e-8 instead of 1e-6: the masks
+                differ only for events within 1e-6 of a pixel boundary.)
+            roi ... dict with xmin, xmax, ymin, ymax (rows, columns), required with ``events`` as in the reference.
+        Returns:
+            {"EPE", "1PE", "2PE", "3PE", "5PE", "10PE", "20PE", "AE"}: np.float64 values.
+        """
+        event_mask = None
+        if events is not None:
+            ev = to_gpu(events, dtype=torch.float64)
+            event_mask = self.orig_imager.create_eventmask(ev)[:, roi["xmin"]:roi["xmax"], roi["ymin"]:roi["ymax"]]
+        err = flow_error.calculate_flow_error_numpy(gt_flow[None], pred_disp[None], event_mask=event_mask)
+        logger.info(f"{err = } for time period {timescale} sec.")
+        return err
+
+    def save_flow_error_as_text(self, nth_frame: int, flow_error_dict: dict, fname: str = "flow_error_per_frame.txt"):
+        """Append ``frame <n>::{...}`` to ``fname`` (under ``visualizer.save_dir`` when there is a visualizer) and list the file in
+        ``evaluation_text_list`` (src/solver/base.py:340-353).  Numeric values are written as plain Python floats: under numpy >= 2
+        the reference's own writer emits ``np.float64(...)``, which its reader ``read_flow_error_text`` (src/utils/misc.py:88-113:
+        "nan" -> "0.0", then ``ast.literal_eval``) cannot parse; these lines it can."""
+        if self.visualizer is not None:
+            save_file_name = os.path.join(self.visualizer.save_dir, fname)
+        else:
+            save_file_name = fname
+        plain = {k: _plain(v) for k, v in flow_error_dict.items()}
+        with open(save_file_name, "a") as f:
+            f.write(f"frame {nth_frame}::" + str(plain) + "\n")
+        if save_file_name not in self.evaluation_text_list and fname != "timestamps_per_frame.txt":
+            self.evaluation_text_list.append(save_file_name)
+
     def set_previous_frame_best_estimation(self, previous_best):
         self.previous_best = previous_best  # warm start hook (src/solver/base.py:355-361)
+
+
+def _plain(v):
+    """A numpy / torch scalar as a plain Python number (so that ``str`` of it is a literal); anything else unchanged."""
+    if isinstance(v, torch.Tensor) and v.numel() == 1:
+        v = v.item()
+    if isinstance(v, np.generic):
+        v = v.item()
+    return v

@@ -971,6 +971,39 @@ int ebos_hot_mask(const ebos_event_source* src, int H, int W, const uint8_t* mas
 int ebos_filter_compact(const ebos_event_source* src, const uint8_t* mask, void* events_out, int16_t* col_out, int16_t* row_out,
                         void* t_out, uint8_t* pol_out, int32_t* n_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Flow-error metrics (src/utils/flow_utils.py:706-823, calculate_flow_error_tensor / calculate_flow_error_numpy) for a
+ * batch of B flows [B, 2, H, W] in one call:
+ *   flow_mask = !isinf(gt_u) & !isinf(gt_v) & |gt_u| > 0 & |gt_v| > 0, total = flow_mask & (event_mask != 0);
+ *   g = gt * total, p = pred * total (multiplied: NaN / inf anywhere gives NaN sums, as in the reference), both times
+ *   time_scale[b] when time_scale is non-NULL; e = sqrt(dx * dx + dy * dy) of d = g - p; n = count(total) + 1e-5;
+ *   EPE = sum(e) / n, kPE = count(e > k) / n for k in {1, 2, 3, 5, 10, 20},
+ *   AE = sum(acos((1 + u u_gt + v v_gt) / (sqrt(1 + u u + v v) sqrt(1 + u_gt u_gt + v_gt v_gt)))) / n.
+ * The reference's IEEE operations in its order, uncontracted, correctly rounded sqrt: float64 e is bit-equal to numpy's.
+ * float32 flows are masked, scaled and differenced in float32; the norm, the AE term and all sums are float64.
+ *
+ * dtype: EBOS_FLOW_ERROR_F32 / _F64, the element type of flow_gt, flow_pred and time_scale ([B], nullable).
+ * Strides are in elements (batch, channel, row); columns are unit-stride, so an ROI view is read in place.  event_mask
+ * (nullable: no event mask) is uint8 [B, H, W] with strides (mask_sb, mask_sr) and unit column stride; any non-zero byte
+ * is true; mask_sb = 0 broadcasts one mask over the batch.  flags: EBOS_FLOW_ERROR_CLAMP_AE clamps the AE cosine to
+ * [-1, 1] (not the reference, whose AE is NaN when rounding pushes it above 1, e.g. for pred == gt).
+ * out: device double [(B + 1) * 9], per item EPE, 1PE, 2PE, 3PE, 5PE, 10PE, 20PE, AE, count(total), then one row of the
+ * means over the batch.  scratch: ebos_flow_error_scratch_bytes(B, H, W) bytes (caller-owned).  Three launches, no
+ * atomics: bit-identical from run to run.  0 < B <= 65535 and H * W < 2^31, else EBOS_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum ebos_flow_error_dtype {
+  EBOS_FLOW_ERROR_F32 = 0,
+  EBOS_FLOW_ERROR_F64 = 1
+} ebos_flow_error_dtype;
+
+#define EBOS_FLOW_ERROR_CLAMP_AE 1
+
+size_t ebos_flow_error_scratch_bytes(int B, int H, int W);
+int ebos_flow_error(int dtype, int B, int H, int W, const void* flow_gt, int64_t gt_sb, int64_t gt_sc, int64_t gt_sr,
+                    const void* flow_pred, int64_t pred_sb, int64_t pred_sc, int64_t pred_sr, const uint8_t* event_mask,
+                    int64_t mask_sb, int64_t mask_sr, const void* time_scale, int flags, double* out, void* scratch,
+                    size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

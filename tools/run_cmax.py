@@ -7,6 +7,7 @@ on a synthetic window (the recorded CCS sequences are not distributable).
     python tools/run_cmax.py --config_file tests/golden/config_hot_plate1.json    # the REFERENCE's configs/hot_plate1.yaml,
                                                                                   # key for key (parsed data, make_golden.py --config)
     python tools/run_cmax.py --config_file tests/golden/config_hot_plate1.json --height 260 --width 346   # BASELINE configs[0] size
+    python tools/run_cmax.py --flow-error     # + EPE / NPE / AE against the synthetic scene's dense truth in the ROI
 
 With the reference's file: 720x1280 and the region of interest rows 0:720, cols 320:960 as declared (:5-6, :23-26), motion model
 2d-translation, Adam, n_iter 600, blur_sigma 3 (:46-70) are taken from it; ``solver.method`` (the release ships no CMax solver,
@@ -33,10 +34,7 @@ def synthetic_window(cfg):
     rs = np.random.RandomState(int(d.get("seed", 0)))
     per_point = 40
     pts = np.stack([rs.uniform(0, h - 1, n // per_point), rs.uniform(0, w - 1, n // per_point)], 1)
-    cy, cx, sig, amp = h / 2, w / 2, min(h, w) / 4, float(d.get("max_displacement", 6.0))
-    g = amp * np.exp(-((pts[:, 0] - cy) ** 2 + (pts[:, 1] - cx) ** 2) / (2 * sig ** 2))
-    base = np.array(d.get("base_displacement", [3.0, -2.0]))  # the whole background texture shifts, plus the bump
-    flow = np.stack([base[0] + g, base[1] - 0.5 * g], 1)  # true displacement over the window at each point
+    flow = np.stack(true_displacement(d, pts[:, 0], pts[:, 1]), 1)  # true displacement over the window at each point
     t = rs.uniform(0, 1, (len(pts), per_point))
     x = (pts[:, None, 0] + t * flow[:, None, 0]).reshape(-1)
     y = (pts[:, None, 1] + t * flow[:, None, 1]).reshape(-1)
@@ -50,6 +48,34 @@ def synthetic_window(cfg):
     ev = np.stack([x, y, 10.0 + 0.0083 * t.reshape(-1), rs.randint(0, 2, x.size)], 1)
     ev = ev[(ev[:, 0] >= 0) & (ev[:, 0] < h) & (ev[:, 1] >= 0) & (ev[:, 1] < w)]
     return ev[np.argsort(ev[:, 2], kind="stable")], (h, w)
+
+
+def true_displacement(d, rows, cols):
+    """(row, column) displacement over the window of the synthetic scene at the given coordinates: a base shift of the whole
+    background texture plus a Gaussian bump in the middle."""
+    h, w = int(d["height"]), int(d["width"])
+    cy, cx, sig, amp = h / 2, w / 2, min(h, w) / 4, float(d.get("max_displacement", 6.0))
+    g = amp * np.exp(-((rows - cy) ** 2 + (cols - cx) ** 2) / (2 * sig ** 2))
+    base = np.array(d.get("base_displacement", [3.0, -2.0]))
+    return base[0] + g, base[1] - 0.5 * g
+
+
+def dense_truth(d):
+    """[2, H, W] true displacement on the pixel grid (the formula of synthetic_window)."""
+    rows, cols = np.meshgrid(np.arange(int(d["height"]), dtype=np.float64), np.arange(int(d["width"]), dtype=np.float64), indexing="ij")
+    return np.stack(true_displacement(d, rows, cols), 0)
+
+
+def flow_errors(solver, flow, truth, events, cp):
+    """The driver's two evaluations (bos_event.py:210-219: ROI without and with the event mask) and the clamped AE of both."""
+    r = (slice(None), slice(cp["xmin"], cp["xmax"]), slice(cp["ymin"], cp["ymax"]))
+    without = solver.calculate_flow_error(flow[r], truth[r])
+    with_mask = solver.calculate_flow_error(flow[r], truth[r], events=events, roi=cp)
+    import torch
+    mask = solver.orig_imager.create_eventmask(torch.from_numpy(np.asarray(events, dtype=np.float64)).cuda())[:, r[1], r[2]]
+    clamped = [float(ebos.flow_error.flow_error_batch(truth[r][None], flow[r][None], m, clamp_angle=True)[1][7]) for m in (None, mask)]
+    fmt = lambda e: {k: float(v) for k, v in e.items()}  # noqa: E731
+    return {"without_mask": fmt(without), "with_mask": fmt(with_mask), "AE_clamped": {"without_mask": clamped[0], "with_mask": clamped[1]}}
 
 
 def load_config(path):
@@ -69,6 +95,8 @@ def main():
     ap.add_argument("--n-iter", type=int, default=None, help="override solver.optimizer.n_iter")
     ap.add_argument("--fractional", action="store_true", help="keep the synthetic events' sub-pixel coordinates (events rectified with a sub-pixel map) "
                                                             "instead of rounding them to the sensor's integer pixels")
+    ap.add_argument("--flow-error", action="store_true", help="also report EPE / NPE / AE in the ROI against the scene's dense truth, "
+                                                            "without and with the event mask (SolverBase.calculate_flow_error)")
     args = ap.parse_args()
     cfg = load_config(args.config_file)
     d, cp = cfg["data"], cfg.setdefault("common_params", {})
@@ -113,6 +141,7 @@ def main():
     warped, _ = solver.orig_warper.warp_event(events, flow, "dense-flow", solver.warp_direction)
     iwe1 = solver.orig_imager.create_iwe(warped, "bilinear_vote", sigma=0)
     roi = (slice(cp["xmin"], cp["xmax"]), slice(cp["ymin"], cp["ymax"]))
+    extra = {"flow_error": flow_errors(solver, flow, dense_truth(d), events, cp)} if args.flow_error else {}
     print(json.dumps({"config_file": os.path.relpath(args.config_file, ROOT), "overrides": overrides, "events_in": n_in,
                       "events": int(len(events)), "image": list(shape), "crop": list(crop_shape), "roi": [cp[k] for k in ("xmin", "xmax", "ymin", "ymax")],
                       "motion_model": solver.motion_model, "optimizer": solver.opt_method, "blur_sigma": solver.blur_sigma,
@@ -123,7 +152,7 @@ def main():
                       "variance_unwarped": float(iwe0.var(ddof=1)), "variance_warped": float(iwe1.var(ddof=1)),
                       "flow_mean_in_roi": [float(flow[0][roi].mean()), float(flow[1][roi].mean())],
                       "true_base_displacement": list(d.get("base_displacement", [3.0, -2.0])),
-                      "flow_abs_max": float(np.abs(flow).max())}))
+                      "flow_abs_max": float(np.abs(flow).max()), **extra}))
 
 
 if __name__ == "__main__":
