@@ -26,6 +26,9 @@ src/solver/base.py:108-139) run on every raw window on the ingest stream before 
 filters' masks chained on the device, one compaction, one host read-back of the kept count per window); the pipeline adds no
 CROP.  The BAF time map of BAF_continuous_update carries over the windows of one ``run`` call in list order and starts from
 zero at every call.  A window solved again after a resident fallback reuses the events it was filtered to the first time.
+
+With ``poisson=True`` the Poisson integration the reference's visualizer runs on every window's flow (``poisson``) is computed for
+all windows of a ``run`` in one batched call on the device and kept in ``poisson_images``; it is read back together with the flows.
 """
 from __future__ import annotations
 
@@ -71,7 +74,8 @@ RESIDENT_TILES = ((32, 32), (32, 64), (45, 80))   # the tiles with resident kern
 
 
 class WindowPipeline(object):
-    def __init__(self, solver: ContrastMaximization, n_concurrent: Optional[int] = None, device="cuda", resident: Optional[bool] = None):
+    def __init__(self, solver: ContrastMaximization, n_concurrent: Optional[int] = None, device="cuda", resident: Optional[bool] = None,
+                 poisson: bool = False):
         # the patch-flow solver, or the 2-DoF Adam loop of the reference's shipped YAML (configs/hot_plate1.yaml:47,70)
         self.two_dof = solver.motion_model in ("2d-translation", "rigid-optical-flow")
         if solver.motion_model != "dense-flow" and not (self.two_dof and solver.opt_method == "Adam"):
@@ -95,6 +99,10 @@ class WindowPipeline(object):
             if section.get("filters") else None
         self.lib = _hip.require_gpu()
         self.histories: List[List[float]] = []
+        # poisson: ``run`` also integrates every window's dense flow (the visualizer's poisson_reconstruct(flow[1], flow[0], zeros),
+        # float64) in one batched call on the device -> ``poisson_images``, read back with the flows
+        self.poisson = bool(poisson)
+        self.poisson_images: Optional[List[np.ndarray]] = None
         # the streams live as long as the process (_pooled_streams): torch's caching allocator pools blocks per stream, so fresh
         # streams per run would turn every buffer of every window into a new hipMalloc -- and fresh streams per pipeline may alias
         # hardware queues
@@ -330,6 +338,8 @@ class WindowPipeline(object):
             cnt = [r["counts"][:1] for r in pending if r["counts"] is not None]
             cnt = iter(torch.cat(cnt).cpu().tolist() if cnt else [])
             self.dropped_events = [int(next(cnt)) if r["counts"] is not None else 0 for r in pending]
+            if self.poisson:
+                return self._flows_and_poisson(pending, H, W)
             if self.two_dof:   # dense flow equivalent of theta: -theta everywhere (src/warp.py:186-187), as ``estimate`` returns it
                 th = (-torch.stack([r["theta"] for r in pending])).cpu().numpy().astype(np.float64) if pending else np.zeros((0, 2))
                 return [np.broadcast_to(t.reshape(2, 1, 1), (2, H, W)).copy() for t in th]
@@ -337,3 +347,24 @@ class WindowPipeline(object):
                 return []
             dense = torch.stack([ops.upsample_patch_flow(r["theta"], r["patch"][0], r["patch"][1], (H, W)) for r in pending])
             return list(dense.cpu().numpy().astype(np.float64))
+
+    def _flows_and_poisson(self, pending: List[dict], H: int, W: int) -> List[np.ndarray]:
+        """The dense flows as float64 (what ``run`` returns), their Poisson integrations in one batched call on the device, and ONE
+        read-back for both."""
+        from ..poisson import poisson_reconstruct_batch
+
+        self.poisson_images = []
+        if not pending:
+            return []
+        if self.two_dof:
+            th = -torch.stack([r["theta"] for r in pending]).to(torch.float64)
+            dense = th.reshape(-1, 2, 1, 1).expand(-1, 2, H, W).contiguous()
+        else:
+            dense = torch.stack([ops.upsample_patch_flow(r["theta"], r["patch"][0], r["patch"][1], (H, W)) for r in pending])
+            dense = dense.to(torch.float64)
+        P = poisson_reconstruct_batch(dense)   # (the flows as ``run`` returns them: float64, so the result is float64)
+        both = torch.cat([dense.reshape(-1), P.reshape(-1)]).cpu().numpy()
+        n = len(pending)
+        flows = both[:n * 2 * H * W].reshape(n, 2, H, W)
+        self.poisson_images = list(both[n * 2 * H * W:].reshape(n, H, W))
+        return list(flows)

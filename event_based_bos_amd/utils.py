@@ -5,7 +5,8 @@ src/utils/event_filters.py:182-202) and of a patch (src/solver/patch_eklt.py:118
 over the whole event array per patch, only to count -- is replaced by ``EventPlan.patch_event_counts``.
 
 The reference's event filters are re-exported from ``event_filters`` under their names, as src/utils/__init__.py:2 does, and
-its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does.
+its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does, and its Poisson integration and
+``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -57,3 +58,5 @@ def crop_event(events: NUMPY_TORCH, x0: int, x1: int, y0: int, y1: int) -> NUMPY
 from .event_filters import (EventFilter, background_activity_filter, continuous_background_activity_filter,  # noqa: E402,F401
                             hot_pixel_filter)
 from .flow_error import calculate_flow_error_numpy, calculate_flow_error_tensor, flow_error_batch  # noqa: E402,F401
+from .poisson import (poisson_image, poisson_reconstruct, poisson_reconstruct_batch,  # noqa: E402,F401
+                      standardize_image_center)

@@ -1004,6 +1004,32 @@ int ebos_flow_error(int dtype, int B, int H, int W, const void* flow_gt, int64_t
                     int64_t mask_sb, int64_t mask_sr, const void* time_scale, int flags, double* out, void* scratch,
                     size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Poisson integration of BOS flows (src/utils/stat_utils.py:142-199, poisson_reconstruct, and the uint8 picture of
+ * src/visualizer.py:419-435) for a batch of B flows [B, 2, H, W] (component 0 = gradx, 1 = grady) in one call:
+ *   F = interior divergence (gx[i, j] - gx[i, j-1]) + (gy[i, j] - gy[i-1, j]), differences in in_dtype, sum in float64, minus the
+ *       5-point stencil of the boundary with its interior zeroed (in out_dtype);
+ *   P = S_h^T ((S_h F S_w^T) / D) S_w on the (H-2) x (W-2) interior, S_N the orthonormal DST-II matrix, D the eigenvalues of the
+ *       5-point Laplacian; out = the boundary with its interior replaced by P (zeros + P without a boundary).
+ * Four fp64 MFMA GEMMs, float64 throughout; no atomics, no split-K: an item's bits do not depend on B or on the run.
+ *
+ * in_dtype: EBOS_POISSON_F32 / _F64, the element type of flow (element strides flow_sb, flow_sc, flow_sr; unit columns).
+ * out_dtype: the element type of boundary (nullable = zeros; strides bnd_sb -- 0 broadcasts one boundary --, bnd_sr) and of out
+ * ([B, H, W], strides out_sb, out_sr).  out_u8 (nullable): device uint8 [B, H, W] contiguous, trunc(P / max|P| * 127 + 128) in
+ * out_dtype (the reference's standardize_image_center(P).astype(np.uint8)); all-zero P gives 128.  scratch:
+ * ebos_poisson_scratch_bytes(B, H, W) bytes, 16-byte aligned (caller-owned).  H, W >= 3, H * W < 2^31, B <= 65535, else
+ * EBOS_ERR_INVALID_ARG; a short scratch is EBOS_ERR_SCRATCH.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum ebos_poisson_dtype {
+  EBOS_POISSON_F32 = 0,
+  EBOS_POISSON_F64 = 1
+} ebos_poisson_dtype;
+
+size_t ebos_poisson_scratch_bytes(int B, int H, int W);
+int ebos_poisson_reconstruct(int in_dtype, int out_dtype, int B, int H, int W, const void* flow, int64_t flow_sb, int64_t flow_sc,
+                             int64_t flow_sr, const void* boundary, int64_t bnd_sb, int64_t bnd_sr, void* out, int64_t out_sb,
+                             int64_t out_sr, uint8_t* out_u8, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ on a synthetic window (the recorded CCS sequences are not distributable).
                                                                                   # key for key (parsed data, make_golden.py --config)
     python tools/run_cmax.py --config_file tests/golden/config_hot_plate1.json --height 260 --width 346   # BASELINE configs[0] size
     python tools/run_cmax.py --flow-error     # + EPE / NPE / AE against the synthetic scene's dense truth in the ROI
+    python tools/run_cmax.py --poisson OUT.npz   # + the Poisson integration (and its uint8 picture) of the estimate and the truth
 
 With the reference's file: 720x1280 and the region of interest rows 0:720, cols 320:960 as declared (:5-6, :23-26), motion model
 2d-translation, Adam, n_iter 600, blur_sigma 3 (:46-70) are taken from it; ``solver.method`` (the release ships no CMax solver,
@@ -78,6 +79,23 @@ def flow_errors(solver, flow, truth, events, cp):
     return {"without_mask": fmt(without), "with_mask": fmt(with_mask), "AE_clamped": {"without_mask": clamped[0], "with_mask": clamped[1]}}
 
 
+def poisson_outputs(flow, truth, path):
+    """The visualizer's Poisson integration (src/visualizer.py:419-435) of the estimate and of the dense truth, as one batched call
+    on the device; saves the float64 fields and the uint8 pictures to ``path`` and returns the call's wall time."""
+    import torch
+    both = np.stack([flow, truth]).astype(np.float64)
+    ebos.poisson.poisson_image(both)   # (warm: code objects, allocator pools)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    P = ebos.poisson.poisson_reconstruct_batch(both)
+    img = ebos.poisson.poisson_image(both)
+    P, img = P.cpu().numpy(), img.cpu().numpy()
+    dt = time.perf_counter() - t0
+    np.savez_compressed(path, poisson_estimate=P[0], poisson_truth=P[1], image_estimate=img[0], image_truth=img[1])
+    return {"path": path, "wall_ms": round(dt * 1e3, 3), "abs_max_estimate": float(np.abs(P[0]).max()),
+            "abs_max_truth": float(np.abs(P[1]).max())}
+
+
 def load_config(path):
     if path.endswith(".json"):  # fixture made from the reference's YAML by tests/golden/make_golden.py --config
         return json.load(open(path))["input"]
@@ -97,6 +115,8 @@ def main():
                                                             "instead of rounding them to the sensor's integer pixels")
     ap.add_argument("--flow-error", action="store_true", help="also report EPE / NPE / AE in the ROI against the scene's dense truth, "
                                                             "without and with the event mask (SolverBase.calculate_flow_error)")
+    ap.add_argument("--poisson", default=None, metavar="OUT.npz", help="save the Poisson integration of the estimate and of the scene's "
+                                                                      "dense truth, and their uint8 pictures, to OUT.npz (ebos.poisson)")
     args = ap.parse_args()
     cfg = load_config(args.config_file)
     d, cp = cfg["data"], cfg.setdefault("common_params", {})
@@ -142,6 +162,8 @@ def main():
     iwe1 = solver.orig_imager.create_iwe(warped, "bilinear_vote", sigma=0)
     roi = (slice(cp["xmin"], cp["xmax"]), slice(cp["ymin"], cp["ymax"]))
     extra = {"flow_error": flow_errors(solver, flow, dense_truth(d), events, cp)} if args.flow_error else {}
+    if args.poisson:
+        extra["poisson"] = poisson_outputs(flow, dense_truth(d), args.poisson)
     print(json.dumps({"config_file": os.path.relpath(args.config_file, ROOT), "overrides": overrides, "events_in": n_in,
                       "events": int(len(events)), "image": list(shape), "crop": list(crop_shape), "roi": [cp[k] for k in ("xmin", "xmax", "ymin", "ymax")],
                       "motion_model": solver.motion_model, "optimizer": solver.opt_method, "blur_sigma": solver.blur_sigma,
