@@ -21,6 +21,7 @@ SPLAT_BILINEAR, SPLAT_COUNT, SPLAT_POLARITY = 0, 1, 2
 GAUSS_REFLECT_SCIPY, GAUSS_REFLECT_TORCH = 0, 1
 PROFILE_SLAB_ACCUMULATE, PROFILE_TILED_BWD, PROFILE_SLAB_COMBINE, PROFILE_GRADMAG_FUSED = 0, 1, 2, 3
 ABI_VERSION = 2
+GML_NO_POLARITY, GML_EVENT_WEIGHTS = 1, 2   # flags of ebos_gml_objective_f64 / ebos_gml_solve_scale_f64
 
 
 
@@ -215,6 +216,12 @@ SIGNATURES = {
     "ebos_flow_error": (_I, [_I, _I, _I, _I, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _P, _I, _P, _P, _Z, _P]),
     "ebos_poisson_scratch_bytes": (_Z, [_I, _I, _I]),
     "ebos_poisson_reconstruct": (_I, [_I, _I, _I, _I, _I, _P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _Z, _P]),
+    "ebos_gml_scratch_bytes": (_Z, [_I, _I, _I]),
+    "ebos_gml_prepare_f64": (_I, [_I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_gml_normalize_f64": (_I, [_L, _P, _P, _Z, _P]),
+    "ebos_gml_objective_f64": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_gml_solve_scale_f64": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _Z,
+                                      _P]),
 }
 
 

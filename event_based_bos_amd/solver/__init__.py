@@ -3,9 +3,11 @@ crop_image_shape, calibration_parameter=..., solver_config=..., visualize_module
 from .base import SolverBase
 from .contrast_maximization import (ContrastMaximization, ContrastMaximizationMixin, make_solver_class, patch_grid_shape,
                                     register_into)
+from .generative import GenerativePatchPyramid, make_generative_class, register_generative_into
 from .window_pipeline import WindowPipeline
 
 collections = {
     "contrast_maximization": ContrastMaximization,
     "cmax": ContrastMaximization,
+    "generative_patch_pyramid": GenerativePatchPyramid,
 }

@@ -1,0 +1,261 @@
+"""The reference's generative BOS solver, ``patch_eklt_pyramid2`` (src/solver/patch_eklt_pyramid2.py on patch_eklt_dependent.py,
+patch_eklt.py and generative_max_likelihood.py), as a native float64 loop on the GPU (csrc/gml.hip).
+
+Per window: the model image's Sobel gradients, the blurred polarity histogram Q of the events (normalised) and the inverse-histogram
+weights are formed on the device (``ebos_gml_prepare_f64``); then, coarse to fine over square patches of 64, 32, 16 and 8 pixels,
+``n_iter // (5 - s + 1)`` Adam steps (lr 0.05) fit the per-patch Poisson potential and warp (p_x, p_y) to Q through
+
+    L = w_dn max_c sum_r |Q M - P| + w_ig mean(|d_r(F M) winv| + |d_c(F M) winv|) + w_fn mean |T M|_2,
+    F = up(Sobel(x0) / 8),  T = up(x[1:3]),  P = P0 / (|P0| + 1e-4) M,  P0 = F0 warp(gx, T) + F1 warp(gy, T)
+
+(``ebos_gml_solve_scale_f64``: seven launches per iteration, no host synchronisation inside a scale, no atomics).  The returned
+flow is ``up(Sobel(x0) / 8) M`` at the finest scale.  The loss history is read once per window.
+
+As in the reference: the initial potentials of the coarsest scale come from numpy's global RandomState (one discarded draw, then
+one per patch, laid out by a reshape, so that p_x and p_y do not start at zero); a finer scale starts from the bilinear resize of
+the coarser result; a scale's result is the parameters after its last step (the reference's ``best_x`` aliases the leaf tensor);
+the cached histogram is divided by its norm again at every scale when there are no event weights.
+
+Not ported, because they do not change the result: the per-patch ``crop_event`` loop of ``run_estimation_per_scale`` (its mask is
+unused by pyramid2) and the visualisation calls (``visualize_evolution``, ``make_video``, ``visualize_scipy_history``).
+Out of scope, raising ``NotImplementedError``: the angle model, the direct-velocity model (``poisson_model: false``),
+``sobel_ksize: 5``, optimizers other than Adam, model images other than current / background / black, cost terms other than
+diff_norm / image_gradient / flow_norm_pxy (or a weight of "inv").  ``flow_norm_pxy`` without ``optimize_warp`` is a
+configuration error (``ValueError``; the reference raises KeyError).
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .. import _hip
+from .._hip import check, ptr, stream_ptr
+from .._staging import to_gpu
+from ..event_image_converter import EPS_NUMPY, EventImageConverter
+from .base import SolverBase
+
+PATCHES = (64, 32, 16, 8)   # prepare_pyramidal_patch(shape, 64, 8): scales 1..4, slide = patch
+FINEST_SCALE = 5
+TERMS = ("diff_norm", "image_gradient", "flow_norm_pxy")
+MODEL_IMAGES = ("current", "background", "black")
+LR = 0.05
+
+
+def grid_shape(image_size, patch: int) -> Tuple[int, int]:
+    """len(arange(0, L - p + p, p)) per axis."""
+    return tuple(-(-int(n) // patch) for n in image_size)
+
+
+def cv_gaussian_taps(sigma: float) -> torch.Tensor:
+    """cv2.getGaussianKernel for cv2.GaussianBlur(ksize=None, sigmaX=sigma) on float64: size round(8 sigma + 1) | 1."""
+    n = int(round(float(sigma) * 8 + 1)) | 1
+    x = torch.arange(n, dtype=torch.float64) - (n - 1) * 0.5
+    t = torch.exp(-0.5 / (float(sigma) * float(sigma)) * x * x)
+    return t * (1.0 / t.sum())
+
+
+def scipy_gaussian_taps(sigma: float, truncate: float = 4.0) -> torch.Tensor:
+    radius = int(truncate * float(sigma) + 0.5)
+    x = torch.arange(-radius, radius + 1, dtype=torch.float64)
+    k = torch.exp(-0.5 / (float(sigma) ** 2) * x ** 2)
+    return k / k.sum()
+
+
+def _flag(cfg: dict, key: str) -> bool:
+    return bool(cfg.get(key, False))
+
+
+class _History(object):
+    """``cost_func.get_history()`` / ``clear_history()`` of the reference's HybridCost: per Adam iteration the loss and each term."""
+
+    def __init__(self, terms):
+        self.terms = tuple(terms)
+        self.clear_history()
+
+    def clear_history(self) -> None:
+        self.history = {"loss": []}
+        self.history.update({k: [] for k in self.terms})
+
+    def get_history(self) -> dict:
+        return {k: list(v) for k, v in self.history.items()}
+
+
+class GenerativeMixin(object):
+    """``estimate(events, frame=..., background=...) -> np.ndarray [2, H, W]`` of the reference's PatchEkltPyramid2."""
+
+    def _gml_setup(self) -> None:
+        cfg = self.slv_config
+        opt = cfg.get("optimizer") or {}
+        gml = dict(cfg.get("generative_ml") or {})
+        if opt.get("method", "Adam") != "Adam":
+            raise NotImplementedError(f"generative solver: optimizer.method {opt.get('method')!r} is not supported (Adam only)")
+        if _flag(gml, "angle_model"):
+            raise NotImplementedError("generative solver: the angle model is not supported (poisson_model only)")
+        if not _flag(gml, "poisson_model"):
+            raise NotImplementedError("generative solver: the direct-velocity model (poisson_model: false) is not supported")
+        if int(gml.get("sobel_ksize", 3)) != 3:
+            raise NotImplementedError("generative solver: sobel_ksize 5 is not supported")
+        if _flag(gml, "px-py_as-angle-magnitude"):
+            raise NotImplementedError("generative solver: px-py_as-angle-magnitude needs the optuna optimizer")
+        mi = gml.get("model_image", "current")
+        if mi not in MODEL_IMAGES:
+            raise NotImplementedError(f"generative solver: model_image {mi!r} is not supported ({', '.join(MODEL_IMAGES)})")
+        cost = dict(cfg.get("cost_with_weight") or {})
+        for k, w in cost.items():
+            if k not in TERMS:
+                raise NotImplementedError(f"generative solver: cost term {k!r} is not supported ({', '.join(TERMS)})")
+            if isinstance(w, str):
+                raise NotImplementedError(f"generative solver: cost weight {w!r} of {k} is not supported (numbers only)")
+        self._gml_warp = _flag(gml, "optimize_warp")
+        if "flow_norm_pxy" in cost and not self._gml_warp:
+            raise ValueError("generative solver: flow_norm_pxy needs generative_ml.optimize_warp (it costs p_x, p_y)")
+        n_iter = int(opt.get("n_iter", 0))
+        if n_iter < 0:
+            raise ValueError(f"generative solver: n_iter {n_iter} < 0")
+        self._gml_cfg = gml
+        self._gml_cost = cost
+        self._gml_n_iter = n_iter
+        self._gml_n_dim = 3 if self._gml_warp else 1
+        H, W = (int(v) for v in self.orig_image_shape)
+        p = (cfg.get("filter") or {}).get("parameters") or {}
+        if "filter" in cfg:
+            roi = tuple(int(p[k]) for k in ("xmin", "xmax", "ymin", "ymax"))
+        else:
+            roi = (0, H, 0, W)
+        xmin, xmax, ymin, ymax = roi
+        roi = (max(0, min(xmin, H)), max(0, min(xmax, H)), max(0, min(ymin, W)), max(0, min(ymax, W)))
+        self._gml_roi = roi
+        self._gml_frame = None
+        self._gml_imager = EventImageConverter((H, W))
+        self.cost_func = _History(cost.keys())
+        self.params_per_scale = {}
+        self.iter_cnt = 0
+
+    # ------------------------------------------------------------------ helpers
+    def _gml_weights(self):
+        w = [float(self._gml_cost.get(k, 0.0)) for k in TERMS]
+        order = [TERMS.index(k) for k in self._gml_cost]
+        return (np.array(w, dtype=np.float64), np.array(order + [0] * (3 - len(order)), dtype=np.int32), len(order))
+
+    def _gml_set_frame(self, frame) -> None:
+        self._gml_frame = to_gpu(frame, dtype=torch.float64).contiguous()
+
+    def poisson_to_flow(self, poisson):
+        """Sobel3 (replicate borders) / 8 of a [gh, gw] potential -> [2, gh, gw] (numpy in, numpy out).  The 3 x 3 stencil of the
+        patch grid, outside the iteration loop."""
+        t = to_gpu(poisson, dtype=torch.float64)
+        k = torch.tensor([[[[-1.0, -2.0, -1.0], [0.0, 0.0, 0.0], [1.0, 2.0, 1.0]]],
+                          [[[-1.0, 0.0, 1.0], [-2.0, 0.0, 2.0], [-1.0, 0.0, 1.0]]]], dtype=torch.float64, device=t.device)
+        x = F.pad(t.reshape(1, 1, *t.shape[-2:]), (1, 1, 1, 1), mode="replicate")
+        out = (F.conv2d(x, k) / 8.)[0]
+        return out.cpu().numpy() if isinstance(poisson, np.ndarray) else out
+
+    # ------------------------------------------------------------------ estimate
+    def estimate(self, events, *args, frame=None, background=None, **kwargs) -> np.ndarray:
+        mi = self._gml_cfg.get("model_image", "current")
+        if "frame" in kwargs and frame is None:
+            frame = kwargs["frame"]
+        if mi == "current":
+            if frame is None:
+                raise ValueError("generative solver: model_image 'current' needs frame=")
+            self._gml_set_frame(frame)
+        elif mi == "black":
+            if frame is None:
+                raise ValueError("generative solver: model_image 'black' needs frame= (for its shape)")
+            self._gml_set_frame(np.zeros(tuple(np.shape(frame)), dtype=np.float64))
+        elif self._gml_frame is None:
+            if background is None:
+                raise ValueError("generative solver: model_image 'background' needs background= on the first window")
+            self._gml_set_frame(background)
+        lib = _hip.require_gpu()
+        H, W = (int(v) for v in self.orig_image_shape)
+        if tuple(self._gml_frame.shape) != (H, W):
+            raise ValueError(f"generative solver: frame shape {tuple(self._gml_frame.shape)} != image shape {(H, W)}")
+        dev = self._gml_frame.device
+        gml, n = self._gml_cfg, H * W
+        ev = to_gpu(events, device=dev, dtype=torch.float64)
+        pol = self._gml_imager._accumulate(ev, 1.0, _hip.SPLAT_POLARITY, EPS_NUMPY, torch.float64)[0].contiguous()  # [2, H, W]
+        d = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)
+        gx, gy, q, winv = d(H, W), d(H, W), d(H, W), d(H, W)
+        use_we = _flag(gml, "weight_loss_by_event_hist")
+        we = d(H, W) if use_we else None
+        blur = cv_gaussian_taps(gml["iwe_sigma"]).to(dev) if gml.get("iwe_sigma") else None
+        wtap = cv_gaussian_taps(gml["weight_sigma"]).to(dev) if use_we else None
+        itap = scipy_gaussian_taps(10).to(dev) if _flag(gml, "weight_loss_by_inverse_event_hist") else None
+        nbytes = int(lib.ebos_gml_scratch_bytes(H, W, PATCHES[-1]))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rad = lambda t: 0 if t is None else (t.numel() - 1) // 2
+        with _hip.on_device(dev):
+            sp = stream_ptr(dev)
+            check(lib.ebos_gml_prepare_f64(H, W, ptr(self._gml_frame), int(_flag(gml, "use_log_intensity")), ptr(pol),
+                                           int(_flag(gml, "no_polarity")), ptr(blur), rad(blur), ptr(wtap), rad(wtap), ptr(itap),
+                                           rad(itap), ptr(gx), ptr(gy), ptr(q), ptr(we), ptr(winv), ptr(scratch), nbytes, sp),
+                  "ebos_gml_prepare_f64")
+            weights, order, n_terms = self._gml_weights()
+            w_t = torch.from_numpy(weights).to(dev)
+            o_t = torch.from_numpy(order).to(dev)
+            flags = (_hip.GML_NO_POLARITY if _flag(gml, "no_polarity") else 0) | (_hip.GML_EVENT_WEIGHTS if use_we else 0)
+            iters = [self._gml_n_iter // (FINEST_SCALE - s + 1) for s in range(1, FINEST_SCALE)]
+            hist = d(max(sum(iters), 1), 4)
+            flow = d(2, H, W)
+            xmin, xmax, ymin, ymax = self._gml_roi
+            x, row, self.params_per_scale = None, 0, {}
+            for s, p in enumerate(PATCHES, start=1):
+                gh, gw = grid_shape((H, W), p)
+                if x is None:
+                    x = torch.from_numpy(self._gml_initial(gh, gw)).to(dev)
+                else:
+                    x = F.interpolate(x[None], size=[gh, gw], mode="bilinear", align_corners=False)[0].contiguous()
+                if s > 1 and not use_we:   # the reference divides its cached histogram in place once per scale
+                    check(lib.ebos_gml_normalize_f64(n, ptr(q), ptr(scratch), nbytes, sp), "ebos_gml_normalize_f64")
+                it = iters[s - 1]
+                check(lib.ebos_gml_solve_scale_f64(H, W, p, self._gml_n_dim, xmin, xmax, ymin, ymax, flags, ptr(w_t), ptr(o_t), n_terms,
+                                                   ptr(gx), ptr(gy), ptr(q), ptr(we), ptr(winv), ptr(x), it, LR, ptr(hist[row:]),
+                                                   ptr(flow) if s == len(PATCHES) else None, ptr(scratch), nbytes, sp),
+                      "ebos_gml_solve_scale_f64")
+                row += it
+                self.params_per_scale[s] = x
+        h = hist[:row].cpu().numpy()   # the one read-back of the window
+        self.cost_func.clear_history()
+        self.cost_func.history["loss"] = list(h[:, 0])
+        for k in self._gml_cost:
+            self.cost_func.history[k] = list(h[:, 1 + TERMS.index(k)])
+        self.params_per_scale = {s: v.cpu().numpy() for s, v in self.params_per_scale.items()}
+        self.iter_cnt += 1
+        return flow.cpu().numpy()
+
+    def _gml_initial(self, gh: int, gw: int) -> np.ndarray:
+        """x0 of the coarsest scale from numpy's global RandomState, as run_estimation_per_scale draws it."""
+        nd = self._gml_n_dim
+        np.random.random()   # len(self._initialize_velocity()): one draw, discarded
+        rows = []
+        for _ in range(gh * gw):
+            base = np.random.random() * 2. - 1
+            rows.append(np.array([base, 0., 0.] if nd == 3 else [base], dtype=np.float64))
+        return np.concatenate(rows).reshape((nd, gh, gw))
+
+
+def make_generative_class(base, name: str = "GenerativePatchPyramid"):
+    """``GenerativePatchPyramid`` composed over ``base`` (a ``SolverBase``), with the reference's constructor signature."""
+
+    def __init__(self, orig_image_shape, crop_image_shape, calibration_parameter=None, solver_config=None, visualize_module=None):
+        base.__init__(self, orig_image_shape, crop_image_shape, {} if calibration_parameter is None else calibration_parameter,
+                      {} if solver_config is None else solver_config, visualize_module)
+        self._gml_setup()
+
+    return type(name, (GenerativeMixin, base), {"__init__": __init__, "__doc__": GenerativeMixin.__doc__, "__module__": __name__})
+
+
+GenerativePatchPyramid = make_generative_class(SolverBase)
+
+
+def register_generative_into(solver_module, names=("patch_eklt_pyramid2",)):
+    """Add the generative solver to ANOTHER solver registry -- the reference's ``src.solver`` -- built over THAT module's
+    ``SolverBase``, so that ``bos_event.py`` drives ``method: patch_eklt_pyramid2`` unchanged.  Returns the class."""
+    cls = make_generative_class(solver_module.SolverBase)
+    for n in names:
+        solver_module.collections[n] = cls
+    return cls

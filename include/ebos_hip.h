@@ -1030,6 +1030,42 @@ int ebos_poisson_reconstruct(int in_dtype, int out_dtype, int B, int H, int W, c
                              int64_t flow_sr, const void* boundary, int64_t bnd_sb, int64_t bnd_sr, void* out, int64_t out_sb,
                              int64_t out_sr, uint8_t* out_u8, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Generative BOS solver (src/solver/patch_eklt_pyramid2.py, the reference YAML's patch_eklt_pyramid2), float64.
+ *
+ * ebos_gml_prepare_f64: per window, from the model image frame [H, W] (log(frame + 1) if use_log) and the polarity IWE
+ *   pol [2, H, W]: gx, gy = cv2.Sobel(f, CV_64F, 0, 1 | 1, 0, ksize=3) (reflect-101); hist = pol0 -+ pol1 (+ if no_polarity);
+ *   q = GaussianBlur(hist) with blur_taps (NULL: no blur), times we = GaussianBlur(|hist|) with weight_taps (both or neither
+ *   of weight_taps / we), divided by its Frobenius norm; winv = 1 - 0.95 clip(g, 0, mean + std / 2) / max with
+ *   g = scipy gaussian_filter(|hist|) with inv_taps (NULL: winv = 1).  Taps are device doubles [2 radius + 1].
+ * ebos_gml_normalize_f64: q /= |q| (the reference divides its cached histogram in place once per scale).
+ * ebos_gml_objective_f64: the objective at x [n_dim, gh, gw] (n_dim 3 = potential, p_x, p_y; 1 = potential) for patch
+ *   = slide = `patch`: parts[4] = (loss, diff_norm, image_gradient, flow_norm_pxy) and grad = d loss / d x.
+ * ebos_gml_solve_scale_f64: `iters` Adam steps (lr, betas 0.9 / 0.999, eps 1e-8, fresh state) on x in place; history
+ *   (nullable) [iters, 4] as parts before each step; flow_out (nullable) [2, H, W] = the final F * M.
+ * weights[3] = (w_diff_norm, w_image_gradient, w_flow_norm_pxy), 0 = absent; order[n_terms] = term indices (0, 1, 2) in the
+ * configuration's order (the loss sums them in that order).  ROI rows [xmin, xmax), columns [ymin, ymax).  flags:
+ * EBOS_GML_NO_POLARITY, EBOS_GML_EVENT_WEIGHTS (we is then required).  scratch: ebos_gml_scratch_bytes(H, W, smallest patch).
+ * No atomics: results are bit-identical from run to run.  H, W >= 3, patch a power of two, else EBOS_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_GML_NO_POLARITY 1
+#define EBOS_GML_EVENT_WEIGHTS 2
+
+size_t ebos_gml_scratch_bytes(int H, int W, int min_patch);
+int ebos_gml_prepare_f64(int H, int W, const double* frame, int use_log, const double* pol, int no_polarity, const double* blur_taps,
+                         int blur_radius, const double* weight_taps, int weight_radius, const double* inv_taps, int inv_radius,
+                         double* gx, double* gy, double* q, double* we, double* winv, void* scratch, size_t scratch_bytes,
+                         ebos_stream_t stream);
+int ebos_gml_normalize_f64(int64_t n, double* q, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_objective_f64(int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags, const double* weights,
+                           const int* order, int n_terms, const double* gx, const double* gy, const double* q, const double* we,
+                           const double* winv, const double* x, double* parts, double* grad, void* scratch, size_t scratch_bytes,
+                           ebos_stream_t stream);
+int ebos_gml_solve_scale_f64(int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags, const double* weights,
+                             const int* order, int n_terms, const double* gx, const double* gy, const double* q, const double* we,
+                             const double* winv, double* x, int iters, double lr, double* history, double* flow_out, void* scratch,
+                             size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

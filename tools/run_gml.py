@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""End-to-end run of the generative BOS solver (solver.GenerativePatchPyramid, the reference's patch_eklt_pyramid2) on a synthetic
+BOS scene with a known displacement field.
+
+    python tools/run_gml.py                                                   # 260 x 346, the reference YAML's options
+    python tools/run_gml.py --size 128 160 --n_iter 120 --json out.json
+    python tools/run_gml.py --config_file tests/golden/config_hot_plate1.json # the REFERENCE's configs/hot_plate1.yaml, as it is
+
+The scene: a textured frame L, a potential phi (two Gaussian bumps) and its gradient d = grad phi as the displacement; events are
+drawn at pixels with probability proportional to |grad L . d|, with the sign of grad L . d as polarity.  Reported: the loss at
+the first and the last Adam iteration, the time per scale and per window, and EPE / AE (event_based_bos_amd.flow_error) and the
+cosine between the recovered flow and d inside the ROI.  The generative model normalises its prediction, so the flow's scale
+is free: the cosine is the meaningful figure, EPE is shown for completeness.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def scene(H, W, n_events, seed=0):
+    rs = np.random.RandomState(seed)
+    r, c = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    frame = 128 + 60 * np.sin(2 * np.pi * r / 19.0) * np.cos(2 * np.pi * c / 27.0) + 20 * np.sin(2 * np.pi * (r + c) / 41.0)
+    phi = np.zeros((H, W))
+    for cy, cx, s, a in ((0.45, 0.4, 0.18, 40.0), (0.6, 0.65, 0.12, -25.0)):
+        phi += a * np.exp(-((r - cy * H) ** 2 + (c - cx * W) ** 2) / (2 * (s * min(H, W)) ** 2))
+    d = np.stack(np.gradient(phi))                     # [2, H, W]: d / d row, d / d column
+    g = np.stack(np.gradient(frame))
+    inc = g[0] * d[0] + g[1] * d[1]
+    prob = np.abs(inc).ravel() / np.abs(inc).sum()
+    idx = rs.choice(H * W, size=n_events, p=prob)
+    ev = np.stack([idx // W, idx % W, np.sort(rs.uniform(0, 0.05, n_events)), (inc.ravel()[idx] > 0)], axis=1).astype(np.float64)
+    return frame, ev, d
+
+
+def default_config(H, W, n_iter):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _gml_cases import YAML_COST, YAML_GML
+    return {"method": "patch_eklt_pyramid2", "filter": {"filters": [], "parameters": {"xmin": 0, "xmax": H, "ymin": 0, "ymax": W}},
+            "cost_with_weight": dict(YAML_COST), "optimizer": {"method": "Adam", "n_iter": n_iter}, "generative_ml": dict(YAML_GML)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--size", type=int, nargs=2, default=(260, 346), metavar=("H", "W"))
+    ap.add_argument("--n_iter", type=int, default=600)
+    ap.add_argument("--events", type=int, default=0, help="events in the window (default 2 per pixel)")
+    ap.add_argument("--config_file", default=None, help="a reference config (JSON with a 'propagated' section, or a solver dict)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--json", default=None, help="also write the result here")
+    args = ap.parse_args()
+
+    import event_based_bos_amd as ebos
+    from event_based_bos_amd.flow_error import calculate_flow_error_numpy
+
+    if args.config_file:
+        with open(args.config_file) as f:
+            cfg = json.load(f)
+        cfg = cfg.get("propagated", cfg)
+        H, W = int(cfg["data"]["height"]), int(cfg["data"]["width"])
+        solver_cfg = cfg["solver"]
+    else:
+        H, W = args.size
+        solver_cfg = default_config(H, W, args.n_iter)
+    method = solver_cfg["method"]
+    frame, events, d = scene(H, W, args.events or 2 * H * W, args.seed)
+    import types
+    reg = types.SimpleNamespace(SolverBase=ebos.solver.SolverBase, collections={})
+    ebos.solver.register_generative_into(reg)          # method patch_eklt_pyramid2, no override
+    solv = reg.collections[method]((H, W), (H, W), {}, solver_cfg)
+    np.random.seed(args.seed)
+    solv.estimate(events, frame=frame, background=frame)   # warm-up (code objects, allocations)
+    import torch
+    torch.cuda.synchronize()
+    np.random.seed(args.seed)
+    t0 = time.perf_counter()
+    flow = solv.estimate(events, frame=frame, background=frame)
+    t_window = time.perf_counter() - t0
+    h = solv.cost_func.get_history()
+    xmin, xmax, ymin, ymax = solv._gml_roi
+    m = np.zeros((H, W), dtype=bool)
+    m[xmin:xmax, ymin:ymax] = True
+    fr, dr = flow[:, m], d[:, m]
+    cos = float((fr * dr).sum() / (np.linalg.norm(fr) * np.linalg.norm(dr) + 1e-300))
+    err = calculate_flow_error_numpy(d[None], flow[None], m[None, None].astype(np.float64))
+    n_it = len(h["loss"])
+    res = {"method": method, "size": [H, W], "roi": [xmin, xmax, ymin, ymax], "iterations": n_it, "events": int(len(events)),
+           "loss_first": float(h["loss"][0]), "loss_last": float(h["loss"][-1]), "window_ms": 1e3 * t_window,
+           "ms_per_iteration": 1e3 * t_window / max(n_it, 1), "cosine_roi": cos,
+           "EPE": float(err["EPE"]), "AE": float(err["AE"])}
+    print(json.dumps(res))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
