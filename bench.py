@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mevents/s through the fused warp + IWE (+ variance contrast) pass at 1280x720.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5] [--dry-run]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dry-run]
+
+A plain run does what its headline figure needs: it sets up the workload, runs the W warm-up steps, times the K steps,
+writes ``--dump-outputs`` if asked and prints the line.  Its set-up is the one the timed block has always started from
+(config 2's timed plan builds, config 4's per-window pass and its cross-check: a few milliseconds of device work).
+``--full`` adds everything the benchmark measures or checks after the timed block: the kernel-timed blocks and the
+rooflines, the informative legs (fwd+bwd, streams, rotating windows, solver), the measured copy bandwidth, config 4's
+host enqueue time and the CPU baseline.  ``--no-extras`` / ``--no-cpu-baseline`` trim a full run.
 
 With ``--gpus N > 1`` and no launcher environment (RANK unset) this process starts the N ranks itself
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>``, as a
@@ -27,8 +34,9 @@ evaluation, as ``value_incl_plan_build`` -- it is NOT in the timed region of ``v
 
 Timing: W warm-up steps, then ONE block of exactly K timed steps, bracketed by barrier + torch.cuda.synchronize() and
 MAX-reduced over the ranks; ``ms_per_step`` is that block / K.  ``--min-seconds S`` repeats the block until >= S of timed
-work and reports the MEDIAN block (``repeats``).  The dominant kernels are then timed by HIP events stamped with their own
-dispatch (hipExtLaunchKernelGGL on the launch stream) during two more blocks (steady-state clocks), outside ``ms_per_step``.
+work and reports the MEDIAN block (``repeats``).  With ``--full`` the dominant kernels are then timed by HIP events stamped
+with their own dispatch (hipExtLaunchKernelGGL on the launch stream) during two more blocks (steady-state clocks), outside
+``ms_per_step``.
 
 ``--dump-outputs DIR`` writes what the last timed step computed -- the arrays a caller of the timed path receives -- as
 DIR/<name>.npy (float32 / float64; rank<r>_<name>.npy per rank of an N-rank job), right after the timed block.  The inputs
@@ -88,8 +96,12 @@ def parse_args(argv=None):
     ap.add_argument("--splits", type=int, default=1)
     ap.add_argument("--flow-max", type=float, default=FLOW_MAX, help="amplitude of the synthetic flow (BASELINE: 30 px)")
     ap.add_argument("--streams", type=int, default=3, help="configs 4 / 5: independent windows / hypotheses kept in flight per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informative legs (fwd+bwd, streams, rotating windows, solver)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed block, measure and check everything beside the headline figure: kernel-timed blocks and "
+                         "rooflines, the informative legs, copy bandwidth, the CPU baseline (default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="skip the raw-column plan build and, with --full, the informative legs (fwd+bwd, streams, rotating windows, solver)")
     ap.add_argument("--batch", type=int, default=64, help="config 4: windows per ebos_iwe_slab_batch_f32 call (16 per launch inside); 0 = one call per window")
     ap.add_argument("--tail-stream", action="store_true", help="config 4, batched: combine / finalize passes of a batch on a second stream beside the next "
                                                                "batch's accumulate pass (measured SLOWER wherever the two really overlap: 1.11 against 0.96 ms per pass "
@@ -428,8 +440,8 @@ class Rank(object):
     def timed_blocks(self, step, lib, profile_kernel=0, launches_per_step=1, profile_blocks=2, outputs=None):
         """Warm-up, then one block of exactly --steps steps (barrier + synchronize on both sides, MAX over ranks), repeated until
         --min-seconds of timed work; returns (block times [s], per-launch kernel times [ms] of the profiled blocks, which are not
-        among the block times).  ``outputs()`` -> {name: tensor} is what the last timed step computed: written for --dump-outputs
-        before the profiled blocks run."""
+        among the block times; --full only).  ``outputs()`` -> {name: tensor} is what the last timed step computed: written for
+        --dump-outputs before the profiled blocks run."""
         import ctypes
 
         import torch
@@ -468,7 +480,7 @@ class Rank(object):
             one_block(False)
         if a.dump_outputs and outputs is not None:
             dump_outputs(a.dump_outputs, outputs(), self.rank, self.world)
-        for _ in range(profile_blocks):  # the profiled blocks come LAST: clocks and caches are in their steady state by then
+        for _ in range(profile_blocks if a.full else 0):  # the profiled blocks come LAST: clocks and caches are in their steady state by then
             one_block(True)
         return blocks, kernel_ms
 
@@ -624,6 +636,9 @@ def run_config2(R):
 
     # the same window as the raw sensor columns a recording holds (src/data_loader/ccs.py:57-66: int16 x / y, int32 microseconds):
     # the lean build straight from them (EventPlan.build_raw) -- informative, beside the build from the reference's float64 [n, 4]
+    # (a plain run keeps these builds too: ~7 ms of device work right before the warm-up, and the timed block has always started from
+    # the state they leave.  Measured without them, the 200-step block read 0.4 - 2.5 % slower in nine alternated pairs out of nine;
+    # ~5 ms of any other device work in their place closed the gap)
     plan_build_raw_ms = None
     if not general and not a.no_extras and not a.no_compact:
         raw_cols = [torch.from_numpy(v).to(dev) for v in (ev[:, 1].astype(np.int16), ev[:, 0].astype(np.int16),
@@ -678,7 +693,7 @@ def run_config2(R):
     # The informative legs (fwd + bwd, streams, rotating windows, solver iteration) run on rank 0 ONLY in an N-rank job: eight ranks
     # each synthesising eight more 10 M-event windows on the host, inside the driver's timeout, buy nothing -- `value` is measured
     # above, by every rank, and the other ranks wait at the final barrier.
-    if not a.no_extras and (world == 1 or rank == 0):
+    if a.full and not a.no_extras and (world == 1 or rank == 0):
         # (1) combine pass of the same step, timed the same way (outside `value`'s blocks)
         _hip.check(lib.ebos_profile_start_kernel(_hip.PROFILE_SLAB_COMBINE, 100), "profile")
         for _ in range(100):
@@ -940,39 +955,23 @@ def run_config2(R):
             except Exception as err:  # the headline measurement must not depend on the solver layer
                 extras["solver_iteration"] = {"error": repr(err)}
 
-    # next to the nominal peak, a bandwidth this box actually delivers -- a device-to-device copy of 1 GiB
-    # (read + write bytes counted), best of 6
-    a_buf = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-    b_buf = torch.empty_like(a_buf)
-    copy_gbs = 0.0
-    for _ in range(6):
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        b_buf.copy_(a_buf)
-        torch.cuda.synchronize()
-        copy_gbs = max(copy_gbs, 2.0 * a_buf.numel() * 4 / (time.perf_counter() - t3) / 1e9)
-    del a_buf, b_buf
+    if a.full:
+        # next to the nominal peak, a bandwidth this box actually delivers -- a device-to-device copy of 1 GiB
+        # (read + write bytes counted), best of 6
+        a_buf = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+        b_buf = torch.empty_like(a_buf)
+        copy_gbs = 0.0
+        for _ in range(6):
+            torch.cuda.synchronize()
+            t3 = time.perf_counter()
+            b_buf.copy_(a_buf)
+            torch.cuda.synchronize()
+            copy_gbs = max(copy_gbs, 2.0 * a_buf.numel() * 4 / (time.perf_counter() - t3) / 1e9)
+        del a_buf, b_buf
 
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
         value = world * n * a.steps / elapsed / 1e6
-        # 12 B/event (x, y, dt; p unused) + flow read (8 B/px) + IWE write (4 B/px)
-        algo_bytes = (16.0 if a.weighted else 12.0) * plan.n + 12.0 * H * W  # (16 B/event with weights)
-        format_bytes = bytes_per_event * plan.n + 12.0 * H * W  # what the plan format actually stores per event
-        k_ms = statistics.mean(kernel_ms) if kernel_ms else float("nan")
-        kname = "iwe_slab_accumulate_kernel<DENSE,DYN>" if a.halo == "auto" else "iwe_slab_accumulate_kernel"
-        if not cptrs[0]:  # other instantiations: the committed counters are the compact unit-weight kernel's
-            kname = "iwe_slab_accumulate_kernel<XY" + (",W>" if a.weighted else ">")
-        elif a.weighted:
-            kname = "iwe_slab_accumulate_kernel<W>"
-        roof = roofline_entry(kname, kernel_ms, algo_bytes,
-                              {"measured_copy_GBps": round(copy_gbs, 1),
-                               "frac_of_measured_copy": round(algo_bytes / (k_ms * 1e-3) / 1e9 / copy_gbs, 4),
-                               "plan_format_bytes": format_bytes,
-                               "plan_format_GBps": round(format_bytes / (k_ms * 1e-3) / 1e9, 1),
-                               "step_frac": round(algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
-        if "rotating_windows" in extras:
-            roof["frac_rotating_windows"] = extras["rotating_windows"]["frac"]
         line = base_line(R, value, ms_per_step, blocks, "weak", {
             "workload": ("BASELINE configs[1]: 10M synthetic events, 1280x720 dense per-pixel flow U(-30,30), "
                          "variance cost, fwd objective (tile accumulate + slab combine + variance)") if (a.flow_max == FLOW_MAX and n == N_EVENTS and not general)
@@ -984,27 +983,45 @@ def run_config2(R):
                        + (" + f32 weight in plan order" if a.weighted else ""))
                       + f", binned by source tile {a.tile[0]}x{a.tile[1]}, halo {a.halo}, splits {a.splits}",
             "parallelism": f"windows sharded, {world} rank(s), no collective"})
-        line["roofline"] = roof
-        clock = device_clock_hz(dev)
-        dyn = a.halo == "auto"
-        line["roofline_issue"] = roofline_issue(kname, kernel_ms, clock, plan.n)
-        if "roofline_bwd" in extras:
-            extras["roofline_bwd_issue"] = roofline_issue("iwe_dense_tiled_bwd_kernel<DENSE,DYN>" if dyn else "iwe_dense_tiled_bwd_kernel",
-                                                          [extras["roofline_bwd"]["kernel_ms"]], clock, plan.n)
-            extras["roofline_bwd"] = lead_with_binding(extras["roofline_bwd"], extras["roofline_bwd_issue"])
-        # the fractions side by side: what each one prices and what it says.  `roofline` leads with the roofline that BINDS (VALU issue /
-        # LDS pipe, from the instruction counters of this kernel source); SURVEY 8(d)'s HBM accounting sits in roofline.hbm_algorithmic
-        hbm_frac, plan_gbs, step_frac = roof["frac"], roof["plan_format_GBps"], roof["step_frac"]
-        roof = line["roofline"] = lead_with_binding(roof, line["roofline_issue"])
-        line["roofline_summary"] = {
-            "hbm_algorithmic_frac": hbm_frac,                           # SURVEY 8(d) bytes (12 B/event + 12 H W) / kernel time / 8 TB/s
-            "hbm_plan_format_frac": round(plan_gbs / HBM_PEAK_GBS, 4),  # the 6 B/event the compact plan really streams
-            "hbm_counter_traffic_frac": (round(roof["traffic"] / (roof["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                         if roof.get("traffic") else None),              # FETCH / WRITE counters of the same source
-            "hbm_step_frac": step_frac,                                 # the WHOLE step (accumulate + combine + finalize) on the same bytes
-            "hbm_rotating_windows_frac": roof.get("frac_rotating_windows"),              # plans cycled beyond the Infinity Cache
-            "issue_frac": line["roofline_issue"].get("frac"),           # what binds: VALU issue / LDS pipe (roofline_issue)
-            "binding": line["roofline_issue"].get("bound", "unknown (no counters for this kernel source)")}
+        if a.full:
+            # 12 B/event (x, y, dt; p unused) + flow read (8 B/px) + IWE write (4 B/px)
+            algo_bytes = (16.0 if a.weighted else 12.0) * plan.n + 12.0 * H * W  # (16 B/event with weights)
+            format_bytes = bytes_per_event * plan.n + 12.0 * H * W  # what the plan format actually stores per event
+            k_ms = statistics.mean(kernel_ms) if kernel_ms else float("nan")
+            kname = "iwe_slab_accumulate_kernel<DENSE,DYN>" if a.halo == "auto" else "iwe_slab_accumulate_kernel"
+            if not cptrs[0]:  # other instantiations: the committed counters are the compact unit-weight kernel's
+                kname = "iwe_slab_accumulate_kernel<XY" + (",W>" if a.weighted else ">")
+            elif a.weighted:
+                kname = "iwe_slab_accumulate_kernel<W>"
+            roof = roofline_entry(kname, kernel_ms, algo_bytes,
+                                  {"measured_copy_GBps": round(copy_gbs, 1),
+                                   "frac_of_measured_copy": round(algo_bytes / (k_ms * 1e-3) / 1e9 / copy_gbs, 4),
+                                   "plan_format_bytes": format_bytes,
+                                   "plan_format_GBps": round(format_bytes / (k_ms * 1e-3) / 1e9, 1),
+                                   "step_frac": round(algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
+            if "rotating_windows" in extras:
+                roof["frac_rotating_windows"] = extras["rotating_windows"]["frac"]
+            line["roofline"] = roof
+            clock = device_clock_hz(dev)
+            dyn = a.halo == "auto"
+            line["roofline_issue"] = roofline_issue(kname, kernel_ms, clock, plan.n)
+            if "roofline_bwd" in extras:
+                extras["roofline_bwd_issue"] = roofline_issue("iwe_dense_tiled_bwd_kernel<DENSE,DYN>" if dyn else "iwe_dense_tiled_bwd_kernel",
+                                                              [extras["roofline_bwd"]["kernel_ms"]], clock, plan.n)
+                extras["roofline_bwd"] = lead_with_binding(extras["roofline_bwd"], extras["roofline_bwd_issue"])
+            # the fractions side by side: what each one prices and what it says.  `roofline` leads with the roofline that BINDS (VALU issue /
+            # LDS pipe, from the instruction counters of this kernel source); SURVEY 8(d)'s HBM accounting sits in roofline.hbm_algorithmic
+            hbm_frac, plan_gbs, step_frac = roof["frac"], roof["plan_format_GBps"], roof["step_frac"]
+            roof = line["roofline"] = lead_with_binding(roof, line["roofline_issue"])
+            line["roofline_summary"] = {
+                "hbm_algorithmic_frac": hbm_frac,                           # SURVEY 8(d) bytes (12 B/event + 12 H W) / kernel time / 8 TB/s
+                "hbm_plan_format_frac": round(plan_gbs / HBM_PEAK_GBS, 4),  # the 6 B/event the compact plan really streams
+                "hbm_counter_traffic_frac": (round(roof["traffic"] / (roof["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                             if roof.get("traffic") else None),              # FETCH / WRITE counters of the same source
+                "hbm_step_frac": step_frac,                                 # the WHOLE step (accumulate + combine + finalize) on the same bytes
+                "hbm_rotating_windows_frac": roof.get("frac_rotating_windows"),              # plans cycled beyond the Infinity Cache
+                "issue_frac": line["roofline_issue"].get("frac"),           # what binds: VALU issue / LDS pipe (roofline_issue)
+                "binding": line["roofline_issue"].get("bound", "unknown (no counters for this kernel source)")}
         line["ranks_seen"] = ranks_seen
         line["plan_build_ms"] = round(plan_build_ms, 3)
         line["plan_build_kind"] = "lean (emit='compact': compact events + offsets only)" if plan.lean else "full (SoA + perm + compact)"
@@ -1020,13 +1037,15 @@ def run_config2(R):
         if "rotating_windows" in extras:
             line["value_hbm_streaming"] = extras["rotating_windows"]["mevents_per_s"]
         # the three regimes of one workload, stated where the driver's line names the workload
+        streaming = (format(line["value_hbm_streaming"], ".0f") if "value_hbm_streaming" in line
+                     else "not measured (" + ("--no-extras" if a.full else "bench.py --full") + ")")
         line["config"]["workload"] += (f" | regimes [Mevents/s]: value = window resident from step to step (the CMax loop re-reads one window hundreds "
                                        f"of times) {line['value']:.0f}; value_hbm_streaming = distinct windows cycled beyond the Infinity Cache "
-                                       f"{(format(line['value_hbm_streaming'], '.0f') if 'value_hbm_streaming' in line else 'not measured (--no-extras)')}; value_incl_plan_build = a fresh window, plan build + one step "
+                                       f"{streaming}; value_incl_plan_build = a fresh window, plan build + one step "
                                        f"{line['value_incl_plan_build']:.0f}")
         line["contrast"] = contrast
         line.update(extras)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sample = min(a.cpu_sample, n)
             line["cpu_baseline"] = cpu_baseline(ev, flow_np, sample)
             line["speedup_vs_cpu_port_f64"] = round(value / line["cpu_baseline"]["value"], 1)
@@ -1118,7 +1137,7 @@ def run_config3(R):
     ranks_seen = R.gather({"rank": rank, "local_rank": int(os.environ.get("LOCAL_RANK", rank)), "device": str(dev), "units": 1,
                            "ingest_s": round(ingest_s, 2)})
     extras = {}
-    if not a.no_extras and rank == 0:
+    if a.full and not a.no_extras and rank == 0:
         for _ in range(5):
             step_fwd_bwd()
         torch.cuda.synchronize()
@@ -1144,11 +1163,6 @@ def run_config3(R):
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
         value = world * n * a.steps / elapsed / 1e6
-        # SURVEY 8(d), cost kernels: 4 H W bytes read (+ 4 H W written for the gradient image)
-        roof = roofline_entry("gradmag_fused_kernel", sobel_ms, 8.0 * H * W,
-                              {"note": "the Sobel pass of the step: reads the IWE once, writes the gradient image once (SURVEY 8(d): 4 H W + 4 H W "
-                                       "bytes); the step's event kernels are config 2's (bench.py --config 2 carries their rooflines)",
-                               "step_frac_on_event_bytes": round((12.0 * plan.n + 12.0 * H * W) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
         line = base_line(R, value, ms_per_step, blocks, "weak", {
             "workload": ("BASELINE configs[2]: 10M synthetic events, 1280x720 dense per-pixel flow U(-30,30), gradient-magnitude cost "
                          "(Sobel 3x3 / 8 on the IWE), fwd objective (tile accumulate + slab combine + one Sobel pass)")
@@ -1156,11 +1170,17 @@ def run_config3(R):
             "events_per_gpu": n, "events_in_plan": plan.n, "height": H, "width": W,
             "layout": f"compact SoA (6 B/event), binned by source tile {a.tile[0]}x{a.tile[1]}, halo {a.halo}, splits {a.splits}",
             "parallelism": f"windows sharded, {world} rank(s), no collective"})
-        line["roofline"] = roof
+        if a.full:
+            # SURVEY 8(d), cost kernels: 4 H W bytes read (+ 4 H W written for the gradient image)
+            line["roofline"] = roofline_entry("gradmag_fused_kernel", sobel_ms, 8.0 * H * W,
+                                              {"note": "the Sobel pass of the step: reads the IWE once, writes the gradient image once (SURVEY 8(d): "
+                                                       "4 H W + 4 H W bytes); the step's event kernels are config 2's (bench.py --config 2 --full "
+                                                       "carries their rooflines)",
+                                               "step_frac_on_event_bytes": round((12.0 * plan.n + 12.0 * H * W) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
         line["ranks_seen"] = ranks_seen
         line["contrast"] = contrast
         line.update(extras)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sample = min(a.cpu_sample, n, 2_000_000)
             line["cpu_baseline"] = cpu_baseline_gradmag(ev, flow_np, sample)
             line["speedup_vs_cpu_port_f64"] = round(value / line["cpu_baseline"]["value"], 1)
@@ -1244,6 +1264,7 @@ def run_config4(R):
             torch.cuda.synchronize()
         return statistics.median(enq) * 1e3
 
+    # (what runs before the timed block runs in a plain run too: it is the state the timed block has always started from)
     eager_step()  # (first call: reserves LDS, creates workspaces' state)
     torch.cuda.synchronize()
     eager_enqueue_ms = measure_enqueue(eager_step)
@@ -1282,34 +1303,39 @@ def run_config4(R):
         if not torch.equal(first, got):
             raise SystemExit(f"config 4: batched contrasts differ from the per-window calls: {first[:4].tolist()} vs {got[:4].tolist()}")
         step, graphed = batch_step, False
+
+    def variances():  # what a pass computed: one contrast per window of this rank
+        return torch.cat([bt.variances for bt in batches]) if batches else outs[:len(mine)]
+
     blocks, _ = R.timed_blocks(step, lib, _hip.PROFILE_SLAB_ACCUMULATE, launches_per_step=max(len(mine), 1), profile_blocks=0,
-                               outputs=lambda: {"variance": torch.cat([bt.variances for bt in batches]) if batches else outs[:len(mine)]})
+                               outputs=lambda: {"variance": variances()})
     elapsed = statistics.median(blocks)
-    if graphed and not torch.equal(first, outs[:len(mine)]):
-        raise SystemExit("config 4: the replayed graph's contrasts differ from the eager pass")
-    host_enqueue_ms = measure_enqueue(step)
-    # roofline leg: the kernel timed on ONE stream, back to back (a dispatch that shares the chip with its neighbours' kernels
-    # has no clean begin-to-end time)
-    import ctypes
-    nrec = max(1, min(len(plans), 16))
-    _hip.check(lib.ebos_profile_start_kernel(_hip.PROFILE_SLAB_ACCUMULATE, nrec), "profile")
-    for k, (pl, g) in enumerate(zip(plans[:nrec], grids[:nrec])):
-        _, ws, iwe, moments = lanes[0]
-        _hip.check(lib.ebos_iwe_patch_slab_f32(*pl._compact_ptrs(), P(pl.key_offsets), pl.n, P(g), gh, gw, ph, pw, sh, sw, H, W,
-                                               a.tile[0], a.tile[1], a.halo_code, splits, 0, 0, P(ws), nws, P(iwe), 1, 0,
-                                               outs.data_ptr() + 4 * k, P(moments), P(pl.part_table), stream), "ebos_iwe_patch_slab")
-    torch.cuda.synchronize()
-    buf = (ctypes.c_float * nrec)()
-    got = lib.ebos_profile_stop(buf, nrec)
-    kernel_ms = [buf[i] for i in range(got)]
-    res = {int(wi): float(v) for wi, v in zip(mine, outs[:len(mine)].tolist())}
+    res = {int(wi): float(v) for wi, v in zip(mine, variances().tolist())}
+    kernel_ms = []
+    if a.full:
+        if graphed and not torch.equal(first, outs[:len(mine)]):
+            raise SystemExit("config 4: the replayed graph's contrasts differ from the eager pass")
+        host_enqueue_ms = measure_enqueue(step)
+        # roofline leg: the kernel timed on ONE stream, back to back (a dispatch that shares the chip with its neighbours' kernels
+        # has no clean begin-to-end time)
+        import ctypes
+        nrec = max(1, min(len(plans), 16))
+        _hip.check(lib.ebos_profile_start_kernel(_hip.PROFILE_SLAB_ACCUMULATE, nrec), "profile")
+        for k, (pl, g) in enumerate(zip(plans[:nrec], grids[:nrec])):
+            _, ws, iwe, moments = lanes[0]
+            _hip.check(lib.ebos_iwe_patch_slab_f32(*pl._compact_ptrs(), P(pl.key_offsets), pl.n, P(g), gh, gw, ph, pw, sh, sw, H, W,
+                                                   a.tile[0], a.tile[1], a.halo_code, splits, 0, 0, P(ws), nws, P(iwe), 1, 0,
+                                                   outs.data_ptr() + 4 * k, P(moments), P(pl.part_table), stream), "ebos_iwe_patch_slab")
+        torch.cuda.synchronize()
+        buf = (ctypes.c_float * nrec)()
+        got = lib.ebos_profile_stop(buf, nrec)
+        kernel_ms = [buf[i] for i in range(got)]
     seen = R.gather({"rank": rank, "local_rank": R.local_rank, "device": torch.cuda.get_device_name(dev),
                      "windows": len(mine), "events": int(sum(p.n for p in plans)), "contrasts": res, "ingest_s": round(ingest_s, 2)})
     if rank == 0:
         total_events = n * n_windows
         ms_per_step = elapsed / a.steps * 1e3
         value = total_events * a.steps / elapsed / 1e6
-        algo = 6.0 * n + 4.0 * H * W + 8.0 * gh * gw  # per launch: compact events (6 B) + IWE write + the patch grid (no dense flow field)
         line = base_line(R, value, ms_per_step, blocks, "strong", {
             "workload": (f"BASELINE configs[3]: {n_windows} time windows x {n} events, {gh}x{gw} patch-flow grid "
                          f"(patch {ph}x{pw}, slide {sh}x{sw}) -> 1280x720, variance cost, fwd objective per window"
@@ -1317,14 +1343,16 @@ def run_config4(R):
             "windows_total": n_windows, "events_per_window": n, "height": H, "width": W,
             "layout": f"compact SoA 6 B/event, tile {a.tile[0]}x{a.tile[1]}, halo {a.halo}; flow sampled from the patch grid per tile",
             "parallelism": f"windows round-robin over {world} rank(s) (bos_event.py:144-220), no collective"})
-        dyn = a.halo == "auto"
-        line["roofline_issue"] = roofline_issue("iwe_slab_accumulate_kernel<GRID,DYN>" if dyn else "iwe_slab_accumulate_kernel<GRID>",
-                                                kernel_ms, device_clock_hz(dev), n)
-        line["roofline"] = roofline_entry("iwe_slab_accumulate_kernel<GRID,DYN>" if dyn else "iwe_slab_accumulate_kernel<GRID>", kernel_ms, algo,
-                                          {"note": "kernel timed on one stream, back to back",
-                                           "ms_per_window_in_step": round(ms_per_step / max(len(mine), 1), 5), "streams": n_lanes,
-                                           **survey_priced(12.0 * n + 4.0 * H * W + 8.0 * gh * gw, kernel_ms)})
-        line["roofline"] = lead_with_binding(line["roofline"], line["roofline_issue"])
+        if a.full:
+            algo = 6.0 * n + 4.0 * H * W + 8.0 * gh * gw  # per launch: compact events (6 B) + IWE write + the patch grid (no dense flow field)
+            dyn = a.halo == "auto"
+            line["roofline_issue"] = roofline_issue("iwe_slab_accumulate_kernel<GRID,DYN>" if dyn else "iwe_slab_accumulate_kernel<GRID>",
+                                                    kernel_ms, device_clock_hz(dev), n)
+            line["roofline"] = roofline_entry("iwe_slab_accumulate_kernel<GRID,DYN>" if dyn else "iwe_slab_accumulate_kernel<GRID>", kernel_ms, algo,
+                                              {"note": "kernel timed on one stream, back to back",
+                                               "ms_per_window_in_step": round(ms_per_step / max(len(mine), 1), 5), "streams": n_lanes,
+                                               **survey_priced(12.0 * n + 4.0 * H * W + 8.0 * gh * gw, kernel_ms)})
+            line["roofline"] = lead_with_binding(line["roofline"], line["roofline_issue"])
         line["ranks_seen"] = [{k: v for k, v in s.items() if k != "contrasts"} for s in seen]
         merged = {}
         for s in seen:
@@ -1332,7 +1360,8 @@ def run_config4(R):
         line["windows_evaluated"] = len(merged)
         line["contrast_first_windows"] = [merged[k] for k in sorted(merged)[:4]]
         line["ingest_s_this_rank"] = round(ingest_s, 2)
-        line["host_enqueue_ms_per_step"] = round(host_enqueue_ms, 4)
+        if a.full:
+            line["host_enqueue_ms_per_step"] = round(host_enqueue_ms, 4)
         line["pass_is_a_replayed_hip_graph"] = graphed
         line["windows_per_launch"] = min(a.batch, 16) if batches else 1
         line["host_enqueue_ms_per_step_eager"] = round(eager_enqueue_ms, 4)
@@ -1374,18 +1403,20 @@ def run_config5(R):
                                outputs=lambda: {"variance": res["v"]})
     elapsed = statistics.median(blocks)
     v = res["v"].cpu().numpy()
-    # roofline leg: the timed sweep keeps three hypotheses in flight on three streams, where a dispatch's begin-to-end time
-    # includes the time it shares the chip with its neighbours; the kernel is therefore timed on ONE stream, back to back
-    import ctypes
-    # (the accumulate pass is one PERSISTENT launch per chunk of 16 hypotheses: its time is quoted per hypothesis)
-    nrec = min(len(mine), 64)
-    _hip.check(lib.ebos_profile_start_kernel(_hip.PROFILE_SLAB_ACCUMULATE, nrec), "profile")
-    plan.variance_2dof(th[:nrec], chunk=16, halo=a.halo, n_streams=1)
-    torch.cuda.synchronize()
-    buf = (ctypes.c_float * nrec)()
-    got = lib.ebos_profile_stop(buf, nrec)
-    sizes = [min(16, nrec - k0) for k0 in range(0, nrec, 16)]
-    kernel_ms = [buf[i] / sizes[i] for i in range(min(got, len(sizes)))]
+    kernel_ms = []
+    if a.full:
+        # roofline leg: the timed sweep keeps three hypotheses in flight on three streams, where a dispatch's begin-to-end time
+        # includes the time it shares the chip with its neighbours; the kernel is therefore timed on ONE stream, back to back
+        import ctypes
+        # (the accumulate pass is one PERSISTENT launch per chunk of 16 hypotheses: its time is quoted per hypothesis)
+        nrec = min(len(mine), 64)
+        _hip.check(lib.ebos_profile_start_kernel(_hip.PROFILE_SLAB_ACCUMULATE, nrec), "profile")
+        plan.variance_2dof(th[:nrec], chunk=16, halo=a.halo, n_streams=1)
+        torch.cuda.synchronize()
+        buf = (ctypes.c_float * nrec)()
+        got = lib.ebos_profile_stop(buf, nrec)
+        sizes = [min(16, nrec - k0) for k0 in range(0, nrec, 16)]
+        kernel_ms = [buf[i] / sizes[i] for i in range(min(got, len(sizes)))]
     seen = R.gather({"rank": rank, "local_rank": R.local_rank, "device": torch.cuda.get_device_name(dev),
                      "hypotheses": len(mine), "events": plan.n, "ingest_s": round(ingest_s, 2),
                      "variances": {int(k): float(x) for k, x in zip(mine, v)}})
@@ -1393,7 +1424,6 @@ def run_config5(R):
         K = grid.shape[0]
         ms_per_step = elapsed / a.steps * 1e3
         value = float(n) * K * a.steps / elapsed / 1e6  # event-warps per second, whole job
-        algo = 6.0 * plan.n + 4.0 * H * W  # per hypothesis launch: compact events (6 B) + IWE write (theta is two floats)
         line = base_line(R, value, ms_per_step, blocks, "strong", {
             "workload": f"BASELINE configs[4]: {K}-hypothesis 2-DoF flow sweep ({g0}x{g1} grid over [-{tm:g},{tm:g})^2) over {n} events, "
                         "1280x720, variance cost per hypothesis",
@@ -1401,26 +1431,28 @@ def run_config5(R):
             "layout": f"compact SoA 6 B/event, tile {a.tile[0]}x{a.tile[1]}, halo {a.halo}; event window replicated per rank",
             "parallelism": f"hypotheses in contiguous blocks over {world} rank(s) (generative_max_likelihood.py:229-236), no collective"})
         line["unit_note"] = "Mevents/s counts event-warps: every hypothesis warps and splats every event"
-        dyn = a.halo == "auto"
-        key5 = "iwe_slab_accumulate_batch_kernel<UNIFORM,DYN>" if dyn else "iwe_slab_accumulate_batch_kernel<UNIFORM>"
-        line["roofline"] = roofline_entry(key5, kernel_ms, algo,
-                                          {"note": "the persistent accumulate pass (one launch per 16 hypotheses) timed on one stream, per hypothesis "
-                                                   "(the timed sweep overlaps three streams)",
-                                           "ms_per_hypothesis_in_sweep": round(ms_per_step / max(len(mine), 1), 5),
-                                           **survey_priced(12.0 * plan.n + 4.0 * H * W, kernel_ms)})
-        # SURVEY 8(d) prices config 5 per pass of K hypotheses: 16 B/event ONCE per K + 4 H W K B of images.  The tile-private path
-        # re-streams the plan once per hypothesis; on that accounting (K = 64, one rank's block of the 8-GPU job) it moves
-        k_pass = 64
-        per_pass = 16.0 * plan.n + 4.0 * H * W * k_pass
-        k_ms_mean = statistics.mean(kernel_ms) if kernel_ms else float("nan")
-        line["roofline"]["per_pass_of_K"] = {"K": k_pass, "algorithmic_bytes_per_pass": per_pass,
-                                             "achieved": round(per_pass / (k_pass * k_ms_mean * 1e-3) / 1e9, 1),
-                                             "frac": round(per_pass / (k_pass * k_ms_mean * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                             "note": "SURVEY 8(d): 16 B/event per pass of K hypotheses + 4 H W K; the kernel is instruction-bound "
-                                                     "(roofline_issue), K hypotheses per event read would save the shared decode only: "
-                                                     "profiles/r03_multi_hypothesis_ablation.txt"}
-        line["roofline_issue"] = roofline_issue(key5, kernel_ms, device_clock_hz(dev), plan.n)
-        line["roofline"] = lead_with_binding(line["roofline"], line["roofline_issue"])
+        if a.full:
+            algo = 6.0 * plan.n + 4.0 * H * W  # per hypothesis launch: compact events (6 B) + IWE write (theta is two floats)
+            dyn = a.halo == "auto"
+            key5 = "iwe_slab_accumulate_batch_kernel<UNIFORM,DYN>" if dyn else "iwe_slab_accumulate_batch_kernel<UNIFORM>"
+            line["roofline"] = roofline_entry(key5, kernel_ms, algo,
+                                              {"note": "the persistent accumulate pass (one launch per 16 hypotheses) timed on one stream, per hypothesis "
+                                                       "(the timed sweep overlaps three streams)",
+                                               "ms_per_hypothesis_in_sweep": round(ms_per_step / max(len(mine), 1), 5),
+                                               **survey_priced(12.0 * plan.n + 4.0 * H * W, kernel_ms)})
+            # SURVEY 8(d) prices config 5 per pass of K hypotheses: 16 B/event ONCE per K + 4 H W K B of images.  The tile-private path
+            # re-streams the plan once per hypothesis; on that accounting (K = 64, one rank's block of the 8-GPU job) it moves
+            k_pass = 64
+            per_pass = 16.0 * plan.n + 4.0 * H * W * k_pass
+            k_ms_mean = statistics.mean(kernel_ms) if kernel_ms else float("nan")
+            line["roofline"]["per_pass_of_K"] = {"K": k_pass, "algorithmic_bytes_per_pass": per_pass,
+                                                 "achieved": round(per_pass / (k_pass * k_ms_mean * 1e-3) / 1e9, 1),
+                                                 "frac": round(per_pass / (k_pass * k_ms_mean * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                                 "note": "SURVEY 8(d): 16 B/event per pass of K hypotheses + 4 H W K; the kernel is instruction-bound "
+                                                         "(roofline_issue), K hypotheses per event read would save the shared decode only: "
+                                                         "profiles/r03_multi_hypothesis_ablation.txt"}
+            line["roofline_issue"] = roofline_issue(key5, kernel_ms, device_clock_hz(dev), plan.n)
+            line["roofline"] = lead_with_binding(line["roofline"], line["roofline_issue"])
         line["ranks_seen"] = [{k: x for k, x in s.items() if k != "variances"} for s in seen]
         merged = {}
         for s in seen:

@@ -153,7 +153,7 @@ CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.gpu
 def test_bench_line_contract_single_gpu():
-    line = _bench("--steps", "20", "--warmup", "5", "--min-seconds", "0.05", "--events", "400000", "--cpu-sample", "400000",
+    line = _bench("--full", "--steps", "20", "--warmup", "5", "--min-seconds", "0.05", "--events", "400000", "--cpu-sample", "400000",
                   "--rotating-windows", "2")
     for k in CONTRACT + ("cpu_baseline", "roofline_bwd", "rotating_windows", "contrast_cpu", "contrast_rel_err", "value_incl_plan_build",
                          "repeats", "ranks_seen", "plan_build_ms"):
@@ -184,6 +184,32 @@ def test_bench_line_contract_single_gpu():
     assert line["contrast_rel_err"] < 1e-5                      # GPU variance == the CPU baseline leg's own result
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] >= 1
     assert line["repeats"] >= 1 and line["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config,flags", [(2, ["--events", "400000"]), (4, ["--windows", "4", "--events", "200000"])])
+def test_bench_plain_run_is_the_headline_of_the_full_one(config, flags, tmp_path):
+    """A plain run prints the headline (no rooflines, legs or CPU baseline: those are --full's) and its timed steps compute what
+    the same steps of a --full run compute, array for array."""
+    common = ("--config", str(config), "--steps", "3", "--warmup", "1", *flags)
+    plain = _bench(*common, "--dump-outputs", str(tmp_path / "plain"))
+    full = _bench(*common, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    for k in CONTRACT:
+        assert k in full, k
+        assert (k in plain) == (k != "roofline"), k
+    for k in ("cpu_baseline", "roofline_issue", "rotating_windows", "solver_iteration", "host_enqueue_ms_per_step"):
+        assert k not in plain, k
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype", "scaling", "n_gpus"):
+        assert plain[k] == full[k], k
+    names = sorted(os.listdir(tmp_path / "full"))
+    assert names and sorted(os.listdir(tmp_path / "plain")) == names
+    for name in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name), err_msg=name)
+    if config == 2:
+        assert plain["contrast"] == full["contrast"]
+    else:
+        assert plain["contrast_first_windows"] == full["contrast_first_windows"] and plain["windows_evaluated"] == 4
 
 
 @pytest.mark.gpu
@@ -258,7 +284,7 @@ def test_two_ranks_on_one_gpu_time_no_collective():
 def test_bench_line_of_the_other_configs_single_gpu(config, flags):
     """`bench.py --config 3 | 4 | 5` on one GPU prints the contract's line too (a regression of round 6: config 3's line referred to a
     field only config 2's carries and died after its timed region -- no test ran it)."""
-    line = _bench("--config", str(config), "--steps", "2", "--warmup", "1", "--min-seconds", "0.01", *flags)
+    line = _bench("--full", "--config", str(config), "--steps", "2", "--warmup", "1", "--min-seconds", "0.01", *flags)
     for k in CONTRACT:
         assert k in line, k
     assert line["n_gpus"] == 1 and line["value"] > 0 and "workload" in line["config"]

@@ -15,7 +15,7 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 "$ROOT/bench.py" --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/prof_bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/prof_bench.err"
 PASSES=("FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU")
 i=0
 for P in "${PASSES[@]}"; do
@@ -52,14 +52,14 @@ if [ $? -ne 0 ]; then
 fi
 cp "$OUT/pmc.json" profiles/pmc_latest.json
 cp "$OUT/kernel_stats.json" profiles/kernel_stats_latest.json
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python bench.py --config 3 > "$OUT/bench_config3.json" 2> "$OUT/bench_config3.err"
-python bench.py --fractional --no-cpu-baseline > "$OUT/bench_fractional.json" 2> "$OUT/bench_fractional.err"
-python bench.py --weighted --no-cpu-baseline > "$OUT/bench_weighted.json" 2> "$OUT/bench_weighted.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full --config 3 > "$OUT/bench_config3.json" 2> "$OUT/bench_config3.err"
+python bench.py --full --fractional --no-cpu-baseline > "$OUT/bench_fractional.json" 2> "$OUT/bench_fractional.err"
+python bench.py --full --weighted --no-cpu-baseline > "$OUT/bench_weighted.json" 2> "$OUT/bench_weighted.err"
 python tools/bench_autograd.py > "$OUT/autograd_path.json" 2> "$OUT/autograd_path.err"
-python bench.py --config 4 > "$OUT/bench_config4.json" 2> "$OUT/bench_config4.err"
-python bench.py --config 5 > "$OUT/bench_config5.json" 2> "$OUT/bench_config5.err"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"   # the driver's form
+python bench.py --full --config 4 > "$OUT/bench_config4.json" 2> "$OUT/bench_config4.err"
+python bench.py --full --config 5 > "$OUT/bench_config5.json" 2> "$OUT/bench_config5.err"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"   # the short form: 20 steps after 5 warm-up steps
 # keep the merge small: drop the per-dispatch traces
 find "$OUT" -name "*kernel_trace.csv" -delete; find "$OUT" -name "*counter_collection.csv" -delete; find "$OUT" -name "*agent_info.csv" -delete
 head -12 "$OUT/kernel_stats_bench.csv" | cut -c1-200

@@ -14,7 +14,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "event_based_bos_amd", "csrc", "iwe_tile_core.h")
 data = open(SRC, "rb").read()
-out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline (tools/collect_round_profiles.sh)",
+out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline (tools/collect_round_profiles.sh)",
        "source_blob_sha": hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest(),
        "commit": sys.argv[3] if len(sys.argv) > 3 else None, "kernels": {}}
 for r in csv.DictReader(open(sys.argv[1])):

@@ -18,8 +18,8 @@ for S in f64 raw; do EBOS_HIP_LIBRARY=$PWD/event_based_bos_amd/lib/libebos_lean_
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$O/prof_plan -- python3 /root/repo/tools/bench_plan_build.py > /dev/null 2> /root/repo/$O/prof_plan.err)
 find $O/prof_plan -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/plan_build_kernel_stats.csv; rm -rf $O/prof_plan
 for F in 2 6; do
-  python bench.py --flow-max $F --halo auto --no-cpu-baseline --no-extras > $O/bench_config2_flow$F.json 2> $O/e2_$F.err
-  python bench.py --config 4 --flow-max $F --halo auto > $O/bench_config4_flow$F.json 2> $O/e4_$F.err
+  python bench.py --full --flow-max $F --halo auto --no-cpu-baseline --no-extras > $O/bench_config2_flow$F.json 2> $O/e2_$F.err
+  python bench.py --full --config 4 --flow-max $F --halo auto > $O/bench_config4_flow$F.json 2> $O/e4_$F.err
 done
 timeout 3000 python -m pytest tests -q -m gpu > $O/tests.log 2>&1; tail -4 $O/tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -3 $O/smoke.txt
