@@ -22,6 +22,7 @@ GAUSS_REFLECT_SCIPY, GAUSS_REFLECT_TORCH = 0, 1
 PROFILE_SLAB_ACCUMULATE, PROFILE_TILED_BWD, PROFILE_SLAB_COMBINE, PROFILE_GRADMAG_FUSED = 0, 1, 2, 3
 ABI_VERSION = 2
 GML_NO_POLARITY, GML_EVENT_WEIGHTS = 1, 2   # flags of ebos_gml_objective_f64 / ebos_gml_solve_scale_f64
+GML_VELOCITY = 4                            # ebos_gml_dep_*: the direct-velocity model
 
 
 
@@ -222,6 +223,11 @@ SIGNATURES = {
     "ebos_gml_objective_f64": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ebos_gml_solve_scale_f64": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _Z,
                                       _P]),
+    "ebos_gml_dep_scratch_bytes": (_Z, [_I] * 10),
+    "ebos_gml_dep_select": (_I, [_I, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _D, _P, _P, _P, _Z, _P]),
+    "ebos_gml_dep_init_f64": (_I, [_I, _I, _I, _P, _P, _P, _P]),
+    "ebos_gml_dep_objective_f64": (_I, [_I] * 10 + [_P, _P, _I] + [_P] * 10 + [_Z, _P]),
+    "ebos_gml_dep_solve_f64": (_I, [_I] * 10 + [_P, _P, _I] + [_P] * 7 + [_I, _D, _P, _P, _P, _Z, _P]),
 }
 
 

@@ -24,6 +24,11 @@
 //   gml_pass_e    per grid cell: the upsample's adjoint, a gather over the pixels the cell reaches (fixed order)
 //   gml_adam      per grid cell: the Sobel adjoint of dS -> dx0, then torch.optim.Adam's update (or, for the objective
 //                 entry, the gradient written out)
+//
+// The single-scale solver, patch_eklt_dependent (src/solver/patch_eklt_dependent.py; ebos_gml_dep_*), runs the same passes on the
+// ROI crop as the whole extent (M = 1, the upsample offset shifted by the crop's origin), over a grid of patch p and slide s (pad
+// k = p / (2s) + 1), with the direct-velocity model as an option (F = up(x[0:2]): no Sobel), a per-cell selection that zeroes
+// the gradient of cells without parameters, and pass E as one thread per cell for small slides (gml_pass_e_cell).
 #pragma clang fp contract(off)
 
 #include <math.h>
@@ -39,8 +44,12 @@ constexpr int kGmlMaxPartA = 512;   // pass-A workgroups (at most)
 constexpr int kGmlScalars = 8;      // N, S, ...
 
 struct GmlGeom {
-  int H, W, p, gh, gw, off_r, off_c;
-  int xmin, xmax, ymin, ymax;       // ROI rows [xmin, xmax), columns [ymin, ymax)
+  int H, W;                         // the objective's extent: the image (pyramid) or the ROI crop (dependent)
+  int s, k, gh, gw, off_r, off_c;   // slide, replicate pad (cells), grid, upsample offset of pixel (0, 0) (the crop's origin included)
+  int xmin, xmax, ymin, ymax;       // ROI rows [xmin, xmax), columns [ymin, ymax) of the extent (the mask M)
+  int nd, t0;                       // parameter channels; first warp channel (p_x, p_y = x[t0], x[t0 + 1])
+  int vel;                          // 1: F = up(x[0:2]) (direct velocity); 0: F = up(Sobel3(x0) / 8)
+  int e_cell;                       // pass E: one thread per grid cell (small slides) instead of one workgroup per cell
   int warp, no_pol, has_we;
   int nbA;                          // pass-A workgroups
   int rbB;                          // pass-B row blocks
@@ -60,6 +69,7 @@ struct GmlBufs {
   double *scal;                     // [kGmlScalars]
   double *gS, *gX;                  // [2, gh, gw] each: d/dS, d/dx[1:3]
   double *m, *v;                    // Adam state [nd, gh, gw]
+  const int* sel;                   // [gh, gw]: 0 = the cell has no parameters (its gradient is zero), NULL = every cell
 };
 
 __host__ __device__ inline int64_t gml_npix(const GmlGeom& g) { return (int64_t)g.H * g.W; }
@@ -86,34 +96,35 @@ GmlLayout gml_layout(int H, int W, int G) {
   L.scal = o; o += gml_align(kGmlScalars * d);
   L.gS = o; o += gml_align(2 * (size_t)G * d);
   L.gX = o; o += gml_align(2 * (size_t)G * d);
-  L.m = o; o += gml_align(3 * (size_t)G * d);
-  L.v = o; o += gml_align(3 * (size_t)G * d);
+  L.m = o; o += gml_align(4 * (size_t)G * d);
+  L.v = o; o += gml_align(4 * (size_t)G * d);
   L.total = o;
   return L;
 }
 
 // ---- the patch -> dense upsample: one axis -----------------------------------------------------------------------------
-// upsampled index o = r + off; source coordinate max((o + 0.5) / p - 0.5, 0) on the (g + 2)-cell padded axis; padded cell i
-// is grid cell clamp(i - 1, 0, g - 1).  (torch's upsample_bilinear2d, align_corners=False, scale = 1 / p.)
+// upsampled index o = r + off; source coordinate max((o + 0.5) / s - 0.5, 0) on the (g + 2k)-cell padded axis; padded cell i
+// is grid cell clamp(i - k, 0, g - 1).  (torch's upsample_bilinear2d, align_corners=False, scale = 1 / s.)  The pyramid has
+// s = p, k = 1.
 struct Tap {
   int c0, c1;
   double l0, l1;
 };
 
-__device__ __forceinline__ Tap up_tap(int r, int off, int p, int g) {
-  const double scale = 1.0 / (double)p;
+__device__ __forceinline__ Tap up_tap(int r, int off, int s, int k, int g) {
+  const double scale = 1.0 / (double)s;
   double src = scale * ((double)(r + off) + 0.5) - 0.5;
   if (src < 0.0) src = 0.0;
   int i0 = (int)src;
-  const int padded = g + 2;
+  const int padded = g + 2 * k;
   const int i1 = i0 + ((i0 < padded - 1) ? 1 : 0);
   double l1 = src - (double)i0;
   l1 = l1 < 0.0 ? 0.0 : (l1 > 1.0 ? 1.0 : l1);
   Tap t;
   t.l1 = l1;
   t.l0 = 1.0 - l1;
-  t.c0 = min(max(i0 - 1, 0), g - 1);
-  t.c1 = min(max(i1 - 1, 0), g - 1);
+  t.c0 = min(max(i0 - k, 0), g - 1);
+  t.c1 = min(max(i1 - k, 0), g - 1);
   return t;
 }
 
@@ -129,7 +140,7 @@ __device__ __forceinline__ bool in_roi(const GmlGeom& g, int r, int c) {
 
 // U_ch(r, c) = F_ch(r, c) M(r, c), the flow the image_gradient term sees.
 __device__ __forceinline__ double u_at(const GmlGeom& g, const double* __restrict__ S, int ch, int r, int c) {
-  const Tap tr = up_tap(r, g.off_r, g.p, g.gh), tc = up_tap(c, g.off_c, g.p, g.gw);
+  const Tap tr = up_tap(r, g.off_r, g.s, g.k, g.gh), tc = up_tap(c, g.off_c, g.s, g.k, g.gw);
   const double m = in_roi(g, r, c) ? 1.0 : 0.0;
   return up_eval(S + (size_t)ch * g.gh * g.gw, g.gw, tr, tc) * m;
 }
@@ -240,13 +251,13 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_a(GmlGeom g, GmlBufs B) {
   double acc[3] = {0.0, 0.0, 0.0};   // sum P0^2, image_gradient sum, pxy-norm sum
   for (int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x; k < n; k += (int64_t)g.nbA * kGmlBlock) {
     const int r = (int)(k / g.W), c = (int)(k % g.W);
-    const Tap tr = up_tap(r, g.off_r, g.p, g.gh), tc = up_tap(c, g.off_c, g.p, g.gw);
+    const Tap tr = up_tap(r, g.off_r, g.s, g.k, g.gh), tc = up_tap(c, g.off_c, g.s, g.k, g.gw);
     const double F0 = up_eval(B.S, g.gw, tr, tc), F1 = up_eval(B.S + G, g.gw, tr, tc);
     const double M = in_roi(g, r, c) ? 1.0 : 0.0;
     double wgx, wgy, T0 = 0.0, T1 = 0.0;
     if (g.warp) {
-      T0 = up_eval(B.x + G, g.gw, tr, tc);
-      T1 = up_eval(B.x + 2 * (size_t)G, g.gw, tr, tc);
+      T0 = up_eval(B.x + (size_t)g.t0 * G, g.gw, tr, tc);
+      T1 = up_eval(B.x + (size_t)(g.t0 + 1) * G, g.gw, tr, tc);
       const Warped w = warp_at(g, B.gx, B.gy, r, c, T0, T1);
       wgx = w.gx;
       wgy = w.gy;
@@ -402,7 +413,7 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_d(GmlGeom g, GmlBufs B) {
   if (k >= n) return;
   const int G = g.gh * g.gw;
   const int r = (int)(k / g.W), c = (int)(k % g.W);
-  const Tap tr = up_tap(r, g.off_r, g.p, g.gh), tc = up_tap(c, g.off_c, g.p, g.gw);
+  const Tap tr = up_tap(r, g.off_r, g.s, g.k, g.gh), tc = up_tap(c, g.off_c, g.s, g.k, g.gw);
   const double F0 = up_eval(B.S, g.gw, tr, tc), F1 = up_eval(B.S + G, g.gw, tr, tc);
   const double M = in_roi(g, r, c) ? 1.0 : 0.0;
   const double N = B.scal[0], Ssum = B.scal[1];
@@ -410,8 +421,8 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_d(GmlGeom g, GmlBufs B) {
   double T0 = 0.0, T1 = 0.0;
   Warped w;
   if (g.warp) {
-    T0 = up_eval(B.x + G, g.gw, tr, tc);
-    T1 = up_eval(B.x + 2 * (size_t)G, g.gw, tr, tc);
+    T0 = up_eval(B.x + (size_t)g.t0 * G, g.gw, tr, tc);
+    T1 = up_eval(B.x + (size_t)(g.t0 + 1) * G, g.gw, tr, tc);
     w = warp_at(g, B.gx, B.gy, r, c, T0, T1);
   } else {
     w.gx = B.gx[k];
@@ -487,33 +498,28 @@ __device__ __forceinline__ double tap_weight(const Tap& t, int cell) {
 }
 
 // pixel range [lo, hi) along an axis whose up_tap can name grid cell `cell`
-__device__ __forceinline__ void cell_range(int cell, int g, int p, int off, int L, int* lo, int* hi) {
-  const int imin = cell == 0 ? 0 : cell + 1;
-  const int imax = cell == g - 1 ? g + 1 : cell + 1;
-  // padded cell i is read by upsampled o with source coordinate in (i - 1, i + 1): o in ((i - 0.5) p - 0.5, (i + 1.5) p - 0.5)
-  const int olo = (int)floor((imin - 0.5) * p - 0.5);
-  const int ohi = (int)ceil((imax + 1.5) * p - 0.5) + 1;
+__device__ __forceinline__ void cell_range(int cell, int g, int s, int k, int off, int L, int* lo, int* hi) {
+  const int imin = cell == 0 ? 0 : cell + k;
+  const int imax = cell == g - 1 ? g + 2 * k - 1 : cell + k;
+  // padded cell i is read by upsampled o with source coordinate in (i - 1, i + 1): o in ((i - 0.5) s - 0.5, (i + 1.5) s - 0.5)
+  const int olo = (int)floor((imin - 0.5) * s - 0.5);
+  const int ohi = (int)ceil((imax + 1.5) * s - 0.5) + 1;
   *lo = max(olo - off, 0);
   *hi = min(ohi - off, L);
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
-  __shared__ double sh[4][kGmlBlock];
-  const int cell = blockIdx.x;
-  const int gi = cell / g.gw, gj = cell % g.gw;
-  const int G = g.gh * g.gw;
+// the adjoint of the upsample at one cell over the pixel rectangle [r0, r1) x [c0, c1), in row-major order from element e0 with
+// stride `step` (pass E's lane mapping; step 1 = one thread walks the whole rectangle)
+__device__ __forceinline__ void cell_gather(const GmlGeom& g, const GmlBufs& B, int gi, int gj, int r0, int r1, int c0, int c1,
+                                            int64_t e0, int step, double* acc) {
   const int64_t n = gml_npix(g);
-  int r0, r1, c0, c1;
-  cell_range(gi, g.gh, g.p, g.off_r, g.H, &r0, &r1);
-  cell_range(gj, g.gw, g.p, g.off_c, g.W, &c0, &c1);
   const int nc = max(c1 - c0, 0);
   const int64_t cnt = (int64_t)max(r1 - r0, 0) * nc;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t e = threadIdx.x; e < cnt; e += kGmlBlock) {
+  for (int64_t e = e0; e < cnt; e += step) {
     const int r = r0 + (int)(e / nc), c = c0 + (int)(e % nc);
-    const double wr = tap_weight(up_tap(r, g.off_r, g.p, g.gh), gi);
+    const double wr = tap_weight(up_tap(r, g.off_r, g.s, g.k, g.gh), gi);
     if (wr == 0.0) continue;
-    const double wc = tap_weight(up_tap(c, g.off_c, g.p, g.gw), gj);
+    const double wc = tap_weight(up_tap(c, g.off_c, g.s, g.k, g.gw), gj);
     if (wc == 0.0) continue;
     const size_t k = (size_t)r * g.W + c;
     const double wgt = wr * wc;
@@ -524,6 +530,18 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
       acc[3] += wgt * B.dT[n + k];
     }
   }
+}
+
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
+  __shared__ double sh[4][kGmlBlock];
+  const int cell = blockIdx.x;
+  const int gi = cell / g.gw, gj = cell % g.gw;
+  const int G = g.gh * g.gw;
+  int r0, r1, c0, c1;
+  cell_range(gi, g.gh, g.s, g.k, g.off_r, g.H, &r0, &r1);
+  cell_range(gj, g.gw, g.s, g.k, g.off_c, g.W, &c0, &c1);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  cell_gather(g, B, gi, gj, r0, r1, c0, c1, threadIdx.x, kGmlBlock, acc);
   block_sum<4>(sh, acc);
   if (threadIdx.x == 0) {
     B.gS[cell] = acc[0];
@@ -531,6 +549,23 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
     B.gX[cell] = acc[2];
     B.gX[G + cell] = acc[3];
   }
+}
+
+// small slides (a cell reaches some (2s + 3)^2 pixels): one thread per cell, its rectangle in row-major order
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_e_cell(GmlGeom g, GmlBufs B) {
+  const int G = g.gh * g.gw;
+  const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
+  if (cell >= G) return;
+  const int gi = cell / g.gw, gj = cell % g.gw;
+  int r0, r1, c0, c1;
+  cell_range(gi, g.gh, g.s, g.k, g.off_r, g.H, &r0, &r1);
+  cell_range(gj, g.gw, g.s, g.k, g.off_c, g.W, &c0, &c1);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  cell_gather(g, B, gi, gj, r0, r1, c0, c1, 0, 1, acc);
+  B.gS[cell] = acc[0];
+  B.gS[G + cell] = acc[1];
+  B.gX[cell] = acc[2];
+  B.gX[G + cell] = acc[3];
 }
 
 // ---- Sobel adjoint + Adam -----------------------------------------------------------------------------------------------------
@@ -541,12 +576,13 @@ struct AdamArgs {
 
 __global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B, AdamArgs a, double* __restrict__ grad_out) {
   const int G = g.gh * g.gw;
-  const int nd = g.warp ? 3 : 1;
   const int k = blockIdx.x * kGmlBlock + threadIdx.x;
-  if (k >= nd * G) return;
+  if (k >= g.nd * G) return;
   const int ch = k / G, cell = k % G;
   double grad;
-  if (ch == 0) {
+  if (g.vel && ch < 2) {
+    grad = B.gS[(size_t)ch * G + cell];
+  } else if (!g.vel && ch == 0) {
     const int u = cell / g.gw, v = cell % g.gw;
     const double KX[3][3] = {{-1.0, -2.0, -1.0}, {0.0, 0.0, 0.0}, {1.0, 2.0, 1.0}};
     const double KY[3][3] = {{-1.0, 0.0, 1.0}, {-2.0, 0.0, 2.0}, {-1.0, 0.0, 1.0}};
@@ -563,8 +599,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B, Adam
       }
     grad = s;
   } else {
-    grad = B.gX[(size_t)(ch - 1) * G + cell];
+    grad = B.gX[(size_t)(ch - g.t0) * G + cell];
   }
+  if (B.sel && B.sel[cell] == 0) grad = 0.0;   // no parameter: from zero state Adam leaves x at exactly 0
   if (!a.step) {
     grad_out[k] = grad;
     return;
@@ -586,7 +623,7 @@ __global__ void __launch_bounds__(kGmlBlock) gml_flow_out(GmlGeom g, const doubl
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= n) return;
   const int r = (int)(k / g.W), c = (int)(k % g.W);
-  const Tap tr = up_tap(r, g.off_r, g.p, g.gh), tc = up_tap(c, g.off_c, g.p, g.gw);
+  const Tap tr = up_tap(r, g.off_r, g.s, g.k, g.gh), tc = up_tap(c, g.off_c, g.s, g.k, g.gw);
   const double M = in_roi(g, r, c) ? 1.0 : 0.0;
   out[k] = up_eval(S, g.gw, tr, tc) * M;
   out[n + k] = up_eval(S + (size_t)g.gh * g.gw, g.gw, tr, tc) * M;
@@ -696,25 +733,24 @@ inline int blocks_for(int64_t n) { return (int)((n + kGmlBlock - 1) / kGmlBlock)
 
 int grid_cells(int L, int p) { return (L + p - 1) / p; }   // len(arange(0, L - p + p, p))
 
-int make_geom(GmlGeom* g, int H, int W, int p, int nd, int xmin, int xmax, int ymin, int ymax, int flags, const double* w,
-              const int* order, int n_terms) {
+// the parts of the geometry both solvers share: extent, ROI mask, channels, flags and cost terms
+int make_geom_common(GmlGeom* g, int H, int W, int nd, int vel, int xmin, int xmax, int ymin, int ymax, int flags, const double* w,
+                     const int* order, int n_terms) {
   EBOS_REQUIRE(H >= 3 && W >= 3 && (int64_t)H * W < ((int64_t)1 << 31), "ebos_gml: bad image size %d x %d", H, W);
-  EBOS_REQUIRE(p >= 1 && (p & (p - 1)) == 0 && p <= 4096, "ebos_gml: patch %d is not a power of two", p);
-  EBOS_REQUIRE(nd == 1 || nd == 3, "ebos_gml: n_dim %d is not 1 or 3", nd);
+  EBOS_REQUIRE(vel ? (nd == 2 || nd == 4) : (nd == 1 || nd == 3), "ebos_gml: n_dim %d does not fit the model", nd);
   EBOS_REQUIRE(0 <= xmin && xmin <= xmax && xmax <= H && 0 <= ymin && ymin <= ymax && ymax <= W, "ebos_gml: bad ROI");
   EBOS_REQUIRE(n_terms >= 0 && n_terms <= 3 && w, "ebos_gml: bad cost terms");
   g->H = H;
   g->W = W;
-  g->p = p;
-  g->gh = grid_cells(H, p);
-  g->gw = grid_cells(W, p);
-  g->off_r = (g->gh + 2) * p / 2 - H / 2;
-  g->off_c = (g->gw + 2) * p / 2 - W / 2;
   g->xmin = xmin;
   g->xmax = xmax;
   g->ymin = ymin;
   g->ymax = ymax;
-  g->warp = nd == 3;
+  g->nd = nd;
+  g->vel = vel;
+  g->t0 = nd - 2;
+  g->e_cell = 0;
+  g->warp = vel ? nd == 4 : nd == 3;
   g->no_pol = (flags & EBOS_GML_NO_POLARITY) != 0;
   g->has_we = (flags & EBOS_GML_EVENT_WEIGHTS) != 0;
   g->nbA = (int)std::min<int64_t>(blocks_for((int64_t)H * W), kGmlMaxPartA);
@@ -727,6 +763,72 @@ int make_geom(GmlGeom* g, int H, int W, int p, int nd, int xmin, int xmax, int y
   for (int i = 0; i < n_terms; ++i) EBOS_REQUIRE(order[i] >= 0 && order[i] <= 2, "ebos_gml: bad term index %d", order[i]);
   EBOS_REQUIRE(!(g->w_fn != 0.0 && !g->warp), "ebos_gml: flow_norm_pxy needs optimize_warp");
   return EBOS_OK;
+}
+
+// the pyramid: patch = slide = p (a power of two), pad 1, the whole image with the ROI as a mask
+int make_geom(GmlGeom* g, int H, int W, int p, int nd, int xmin, int xmax, int ymin, int ymax, int flags, const double* w,
+              const int* order, int n_terms) {
+  EBOS_REQUIRE(p >= 1 && (p & (p - 1)) == 0 && p <= 4096, "ebos_gml: patch %d is not a power of two", p);
+  int rc = make_geom_common(g, H, W, nd, 0, xmin, xmax, ymin, ymax, flags, w, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  g->s = p;
+  g->k = 1;
+  g->gh = grid_cells(H, p);
+  g->gw = grid_cells(W, p);
+  g->off_r = (g->gh + 2) * p / 2 - H / 2;
+  g->off_c = (g->gw + 2) * p / 2 - W / 2;
+  return EBOS_OK;
+}
+
+// ---- patch_eklt_dependent: patch p, slide s, the objective on the ROI crop ------------------------------------------------------
+// Grid len(arange(0, L - p + s, s)) per axis, pad k = int(p / 2 // s) + 1, upsample to (g + 2k) s, centre crop at
+// h1 = (g + 2k) s // 2 - L // 2 (prepare_patch, interpolate_dense_flow_from_patch_tensor).
+struct DepAxis {
+  int g, k, off;
+};
+
+int dep_axis(int L, int p, int s, DepAxis* a) {
+  EBOS_REQUIRE(p >= 1 && s >= 1 && p <= L && s <= 4096 && p <= 4096, "ebos_gml_dep: patch %d / slide %d do not fit %d", p, s, L);
+  a->g = (L - p + s + s - 1) / s;
+  a->k = p / (2 * s) + 1;
+  const int up = (a->g + 2 * a->k) * s;
+  a->off = up / 2 - L / 2;
+  EBOS_REQUIRE(a->off >= 0 && a->off + L <= up, "ebos_gml_dep: the centre crop leaves the upsampled canvas (%d of %d)", L, up);
+  return EBOS_OK;
+}
+
+// the objective's geometry: the crop [xmin, xmax) x [ymin, ymax) is the whole extent (M = 1), offsets shifted by its origin
+int make_dep_geom(GmlGeom* g, int H, int W, int p, int s, int nd, int xmin, int xmax, int ymin, int ymax, int flags, const double* w,
+                  const int* order, int n_terms) {
+  EBOS_REQUIRE(0 <= xmin && xmin <= xmax && xmax <= H && 0 <= ymin && ymin <= ymax && ymax <= W, "ebos_gml_dep: bad ROI");
+  DepAxis ar, ac;
+  int rc;
+  if ((rc = dep_axis(H, p, s, &ar)) != EBOS_OK || (rc = dep_axis(W, p, s, &ac)) != EBOS_OK) return rc;
+  const int h = xmax - xmin, wd = ymax - ymin;
+  rc = make_geom_common(g, h, wd, nd, (flags & EBOS_GML_VELOCITY) != 0, 0, h, 0, wd, flags, w, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  g->s = s;
+  g->k = ar.k;   // ar.k == ac.k: one patch and slide for both axes
+  g->gh = ar.g;
+  g->gw = ac.g;
+  g->off_r = ar.off + xmin;
+  g->off_c = ac.off + ymin;
+  g->e_cell = s <= 8;
+  return EBOS_OK;
+}
+
+// the output's geometry: the full image, unmasked
+GmlGeom dep_out_geom(const GmlGeom& g, int H, int W, int xmin, int ymin) {
+  GmlGeom o = g;
+  o.H = H;
+  o.W = W;
+  o.xmin = 0;
+  o.xmax = H;
+  o.ymin = 0;
+  o.ymax = W;
+  o.off_r = g.off_r - xmin;
+  o.off_c = g.off_c - ymin;
+  return o;
 }
 
 GmlBufs make_bufs(const GmlLayout& L, char* s, const double* gx, const double* gy, const double* q, const double* we, const double* winv,
@@ -750,6 +852,7 @@ GmlBufs make_bufs(const GmlLayout& L, char* s, const double* gx, const double* g
   b.gX = reinterpret_cast<double*>(s + L.gX);
   b.m = reinterpret_cast<double*>(s + L.m);
   b.v = reinterpret_cast<double*>(s + L.v);
+  b.sel = nullptr;
   return b;
 }
 
@@ -757,13 +860,143 @@ GmlBufs make_bufs(const GmlLayout& L, char* s, const double* gx, const double* g
 int gml_forward_backward(const GmlGeom& g, const GmlBufs& B, double* hist_row, hipStream_t st) {
   const int G = g.gh * g.gw;
   const int64_t n = gml_npix(g);
-  hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B.x, B.S);
+  if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B.x, B.S);
   hipLaunchKernelGGL(gml_pass_a, dim3(g.nbA), dim3(kGmlBlock), 0, st, g, B);
   hipLaunchKernelGGL(gml_pass_b, dim3((g.W + kGmlBlock - 1) / kGmlBlock, g.rbB), dim3(kGmlBlock), 0, st, g, B);
   hipLaunchKernelGGL(gml_pass_c, dim3(1), dim3(kGmlBlock), 0, st, g, B, hist_row);
   hipLaunchKernelGGL(gml_pass_d, dim3(blocks_for(n)), dim3(kGmlBlock), 0, st, g, B);
-  hipLaunchKernelGGL(gml_pass_e, dim3(G), dim3(kGmlBlock), 0, st, g, B);
+  if (g.e_cell)
+    hipLaunchKernelGGL(gml_pass_e_cell, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B);
+  else
+    hipLaunchKernelGGL(gml_pass_e, dim3(G), dim3(kGmlBlock), 0, st, g, B);
   EBOS_CHECK_LAUNCH("ebos_gml passes");
+  return EBOS_OK;
+}
+
+// ---- patch_eklt_dependent: the crop, the selection, the initial parameters ---------------------------------------------------
+// dst[h, w] = src[xmin + r, ymin + c] of a [., W] plane
+__global__ void __launch_bounds__(kGmlBlock) gml_crop(int W, int xmin, int ymin, int h, int w, const double* __restrict__ src,
+                                                       double* __restrict__ dst) {
+  const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
+  if (k >= (int64_t)h * w) return;
+  const int r = (int)(k / w), c = (int)(k % w);
+  dst[k] = src[(size_t)(xmin + r) * W + (ymin + c)];
+}
+
+// events [n, 4] (x = row, y = column, t, p) binned by (floor(x), floor(y)) into the (hc + 1) x (wc + 1) count canvas, offset by
+// one row and one column (row 0 and column 0 stay 0 for the summed-area table); events off the canvas are not counted
+__global__ void __launch_bounds__(kGmlBlock) gml_count_events(int64_t n, const double* __restrict__ ev, int hc, int wc,
+                                                               int* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
+  if (i >= n) return;
+  const double fx = floor(ev[4 * i]), fy = floor(ev[4 * i + 1]);
+  if (!(fx >= 0.0 && fx < (double)hc && fy >= 0.0 && fy < (double)wc)) return;
+  atomicAdd(cnt + (size_t)((int)fx + 1) * (wc + 1) + ((int)fy + 1), 1);   // integer counts: the same in any order
+}
+
+// summed-area table in place: prefix sums along each row, then along each column (one thread per row / column)
+__global__ void __launch_bounds__(kGmlBlock) gml_scan_rows(int hc, int wc, int* __restrict__ cnt) {
+  const int r = blockIdx.x * kGmlBlock + threadIdx.x + 1;
+  if (r > hc) return;
+  int* row = cnt + (size_t)r * (wc + 1);
+  for (int c = 1; c <= wc; ++c) row[c] += row[c - 1];
+}
+
+__global__ void __launch_bounds__(kGmlBlock) gml_scan_cols(int hc, int wc, int* __restrict__ cnt) {
+  const int c = blockIdx.x * kGmlBlock + threadIdx.x + 1;
+  if (c > wc) return;
+  for (int r = 1; r <= hc; ++r) cnt[(size_t)r * (wc + 1) + c] += cnt[(size_t)(r - 1) * (wc + 1) + c];
+}
+
+// flag[cell] = the cell's centre lies in the ROI (row_box / col_box [g, 3]: box start, box end, in-ROI) and, when thresholding,
+// its event box [x0, x1) x [y0, y1) holds more than `thres` events
+__global__ void __launch_bounds__(kGmlBlock) gml_select(int gh, int gw, const int* __restrict__ row_box, const int* __restrict__ col_box,
+                                                         const int* __restrict__ sat, int hc, int wc, int thresholding, double thres,
+                                                         int* __restrict__ flag) {
+  const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
+  if (cell >= gh * gw) return;
+  const int i = cell / gw, j = cell % gw;
+  int ok = row_box[3 * i + 2] && col_box[3 * j + 2];
+  if (ok && thresholding) {
+    const int x0 = min(max(row_box[3 * i], 0), hc), x1 = min(max(row_box[3 * i + 1], x0), hc);
+    const int y0 = min(max(col_box[3 * j], 0), wc), y1 = min(max(col_box[3 * j + 1], y0), wc);
+    const int ld = wc + 1;
+    const int c = sat[(size_t)x1 * ld + y1] - sat[(size_t)x0 * ld + y1] - sat[(size_t)x1 * ld + y0] + sat[(size_t)x0 * ld + y0];
+    ok = (double)c > thres;
+  }
+  flag[cell] = ok;
+}
+
+// one workgroup: sel[cell] = 1 + the cell's rank among the selected cells in row-major order (0 = not selected); count[0] = their
+// number.  A block-wide inclusive scan per 256-cell chunk.
+__global__ void __launch_bounds__(kGmlBlock) gml_rank(int G, int* __restrict__ sel, int* __restrict__ count) {
+  __shared__ int sh[kGmlBlock];
+  const int t = threadIdx.x;
+  int base = 0;
+  for (int c0 = 0; c0 < G; c0 += kGmlBlock) {
+    const int cell = c0 + t;
+    const int f = cell < G ? (sel[cell] != 0) : 0;
+    sh[t] = f;
+    __syncthreads();
+    for (int o = 1; o < kGmlBlock; o <<= 1) {
+      const int v = t >= o ? sh[t - o] : 0;
+      __syncthreads();
+      sh[t] += v;
+      __syncthreads();
+    }
+    if (cell < G) sel[cell] = f ? base + sh[t] : 0;
+    base += sh[kGmlBlock - 1];
+    __syncthreads();
+  }
+  if (t == 0) count[0] = base;
+}
+
+// x [nd, gh, gw] = 0, and x[0] = draws[rank] on the selected cells when draws is not NULL (the Poisson model's potentials)
+__global__ void __launch_bounds__(kGmlBlock) gml_dep_init(int G, int nd, const int* __restrict__ sel, const double* __restrict__ draws,
+                                                           double* __restrict__ x) {
+  const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
+  if (cell >= G) return;
+  for (int ch = 0; ch < nd; ++ch) x[(size_t)ch * G + cell] = 0.0;
+  if (draws && sel[cell] != 0) x[cell] = draws[sel[cell] - 1];
+}
+
+// scratch of the dependent solver: the five crop planes, then the iteration layout
+struct DepLayout {
+  size_t gx, gy, q, we, winv, iter, total;
+  GmlLayout L;
+};
+
+DepLayout dep_layout(int h, int w, int G) {
+  const size_t plane = gml_align((size_t)h * w * sizeof(double));
+  DepLayout D;
+  D.gx = 0;
+  D.gy = plane;
+  D.q = 2 * plane;
+  D.we = 3 * plane;
+  D.winv = 4 * plane;
+  D.iter = 5 * plane;
+  D.L = gml_layout(h, w, G);
+  D.total = D.iter + D.L.total;
+  return D;
+}
+
+// crop the five fields into the scratch and divide the cropped measurement by its own norm; -> the iteration buffers
+int dep_bufs(const GmlGeom& g, int W, int xmin, int ymin, const DepLayout& D, char* s, const double* gx, const double* gy, const double* q,
+             const double* we, const double* winv, double* x, const int* sel, hipStream_t st, GmlBufs* out) {
+  const int64_t n = gml_npix(g);
+  const int nb = blocks_for(n);
+  double* c[5] = {reinterpret_cast<double*>(s + D.gx), reinterpret_cast<double*>(s + D.gy), reinterpret_cast<double*>(s + D.q),
+                  reinterpret_cast<double*>(s + D.we), reinterpret_cast<double*>(s + D.winv)};
+  const double* src[5] = {gx, gy, q, we, winv};
+  for (int i = 0; i < 5; ++i)
+    if (src[i]) hipLaunchKernelGGL(gml_crop, dim3(nb), dim3(kGmlBlock), 0, st, W, xmin, ymin, g.H, g.W, src[i], c[i]);
+  GmlBufs B = make_bufs(D.L, s + D.iter, c[0], c[1], c[2], we ? c[3] : nullptr, c[4], x);
+  hipLaunchKernelGGL(gml_reduce, dim3(1), dim3(kGmlBlock), 0, st, n, c[2], 0, B.scal + 2);
+  hipLaunchKernelGGL(gml_scale_by, dim3(nb), dim3(kGmlBlock), 0, st, n, c[2], B.scal + 2);
+  EBOS_CHECK_LAUNCH("ebos_gml_dep: crop");
+  if (g.vel) B.S = x;   // F = up(x[0:2])
+  B.sel = sel;
+  *out = B;
   return EBOS_OK;
 }
 
@@ -907,6 +1140,142 @@ int ebos_gml_solve_scale_f64(int H, int W, int patch, int n_dim, int xmin, int x
     hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B.x, B.S);
     hipLaunchKernelGGL(gml_flow_out, dim3(blocks_for(gml_npix(g))), dim3(kGmlBlock), 0, st, g, B.S, flow_out);
     EBOS_CHECK_LAUNCH("ebos_gml_solve_scale_f64: flow");
+  }
+  return EBOS_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t ebos_gml_dep_scratch_bytes(int H, int W, int patch, int slide, int xmin, int xmax, int ymin, int ymax, int canvas_h, int canvas_w) {
+  using namespace ebos;
+  DepAxis ar, ac;
+  if (H < 3 || W < 3 || dep_axis(H, patch, slide, &ar) != EBOS_OK || dep_axis(W, patch, slide, &ac) != EBOS_OK) return 0;
+  if (!(0 <= xmin && xmin <= xmax && xmax <= H && 0 <= ymin && ymin <= ymax && ymax <= W) || canvas_h < 0 || canvas_w < 0) return 0;
+  const size_t prep = 4 * gml_align((size_t)H * W * sizeof(double)) + gml_align(8 * sizeof(double));
+  const size_t solve = dep_layout(xmax - xmin, ymax - ymin, ar.g * ac.g).total;
+  const size_t sel = gml_align((size_t)(canvas_h + 1) * (canvas_w + 1) * sizeof(int));
+  return std::max(std::max(prep, solve), sel);
+}
+
+int ebos_gml_dep_select(int H, int W, int patch, int slide, const int* row_box, const int* col_box, const double* events, int64_t n_events,
+                        int canvas_h, int canvas_w, int thresholding, double event_thres, int* sel, int* count, void* scratch,
+                        size_t scratch_bytes, ebos_stream_t stream) {
+  using namespace ebos;
+  DepAxis ar, ac;
+  int rc;
+  EBOS_REQUIRE(H >= 3 && W >= 3, "ebos_gml_dep_select: bad image size %d x %d", H, W);
+  if ((rc = dep_axis(H, patch, slide, &ar)) != EBOS_OK || (rc = dep_axis(W, patch, slide, &ac)) != EBOS_OK) return rc;
+  EBOS_REQUIRE(row_box && col_box && sel && count, "ebos_gml_dep_select: NULL buffer");
+  EBOS_REQUIRE(!thresholding || ((events || n_events == 0) && n_events >= 0 && n_events < ((int64_t)1 << 31) && scratch),
+               "ebos_gml_dep_select: bad events or NULL scratch");
+  EBOS_REQUIRE(canvas_h >= 0 && canvas_w >= 0 && (int64_t)(canvas_h + 1) * (canvas_w + 1) < ((int64_t)1 << 31),
+               "ebos_gml_dep_select: bad canvas %d x %d", canvas_h, canvas_w);
+  const hipStream_t st = as_stream(stream);
+  const int G = ar.g * ac.g;
+  int* sat = static_cast<int*>(scratch);
+  if (thresholding) {
+    const size_t need = (size_t)(canvas_h + 1) * (canvas_w + 1) * sizeof(int);
+    if (scratch_bytes < need) {
+      set_error("ebos_gml_dep_select: scratch too small (%zu < %zu)", scratch_bytes, need);
+      return EBOS_ERR_SCRATCH;
+    }
+    if (hipMemsetAsync(sat, 0, need, st) != hipSuccess) {
+      set_error("ebos_gml_dep_select: memset failed");
+      return EBOS_ERR_LAUNCH;
+    }
+    if (n_events > 0) hipLaunchKernelGGL(gml_count_events, dim3(blocks_for(n_events)), dim3(kGmlBlock), 0, st, n_events, events, canvas_h,
+                                         canvas_w, sat);
+    hipLaunchKernelGGL(gml_scan_rows, dim3(blocks_for(canvas_h)), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat);
+    hipLaunchKernelGGL(gml_scan_cols, dim3(blocks_for(canvas_w)), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat);
+  }
+  hipLaunchKernelGGL(gml_select, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, ar.g, ac.g, row_box, col_box, thresholding ? sat : nullptr,
+                     canvas_h, canvas_w, thresholding, event_thres, sel);
+  hipLaunchKernelGGL(gml_rank, dim3(1), dim3(kGmlBlock), 0, st, G, sel, count);
+  EBOS_CHECK_LAUNCH("ebos_gml_dep_select");
+  return EBOS_OK;
+}
+
+int ebos_gml_dep_init_f64(int gh, int gw, int n_dim, const int* sel, const double* draws, double* x, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(gh >= 1 && gw >= 1 && n_dim >= 1 && n_dim <= 4 && sel && x, "ebos_gml_dep_init_f64: bad arguments");
+  const int G = gh * gw;
+  hipLaunchKernelGGL(gml_dep_init, dim3(blocks_for(G)), dim3(kGmlBlock), 0, as_stream(stream), G, n_dim, sel, draws, x);
+  EBOS_CHECK_LAUNCH("ebos_gml_dep_init_f64");
+  return EBOS_OK;
+}
+
+int ebos_gml_dep_objective_f64(int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                               const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
+                               const double* we, const double* winv, const int* sel, const double* x, double* parts, double* grad,
+                               void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
+  using namespace ebos;
+  GmlGeom g;
+  int rc = make_dep_geom(&g, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  EBOS_REQUIRE(gx && gy && q && winv && sel && x && parts && grad && scratch && (!g.has_we || we), "ebos_gml_dep_objective_f64: NULL buffer");
+  const int G = g.gh * g.gw;
+  const DepLayout D = dep_layout(g.H, g.W, G);
+  if (scratch_bytes < D.total) {
+    set_error("ebos_gml_dep_objective_f64: scratch too small (%zu < %zu)", scratch_bytes, D.total);
+    return EBOS_ERR_SCRATCH;
+  }
+  const hipStream_t st = as_stream(stream);
+  GmlBufs B;
+  if ((rc = dep_bufs(g, W, xmin, ymin, D, static_cast<char*>(scratch), gx, gy, q, g.has_we ? we : nullptr, winv, const_cast<double*>(x),
+                     sel, st, &B)) != EBOS_OK)
+    return rc;
+  if ((rc = gml_forward_backward(g, B, parts, st)) != EBOS_OK) return rc;
+  AdamArgs a = {};
+  hipLaunchKernelGGL(gml_adam, dim3(blocks_for((int64_t)n_dim * G)), dim3(kGmlBlock), 0, st, g, B, a, grad);
+  EBOS_CHECK_LAUNCH("ebos_gml_dep_objective_f64");
+  return EBOS_OK;
+}
+
+int ebos_gml_dep_solve_f64(int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                           const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
+                           const double* we, const double* winv, const int* sel, double* x, int iters, double lr, double* history,
+                           double* flow_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
+  using namespace ebos;
+  GmlGeom g;
+  int rc = make_dep_geom(&g, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  EBOS_REQUIRE(gx && gy && q && winv && sel && x && scratch && (!g.has_we || we), "ebos_gml_dep_solve_f64: NULL buffer");
+  EBOS_REQUIRE(iters >= 0, "ebos_gml_dep_solve_f64: iters %d < 0", iters);
+  const int G = g.gh * g.gw;
+  const DepLayout D = dep_layout(g.H, g.W, G);
+  if (scratch_bytes < D.total) {
+    set_error("ebos_gml_dep_solve_f64: scratch too small (%zu < %zu)", scratch_bytes, D.total);
+    return EBOS_ERR_SCRATCH;
+  }
+  const hipStream_t st = as_stream(stream);
+  GmlBufs B;
+  if ((rc = dep_bufs(g, W, xmin, ymin, D, static_cast<char*>(scratch), gx, gy, q, g.has_we ? we : nullptr, winv, x, sel, st, &B)) !=
+      EBOS_OK)
+    return rc;
+  const int64_t np = (int64_t)n_dim * G;
+  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.m, 0.0);
+  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.v, 0.0);
+  AdamArgs a;
+  a.lr = lr;
+  a.beta1 = 0.9;
+  a.beta2 = 0.999;
+  a.eps = 1e-8;
+  a.step = 1;
+  for (int it = 0; it < iters; ++it) {
+    if ((rc = gml_forward_backward(g, B, history ? history + 4 * (size_t)it : nullptr, st)) != EBOS_OK) return rc;
+    const double t = (double)(it + 1);
+    a.step_size = lr / (1.0 - pow(a.beta1, t));
+    a.bc2_sqrt = pow(1.0 - pow(a.beta2, t), 0.5);
+    hipLaunchKernelGGL(gml_adam, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, g, B, a, nullptr);
+    EBOS_CHECK_LAUNCH("ebos_gml_dep_solve_f64: adam");
+  }
+  if (flow_out) {
+    const GmlGeom o = dep_out_geom(g, H, W, xmin, ymin);
+    if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, o, B.x, B.S);
+    hipLaunchKernelGGL(gml_flow_out, dim3(blocks_for(gml_npix(o))), dim3(kGmlBlock), 0, st, o, B.S, flow_out);
+    EBOS_CHECK_LAUNCH("ebos_gml_dep_solve_f64: flow");
   }
   return EBOS_OK;
 }

@@ -4,10 +4,12 @@ from .base import SolverBase
 from .contrast_maximization import (ContrastMaximization, ContrastMaximizationMixin, make_solver_class, patch_grid_shape,
                                     register_into)
 from .generative import GenerativePatchPyramid, make_generative_class, register_generative_into
+from .generative_dependent import GenerativePatchDependent, make_dependent_class, register_dependent_into
 from .window_pipeline import WindowPipeline
 
 collections = {
     "contrast_maximization": ContrastMaximization,
     "cmax": ContrastMaximization,
     "generative_patch_pyramid": GenerativePatchPyramid,
+    "generative_patch_dependent": GenerativePatchDependent,
 }

@@ -86,7 +86,7 @@ class _History(object):
 class GenerativeMixin(object):
     """``estimate(events, frame=..., background=...) -> np.ndarray [2, H, W]`` of the reference's PatchEkltPyramid2."""
 
-    def _gml_setup(self) -> None:
+    def _gml_setup(self, allow_velocity: bool = False) -> None:
         cfg = self.slv_config
         opt = cfg.get("optimizer") or {}
         gml = dict(cfg.get("generative_ml") or {})
@@ -94,7 +94,7 @@ class GenerativeMixin(object):
             raise NotImplementedError(f"generative solver: optimizer.method {opt.get('method')!r} is not supported (Adam only)")
         if _flag(gml, "angle_model"):
             raise NotImplementedError("generative solver: the angle model is not supported (poisson_model only)")
-        if not _flag(gml, "poisson_model"):
+        if not _flag(gml, "poisson_model") and not allow_velocity:
             raise NotImplementedError("generative solver: the direct-velocity model (poisson_model: false) is not supported")
         if int(gml.get("sobel_ksize", 3)) != 3:
             raise NotImplementedError("generative solver: sobel_ksize 5 is not supported")
@@ -118,7 +118,8 @@ class GenerativeMixin(object):
         self._gml_cfg = gml
         self._gml_cost = cost
         self._gml_n_iter = n_iter
-        self._gml_n_dim = 3 if self._gml_warp else 1
+        self._gml_velocity = not _flag(gml, "poisson_model")
+        self._gml_n_dim = (4 if self._gml_warp else 2) if self._gml_velocity else (3 if self._gml_warp else 1)
         H, W = (int(v) for v in self.orig_image_shape)
         p = (cfg.get("filter") or {}).get("parameters") or {}
         if "filter" in cfg:

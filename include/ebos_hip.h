@@ -1066,6 +1066,39 @@ int ebos_gml_solve_scale_f64(int H, int W, int patch, int n_dim, int xmin, int x
                              const double* winv, double* x, int iters, double lr, double* history, double* flow_out, void* scratch,
                              size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Generative BOS solver, single scale (src/solver/patch_eklt_dependent.py, patch_eklt_dependent), float64.
+ *
+ * The grid: patch `patch`, slide `slide`, len(arange(0, L - patch + slide, slide)) cells per axis; pad k = patch / (2 slide) + 1
+ * cells; the upsample is bilinear to (g + 2k) slide, centre-cropped (EBOS_ERR_INVALID_ARG where that crop leaves the canvas).
+ * ebos_gml_dep_scratch_bytes: scratch of every entry below and of ebos_gml_prepare_f64 (canvas 0 x 0 without thresholding);
+ *   0 for an invalid geometry.
+ * ebos_gml_dep_select: sel [gh, gw] int32 = 1 + the cell's rank among the selected cells in row-major order, 0 = unselected;
+ *   count[0] = the number selected.  row_box [gh, 3] / col_box [gw, 3] (device int32): the cell's event box [start, end) along
+ *   the axis and whether its centre lies in the ROI (bounds inclusive).  With `thresholding` a cell must also hold more than
+ *   event_thres of the events [n, 4] (x = row, y = column, ...), binned by floor into a canvas_h x canvas_w count image.
+ * ebos_gml_dep_init_f64: x [n_dim, gh, gw] = 0, then x[0] = draws[rank] on the selected cells (draws NULL: all zero).
+ * ebos_gml_dep_objective_f64 / ebos_gml_dep_solve_f64: as ebos_gml_objective_f64 / ebos_gml_solve_scale_f64, with the objective
+ *   on the ROI crop [xmin, xmax) x [ymin, ymax) of the full-image gx, gy, q, we, winv (q is cropped and divided by the crop's
+ *   norm), the gradient of unselected cells zero, and flow_out [2, H, W] the unmasked flow over the full image.  n_dim 1 / 3:
+ *   Poisson model (F = up(Sobel3(x0) / 8)); with EBOS_GML_VELOCITY n_dim 2 / 4 (F = up(x[0:2])).  p_x, p_y = x[-2:].
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_GML_VELOCITY 4
+
+size_t ebos_gml_dep_scratch_bytes(int H, int W, int patch, int slide, int xmin, int xmax, int ymin, int ymax, int canvas_h, int canvas_w);
+int ebos_gml_dep_select(int H, int W, int patch, int slide, const int* row_box, const int* col_box, const double* events, int64_t n_events,
+                        int canvas_h, int canvas_w, int thresholding, double event_thres, int* sel, int* count, void* scratch,
+                        size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_dep_init_f64(int gh, int gw, int n_dim, const int* sel, const double* draws, double* x, ebos_stream_t stream);
+int ebos_gml_dep_objective_f64(int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                               const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
+                               const double* we, const double* winv, const int* sel, const double* x, double* parts, double* grad,
+                               void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_dep_solve_f64(int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                           const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
+                           const double* we, const double* winv, const int* sel, double* x, int iters, double lr, double* history,
+                           double* flow_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,13 @@ Per size (720 x 1280 and 260 x 346, the reference YAML's options, ROI = the YAML
   torch_cpu_ms_per_iter the same on the CPU (a few iterations);
   bytes_per_iter        the float64 traffic the seven passes need at the pixel level (formula below), and its rate against
                         the rate of a device-to-device copy of 256 MiB measured in the same run.
+
+With ``--method patch_eklt_dependent``, the single-scale solver (GenerativePatchDependent) with the YAML's patch_eklt block
+(patch 4, slide 2) and the YAML's ROI (the central half of the columns):
+  hip_window_ms         one estimate with n_iter 600, host clock around a synchronised call (best of 3);
+  hip_ms_per_iter       (window at n_iter 600 - window at n_iter 100) / 500;
+  torch_gpu_ms_per_iter _gml_dep_ref.Model forward + backward + torch.optim.Adam step on the GPU, float64 (eager baseline);
+  torch_gpu_window_ms   the same iteration times 600.
 """
 import argparse
 import json
@@ -25,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import _gml_dep_ref as D  # noqa: E402
 import _gml_ref as R  # noqa: E402
 from _gml_cases import YAML_COST, YAML_GML, frame_image, synth_events  # noqa: E402
 
@@ -123,12 +131,82 @@ def bench_size(H, W, iters, cpu_iters):
     return out
 
 
+def dep_config(H, W, n_iter):
+    cfg = config(H, W, n_iter)
+    cfg["method"] = "patch_eklt_dependent"
+    cfg["patch_eklt"] = {"patch_size": 4, "sliding_window": 2, "do_event_thresholding": False, "event_thres": 8}
+    return cfg
+
+
+def bench_dep_size(H, W):
+    import event_based_bos_amd as ebos
+    frame, events = frame_image(H, W, 1), synth_events(2 * H * W, H, W, 2)
+    out = {"method": "patch_eklt_dependent", "size": [H, W]}
+
+    def window(n_iter, reps=3):
+        solv = ebos.solver.GenerativePatchDependent((H, W), (H, W), {}, dep_config(H, W, n_iter))
+        np.random.seed(0)
+        solv.estimate(events, frame=frame)
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            np.random.seed(0)
+            t0 = time.perf_counter()
+            solv.estimate(events, frame=frame)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return solv, [1e3 * t for t in ts]
+
+    solv, t600 = window(600)
+    _, t100 = window(100)
+    out["hip_window_ms"] = min(t600)
+    out["hip_window_ms_all"] = t600
+    out["hip_window_ms_n100"] = min(t100)
+    out["hip_ms_per_iter"] = (min(t600) - min(t100)) / 500
+    out["selected_patches"] = int(len(solv.estimate_indices))
+    out["grid"] = list(solv.patch_image_size)
+    cfg = dep_config(H, W, 600)
+    roi = tuple(cfg["filter"]["parameters"][k] for k in ("xmin", "xmax", "ymin", "ymax"))
+    st = R.prepare(frame, R.polarity_image(events, (H, W)), YAML_GML, roi)
+    idx = solv.estimate_indices
+    model = D.Model(st, YAML_GML, YAML_COST, 4, 2, roi, idx, "cuda")
+    xt = model.from_grid(solv.params).clone().requires_grad_()
+    opt = torch.optim.Adam([xt], lr=0.05)
+
+    def step():
+        opt.zero_grad()
+        loss, _ = model.parts(xt)
+        loss.backward()
+        opt.step()
+    step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(10):
+        step()
+    torch.cuda.synchronize()
+    out["torch_gpu_ms_per_iter"] = 1e3 * (time.perf_counter() - t0) / 10
+    out["torch_gpu_window_ms"] = 600 * out["torch_gpu_ms_per_iter"]
+    out["speedup_vs_torch_gpu"] = out["torch_gpu_ms_per_iter"] / out["hip_ms_per_iter"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_gml.py measures on the GPU"
+    if args.method == "patch_eklt_dependent":
+        res = {"sizes": []}
+        for H, W in ((720, 1280), (260, 346)):
+            r = bench_dep_size(H, W)
+            res["sizes"].append(r)
+            print(json.dumps(r), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     rate = copy_rate()
     res = {"copy_bytes_per_s": rate, "sizes": []}
     for (H, W), cpu_iters in (((720, 1280), 2), ((260, 346), 5)):

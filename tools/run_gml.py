@@ -5,6 +5,7 @@ BOS scene with a known displacement field.
     python tools/run_gml.py                                                   # 260 x 346, the reference YAML's options
     python tools/run_gml.py --size 128 160 --n_iter 120 --json out.json
     python tools/run_gml.py --config_file tests/golden/config_hot_plate1.json # the REFERENCE's configs/hot_plate1.yaml, as it is
+    python tools/run_gml.py --method patch_eklt_dependent                     # the single-scale solver, the YAML's patch_eklt block
 
 The scene: a textured frame L, a potential phi (two Gaussian bumps) and its gradient d = grad phi as the displacement; events are
 drawn at pixels with probability proportional to |grad L . d|, with the sign of grad L . d as polarity.  Reported: the loss at
@@ -40,11 +41,14 @@ def scene(H, W, n_events, seed=0):
     return frame, ev, d
 
 
-def default_config(H, W, n_iter):
+def default_config(H, W, n_iter, method="patch_eklt_pyramid2"):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from _gml_cases import YAML_COST, YAML_GML
-    return {"method": "patch_eklt_pyramid2", "filter": {"filters": [], "parameters": {"xmin": 0, "xmax": H, "ymin": 0, "ymax": W}},
-            "cost_with_weight": dict(YAML_COST), "optimizer": {"method": "Adam", "n_iter": n_iter}, "generative_ml": dict(YAML_GML)}
+    cfg = {"method": method, "filter": {"filters": [], "parameters": {"xmin": 0, "xmax": H, "ymin": 0, "ymax": W}},
+           "cost_with_weight": dict(YAML_COST), "optimizer": {"method": "Adam", "n_iter": n_iter}, "generative_ml": dict(YAML_GML)}
+    if method == "patch_eklt_dependent":
+        cfg["patch_eklt"] = {"patch_size": 4, "sliding_window": 2, "do_event_thresholding": False, "event_thres": 8}
+    return cfg
 
 
 def main():
@@ -54,6 +58,8 @@ def main():
     ap.add_argument("--events", type=int, default=0, help="events in the window (default 2 per pixel)")
     ap.add_argument("--config_file", default=None, help="a reference config (JSON with a 'propagated' section, or a solver dict)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent"),
+                    help="the solver when no --config_file is given")
     ap.add_argument("--json", default=None, help="also write the result here")
     args = ap.parse_args()
 
@@ -68,12 +74,13 @@ def main():
         solver_cfg = cfg["solver"]
     else:
         H, W = args.size
-        solver_cfg = default_config(H, W, args.n_iter)
+        solver_cfg = default_config(H, W, args.n_iter, args.method)
     method = solver_cfg["method"]
     frame, events, d = scene(H, W, args.events or 2 * H * W, args.seed)
     import types
     reg = types.SimpleNamespace(SolverBase=ebos.solver.SolverBase, collections={})
     ebos.solver.register_generative_into(reg)          # method patch_eklt_pyramid2, no override
+    ebos.solver.register_dependent_into(reg)           # method patch_eklt_dependent
     solv = reg.collections[method]((H, W), (H, W), {}, solver_cfg)
     np.random.seed(args.seed)
     solv.estimate(events, frame=frame, background=frame)   # warm-up (code objects, allocations)
