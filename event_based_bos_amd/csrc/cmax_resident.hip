@@ -81,8 +81,54 @@ bool resident_padding_ok(int pad_h, int pad_w, int tile_h, int tile_w, int halo,
   return true;
 }
 
+// the tile shapes with a resident kernel (one translation unit each, cmax_resident_<tile>[_2dof].hip), all at halo 32
+struct ResidentTile {
+  int tile_h, tile_w;
+  int (*patch)(const ebos_cmax_patch_problem*, int, void*, double, hipStream_t);
+  int (*two_dof)(const ebos_cmax_2dof_problem*, float, int, void*, double, hipStream_t);
+};
+constexpr int kResidentHalo = 32;
+constexpr ResidentTile kResidentTiles[] = {
+    {45, 80, resident_launch_45x80, resident_launch_2dof_45x80},
+    {32, 32, resident_launch_32x32, resident_launch_2dof_32x32},
+    {32, 64, resident_launch_32x64, resident_launch_2dof_32x64},   // (720 x 640: hot_plate1's ROI)
+};
+
+const ResidentTile* resident_tile(int tile_h, int tile_w, int halo) {
+  for (const ResidentTile& t : kResidentTiles)
+    if (halo == kResidentHalo && t.tile_h == tile_h && t.tile_w == tile_w) return &t;
+  return nullptr;
+}
+
+int tile_count(int H, int W, int tile_h, int tile_w) { return ((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w); }
+
+// what every resident launch needs, in this order (reason in ebos_last_error, prefixed with `what`): one work item per tile, the padding
+// inside the windows, the launch's own objective (`objective_ok`), a built tile, at most kBlock tiles, all of them co-resident
+template <class Problem, class ObjectiveOk>
+bool resident_common_ok(const Problem* q, const char* what, ObjectiveOk objective_ok) {
+  const int halo = decode_halo(q->halo).halo;
+  // splits: 1, or 0 = "adaptive work items" (a table the four-launch pipeline splits crowded tiles by: the resident kernel always
+  // runs one workgroup per tile and does not read it -- same objective, slab sums in another order where a tile was split)
+  if (q->splits > 1 || q->splits < 0) {
+    set_error("%s: one work item per tile (splits = %d)", what, q->splits);
+    return false;
+  }
+  if (!resident_padding_ok(q->pad_h, q->pad_w, q->tile_h, q->tile_w, halo, what)) return false;
+  if (!objective_ok()) return false;
+  if (!resident_tile(q->tile_h, q->tile_w, halo)) {
+    set_error("%s: no resident kernel built for tile %dx%d halo %d", what, q->tile_h, q->tile_w, halo);
+    return false;
+  }
+  const int n_tiles = tile_count(q->H, q->W, q->tile_h, q->tile_w);
+  if (n_tiles > kBlock) {
+    set_error("%s: %d tiles (one record per thread: <= %d)", what, n_tiles, kBlock);
+    return false;
+  }
+  return tiles_fit_device(n_tiles, what);
+}
+
 // the geometry / objective a resident launch takes; reason in ebos_last_error otherwise
-bool resident_problem_ok(const ebos_cmax_patch_problem* q) {
+bool resident_ok(const ebos_cmax_patch_problem* q) {
   const int halo = decode_halo(q->halo).halo;
   // (integer source pixels: the loop object of the grid-sampling route, whose four launches can take over; fractional ones: the
   // compact arrays with the fractions per slot -- that window's four-launch loop runs on the dense route)
@@ -90,38 +136,24 @@ bool resident_problem_ok(const ebos_cmax_patch_problem* q) {
     set_error("resident solve: needs a compact plan -- of the grid-sampling route (grad_partials), or with the fractions of undistorted events (cfx / cfy)");
     return false;
   }
-  // splits: 1, or 0 = "adaptive work items" (a table the four-launch pipeline splits crowded tiles by: the resident kernel always
-  // runs one workgroup per tile and does not read it -- same objective, slab sums in another order where a tile was split)
-  if (q->splits > 1 || q->splits < 0) {
-    set_error("resident solve: one work item per tile (splits = %d)", q->splits);
-    return false;
-  }
-  if (!resident_padding_ok(q->pad_h, q->pad_w, q->tile_h, q->tile_w, halo, "resident solve")) return false;
-  if ((q->w_gradient_magnitude != 0.0f) == (q->w_variance != 0.0f)) {
-    set_error("resident solve: exactly one of w_variance / w_gradient_magnitude must be non-zero");
-    return false;
-  }
-  if (q->w_gradient_magnitude != 0.0f && q->blur_k0 != 0.0f) {
-    set_error("resident solve: the blurred image goes with the variance contrast only");
-    return false;
-  }
-  if (!ebos_patch_fused_supported(q->tile_h, q->tile_w, q->halo, q->slide_h, q->slide_w)) {
-    set_error("resident solve: tile %dx%d halo %d / sliding window %dx%d is outside ebos_patch_fused_supported", q->tile_h, q->tile_w,
-              halo, q->slide_h, q->slide_w);
-    return false;
-  }
-  const bool built = halo == 32 && ((q->tile_h == 45 && q->tile_w == 80) || (q->tile_h == 32 && q->tile_w == 32) ||
-                                    (q->tile_h == 32 && q->tile_w == 64));
-  if (!built) {
-    set_error("resident solve: no resident kernel built for tile %dx%d halo %d", q->tile_h, q->tile_w, halo);
-    return false;
-  }
+  const bool common = resident_common_ok(q, "resident solve", [&] {
+    if ((q->w_gradient_magnitude != 0.0f) == (q->w_variance != 0.0f)) {
+      set_error("resident solve: exactly one of w_variance / w_gradient_magnitude must be non-zero");
+      return false;
+    }
+    if (q->w_gradient_magnitude != 0.0f && q->blur_k0 != 0.0f) {
+      set_error("resident solve: the blurred image goes with the variance contrast only");
+      return false;
+    }
+    if (!ebos_patch_fused_supported(q->tile_h, q->tile_w, q->halo, q->slide_h, q->slide_w)) {
+      set_error("resident solve: tile %dx%d halo %d / sliding window %dx%d is outside ebos_patch_fused_supported", q->tile_h, q->tile_w,
+                halo, q->slide_h, q->slide_w);
+      return false;
+    }
+    return true;
+  });
+  if (!common) return false;
   const int tiles_y = (q->H + q->tile_h - 1) / q->tile_h, tiles_x = (q->W + q->tile_w - 1) / q->tile_w;
-  if (tiles_y * tiles_x > kBlock) {
-    set_error("resident solve: %d tiles (one record per thread: <= %d)", tiles_y * tiles_x, kBlock);
-    return false;
-  }
-  if (!tiles_fit_device(tiles_y * tiles_x, "resident solve")) return false;
   if (((q->tile_h + 2 * kBwdApron) / q->slide_h + 3) * ((q->tile_w + 2 * kBwdApron) / q->slide_w + 3) * 2 > kResElems) {
     set_error("resident solve: sliding window %dx%d: a tile's block of grid cells has more than %d elements", q->slide_h, q->slide_w, kResElems);
     return false;
@@ -170,8 +202,7 @@ bool resident_problem_ok(const ebos_cmax_patch_problem* q) {
 
 
 // ... and the 2-DoF problem a resident launch takes
-bool resident_2dof_ok(const ebos_cmax_2dof_problem* q) {
-  const int halo = decode_halo(q->halo).halo;
+bool resident_ok(const ebos_cmax_2dof_problem* q) {
   if (!q->grp_offsets || !q->cpix || !q->cdt) {
     set_error("resident 2-DoF solve: needs the compact plan (integer source pixels)");
     return false;
@@ -180,32 +211,45 @@ bool resident_2dof_ok(const ebos_cmax_2dof_problem* q) {
     set_error("resident 2-DoF solve: cfx and cfy come together (fractional source coordinates) or not at all");
     return false;
   }
-  if (q->splits > 1 || q->splits < 0) {
-    set_error("resident 2-DoF solve: one work item per tile (splits = %d)", q->splits);
-    return false;
-  }
-  if (!resident_padding_ok(q->pad_h, q->pad_w, q->tile_h, q->tile_w, halo, "resident 2-DoF solve")) return false;
-  if (q->w_variance == 0.0f) {
-    set_error("resident 2-DoF solve: w_variance is 0");
-    return false;
-  }
-  const bool built = halo == 32 && ((q->tile_h == 45 && q->tile_w == 80) || (q->tile_h == 32 && q->tile_w == 32) ||
-                                    (q->tile_h == 32 && q->tile_w == 64));
-  if (!built) {
-    set_error("resident 2-DoF solve: no resident kernel built for tile %dx%d halo %d", q->tile_h, q->tile_w, halo);
-    return false;
-  }
-  const int tiles_y = (q->H + q->tile_h - 1) / q->tile_h, tiles_x = (q->W + q->tile_w - 1) / q->tile_w;
-  if (tiles_y * tiles_x > kBlock) {
-    set_error("resident 2-DoF solve: %d tiles (one record per thread: <= %d)", tiles_y * tiles_x, kBlock);
-    return false;
-  }
-  if (!tiles_fit_device(tiles_y * tiles_x, "resident 2-DoF solve")) return false;
+  const bool common = resident_common_ok(q, "resident 2-DoF solve", [&] {
+    if (q->w_variance == 0.0f) {
+      set_error("resident 2-DoF solve: w_variance is 0");
+      return false;
+    }
+    return true;
+  });
+  if (!common) return false;
   if (q->blur_k0 != 0.0f && (q->blur_k0 < 0.0f || q->blur_k1 <= 0.0f || q->H < 2 || q->W < 2)) {
     set_error("resident 2-DoF solve: bad blur taps / image smaller than 2 x 2");
     return false;
   }
   return true;
+}
+
+// the checks both ebos_cmax_*_solve_resident_f32 entry points make, in order (messages prefixed with the entry's name `fn`): the
+// arguments, the problem (resident_ok), the mailbox and workspace sizes; *tile: the launchers of the problem's tile
+template <class Problem>
+int resident_solve_checks(const Problem* q, int n_iter, const void* mailbox, size_t mailbox_bytes, double spin_timeout_s, const char* fn,
+                          const ResidentTile** tile) {
+  EBOS_REQUIRE(q != nullptr && n_iter >= 0 && q->steps_done >= 0, "%s: NULL problem or negative counts", fn);
+  EBOS_REQUIRE(q->theta && q->d_theta && q->exp_avg && q->exp_avg_sq && q->step && q->iwe && q->variance && q->moments && q->workspace &&
+                   q->key_offsets,
+               "%s: NULL buffer", fn);
+  EBOS_REQUIRE(mailbox != nullptr && spin_timeout_s > 0.0, "%s: NULL mailbox or no spin cap", fn);
+  if (!resident_ok(q)) return EBOS_ERR_UNSUPPORTED;
+  const HaloArg ha = decode_halo(q->halo);
+  const MailboxLayout m = mailbox_layout(tile_count(q->H, q->W, q->tile_h, q->tile_w));
+  if (mailbox_bytes < m.total) {
+    set_error("%s: mailbox too small (%zu < %zu)", fn, mailbox_bytes, m.total);
+    return EBOS_ERR_SCRATCH;
+  }
+  const size_t need = ebos_iwe_slab_workspace_bytes(q->H, q->W, q->tile_h, q->tile_w, ha.halo, 1, 0, 0);
+  if (q->workspace_bytes < need) {
+    set_error("%s: workspace too small (%zu < %zu)", fn, q->workspace_bytes, need);
+    return EBOS_ERR_SCRATCH;
+  }
+  *tile = resident_tile(q->tile_h, q->tile_w, ha.halo);
+  return EBOS_OK;
 }
 
 }  // namespace
@@ -216,45 +260,26 @@ extern "C" {
 
 size_t ebos_cmax_resident_mailbox_bytes(int H, int W, int tile_h, int tile_w) {
   if (H <= 0 || W <= 0 || tile_h <= 0 || tile_w <= 0) return 0;
-  return ebos::mailbox_layout(((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w)).total;
+  return ebos::mailbox_layout(ebos::tile_count(H, W, tile_h, tile_w)).total;
 }
 
 int ebos_cmax_resident_supported(const ebos_cmax_patch_problem* q) {
   using namespace ebos;
   if (q == nullptr) return 0;
-  return resident_problem_ok(q) ? 1 : 0;
+  return resident_ok(q) ? 1 : 0;
 }
 
 int ebos_cmax_patch_solve_resident_f32(const ebos_cmax_patch_problem* q, int n_iter, void* mailbox, size_t mailbox_bytes,
                                        double spin_timeout_s, ebos_stream_t stream) {
   using namespace ebos;
-  EBOS_REQUIRE(q != nullptr && n_iter >= 0 && q->steps_done >= 0, "ebos_cmax_patch_solve_resident: NULL problem or negative counts");
-  EBOS_REQUIRE(q->theta && q->d_theta && q->exp_avg && q->exp_avg_sq && q->step && q->iwe && q->variance && q->moments && q->workspace &&
-                   q->key_offsets,
-               "ebos_cmax_patch_solve_resident: NULL buffer");
-  EBOS_REQUIRE(mailbox != nullptr && spin_timeout_s > 0.0, "ebos_cmax_patch_solve_resident: NULL mailbox or no spin cap");
-  if (!resident_problem_ok(q)) return EBOS_ERR_UNSUPPORTED;
-  const HaloArg ha = decode_halo(q->halo);
-  const int tiles_y = (q->H + q->tile_h - 1) / q->tile_h, tiles_x = (q->W + q->tile_w - 1) / q->tile_w, n_tiles = tiles_y * tiles_x;
-  const MailboxLayout m = mailbox_layout(n_tiles);
-  if (mailbox_bytes < m.total) {
-    set_error("ebos_cmax_patch_solve_resident: mailbox too small (%zu < %zu)", mailbox_bytes, m.total);
-    return EBOS_ERR_SCRATCH;
-  }
-  const size_t need = ebos_iwe_slab_workspace_bytes(q->H, q->W, q->tile_h, q->tile_w, ha.halo, 1, 0, 0);
-  if (q->workspace_bytes < need) {
-    set_error("ebos_cmax_patch_solve_resident: workspace too small (%zu < %zu)", q->workspace_bytes, need);
-    return EBOS_ERR_SCRATCH;
-  }
+  const ResidentTile* tile = nullptr;
+  int rc = resident_solve_checks(q, n_iter, mailbox, mailbox_bytes, spin_timeout_s, "ebos_cmax_patch_solve_resident", &tile);
+  if (rc != EBOS_OK) return rc;
   if (q->grad_partials != nullptr && q->grad_partials_bytes < ebos_patch_grad_partials_bytes(q->H, q->W, q->tile_h, q->tile_w, 0)) {
     set_error("ebos_cmax_patch_solve_resident: grad_partials too small");
     return EBOS_ERR_SCRATCH;
   }
-  hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-  if (q->tile_h == 45 && q->tile_w == 80 && ha.halo == 32) rc = resident_launch_45x80(q, n_iter, mailbox, spin_timeout_s, s);
-  else if (q->tile_h == 32 && q->tile_w == 32 && ha.halo == 32) rc = resident_launch_32x32(q, n_iter, mailbox, spin_timeout_s, s);
-  else if (q->tile_h == 32 && q->tile_w == 64 && ha.halo == 32) rc = resident_launch_32x64(q, n_iter, mailbox, spin_timeout_s, s);  // (720 x 640: hot_plate1's ROI)
+  rc = tile->patch(q, n_iter, mailbox, spin_timeout_s, as_stream(stream));
   if (rc != EBOS_OK) return rc;
   EBOS_CHECK_LAUNCH("ebos_cmax_patch_solve_resident");
   return EBOS_OK;
@@ -263,35 +288,16 @@ int ebos_cmax_patch_solve_resident_f32(const ebos_cmax_patch_problem* q, int n_i
 int ebos_cmax_2dof_resident_supported(const ebos_cmax_2dof_problem* q) {
   using namespace ebos;
   if (q == nullptr) return 0;
-  return resident_2dof_ok(q) ? 1 : 0;
+  return resident_ok(q) ? 1 : 0;
 }
 
 int ebos_cmax_2dof_solve_resident_f32(const ebos_cmax_2dof_problem* q, int n_iter, void* mailbox, size_t mailbox_bytes,
                                       double spin_timeout_s, ebos_stream_t stream) {
   using namespace ebos;
-  EBOS_REQUIRE(q != nullptr && n_iter >= 0 && q->steps_done >= 0, "ebos_cmax_2dof_solve_resident: NULL problem or negative counts");
-  EBOS_REQUIRE(q->theta && q->d_theta && q->exp_avg && q->exp_avg_sq && q->step && q->iwe && q->variance && q->moments && q->workspace &&
-                   q->key_offsets,
-               "ebos_cmax_2dof_solve_resident: NULL buffer");
-  EBOS_REQUIRE(mailbox != nullptr && spin_timeout_s > 0.0, "ebos_cmax_2dof_solve_resident: NULL mailbox or no spin cap");
-  if (!resident_2dof_ok(q)) return EBOS_ERR_UNSUPPORTED;
-  const HaloArg ha = decode_halo(q->halo);
-  const int tiles_y = (q->H + q->tile_h - 1) / q->tile_h, tiles_x = (q->W + q->tile_w - 1) / q->tile_w, n_tiles = tiles_y * tiles_x;
-  const MailboxLayout m = mailbox_layout(n_tiles);
-  if (mailbox_bytes < m.total) {
-    set_error("ebos_cmax_2dof_solve_resident: mailbox too small (%zu < %zu)", mailbox_bytes, m.total);
-    return EBOS_ERR_SCRATCH;
-  }
-  const size_t need = ebos_iwe_slab_workspace_bytes(q->H, q->W, q->tile_h, q->tile_w, ha.halo, 1, 0, 0);
-  if (q->workspace_bytes < need) {
-    set_error("ebos_cmax_2dof_solve_resident: workspace too small (%zu < %zu)", q->workspace_bytes, need);
-    return EBOS_ERR_SCRATCH;
-  }
-  hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-  if (q->tile_h == 45 && q->tile_w == 80 && ha.halo == 32) rc = resident_launch_2dof_45x80(q, q->w_variance, n_iter, mailbox, spin_timeout_s, s);
-  else if (q->tile_h == 32 && q->tile_w == 32 && ha.halo == 32) rc = resident_launch_2dof_32x32(q, q->w_variance, n_iter, mailbox, spin_timeout_s, s);
-  else if (q->tile_h == 32 && q->tile_w == 64 && ha.halo == 32) rc = resident_launch_2dof_32x64(q, q->w_variance, n_iter, mailbox, spin_timeout_s, s);
+  const ResidentTile* tile = nullptr;
+  int rc = resident_solve_checks(q, n_iter, mailbox, mailbox_bytes, spin_timeout_s, "ebos_cmax_2dof_solve_resident", &tile);
+  if (rc != EBOS_OK) return rc;
+  rc = tile->two_dof(q, q->w_variance, n_iter, mailbox, spin_timeout_s, as_stream(stream));
   if (rc != EBOS_OK) return rc;
   EBOS_CHECK_LAUNCH("ebos_cmax_2dof_solve_resident");
   return EBOS_OK;

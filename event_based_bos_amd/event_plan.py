@@ -13,7 +13,7 @@ and every objective evaluation afterwards is one fused kernel over 12-16 B/event
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import Optional, Tuple, Union
 
 import torch
@@ -207,11 +207,31 @@ class EventPlan:
         return (ptr(self.grp_offsets), ptr(self.cpix), ptr(self.cdt)) if self.compact else (None, None, None)
 
     @property
+    def fractional(self) -> bool:
+        """True when ``bin()`` found fractional source coordinates (undistorted events) and ``frac_compact`` is, or will be, the
+        layout of the grid-sampling and resident kernels.  Launches nothing."""
+        return bool(self.__dict__.get("_frac_pending")) or self.__dict__.get("_frac") is not None
+
+    def _frac_ptrs(self, query: bool = False):
+        """Pointers of ``frac_compact``.  ``query``: for a ``*_supported`` check, which reads whether a launch gets the arrays, never
+        what they hold -- a layout not built yet stays so, named by non-NULL stand-ins."""
+        if query and self.__dict__.get("_frac") is None:
+            return (1,) * 5
+        return tuple(ptr(t) for t in self.frac_compact)
+
+    def record_stream(self, stream: torch.cuda.Stream) -> None:
+        """Mark every device tensor of the plan -- the fraction layout once it is built -- as in use on ``stream`` (a plan built
+        on one stream and read on another)."""
+        for t in (*(getattr(self, f.name) for f in fields(self)), *(self.__dict__.get("_frac") or ())):
+            if isinstance(t, torch.Tensor):
+                t.record_stream(stream)
+
+    @property
     def frac_compact(self):
         """(grp_offsets, cpix, cdt, cfx, cfy) of a plan whose source coordinates are fractional (undistorted events) -- the compact
         layout with the fractions per slot, read by the resident loops and the grid-sampling launches --, or None.  Built on the first
         access, on the current stream (``ebos_plan_compact_frac_f32``: every source pixel's events in a canonical order, so two builds
-        of one window hold identical slots)."""
+        of one window hold identical slots): only launches read it, yes/no questions ask ``fractional``."""
         d = self.__dict__
         if d.get("_frac") is None and d.get("_frac_pending"):
             lib = _hip.require_gpu()

@@ -159,7 +159,7 @@ class ContrastMaximizationMixin(object):
         # integer coordinates again; either build is valid for either kind of window)
         plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
                                emit="full" if getattr(self, "_fractional_stream", False) else "compact")
-        self._fractional_stream = plan.frac_compact is not None
+        self._fractional_stream = plan.fractional
         self.history = []
         # The optimisation loops below call loss.backward() thousands of times on graphs of one or two nodes: with the autograd
         # engine's device thread each call pays two thread hand-offs (~35 us of a ~100 us iteration, tools/bench_autograd.py);
@@ -255,16 +255,10 @@ class ContrastMaximizationMixin(object):
                                                  w_gradient_magnitude=self.contrast_terms.get("gradient_magnitude", 0.0), theta_mask=mask,
                                                  blur_sigma=self.blur_sigma)
 
-            loop = make_loop()
-            try:
-                losses = loop.run(n_iter, resident=None if self.resident is None else bool(self.resident) and loop.resident_supported())
-            except fused_loop.ResidentStateTorn as e:   # as WindowPipeline does: re-solve the window from its start with the four launches
-                logger.warning("%s; re-solving the window with the four launches", e)
-                loop = make_loop()
-                losses = loop.run(n_iter, resident=False)
+            loop = fused_loop.run_rebuilding_torn(make_loop, n_iter, self.resident)
             self.graphed, self.fused, self.loop_mode = loop.graphed, True, loop.last_run_mode
             self.loop_modes.append(loop.last_run_mode)  # (per pyramid scale, coarse to fine)
-            self.history += losses.cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
+            self.history += loop.losses[:n_iter].cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
             return loop.theta
         self.fused = False
         if self.opt_method in SCIPY_METHODS:
@@ -405,15 +399,9 @@ class ContrastMaximizationMixin(object):
                 return fused_loop.Fused2dofLoop(plan, theta0.detach().clone(), self.contrast_terms["image_variance"], self.omit_boundary, self.pad,
                                                 self.halo, self.lr, capacity=max(n_iter, 1), blur_sigma=self.blur_sigma)
 
-            loop = make_loop()
-            try:
-                losses = loop.run(n_iter, resident=None if self.resident is None else bool(self.resident) and loop.resident_supported())
-            except fused_loop.ResidentStateTorn as e:   # theta0 is untouched (the loop works on its own copy): start over, four launches
-                logger.warning("%s; re-solving the window with the four launches", e)
-                loop = make_loop()
-                losses = loop.run(n_iter, resident=False)
+            loop = fused_loop.run_rebuilding_torn(make_loop, n_iter, self.resident)   # (the loop works on a copy of theta0)
             self.fused, self.loop_mode = True, loop.last_run_mode
-            self.history += losses.cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
+            self.history += loop.losses[:n_iter].cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
             return loop.theta
         self.fused = False
         theta = theta0.clone().requires_grad_(True)

@@ -29,6 +29,8 @@ even as a replayed HIP graph; this pipeline is bounded by its event kernels.  An
 """
 from __future__ import annotations
 
+import ctypes
+import logging
 import os
 from typing import Dict, Optional, Tuple
 
@@ -39,6 +41,8 @@ from .._hip import check, ptr, stream_ptr
 from ..event_plan import EventPlan, _slab_ok, _workspace
 
 FLOW_TERMS = ("flow_norm", "image_gradient")
+logger = logging.getLogger(__name__)
+
 RESIDENT_BLUR = True   # the resident kernel blurs its gathered window in LDS (EBOS_RESIDENT_BLUR=0: the blurred loop stays four + one launches)
 
 
@@ -93,7 +97,140 @@ class ResidentStateTorn(RuntimeError):
     the four launches (``ContrastMaximization`` and ``WindowPipeline`` both do)."""
 
 
-class FusedPatchLoop(object):
+def run_rebuilding_torn(make_loop, n_iter: int, resident: Optional[bool]):
+    """``make_loop().run(n_iter)`` -- ``resident``: a solver's ``optimizer.resident`` (None: the loop's default; otherwise resident
+    where supported) --; a torn resident launch (``ResidentStateTorn``) is logged and the window solved again from its start on a
+    fresh loop with the four launches, as ``WindowPipeline`` does.  Returns the loop that ran."""
+    loop = make_loop()
+    try:
+        loop.run(n_iter, resident=None if resident is None else bool(resident) and loop.resident_supported())
+    except ResidentStateTorn as e:
+        logger.warning("%s; re-solving the window with the four launches", e)
+        loop = make_loop()
+        loop.run(n_iter, resident=False)
+    return loop
+
+
+class _ResidentLoop(object):
+    """The host side of the ONE-launch resident solver (mailbox, status, hand-over, refusal), shared by the patch-flow and the
+    2-DoF loop.  A subclass sets its two C entry points and supplies ``problem(query)``, its own gates (``_resident_gates``) and the
+    four-launch pipeline for what the resident launch leaves (``run`` hands it to ``_run``)."""
+    _supported_fn = _solve_fn = ""  # ebos_cmax_*_resident_supported / ebos_cmax_*_solve_resident_f32
+    _mailbox = None          # flags / records / status word of the resident launch (allocated on first use)
+    resident_status = 0      # status of the last resident launch (0 = completed)
+    resident_iterations = 0  # iterations it completed
+    last_run_mode = "pipeline"
+    _resident_refused = False
+
+    def _resident_gates(self) -> bool:
+        return True
+
+    def _resident_problem(self, query: bool = False):
+        """``problem()`` for the resident launch: a BUILT halo of 32 becomes "run-time windows of at most 32 px" where the plan knows
+        its |dt| bound -- with every window the full one the resident kernel publishes and re-reads the image in every iteration
+        and scatters in f64 (45.7 us per iteration at 2 M events: no faster than the four launches; 28.9 with run-time windows).
+        Values are the same; the gradient's fixed-point unit follows the staged window, so against the four-launch pipeline at the
+        built halo the trajectory agrees to rounding (~1e-6 per iteration), not bit for bit -- with ``halo="auto"`` it is identical."""
+        q = self.problem(query)
+        if self.halo >= 0 and self.plan.dt_bound is not None:
+            q.halo = int(self.lib.ebos_halo_auto(int(self.halo), float(self.plan.dt_bound)))
+        if self.plan.fractional:  # a window of undistorted events: the compact layout with the fractions per slot (FRAC kernels)
+            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = self.plan._frac_ptrs(query)
+        return q
+
+    def resident_supported(self) -> bool:
+        """Can ``run`` take the ONE-launch resident kernel?  A compact plan -- of integer source pixels, or with the fractions of
+        undistorted events --, one work item per tile (the resident kernel runs one workgroup per tile whatever the plan's work-item
+        table says: against a pipeline that split crowded tiles it agrees to rounding, not bit for bit), image padding below half a
+        tile, a tile / halo with a resident kernel, few enough tiles to be co-resident (reason in ``ebos_last_error``).  Launches
+        nothing."""
+        plan = self.plan
+        if not (plan.compact or plan.fractional) or self.splits not in (0, 1) or not self._resident_gates():
+            return False
+        if self.pad != (0, 0) and os.environ.get("EBOS_RESIDENT_PAD", "1") == "0":   # (the library checks that the padding fits the windows)
+            return False
+        if self.blur_sigma > 0 and os.environ.get("EBOS_RESIDENT_BLUR", "1") == "0":
+            return False
+        if crowded_for_resident(plan):
+            return False
+        return bool(getattr(self.lib, self._supported_fn)(ctypes.byref(self._resident_problem(query=True))))
+
+    def enqueue_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> torch.Tensor:
+        """Enqueue ``n_iter`` iterations as one resident launch on the current stream WITHOUT waiting for it; returns the launch's
+        status word as a 1-element int32 tensor (a stream-ordered copy).  0 = completed.  Otherwise the low 8 bits say why it ended
+        early -- 1 a wait passed its cap, 2 a tap left the largest LDS window (bits 8 and up: the iteration k it happened in), 3
+        geometry, 4 a crowded tile -- and theta / exp_avg / exp_avg_sq / step / losses are unchanged, EXCEPT after a spill in
+        iteration k >= 1: the launch then handed over the state of its k completed iterations (``ebos_cmax_resident_iterations``).
+        ``self.t`` is advanced by ``n_iter`` here regardless: a caller that sees a non-zero word must not continue this loop
+        object (solver.WindowPipeline solves such a window again from its start); everybody else: ``run``, which books what
+        really happened."""
+        if self._mailbox is None:
+            H, W = self.plan.image_size
+            nb = int(self.lib.ebos_cmax_resident_mailbox_bytes(H, W, self.plan.tile[0], self.plan.tile[1]))
+            self._mailbox = torch.zeros(nb, dtype=torch.uint8, device=self.plan.device)
+        check(getattr(self.lib, self._solve_fn)(ctypes.byref(self._resident_problem()), int(n_iter), ptr(self._mailbox),
+                                                self._mailbox.numel(), float(spin_timeout_s), stream_ptr()),
+              self._solve_fn[:-len("_f32")])
+        self.t += int(n_iter)
+        self.last_run_mode = "resident"
+        return self._mailbox[:4].view(torch.int32).clone()
+
+    def run_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> int:
+        """``n_iter`` iterations as one resident launch; returns its status after synchronising: 0, or a negative code when the
+        launch ended early (-101 a wait passed the cap, -102 a tap left the largest LDS window -- or, with the blurred contrast, the
+        windows outgrew the blur's LDS region --, -103 geometry, -104 one tile far more crowded than the average one: the
+        pipeline's work items split such tiles).  theta and the optimiser state are then UNCHANGED -- except after -102 in iteration
+        k >= 1: ``self.resident_iterations`` = k iterations were completed and handed over (state, losses, step counter are those of
+        k iterations) -- and the caller runs the four-launch pipeline for the rest (``run`` does)."""
+        t, mode = self.t, self.last_run_mode
+        self.enqueue_resident(n_iter, spin_timeout_s)
+        self.t, self.last_run_mode = t, mode   # (``run`` books the iterations once it has seen the status)
+        status = int(self.lib.ebos_cmax_resident_status(ptr(self._mailbox), stream_ptr()))
+        # iterations the launch completed: all of them, none -- or, after a spill in iteration k >= 1, the k before it (the state IS
+        # that of k iterations then: the launch hands over instead of discarding its work)
+        self.resident_iterations = int(self.lib.ebos_cmax_resident_iterations(ptr(self._mailbox), stream_ptr()))
+        if self.resident_iterations < 0:
+            raise ResidentStateTorn("resident launch ended with two different verdicts among its workgroups (a wait past its cap AND a "
+                                    "hand-over): theta and the optimiser state are partly written -- rebuild the loop from a saved state")
+        return status
+
+    def _run(self, n_iter: int, resident: Optional[bool], pipeline) -> torch.Tensor:
+        """``run``: the resident attempt and its booking, then ``pipeline(k)`` -- which runs k iterations as launches and advances
+        ``self.t`` -- for whatever the resident launch left."""
+        n_iter = n_total = int(n_iter)
+        if self.t + n_iter > self.losses.numel():
+            raise ValueError(f"capacity {self.losses.numel()} < {self.t} steps done + {n_iter}")
+        t0 = self.t
+        if resident is None:
+            # (a launch that ended with -104 -- one tile far more crowded than the average: the pipeline splits such tiles -- or with
+            # -102 -- displacements beyond the largest LDS window: the pipeline's spill path -- is not tried again on this window)
+            resident = os.environ.get("EBOS_RESIDENT", "1") != "0" and not self._resident_refused and self.resident_supported()
+        elif resident and not self.resident_supported():
+            raise ValueError("resident=True: " + (self.lib.ebos_last_error() or b"").decode())
+        self.last_run_mode = "pipeline"
+        with _hip.on_device(self.plan.device):
+            if resident and n_iter > 0:
+                self.resident_status = self.run_resident(n_iter)
+                # (a wait past its cap -- the grid could not become co-resident, e.g. another process on the device --, flows beyond
+                # the windows, a crowded tile: not tried again on this window)
+                self._resident_refused = self.resident_status in (-101, -102, -104)
+                if self.resident_status == 0:
+                    self.t += n_iter
+                    self.last_run_mode = "resident"
+                    return self.losses[t0:t0 + n_iter]
+                if self.resident_status == -102 and self.resident_iterations > 0:
+                    # a flow left the LDS windows in iteration k: the first k iterations are done (state, losses, step counter);
+                    # the launches below continue with the rest
+                    self.t += self.resident_iterations
+                    n_iter -= self.resident_iterations
+                    self.last_run_mode = "resident+pipeline"
+            pipeline(n_iter)
+        return self.losses[t0:t0 + n_total]
+
+
+class FusedPatchLoop(_ResidentLoop):
+    _supported_fn, _solve_fn = "ebos_cmax_resident_supported", "ebos_cmax_patch_solve_resident_f32"
+
     def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
                  w_variance: float, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0, omit_boundary: bool = False,
                  pad: int = 0, halo: int = 32, lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, capacity: int = 1024,
@@ -126,7 +263,7 @@ class FusedPatchLoop(object):
         # themselves (ebos_iwe_patch_*): no upsample / adjoint launches, no [2, H, W] flow and gradient fields
         # (a window of fractional source coordinates -- undistorted events -- takes them on the compact layout WITH the fractions per
         # slot: general event loops, ebos_iwe_patch_slab_frac_f32 / _tiled_bwd_frac_f32; EBOS_FRAC_GRID=0: its dense route, A/B)
-        frac_ok = plan.frac_compact is not None and os.environ.get("EBOS_FRAC_GRID", "1") != "0"
+        frac_ok = plan.fractional and os.environ.get("EBOS_FRAC_GRID", "1") != "0"
         can = bool((plan.compact or frac_ok) and self.lib.ebos_patch_fused_supported(plan.tile[0], plan.tile[1], self.halo, self.slide[0],
                                                                                     self.slide[1]))
         if sample_grid and not can:
@@ -171,15 +308,9 @@ class FusedPatchLoop(object):
         self.reg_partials = torch.zeros(max(self.n_reg, 1), dtype=torch.float64, device=dev)
         self.ws = _workspace(plan, self.pad, self.halo, self.splits)
         self.graphed = False  # kept for callers that report it: this loop is never graph-replayed
-        self._mailbox = None          # flags / records / status word of the resident launch (allocated on first use)
-        self.resident_status = 0      # status of the last resident launch (0 = completed)
-        self.resident_iterations = 0  # iterations it completed
-        self.last_run_mode = "pipeline"
-        self._resident_refused = False
-        import ctypes as C
-        off, n_parts, n_px = C.c_size_t(), C.c_int64(), C.c_int64()
+        off, n_parts, n_px = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int64()
         check(self.lib.ebos_iwe_slab_partials(H, W, plan.tile[0], plan.tile[1], self.halo, self.splits, self.pad[0], self.pad[1],
-                                              int(self.omit), C.byref(off), C.byref(n_parts), C.byref(n_px)),
+                                              int(self.omit), ctypes.byref(off), ctypes.byref(n_parts), ctypes.byref(n_px)),
               "ebos_iwe_slab_partials")
         self._var_partials = (off.value, n_parts.value, n_px.value)
 
@@ -285,22 +416,9 @@ class FusedPatchLoop(object):
                 loss = loss + self.reg_partials.sum().to(torch.float32)
         return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask)
 
-    def _resident_problem(self) -> "_hip.CmaxPatchProblem":
-        """``problem()`` for the resident launch: a BUILT halo of 32 becomes "run-time windows of at most 32 px" where the plan knows
-        its |dt| bound -- with every window the full one the resident kernel publishes and re-reads the image in every iteration
-        and scatters in f64 (45.7 us per iteration at 2 M events: no faster than the four launches; 28.9 with run-time windows).
-        Values are the same; the gradient's fixed-point unit follows the staged window, so against the four-launch pipeline at the
-        built halo the trajectory agrees to rounding (~1e-6 per iteration), not bit for bit -- with ``halo="auto"`` it is identical."""
-        q = self.problem()
-        if self.halo >= 0 and self.plan.dt_bound is not None:
-            q.halo = int(self.lib.ebos_halo_auto(int(self.halo), float(self.plan.dt_bound)))
-        frac = self.plan.frac_compact
-        if frac is not None:  # a window of undistorted events: the compact layout with the fractions per slot (FRAC kernels)
-            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = (ptr(t) for t in frac)
-        return q
-
-    def problem(self) -> "_hip.CmaxPatchProblem":
-        """The loop's buffers as the ``ebos_cmax_patch_problem`` struct of the C ABI."""
+    def problem(self, query: bool = False) -> "_hip.CmaxPatchProblem":
+        """The loop's buffers as the ``ebos_cmax_patch_problem`` struct of the C ABI (``query``: for a supported check, which builds
+        no fraction layout -- ``EventPlan._frac_ptrs``)."""
         plan = self.plan
         H, W = plan.image_size
         gp, cp, cd = plan._compact_ptrs()
@@ -327,7 +445,7 @@ class FusedPatchLoop(object):
         q.grad_partials_bytes = self.grad_partials.numel() * 4 if self.grad_partials is not None else 0
         q.blur_k0, q.blur_k1, q.blur_image = self.blur[0], self.blur[1], ptr(self.blur_image)
         if self.sample_grid and not plan.compact:  # fractional source coordinates: the compact layout with the fractions per slot
-            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = self._grid_ptrs()
+            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = plan._frac_ptrs(query)
         return q
 
     def _grid_ptrs(self):
@@ -336,71 +454,20 @@ class FusedPatchLoop(object):
         plan = self.plan
         if plan.compact:
             return plan._compact_ptrs() + (None, None)
-        return tuple(ptr(t) for t in plan.frac_compact)
+        return plan._frac_ptrs()
 
-    def resident_supported(self) -> bool:
-        """Can ``run`` take the ONE-launch resident kernel (ebos_cmax_patch_solve_resident_f32)?  Grid-sampling route, either
-        contrast (the blurred image with the variance only), image padding below half a tile, a tile / halo with a resident kernel, few enough tiles to
-        be co-resident.  (The resident kernel runs one workgroup per tile whatever the plan's work-item table says: against a
-        pipeline that split crowded tiles it agrees to rounding, not bit for bit.)"""
-        frac = self.plan.frac_compact is not None   # fractional source coordinates: the four launches run the dense route, the resident
-        # launch the compact layout with the fractions per slot (62 -> 31 us per iteration at 2 M events)
-        if not (self.sample_grid or frac) or self.splits not in (0, 1):
-            return False
-        if self.pad != (0, 0) and os.environ.get("EBOS_RESIDENT_PAD", "1") == "0":   # (the library checks that the padding fits the windows)
+    def _resident_gates(self) -> bool:
+        """(``resident_supported``) the grid-sampling route, or fractional source coordinates -- the four launches run the dense
+        route, the resident launch the compact layout with the fractions per slot (62 -> 31 us per iteration at 2 M events) --;
+        either contrast, the blurred image with the variance only."""
+        frac = self.plan.fractional
+        if not (self.sample_grid or frac):
             return False
         if frac and os.environ.get("EBOS_RESIDENT_FRAC", "1") == "0":
             return False
         if self.w_gm and os.environ.get("EBOS_RESIDENT_GM", "1") == "0":
             return False
-        if crowded_for_resident(self.plan):
-            return False
-        if self.blur_sigma > 0 and not (RESIDENT_BLUR and os.environ.get("EBOS_RESIDENT_BLUR", "1") != "0"):
-            return False
-        import ctypes
-
-        return bool(self.lib.ebos_cmax_resident_supported(ctypes.byref(self._resident_problem())))
-
-    def enqueue_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> torch.Tensor:
-        """Enqueue ``n_iter`` iterations as one resident launch on the current stream WITHOUT waiting for it; returns the launch's
-        status word as a 1-element int32 tensor (a stream-ordered copy).  0 = completed.  Otherwise the low 8 bits say why it ended
-        early -- 1 a wait passed its cap, 2 a tap left the largest LDS window (bits 8 and up: the iteration k it happened in), 3
-        geometry, 4 a crowded tile -- and theta / exp_avg / exp_avg_sq / step / losses are unchanged, EXCEPT after a spill in
-        iteration k >= 1: the launch then handed over the state of its k completed iterations (``ebos_cmax_resident_iterations``).
-        ``self.t`` is advanced by ``n_iter`` here regardless: a caller that sees a non-zero word must not continue this loop
-        object (solver.WindowPipeline solves such a window again from its start); everybody else: ``run``, which books what
-        really happened."""
-        import ctypes
-
-        if self._mailbox is None:
-            H, W = self.plan.image_size
-            nb = int(self.lib.ebos_cmax_resident_mailbox_bytes(H, W, self.plan.tile[0], self.plan.tile[1]))
-            self._mailbox = torch.zeros(nb, dtype=torch.uint8, device=self.plan.device)
-        check(self.lib.ebos_cmax_patch_solve_resident_f32(ctypes.byref(self._resident_problem()), int(n_iter), ptr(self._mailbox),
-                                                          self._mailbox.numel(), float(spin_timeout_s), stream_ptr()),
-              "ebos_cmax_patch_solve_resident")
-        self.t += int(n_iter)
-        self.last_run_mode = "resident"
-        return self._mailbox[:4].view(torch.int32).clone()
-
-    def run_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> int:
-        """``n_iter`` iterations as one resident launch; returns its status after synchronising: 0, or a negative code when the
-        launch ended early (-101 a wait passed the cap, -102 a tap left the largest LDS window -- or, with the blurred contrast, the
-        windows outgrew the blur's LDS region --, -103 geometry, -104 one tile far more crowded than the average one: the
-        pipeline's work items split such tiles).  theta and the optimiser state are then UNCHANGED -- except after -102 in iteration
-        k >= 1: ``self.resident_iterations`` = k iterations were completed and handed over (state, losses, step counter are those of
-        k iterations) -- and the caller runs the four-launch pipeline for the rest (``run`` does)."""
-        t, mode = self.t, self.last_run_mode
-        self.enqueue_resident(n_iter, spin_timeout_s)
-        self.t, self.last_run_mode = t, mode   # (``run`` books the iterations once it has seen the status)
-        status = int(self.lib.ebos_cmax_resident_status(ptr(self._mailbox), stream_ptr()))
-        # iterations the launch completed: all of them, none -- or, after a spill in iteration k >= 1, the k before it (the state IS
-        # that of k iterations then: the launch hands over instead of discarding its work)
-        self.resident_iterations = int(self.lib.ebos_cmax_resident_iterations(ptr(self._mailbox), stream_ptr()))
-        if self.resident_iterations < 0:
-            raise ResidentStateTorn("resident launch ended with two different verdicts among its workgroups (a wait past its cap AND a "
-                                    "hand-over): theta and the optimiser state are partly written -- rebuild the loop from a saved state")
-        return status
+        return not (self.blur_sigma > 0 and not RESIDENT_BLUR)
 
     def run(self, n_iter: int, native: bool = True, resident: Optional[bool] = None) -> torch.Tensor:
         """``n_iter`` more iterations; returns their losses [n_iter] (device).
@@ -410,52 +477,26 @@ class FusedPatchLoop(object):
         ``native`` (default): one C call enqueues the whole loop (ebos_cmax_patch_solve_f32); otherwise one Python call
         per kernel group.  (A HIP-graph replay of the iteration was measured slower than plain launches on ROCm 7.2 --
         172 vs 111 us at 2 M events -- and cannot carry the step number, which is a kernel argument.)"""
-        n_iter = n_total = int(n_iter)
-        if self.t + n_iter > self.losses.numel():
-            raise ValueError(f"capacity {self.losses.numel()} < {self.t} steps done + {n_iter}")
-        t0 = self.t
-        if resident is None:
-            # (a launch that ended with -104 -- one tile far more crowded than the average: the pipeline splits such tiles -- or with
-            # -102 -- displacements beyond the largest LDS window: the pipeline's spill path -- is not tried again on this window)
-            resident = native and os.environ.get("EBOS_RESIDENT", "1") != "0" and not self._resident_refused and self.resident_supported()
-        elif resident and not self.resident_supported():
-            raise ValueError("resident=True: " + (self.lib.ebos_last_error() or b"").decode())
-        self.last_run_mode = "pipeline"
-        with _hip.on_device(self.plan.device):
-            if resident and n_iter > 0:
-                self.resident_status = self.run_resident(n_iter)
-                # (a wait past its cap -- the grid could not become co-resident, e.g. another process on the device --, flows beyond
-                # the windows, a crowded tile: not tried again on this window)
-                self._resident_refused = self.resident_status in (-101, -102, -104)
-                if self.resident_status == 0:
-                    self.t += n_iter
-                    self.last_run_mode = "resident"
-                    return self.losses[t0:t0 + n_iter]
-                if self.resident_status == -102 and self.resident_iterations > 0:
-                    # a flow left the LDS windows in iteration k: the first k iterations are done (state, losses, step counter);
-                    # the four launches below continue with the rest
-                    self.t += self.resident_iterations
-                    n_iter -= self.resident_iterations
-                    self.last_run_mode = "resident+pipeline"
-            if not native and self.blur_sigma > 0:
-                raise NotImplementedError("blur_sigma > 0 needs native=True")
-            if native:
-                import ctypes
+        return self._run(n_iter, False if resident is None and not native else resident,
+                         self._pipeline if native else self._iterations)
 
-                check(self.lib.ebos_cmax_patch_solve_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()),
-                      "ebos_cmax_patch_solve")
-                self.t += n_iter
-            else:
-                for _ in range(n_iter):
-                    self.iteration()
-        return self.losses[t0:t0 + n_total]
+    def _pipeline(self, n_iter: int) -> None:
+        check(self.lib.ebos_cmax_patch_solve_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_patch_solve")
+        self.t += n_iter
+
+    def _iterations(self, n_iter: int) -> None:
+        if self.blur_sigma > 0:
+            raise NotImplementedError("blur_sigma > 0 needs native=True")
+        for _ in range(n_iter):
+            self.iteration()
 
 
-class Fused2dofLoop(object):
+class Fused2dofLoop(_ResidentLoop):
     """The Adam loop of the 2-DoF motion model ("2d-translation" / "rigid-optical-flow": x' = x + dt theta, src/warp.py:364-383)
     on loss(theta) = -w var([blur3] IWE(theta)), enqueued natively (ebos_cmax_2dof_solve_f32): four launches per iteration (five
     with iwe.blur_sigma > 0), no host synchronisation -- the loop shape of src/solver/generative_max_likelihood.py:306-341 that
     configs/hot_plate1.yaml:47,65,70 selects (Adam, n_iter 600, blur_sigma 3)."""
+    _supported_fn, _solve_fn = "ebos_cmax_2dof_resident_supported", "ebos_cmax_2dof_solve_resident_f32"
 
     def __init__(self, plan: EventPlan, theta0: torch.Tensor, w_variance: float = 1.0, omit_boundary: bool = False, pad: int = 0,
                  halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, capacity: int = 1024,
@@ -492,81 +533,19 @@ class Fused2dofLoop(object):
         self.losses = torch.zeros(max(int(capacity), 1), **f32)
         self.splits = plan.resolve_loop_splits(splits)
         self.ws = _workspace(plan, self.pad, self.halo, self.splits)
-        self.last_run_mode = "pipeline"
-        self._mailbox = None
-        self.resident_status = 0
-        self.resident_iterations = 0
-        self._resident_refused = False
 
-    def _resident_problem(self) -> "_hip.Cmax2dofProblem":
-        """``problem()`` for the resident launch: a BUILT halo becomes "run-time windows of at most that many pixels" where the plan
-        knows its |dt| bound (as ``FusedPatchLoop._resident_problem``)."""
-        q = self.problem()
-        if self.halo >= 0 and self.plan.dt_bound is not None:
-            q.halo = int(self.lib.ebos_halo_auto(int(self.halo), float(self.plan.dt_bound)))
-        fr = self.plan.frac_compact
-        if not self.plan.compact and fr is not None:  # fractional source coordinates: the compact layout with the fractions
-            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = (ptr(t) for t in fr)
-        return q
-
-    def resident_supported(self) -> bool:
-        """Can ``run`` take the ONE-launch resident kernel (ebos_cmax_2dof_solve_resident_f32)?  Compact plan -- of integer source
-        pixels, or with the fractions of undistorted events (``EventPlan.frac_compact``) --, image padding below half a tile, a tile /
-        halo with a resident kernel."""
-        import ctypes
-
-        if not (self.plan.compact or self.plan.frac_compact is not None) or self.splits not in (0, 1):
-            return False
-        if self.pad != (0, 0) and os.environ.get("EBOS_RESIDENT_PAD", "1") == "0":   # (the library checks that the padding fits the windows)
-            return False
-        if self.blur_sigma > 0 and os.environ.get("EBOS_RESIDENT_BLUR", "1") == "0":
-            return False
-        if crowded_for_resident(self.plan):
-            return False
-        return bool(self.lib.ebos_cmax_2dof_resident_supported(ctypes.byref(self._resident_problem())))
-
-    def enqueue_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> torch.Tensor:
-        """Enqueue ``n_iter`` iterations as one resident launch on the current stream WITHOUT waiting for it; returns the launch's
-        status word as a 1-element int32 tensor (a stream-ordered copy; 0 = completed -- as ``FusedPatchLoop.enqueue_resident``).
-        ``self.t`` is advanced by ``n_iter`` regardless: a caller that sees a non-zero word solves the window again
-        (solver.WindowPipeline does); everybody else: ``run``."""
-        import ctypes
-
-        if self._mailbox is None:
-            H, W = self.plan.image_size
-            nb = int(self.lib.ebos_cmax_resident_mailbox_bytes(H, W, self.plan.tile[0], self.plan.tile[1]))
-            self._mailbox = torch.zeros(nb, dtype=torch.uint8, device=self.plan.device)
-        check(self.lib.ebos_cmax_2dof_solve_resident_f32(ctypes.byref(self._resident_problem()), int(n_iter), ptr(self._mailbox),
-                                                         self._mailbox.numel(), float(spin_timeout_s), stream_ptr()),
-              "ebos_cmax_2dof_solve_resident")
-        self.t += int(n_iter)
-        self.last_run_mode = "resident"
-        return self._mailbox[:4].view(torch.int32).clone()
-
-    def run_resident(self, n_iter: int, spin_timeout_s: float = 2.0) -> int:
-        """``n_iter`` iterations as one resident launch; returns its status after synchronising (0, or -101 ... -104 as
-        ``FusedPatchLoop.run_resident``; after -102 ``resident_iterations`` of them are done and handed over)."""
-        t, mode = self.t, self.last_run_mode
-        self.enqueue_resident(n_iter, spin_timeout_s)
-        self.t, self.last_run_mode = t, mode   # (``run`` books the iterations once it has seen the status)
-        status = int(self.lib.ebos_cmax_resident_status(ptr(self._mailbox), stream_ptr()))
-        self.resident_iterations = int(self.lib.ebos_cmax_resident_iterations(ptr(self._mailbox), stream_ptr()))
-        if self.resident_iterations < 0:
-            raise ResidentStateTorn("resident launch ended with two different verdicts among its workgroups: theta and the optimiser "
-                               "state are partly written -- rebuild the loop from a saved state")
-        return status
-
-    def problem(self) -> "_hip.Cmax2dofProblem":
+    def problem(self, query: bool = False) -> "_hip.Cmax2dofProblem":
+        """The loop's buffers as the ``ebos_cmax_2dof_problem`` struct of the C ABI (``query``: as ``FusedPatchLoop.problem``)."""
         plan = self.plan
         H, W = plan.image_size
         gp, cp, cd = plan._compact_ptrs()
         q = _hip.Cmax2dofProblem()
         q.xs, q.ys, q.dts = ptr(plan.x), ptr(plan.y), ptr(plan.dt)
         q.grp_offsets, q.cpix, q.cdt, q.key_offsets, q.n = gp, cp, cd, ptr(plan.key_offsets), plan.n
-        if plan.frac_compact is not None and os.environ.get("EBOS_FRAC_GRID", "1") != "0":
+        if plan.fractional and os.environ.get("EBOS_FRAC_GRID", "1") != "0":
             # fractional source coordinates: the compact layout with the fractions per slot (the launches and the resident kernel then
             # run the same arithmetic; EBOS_FRAC_GRID=0: the launches on the (x, y, dt) arrays)
-            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = (ptr(t) for t in plan.frac_compact)
+            q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = plan._frac_ptrs(query)
         q.H, q.W, q.tile_h, q.tile_w, q.halo = H, W, plan.tile[0], plan.tile[1], self.halo
         q.pad_h, q.pad_w, q.omit_boundary = self.pad[0], self.pad[1], int(self.omit)
         q.splits, q.part_table = self.splits, ptr(plan.part_table)
@@ -589,29 +568,8 @@ class Fused2dofLoop(object):
         ``resident_supported()``; ``EBOS_RESIDENT=0`` turns the default off): the whole loop as ONE resident launch (one
         synchronisation, to read its status); a launch that ends early leaves the state untouched -- or, after a hand-over in
         iteration k, that of k iterations -- and the four (five) launches per iteration below run the rest."""
-        import ctypes
+        return self._run(n_iter, resident, self._pipeline)
 
-        n_iter = n_total = int(n_iter)
-        if self.t + n_iter > self.losses.numel():
-            raise ValueError(f"capacity {self.losses.numel()} < {self.t} steps done + {n_iter}")
-        t0 = self.t
-        if resident is None:
-            resident = os.environ.get("EBOS_RESIDENT", "1") != "0" and not self._resident_refused and self.resident_supported()
-        elif resident and not self.resident_supported():
-            raise ValueError("resident=True: " + (self.lib.ebos_last_error() or b"").decode())
-        self.last_run_mode = "pipeline"
-        with _hip.on_device(self.plan.device):
-            if resident and n_iter > 0:
-                self.resident_status = self.run_resident(n_iter)
-                self._resident_refused = self.resident_status in (-101, -102, -104)
-                if self.resident_status == 0:
-                    self.t += n_iter
-                    self.last_run_mode = "resident"
-                    return self.losses[t0:t0 + n_iter]
-                if self.resident_status == -102 and self.resident_iterations > 0:
-                    self.t += self.resident_iterations
-                    n_iter -= self.resident_iterations
-                    self.last_run_mode = "resident+pipeline"
-            check(self.lib.ebos_cmax_2dof_solve_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_2dof_solve")
+    def _pipeline(self, n_iter: int) -> None:
+        check(self.lib.ebos_cmax_2dof_solve_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_2dof_solve")
         self.t += n_iter
-        return self.losses[t0:t0 + n_total]

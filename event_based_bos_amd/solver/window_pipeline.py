@@ -224,10 +224,7 @@ class WindowPipeline(object):
                     losses[w].append(lp.losses[:n_iter].clone())
             last = (patch_size, sliding_window)
         for w, plan in enumerate(plans):  # the plan was built on the ingest stream and read on streams[w]
-            for t in (plan.x, plan.y, plan.dt, plan.p, plan.key_offsets, plan.perm, plan.grp_offsets, plan.cpix, plan.cdt,
-                      plan.part_table):
-                if t is not None:
-                    t.record_stream(streams[w])
+            plan.record_stream(streams[w])
         return [dict(theta=thetas[w], losses=losses[w], patch=last, counts=plans[w].__dict__.get("_counts"), status=statuses[w],
                      modes=modes[w]) for w in range(len(plans))]
 
@@ -252,9 +249,7 @@ class WindowPipeline(object):
                         check(self.lib.ebos_cmax_2dof_solve_f32(ctypes.byref(loop.problem()), int(s.n_iter), stream_ptr()), "ebos_cmax_2dof_solve")
                 out.append(dict(theta=loop.theta.clone(), losses=[loop.losses[:s.n_iter].clone()], patch=None,
                                 counts=plan.__dict__.get("_counts"), status=status, modes=[mode]))
-            for t in (plan.x, plan.y, plan.dt, plan.p, plan.key_offsets, plan.perm, plan.grp_offsets, plan.cpix, plan.cdt, plan.part_table):
-                if t is not None:
-                    t.record_stream(streams[w])
+            plan.record_stream(streams[w])
         return out
 
     # ------------------------------------------------------------------ driver

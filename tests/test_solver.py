@@ -1655,3 +1655,98 @@ def test_resident_2dof_loop_with_outer_padding(size, n_ev, pad, omit, sigma, fra
     assert torch.equal(ref.iwe, res.iwe) or float((ref.iwe - res.iwe).abs().max()) <= 1e-5 * float(ref.iwe.abs().max())
     np.testing.assert_allclose(l_res, l_ref, rtol=2e-6)
     np.testing.assert_allclose(res.theta.cpu().numpy(), ref.theta.cpu().numpy(), rtol=0, atol=1e-4)
+
+
+def _scripted_resident_loop(outcomes):
+    """A loop whose resident launches end as scripted ((status, iterations completed) or "torn"): ``run``'s booking without a GPU."""
+    from event_based_bos_amd.solver import fused_loop
+
+    class Loop(fused_loop._ResidentLoop):
+        plan = type("Plan", (), {"device": torch.device("cpu")})()
+
+        def __init__(self):
+            self.losses, self.t = torch.arange(32, dtype=torch.float32), 0
+            self.outcomes, self.launches, self.piped = list(outcomes), [], []
+
+        def resident_supported(self):
+            return True
+
+        def run_resident(self, n_iter, spin_timeout_s=2.0):
+            self.launches.append(n_iter)
+            outcome = self.outcomes.pop(0)
+            if outcome == "torn":
+                raise fused_loop.ResidentStateTorn("resident launch ended with two different verdicts (scripted)")
+            status, self.resident_iterations = outcome
+            return status
+
+        def run(self, n_iter, resident=None):
+            return self._run(n_iter, resident, self._pipeline)
+
+        def _pipeline(self, n_iter):
+            self.piped.append(n_iter)
+            self.t += n_iter
+
+    return Loop()
+
+
+def test_resident_run_booking(monkeypatch, caplog):
+    """The resident protocol both fused loops share: a completed launch; a hand-over after k iterations (-102: the launches run the
+    rest, the window is not tried again); a refusal (-104: all iterations as launches, not tried again); a torn launch, after which
+    ``run_rebuilding_torn`` solves the window again on a fresh loop with the launches."""
+    from event_based_bos_amd.solver import fused_loop
+
+    monkeypatch.delenv("EBOS_RESIDENT", raising=False)
+    done = _scripted_resident_loop([(0, 10)])
+    assert done.run(10).tolist() == list(range(10))
+    assert (done.t, done.last_run_mode, done.resident_status, done.launches, done.piped) == (10, "resident", 0, [10], [])
+    assert not done._resident_refused
+
+    handed = _scripted_resident_loop([(-102, 4)])
+    assert handed.run(10).tolist() == list(range(10))
+    assert (handed.t, handed.last_run_mode, handed.resident_iterations, handed.piped) == (10, "resident+pipeline", 4, [6])
+    handed.run(3)
+    assert (handed.t, handed.last_run_mode, handed.launches, handed.piped) == (13, "pipeline", [10], [6, 3])
+
+    refused = _scripted_resident_loop([(-104, 0)])
+    assert refused.run(10).tolist() == list(range(10))
+    assert (refused.t, refused.last_run_mode, refused.resident_status, refused.piped) == (10, "pipeline", -104, [10])
+    refused.run(2)
+    assert refused.launches == [10] and refused.piped == [10, 2] and refused.t == 12
+
+    with pytest.raises(ValueError, match="capacity"):
+        refused.run(30)
+
+    made = []
+
+    def make_loop():
+        made.append(_scripted_resident_loop(["torn"]))
+        return made[-1]
+
+    with caplog.at_level("WARNING"):
+        loop = fused_loop.run_rebuilding_torn(make_loop, 7, None)
+    assert len(made) == 2 and loop is made[1] and "re-solving the window with the four launches" in caplog.text
+    assert made[0].launches == [7] and loop.launches == [] and loop.piped == [7]
+    assert (loop.t, loop.last_run_mode) == (7, "pipeline")
+
+
+@pytest.mark.gpu
+def test_resident_supported_builds_no_fraction_layout():
+    """``resident_supported()`` of either loop on a fresh plan of fractional source coordinates asks ``EventPlan.fractional`` and
+    launches nothing: the fraction layout is built by the first launch that reads it."""
+    import event_based_bos_amd as ebos
+    from event_based_bos_amd.solver.fused_loop import Fused2dofLoop, FusedPatchLoop
+
+    h, w, n = 260, 346, 50_000
+    rs = np.random.RandomState(3)
+    ev = np.stack([rs.uniform(0, h - 1, n), rs.uniform(0, w - 1, n), np.sort(rs.uniform(0, 0.5, n)), rs.randint(0, 2, n)], 1)
+    plan = ebos.EventPlan.build(torch.from_numpy(ev).cuda(), (h, w), "first", True, tile="auto")
+    assert plan.fractional and not plan.compact and plan.__dict__["_frac"] is None
+    gh, gw = ebos.solver.patch_grid_shape((h, w), (20, 20), (20, 20))
+    patch = FusedPatchLoop(plan, (20, 20), (20, 20), torch.zeros((2, gh, gw)), 1.0, halo="auto", capacity=4)
+    two = Fused2dofLoop(plan, torch.tensor([1.0, -0.5]), 1.0, halo="auto", capacity=4)
+    assert patch.resident_supported(), ebos.load_library().ebos_last_error()
+    assert two.resident_supported(), ebos.load_library().ebos_last_error()
+    assert plan.__dict__["_frac"] is None
+    patch.run(2)
+    assert patch.last_run_mode == "resident" and plan.__dict__["_frac"] is not None
+    assert two.run(2).shape == (2,) and two.last_run_mode == "resident"
