@@ -14,6 +14,7 @@ tub-rip/event_based_bos:
     event_filters        the reference's BAF / HOT event filters and EventFilter, on the GPU
     flow_error           the reference's flow-error metrics (EPE, NPE, AE), batched, on the GPU
     poisson              the reference's Poisson integration of a flow (and its uint8 picture), batched, on fp64 matrix cores
+    frame_flow           the reference's frame-based flow (cv2.calcOpticalFlowFarneback, FrameFlowEstimator), batched
     data_loader          raw-column event store (the CCS raw_events layout) feeding EventPlan.build_raw
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
@@ -24,6 +25,6 @@ from ._hip import HipUnavailableError, load_library  # noqa: F401
 from .warp import MotionModelKeyError, Warp  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
 from .event_plan import EventPlan, SlabBatch  # noqa: F401
-from . import costs, data_loader, event_filters, flow_error, fusion, ops, poisson, solver, types, utils  # noqa: F401
+from . import costs, data_loader, event_filters, flow_error, frame_flow, fusion, ops, poisson, solver, types, utils  # noqa: F401
 
 __version__ = "0.1.0"

@@ -217,6 +217,8 @@ SIGNATURES = {
     "ebos_flow_error": (_I, [_I, _I, _I, _I, _P, _L, _L, _L, _P, _L, _L, _L, _P, _L, _L, _P, _I, _P, _P, _Z, _P]),
     "ebos_poisson_scratch_bytes": (_Z, [_I, _I, _I]),
     "ebos_poisson_reconstruct": (_I, [_I, _I, _I, _I, _I, _P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _Z, _P]),
+    "ebos_farneback_scratch_bytes": (_Z, [_I, _I, _I, _I]),
+    "ebos_farneback": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _D, _I, _I, _I, _I, _D, _I, _P, _L, _L, _L, _L, _P, _Z, _P]),
     "ebos_gml_scratch_bytes": (_Z, [_I, _I, _I]),
     "ebos_gml_prepare_f64": (_I, [_I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ebos_gml_normalize_f64": (_I, [_L, _P, _P, _Z, _P]),
@@ -236,6 +238,7 @@ FILTER_SRC_F32, FILTER_SRC_F64, FILTER_SRC_RAW32, FILTER_SRC_RAW64 = 0, 1, 2, 3
 FILTER_STATUS_OUT_OF_SENSOR, FILTER_STATUS_CLIPPED = 0, 1
 FLOW_ERROR_F32, FLOW_ERROR_F64, FLOW_ERROR_CLAMP_AE = 0, 1, 1
 POISSON_F32, POISSON_F64 = 0, 1
+FARNEBACK_U8, FARNEBACK_F32, FARNEBACK_F64 = 0, 1, 2
 
 
 class EventSource(C.Structure):

@@ -6,7 +6,8 @@ over the whole event array per patch, only to count -- is replaced by ``EventPla
 
 The reference's event filters are re-exported from ``event_filters`` under their names, as src/utils/__init__.py:2 does, and
 its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does, and its Poisson integration and
-``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does.
+``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does, and ``bos_optical_flow`` and
+``pad_to_same_resolution`` from ``frame_flow``, as src/utils/__init__.py:34-42 does.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -60,3 +61,4 @@ from .event_filters import (EventFilter, background_activity_filter, continuous_
 from .flow_error import calculate_flow_error_numpy, calculate_flow_error_tensor, flow_error_batch  # noqa: E402,F401
 from .poisson import (poisson_image, poisson_reconstruct, poisson_reconstruct_batch,  # noqa: E402,F401
                       standardize_image_center)
+from .frame_flow import bos_optical_flow, pad_to_same_resolution  # noqa: E402,F401

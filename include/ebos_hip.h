@@ -1031,6 +1031,38 @@ int ebos_poisson_reconstruct(int in_dtype, int out_dtype, int B, int H, int W, c
                              int64_t out_sr, uint8_t* out_u8, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * Dense optical flow between frame pairs: OpenCV's calcOpticalFlowFarneback with flags 0, the frame-based flow of the reference
+ * (src/frame_flow_estimator.py:30-95 -> src/utils/frame_utils.py:160-183), for B pairs (prev[b], next[b]) in one call.
+ *   per level k = levels' .. 0 (levels' cut where a side of the frame times pyr_scale^k falls below 32 pixels): both frames
+ *   converted to float32, Gaussian-blurred at full resolution (sigma_k = (1 / pyr_scale^k - 1) / 2, s = max(round(5 sigma_k) | 1, 3)
+ *   taps, BORDER_REFLECT_101) and resized INTER_LINEAR to round(H pyr_scale^k) x round(W pyr_scale^k); the polynomial expansion
+ *   (poly_n, poly_sigma); the starting flow (zero, or the coarser level's resized and divided by pyr_scale); `iterations` times the
+ *   (winsize / 2 * 2 + 1)^2 window sum of the matrices in float64, scaled by 1 / winsize^2, and the regularised 2 x 2 solve.
+ *   tests/_farneback_ref.py restates every step in numpy.
+ * No atomics and no host synchronisation: a pair's bits do not depend on B or on the run.
+ *
+ * in_dtype: EBOS_FARNEBACK_U8 / _F32 / _F64, the element type of prev and next (element strides prev_sb, prev_sr, next_sb,
+ * next_sr; unit columns).  prev_sb = 0 shares one prev frame among all pairs (it is then expanded once).  out: device float32, the
+ * flow (dx = column displacement, dy = row displacement) of pair b at row y, column x is out[b sb + y sr + x sx] = dx and
+ * out[b sb + sc + y sr + x sx] = dy (element strides; [H, W, 2] and [2, H, W] layouts, or a view inside a larger frame).
+ * pyr_scale in (0, 1), levels >= 0, winsize >= 1, iterations >= 1, poly_n 5 or 7, H, W >= 2, H * W < 2^31, B < 65535, else
+ * EBOS_ERR_INVALID_ARG; flags other than 0 (OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_FARNEBACK_GAUSSIAN) are EBOS_ERR_UNSUPPORTED.
+ * scratch: ebos_farneback_scratch_bytes(B, H, W, prev_sb == 0) bytes, 16-byte aligned (caller-owned); a short scratch is
+ * EBOS_ERR_SCRATCH.  4 + iterations launches per level on `stream`.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum ebos_farneback_dtype {
+  EBOS_FARNEBACK_U8 = 0,
+  EBOS_FARNEBACK_F32 = 1,
+  EBOS_FARNEBACK_F64 = 2
+} ebos_farneback_dtype;
+
+size_t ebos_farneback_scratch_bytes(int B, int H, int W, int prev_shared);
+int ebos_farneback(int in_dtype, int B, int H, int W, const void* prev, int64_t prev_sb, int64_t prev_sr, const void* next,
+                   int64_t next_sb, int64_t next_sr, double pyr_scale, int levels, int winsize, int iterations, int poly_n,
+                   double poly_sigma, int flags, float* out, int64_t out_sb, int64_t out_sc, int64_t out_sr, int64_t out_sx,
+                   void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Generative BOS solver (src/solver/patch_eklt_pyramid2.py, the reference YAML's patch_eklt_pyramid2), float64.
  *
  * ebos_gml_prepare_f64: per window, from the model image frame [H, W] (log(frame + 1) if use_log) and the polarity IWE
