@@ -230,6 +230,15 @@ SIGNATURES = {
     "ebos_gml_dep_init_f64": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "ebos_gml_dep_objective_f64": (_I, [_I] * 10 + [_P, _P, _I] + [_P] * 10 + [_Z, _P]),
     "ebos_gml_dep_solve_f64": (_I, [_I] * 10 + [_P, _P, _I] + [_P] * 7 + [_I, _D, _P, _P, _P, _Z, _P]),
+    # the window axis: n_windows first, strides next to the arrays they belong to
+    "ebos_gml_scratch_bytes_batch": (_Z, [_I, _I, _I, _I]),
+    "ebos_gml_prepare_batch_f64": (_I, [_I, _I, _I, _P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_gml_normalize_batch_f64": (_I, [_I, _L, _P, _P, _Z, _P]),
+    "ebos_gml_solve_scale_batch_f64": (_I, [_I] * 10 + [_P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _I, _D, _P, _L, _P, _P, _Z, _Z, _P]),
+    "ebos_gml_dep_scratch_bytes_batch": (_Z, [_I] * 11),
+    "ebos_gml_dep_select_batch": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _D, _P, _P, _P, _Z, _Z, _P]),
+    "ebos_gml_dep_init_batch_f64": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
+    "ebos_gml_dep_solve_batch_f64": (_I, [_I] * 11 + [_P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _D, _P, _L, _P, _P, _Z, _Z, _P]),
 }
 
 

@@ -74,6 +74,48 @@ struct GmlBufs {
 
 __host__ __device__ inline int64_t gml_npix(const GmlGeom& g) { return (int64_t)g.H * g.W; }
 
+// The window axis: every launch carries the window as gridDim.z, and window b = blockIdx.z works on its own slice of every
+// per-window array.  Strides between consecutive windows, in elements; all zero for a single window.  The body of a pass sees
+// only the view of its window, so window b is computed by the operations, in the order, of a single-window launch.
+struct GmlWin {
+  size_t grad;      // gx, gy (0: one model image for every window)
+  size_t field;     // q, we, winv
+  size_t x;         // the parameters [nd, gh, gw]
+  size_t scr;       // the scratch slice (S ... v), in doubles
+  size_t sel;       // the selection [gh, gw]
+  size_t hist;      // the history rows of one window, in doubles
+  size_t out;       // the flow [2, H, W] (or the gradient of the objective entries)
+};
+
+__device__ __forceinline__ GmlBufs gml_window(const GmlGeom& g, GmlBufs B, const GmlWin& w) {
+  const size_t b = blockIdx.z;
+  if (b == 0) {   // window 0 (a single window always): the buffers as they are; a uniform branch past ~60 scalar instructions
+    if (g.vel) B.S = B.x;
+    return B;
+  }
+  B.gx += b * w.grad;
+  B.gy += b * w.grad;
+  B.q += b * w.field;
+  if (B.we) B.we += b * w.field;
+  B.winv += b * w.field;
+  B.x += b * w.x;
+  const size_t o = b * w.scr;
+  B.S = g.vel ? B.x : B.S + o;   // the direct-velocity model: F = up(x[0:2])
+  B.P0 += o;
+  B.dF += o;
+  B.dT += o;
+  B.partA += o;
+  B.colpart += o;
+  B.colw += o;
+  B.scal += o;
+  B.gS += o;
+  B.gX += o;
+  B.m += o;
+  B.v += o;
+  if (B.sel) B.sel += b * w.sel;
+  return B;
+}
+
 size_t gml_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct GmlLayout {
@@ -224,7 +266,10 @@ __device__ __forceinline__ void block_sum(double (*sh)[kGmlBlock], double* v) {
 }
 
 // ---- prologue: S = Sobel3(x0) / 8, replicate borders -------------------------------------------------------------------
-__global__ void __launch_bounds__(kGmlBlock) gml_sobel(GmlGeom g, const double* __restrict__ x, double* __restrict__ S) {
+__global__ void __launch_bounds__(kGmlBlock) gml_sobel(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
+  const double* __restrict__ x = B.x;
+  double* __restrict__ S = B.S;
   const int G = g.gh * g.gw;
   const int k = blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= G) return;
@@ -244,7 +289,8 @@ __global__ void __launch_bounds__(kGmlBlock) gml_sobel(GmlGeom g, const double* 
 }
 
 // ---- pass A ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_a(GmlGeom g, GmlBufs B) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_a(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
   __shared__ double sh[3][kGmlBlock];
   const int64_t n = gml_npix(g);
   const int G = g.gh * g.gw;
@@ -298,7 +344,8 @@ __device__ double gml_norm(const GmlGeom& g, const double* __restrict__ partA, d
 }
 
 // ---- pass B ---------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_b(GmlGeom g, GmlBufs B) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_b(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
   __shared__ double sh[1][kGmlBlock];
   const double N = gml_norm(g, B.partA, sh);
   const double den = N + 0.0001;
@@ -318,7 +365,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_b(GmlGeom g, GmlBufs B) {
 }
 
 // ---- pass C (one workgroup) -------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_c(GmlGeom g, GmlBufs B, double* __restrict__ hist_row) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_c(GmlGeom g, GmlBufs B0, GmlWin win, double* __restrict__ hist_row) {
+  const GmlBufs B = gml_window(g, B0, win);
+  if (hist_row) hist_row += blockIdx.z * win.hist;
   __shared__ double sh[3][kGmlBlock];
   __shared__ double s_max;
   __shared__ int s_ties;
@@ -407,7 +456,8 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_c(GmlGeom g, GmlBufs B, do
 }
 
 // ---- pass D -----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_d(GmlGeom g, GmlBufs B) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_d(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
   const int64_t n = gml_npix(g);
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= n) return;
@@ -532,7 +582,8 @@ __device__ __forceinline__ void cell_gather(const GmlGeom& g, const GmlBufs& B, 
   }
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
   __shared__ double sh[4][kGmlBlock];
   const int cell = blockIdx.x;
   const int gi = cell / g.gw, gj = cell % g.gw;
@@ -552,7 +603,8 @@ __global__ void __launch_bounds__(kGmlBlock) gml_pass_e(GmlGeom g, GmlBufs B) {
 }
 
 // small slides (a cell reaches some (2s + 3)^2 pixels): one thread per cell, its rectangle in row-major order
-__global__ void __launch_bounds__(kGmlBlock) gml_pass_e_cell(GmlGeom g, GmlBufs B) {
+__global__ void __launch_bounds__(kGmlBlock) gml_pass_e_cell(GmlGeom g, GmlBufs B0, GmlWin win) {
+  const GmlBufs B = gml_window(g, B0, win);
   const int G = g.gh * g.gw;
   const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
   if (cell >= G) return;
@@ -574,7 +626,8 @@ struct AdamArgs {
   int step;   // 0: write the gradient to `grad_out` instead of stepping
 };
 
-__global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B, AdamArgs a, double* __restrict__ grad_out) {
+__global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B0, GmlWin win, AdamArgs a, double* __restrict__ grad_out) {
+  const GmlBufs B = gml_window(g, B0, win);
   const int G = g.gh * g.gw;
   const int k = blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= g.nd * G) return;
@@ -603,7 +656,7 @@ __global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B, Adam
   }
   if (B.sel && B.sel[cell] == 0) grad = 0.0;   // no parameter: from zero state Adam leaves x at exactly 0
   if (!a.step) {
-    grad_out[k] = grad;
+    grad_out[blockIdx.z * win.out + k] = grad;
     return;
   }
   // torch.optim.Adam, single-tensor path: lerp, mul + addcmul, sqrt / bc2_sqrt + eps, addcdiv
@@ -618,7 +671,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_adam(GmlGeom g, GmlBufs B, Adam
   B.x[k] = B.x[k] + (-a.step_size) * (m / denom);
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_flow_out(GmlGeom g, const double* __restrict__ S, double* __restrict__ out) {
+__global__ void __launch_bounds__(kGmlBlock) gml_flow_out(GmlGeom g, GmlBufs B0, GmlWin win, double* __restrict__ out) {
+  const double* __restrict__ S = gml_window(g, B0, win).S;
+  out += blockIdx.z * win.out;
   const int64_t n = gml_npix(g);
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= n) return;
@@ -639,10 +694,13 @@ __device__ __forceinline__ int reflect101(int i, int L) {
   return i < L ? i : P - i;
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_frame_sobel(int H, int W, const double* __restrict__ frame, int use_log,
-                                                              double* __restrict__ gx, double* __restrict__ gy) {
+__global__ void __launch_bounds__(kGmlBlock) gml_frame_sobel(int H, int W, const double* __restrict__ frame, size_t frame_stride,
+                                                              int use_log, double* __restrict__ gx, double* __restrict__ gy) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= (int64_t)H * W) return;
+  frame += blockIdx.z * frame_stride;   // the window axis: planes of H W elements, one per window
+  gx += blockIdx.z * ((size_t)H * W);
+  gy += blockIdx.z * ((size_t)H * W);
   const int r = (int)(k / W), c = (int)(k % W);
   double v[3][3];
   for (int a = 0; a < 3; ++a)
@@ -658,6 +716,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_hist(int64_t n, const double* _
                                                        double* __restrict__ absh) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= n) return;
+  pol += blockIdx.z * (size_t)(2 * n);
+  hist += blockIdx.z * (size_t)n;
+  absh += blockIdx.z * (size_t)n;
   const double h = no_pol ? pol[k] + pol[n + k] : pol[k] - pol[n + k];
   hist[k] = h;
   absh[k] = fabs(h);
@@ -668,10 +729,13 @@ __global__ void __launch_bounds__(kGmlBlock) gml_mul(int64_t n, const double* __
   if (k < n) b[k] = a[k] * b[k];
 }
 
-// one workgroup: out[0] = sqrt(sum x^2), or the moments of x (mean, population std, max) -> out[0..2]
-__global__ void __launch_bounds__(kGmlBlock) gml_reduce(int64_t n, const double* __restrict__ x, int what, double* __restrict__ out) {
+// one workgroup per window: out[0] = sqrt(sum x^2), or the moments of x (mean, population std, max) -> out[0..2]
+__global__ void __launch_bounds__(kGmlBlock) gml_reduce(int64_t n, const double* __restrict__ x, size_t x_stride, int what,
+                                                         double* __restrict__ out, size_t out_stride) {
   __shared__ double sh[2][kGmlBlock];
   const int t = threadIdx.x;
+  x += blockIdx.z * x_stride;
+  out += blockIdx.z * out_stride;
   if (what == 0) {
     double v[1] = {0.0};
     for (int64_t k = t; k < n; k += kGmlBlock) v[0] += x[k] * x[k];
@@ -707,16 +771,22 @@ __global__ void __launch_bounds__(kGmlBlock) gml_reduce(int64_t n, const double*
   }
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_scale_by(int64_t n, double* __restrict__ x, const double* __restrict__ nrm) {
+__global__ void __launch_bounds__(kGmlBlock) gml_scale_by(int64_t n, double* __restrict__ x, size_t x_stride, const double* __restrict__ nrm,
+                                                           size_t nrm_stride) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
+  x += blockIdx.z * x_stride;
+  nrm += blockIdx.z * nrm_stride;
   if (k < n) x[k] = x[k] / nrm[0];
 }
 
 // winv = 1 - 0.95 clip(g, 0, mean + std / 2) / max(clip(...)); g >= 0, so the max of the clipped field is min(max g, mean + std / 2)
 __global__ void __launch_bounds__(kGmlBlock) gml_winv(int64_t n, const double* __restrict__ gf, const double* __restrict__ mom,
-                                                       double* __restrict__ winv) {
+                                                       size_t mom_stride, double* __restrict__ winv) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= n) return;
+  gf += blockIdx.z * (size_t)n;
+  winv += blockIdx.z * (size_t)n;
+  mom += blockIdx.z * mom_stride;
   const double hi = mom[0] + mom[1] / 2.;
   const double mx = fmin(fmax(mom[2], 0.0), hi);
   double v = fmin(fmax(gf[k], 0.0), hi);
@@ -724,9 +794,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_winv(int64_t n, const double* _
   winv[k] = 1.0 - 0.95 * v;
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_fill(int64_t n, double* __restrict__ x, double v) {
+__global__ void __launch_bounds__(kGmlBlock) gml_fill(int64_t n, double* __restrict__ x, size_t x_stride, double v) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
-  if (k < n) x[k] = v;
+  if (k < n) x[blockIdx.z * x_stride + k] = v;
 }
 
 inline int blocks_for(int64_t n) { return (int)((n + kGmlBlock - 1) / kGmlBlock); }
@@ -857,37 +927,79 @@ GmlBufs make_bufs(const GmlLayout& L, char* s, const double* gx, const double* g
 }
 
 // one objective + gradient evaluation: everything up to the adjoint of the upsample
-int gml_forward_backward(const GmlGeom& g, const GmlBufs& B, double* hist_row, hipStream_t st) {
+// (`nw` windows per launch: the grid's z extent; `hist_row` is window 0's row)
+int gml_forward_backward(const GmlGeom& g, const GmlBufs& B, const GmlWin& win, int nw, double* hist_row, hipStream_t st) {
   const int G = g.gh * g.gw;
   const int64_t n = gml_npix(g);
-  if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B.x, B.S);
-  hipLaunchKernelGGL(gml_pass_a, dim3(g.nbA), dim3(kGmlBlock), 0, st, g, B);
-  hipLaunchKernelGGL(gml_pass_b, dim3((g.W + kGmlBlock - 1) / kGmlBlock, g.rbB), dim3(kGmlBlock), 0, st, g, B);
-  hipLaunchKernelGGL(gml_pass_c, dim3(1), dim3(kGmlBlock), 0, st, g, B, hist_row);
-  hipLaunchKernelGGL(gml_pass_d, dim3(blocks_for(n)), dim3(kGmlBlock), 0, st, g, B);
+  if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G), 1, nw), dim3(kGmlBlock), 0, st, g, B, win);
+  hipLaunchKernelGGL(gml_pass_a, dim3(g.nbA, 1, nw), dim3(kGmlBlock), 0, st, g, B, win);
+  hipLaunchKernelGGL(gml_pass_b, dim3((g.W + kGmlBlock - 1) / kGmlBlock, g.rbB, nw), dim3(kGmlBlock), 0, st, g, B, win);
+  hipLaunchKernelGGL(gml_pass_c, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, g, B, win, hist_row);
+  hipLaunchKernelGGL(gml_pass_d, dim3(blocks_for(n), 1, nw), dim3(kGmlBlock), 0, st, g, B, win);
   if (g.e_cell)
-    hipLaunchKernelGGL(gml_pass_e_cell, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B);
+    hipLaunchKernelGGL(gml_pass_e_cell, dim3(blocks_for(G), 1, nw), dim3(kGmlBlock), 0, st, g, B, win);
   else
-    hipLaunchKernelGGL(gml_pass_e, dim3(G), dim3(kGmlBlock), 0, st, g, B);
+    hipLaunchKernelGGL(gml_pass_e, dim3(G, 1, nw), dim3(kGmlBlock), 0, st, g, B, win);
   EBOS_CHECK_LAUNCH("ebos_gml passes");
+  return EBOS_OK;
+}
+
+constexpr int kGmlMaxWindows = 65535;   // gridDim.z
+
+// `iters` Adam steps on every window's x in place (fresh state), then the flow of each window over the geometry `o`
+int gml_adam_loop(const GmlGeom& g, const GmlGeom& o, const GmlBufs& B, const GmlWin& win, int nw, int iters, double lr, double* history,
+                  double* flow_out, hipStream_t st) {
+  const int G = g.gh * g.gw;
+  const int64_t np = (int64_t)g.nd * G;
+  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np), 1, nw), dim3(kGmlBlock), 0, st, np, B.m, win.scr, 0.0);
+  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np), 1, nw), dim3(kGmlBlock), 0, st, np, B.v, win.scr, 0.0);
+  AdamArgs a;
+  a.lr = lr;
+  a.beta1 = 0.9;
+  a.beta2 = 0.999;
+  a.eps = 1e-8;
+  a.step = 1;
+  int rc;
+  for (int it = 0; it < iters; ++it) {
+    if ((rc = gml_forward_backward(g, B, win, nw, history ? history + 4 * (size_t)it : nullptr, st)) != EBOS_OK) return rc;
+    const double t = (double)(it + 1);
+    a.step_size = lr / (1.0 - pow(a.beta1, t));
+    a.bc2_sqrt = pow(1.0 - pow(a.beta2, t), 0.5);
+    hipLaunchKernelGGL(gml_adam, dim3(blocks_for(np), 1, nw), dim3(kGmlBlock), 0, st, g, B, win, a, nullptr);
+    EBOS_CHECK_LAUNCH("ebos_gml: adam");
+  }
+  if (flow_out) {
+    if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G), 1, nw), dim3(kGmlBlock), 0, st, o, B, win);
+    hipLaunchKernelGGL(gml_flow_out, dim3(blocks_for(gml_npix(o)), 1, nw), dim3(kGmlBlock), 0, st, o, B, win, flow_out);
+    EBOS_CHECK_LAUNCH("ebos_gml: flow");
+  }
   return EBOS_OK;
 }
 
 // ---- patch_eklt_dependent: the crop, the selection, the initial parameters ---------------------------------------------------
 // dst[h, w] = src[xmin + r, ymin + c] of a [., W] plane
 __global__ void __launch_bounds__(kGmlBlock) gml_crop(int W, int xmin, int ymin, int h, int w, const double* __restrict__ src,
-                                                       double* __restrict__ dst) {
+                                                       size_t src_stride, double* __restrict__ dst, size_t dst_stride) {
   const int64_t k = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
   if (k >= (int64_t)h * w) return;
+  src += blockIdx.z * src_stride;
+  dst += blockIdx.z * dst_stride;
   const int r = (int)(k / w), c = (int)(k % w);
   dst[k] = src[(size_t)(xmin + r) * W + (ymin + c)];
 }
 
 // events [n, 4] (x = row, y = column, t, p) binned by (floor(x), floor(y)) into the (hc + 1) x (wc + 1) count canvas, offset by
-// one row and one column (row 0 and column 0 stay 0 for the summed-area table); events off the canvas are not counted
-__global__ void __launch_bounds__(kGmlBlock) gml_count_events(int64_t n, const double* __restrict__ ev, int hc, int wc,
-                                                               int* __restrict__ cnt) {
+// one row and one column (row 0 and column 0 stay 0 for the summed-area table); events off the canvas are not counted.  With
+// `offsets` [windows + 1], window b = blockIdx.z owns events [offsets[b], offsets[b + 1]) of the concatenated array.
+__global__ void __launch_bounds__(kGmlBlock) gml_count_events(int64_t n, const int64_t* __restrict__ offsets,
+                                                               const double* __restrict__ ev, int hc, int wc, int* __restrict__ cnt,
+                                                               size_t cnt_stride) {
   const int64_t i = (int64_t)blockIdx.x * kGmlBlock + threadIdx.x;
+  if (offsets) {
+    ev += 4 * offsets[blockIdx.z];
+    n = offsets[blockIdx.z + 1] - offsets[blockIdx.z];
+  }
+  cnt += blockIdx.z * cnt_stride;
   if (i >= n) return;
   const double fx = floor(ev[4 * i]), fy = floor(ev[4 * i + 1]);
   if (!(fx >= 0.0 && fx < (double)hc && fy >= 0.0 && fy < (double)wc)) return;
@@ -895,26 +1007,30 @@ __global__ void __launch_bounds__(kGmlBlock) gml_count_events(int64_t n, const d
 }
 
 // summed-area table in place: prefix sums along each row, then along each column (one thread per row / column)
-__global__ void __launch_bounds__(kGmlBlock) gml_scan_rows(int hc, int wc, int* __restrict__ cnt) {
+__global__ void __launch_bounds__(kGmlBlock) gml_scan_rows(int hc, int wc, int* __restrict__ cnt, size_t cnt_stride) {
   const int r = blockIdx.x * kGmlBlock + threadIdx.x + 1;
   if (r > hc) return;
+  cnt += blockIdx.z * cnt_stride;
   int* row = cnt + (size_t)r * (wc + 1);
   for (int c = 1; c <= wc; ++c) row[c] += row[c - 1];
 }
 
-__global__ void __launch_bounds__(kGmlBlock) gml_scan_cols(int hc, int wc, int* __restrict__ cnt) {
+__global__ void __launch_bounds__(kGmlBlock) gml_scan_cols(int hc, int wc, int* __restrict__ cnt, size_t cnt_stride) {
   const int c = blockIdx.x * kGmlBlock + threadIdx.x + 1;
   if (c > wc) return;
+  cnt += blockIdx.z * cnt_stride;
   for (int r = 1; r <= hc; ++r) cnt[(size_t)r * (wc + 1) + c] += cnt[(size_t)(r - 1) * (wc + 1) + c];
 }
 
 // flag[cell] = the cell's centre lies in the ROI (row_box / col_box [g, 3]: box start, box end, in-ROI) and, when thresholding,
 // its event box [x0, x1) x [y0, y1) holds more than `thres` events
 __global__ void __launch_bounds__(kGmlBlock) gml_select(int gh, int gw, const int* __restrict__ row_box, const int* __restrict__ col_box,
-                                                         const int* __restrict__ sat, int hc, int wc, int thresholding, double thres,
-                                                         int* __restrict__ flag) {
+                                                         const int* __restrict__ sat, size_t sat_stride, int hc, int wc,
+                                                         int thresholding, double thres, int* __restrict__ flag) {
   const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
   if (cell >= gh * gw) return;
+  if (sat) sat += blockIdx.z * sat_stride;
+  flag += blockIdx.z * (size_t)(gh * gw);
   const int i = cell / gw, j = cell % gw;
   int ok = row_box[3 * i + 2] && col_box[3 * j + 2];
   if (ok && thresholding) {
@@ -927,11 +1043,13 @@ __global__ void __launch_bounds__(kGmlBlock) gml_select(int gh, int gw, const in
   flag[cell] = ok;
 }
 
-// one workgroup: sel[cell] = 1 + the cell's rank among the selected cells in row-major order (0 = not selected); count[0] = their
+// one workgroup per window: sel[cell] = 1 + the cell's rank among the selected cells in row-major order (0 = not selected); count[0] = their
 // number.  A block-wide inclusive scan per 256-cell chunk.
 __global__ void __launch_bounds__(kGmlBlock) gml_rank(int G, int* __restrict__ sel, int* __restrict__ count) {
   __shared__ int sh[kGmlBlock];
   const int t = threadIdx.x;
+  sel += blockIdx.z * (size_t)G;
+  count += blockIdx.z;
   int base = 0;
   for (int c0 = 0; c0 < G; c0 += kGmlBlock) {
     const int cell = c0 + t;
@@ -956,6 +1074,9 @@ __global__ void __launch_bounds__(kGmlBlock) gml_dep_init(int G, int nd, const i
                                                            double* __restrict__ x) {
   const int cell = blockIdx.x * kGmlBlock + threadIdx.x;
   if (cell >= G) return;
+  sel += blockIdx.z * (size_t)G;   // per window: sel [G], draws [G] (the first `count` are used), x [nd, G]
+  if (draws) draws += blockIdx.z * (size_t)G;
+  x += blockIdx.z * (size_t)nd * G;
   for (int ch = 0; ch < nd; ++ch) x[(size_t)ch * G + cell] = 0.0;
   if (draws && sel[cell] != 0) x[cell] = draws[sel[cell] - 1];
 }
@@ -981,23 +1102,223 @@ DepLayout dep_layout(int h, int w, int G) {
 }
 
 // crop the five fields into the scratch and divide the cropped measurement by its own norm; -> the iteration buffers
+// (window 0's; the others follow at `scr` doubles.  `src_win`: the strides of the full-image fields)
 int dep_bufs(const GmlGeom& g, int W, int xmin, int ymin, const DepLayout& D, char* s, const double* gx, const double* gy, const double* q,
-             const double* we, const double* winv, double* x, const int* sel, hipStream_t st, GmlBufs* out) {
+             const double* we, const double* winv, double* x, const int* sel, const GmlWin& src_win, size_t scr, int nw, hipStream_t st,
+             GmlBufs* out) {
   const int64_t n = gml_npix(g);
   const int nb = blocks_for(n);
+  const size_t ss[5] = {src_win.grad, src_win.grad, src_win.field, src_win.field, src_win.field};
   double* c[5] = {reinterpret_cast<double*>(s + D.gx), reinterpret_cast<double*>(s + D.gy), reinterpret_cast<double*>(s + D.q),
                   reinterpret_cast<double*>(s + D.we), reinterpret_cast<double*>(s + D.winv)};
   const double* src[5] = {gx, gy, q, we, winv};
   for (int i = 0; i < 5; ++i)
-    if (src[i]) hipLaunchKernelGGL(gml_crop, dim3(nb), dim3(kGmlBlock), 0, st, W, xmin, ymin, g.H, g.W, src[i], c[i]);
+    if (src[i])
+      hipLaunchKernelGGL(gml_crop, dim3(nb, 1, nw), dim3(kGmlBlock), 0, st, W, xmin, ymin, g.H, g.W, src[i], ss[i], c[i], scr);
   GmlBufs B = make_bufs(D.L, s + D.iter, c[0], c[1], c[2], we ? c[3] : nullptr, c[4], x);
-  hipLaunchKernelGGL(gml_reduce, dim3(1), dim3(kGmlBlock), 0, st, n, c[2], 0, B.scal + 2);
-  hipLaunchKernelGGL(gml_scale_by, dim3(nb), dim3(kGmlBlock), 0, st, n, c[2], B.scal + 2);
+  hipLaunchKernelGGL(gml_reduce, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, n, c[2], scr, 0, B.scal + 2, scr);
+  hipLaunchKernelGGL(gml_scale_by, dim3(nb, 1, nw), dim3(kGmlBlock), 0, st, n, c[2], scr, B.scal + 2, scr);
   EBOS_CHECK_LAUNCH("ebos_gml_dep: crop");
-  if (g.vel) B.S = x;   // F = up(x[0:2])
   B.sel = sel;
   *out = B;
   return EBOS_OK;
+}
+
+
+bool gml_windows_ok(int nw) { return nw >= 1 && nw <= kGmlMaxWindows; }
+
+// a batch's scratch: window b's slice starts at b * stride bytes; a slice holds `need` bytes and keeps the 256-byte alignment
+int gml_check_slices(const char* who, int nw, size_t need, size_t stride, size_t bytes) {
+  if (nw > 1 && (stride % 256 != 0 || stride < need)) {
+    set_error("%s: scratch stride %zu is not a multiple of 256 or is below a window's %zu bytes", who, stride, need);
+    return EBOS_ERR_SCRATCH;
+  }
+  if (bytes < (size_t)(nw - 1) * stride + need) {
+    set_error("%s: scratch too small (%zu < %zu)", who, bytes, (size_t)(nw - 1) * stride + need);
+    return EBOS_ERR_SCRATCH;
+  }
+  return EBOS_OK;
+}
+
+// prepare of `nw` windows: every field is [nw, H, W] contiguous (the frame: stride 0 = one model image, whose gradients are
+// formed once), and so are the four work planes in the scratch, so that one separable-filter call covers the batch
+int gml_prepare(int nw, int H, int W, const double* frame, size_t frame_stride, int use_log, const double* pol, int no_polarity,
+                const double* blur_taps, int blur_radius, const double* weight_taps, int weight_radius, const double* inv_taps,
+                int inv_radius, double* gx, double* gy, double* q, double* we, double* winv, void* scratch, size_t scratch_bytes,
+                ebos_stream_t stream) {
+  EBOS_REQUIRE(gml_windows_ok(nw), "ebos_gml_prepare: %d windows", nw);
+  EBOS_REQUIRE(H >= 3 && W >= 3 && (int64_t)H * W < ((int64_t)1 << 31), "ebos_gml_prepare_f64: bad image size %d x %d", H, W);
+  EBOS_REQUIRE(frame && pol && gx && gy && q && winv && scratch, "ebos_gml_prepare_f64: NULL buffer");
+  EBOS_REQUIRE(!weight_taps == !we, "ebos_gml_prepare_f64: weight_taps and we go together");
+  EBOS_REQUIRE(blur_radius >= 0 && weight_radius >= 0 && inv_radius >= 0, "ebos_gml_prepare_f64: negative radius");
+  EBOS_REQUIRE(frame_stride == 0 || frame_stride == (size_t)H * W, "ebos_gml_prepare_f64: frame stride is neither 0 nor H W");
+  const int64_t n = (int64_t)H * W;
+  const size_t plane = gml_align((size_t)nw * n * sizeof(double));
+  EBOS_REQUIRE(scratch_bytes >= 4 * plane + gml_align((size_t)nw * 8 * sizeof(double)), "ebos_gml_prepare_f64: scratch too small");
+  char* s = static_cast<char*>(scratch);
+  double* hist = reinterpret_cast<double*>(s);
+  double* absh = reinterpret_cast<double*>(s + plane);
+  double* t1 = reinterpret_cast<double*>(s + 2 * plane);
+  double* t2 = reinterpret_cast<double*>(s + 3 * plane);
+  double* sc = reinterpret_cast<double*>(s + 4 * plane);   // [nw, 8]
+  const hipStream_t st = as_stream(stream);
+  const int nb = blocks_for(n);
+  const int nbw = blocks_for(n * nw);
+  const int64_t R = (int64_t)nw * H;   // rows of the batch
+  hipLaunchKernelGGL(gml_frame_sobel, dim3(nb, 1, frame_stride ? nw : 1), dim3(kGmlBlock), 0, st, H, W, frame, frame_stride, use_log, gx,
+                     gy);
+  hipLaunchKernelGGL(gml_hist, dim3(nb, 1, nw), dim3(kGmlBlock), 0, st, n, pol, no_polarity, hist, absh);
+  EBOS_CHECK_LAUNCH("ebos_gml_prepare_f64");
+  int rc;
+  // cv2.GaussianBlur: the row filter (along columns) first, then the column filter; reflect-101 = boundary 1
+  if (blur_taps) {
+    if ((rc = ebos_gauss1d_f64(hist, t1, R, W, 1, blur_taps, blur_radius, 1, stream)) != EBOS_OK) return rc;
+    if ((rc = ebos_gauss1d_f64(t1, q, nw, H, W, blur_taps, blur_radius, 1, stream)) != EBOS_OK) return rc;
+  } else {
+    if (hipMemcpyAsync(q, hist, (size_t)nw * n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      set_error("ebos_gml_prepare_f64: copy failed");
+      return EBOS_ERR_LAUNCH;
+    }
+  }
+  if (weight_taps) {
+    if ((rc = ebos_gauss1d_f64(absh, t1, R, W, 1, weight_taps, weight_radius, 1, stream)) != EBOS_OK) return rc;
+    if ((rc = ebos_gauss1d_f64(t1, we, nw, H, W, weight_taps, weight_radius, 1, stream)) != EBOS_OK) return rc;
+    hipLaunchKernelGGL(gml_mul, dim3(nbw), dim3(kGmlBlock), 0, st, n * nw, we, q);
+  }
+  hipLaunchKernelGGL(gml_reduce, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, n, q, (size_t)n, 0, sc, (size_t)8);
+  hipLaunchKernelGGL(gml_scale_by, dim3(nb, 1, nw), dim3(kGmlBlock), 0, st, n, q, (size_t)n, sc, (size_t)8);
+  if (inv_taps) {
+    // scipy gaussian_filter(|hist|, 10): axis 0, then axis 1, mode 'reflect' = boundary 0
+    if ((rc = ebos_gauss1d_f64(absh, t1, nw, H, W, inv_taps, inv_radius, 0, stream)) != EBOS_OK) return rc;
+    if ((rc = ebos_gauss1d_f64(t1, t2, R, W, 1, inv_taps, inv_radius, 0, stream)) != EBOS_OK) return rc;
+    hipLaunchKernelGGL(gml_reduce, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, n, t2, (size_t)n, 1, sc + 1, (size_t)8);
+    hipLaunchKernelGGL(gml_winv, dim3(nb, 1, nw), dim3(kGmlBlock), 0, st, n, t2, sc + 1, (size_t)8, winv);
+  } else {
+    hipLaunchKernelGGL(gml_fill, dim3(nbw), dim3(kGmlBlock), 0, st, n * nw, winv, (size_t)0, 1.0);
+  }
+  EBOS_CHECK_LAUNCH("ebos_gml_prepare_f64");
+  return EBOS_OK;
+}
+
+int gml_normalize(int nw, int64_t n, double* q, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(gml_windows_ok(nw) && n > 0 && q && scratch && scratch_bytes >= (size_t)nw * sizeof(double),
+               "ebos_gml_normalize_f64: bad arguments");
+  const hipStream_t st = as_stream(stream);
+  double* sc = static_cast<double*>(scratch);   // [nw]
+  hipLaunchKernelGGL(gml_reduce, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, n, q, (size_t)n, 0, sc, (size_t)1);
+  hipLaunchKernelGGL(gml_scale_by, dim3(blocks_for(n), 1, nw), dim3(kGmlBlock), 0, st, n, q, (size_t)n, sc, (size_t)1);
+  EBOS_CHECK_LAUNCH("ebos_gml_normalize_f64");
+  return EBOS_OK;
+}
+
+// one pyramid scale of `nw` windows: fields [nw, H, W] (gx, gy: stride `grad_stride`, 0 or H W), x [nw, n_dim, gh, gw],
+// history rows `history_stride` doubles apart, flow [nw, 2, H, W]
+int gml_solve_scale(int nw, int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags, const double* weights,
+                    const int* order, int n_terms, const double* gx, const double* gy, size_t grad_stride, const double* q,
+                    const double* we, const double* winv, double* x, int iters, double lr, double* history, size_t history_stride,
+                    double* flow_out, void* scratch, size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(gml_windows_ok(nw), "ebos_gml_solve_scale: %d windows", nw);
+  GmlGeom g;
+  int rc = make_geom(&g, H, W, patch, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  EBOS_REQUIRE(gx && gy && q && winv && x && scratch && (!g.has_we || we), "ebos_gml_solve_scale_f64: NULL buffer");
+  EBOS_REQUIRE(iters >= 0, "ebos_gml_solve_scale_f64: iters %d < 0", iters);
+  EBOS_REQUIRE(grad_stride == 0 || grad_stride == (size_t)H * W, "ebos_gml_solve_scale: gradient stride is neither 0 nor H W");
+  const int G = g.gh * g.gw;
+  const GmlLayout L = gml_layout(H, W, G);
+  if ((rc = gml_check_slices("ebos_gml_solve_scale_f64", nw, L.total, scratch_stride, scratch_bytes)) != EBOS_OK) return rc;
+  GmlBufs B = make_bufs(L, static_cast<char*>(scratch), gx, gy, q, we, winv, x);
+  GmlWin win = {};
+  if (nw > 1) {
+    win.grad = grad_stride;
+    win.field = (size_t)H * W;
+    win.x = (size_t)n_dim * G;
+    win.scr = scratch_stride / sizeof(double);
+    win.hist = history_stride;
+    win.out = 2 * (size_t)H * W;
+  }
+  return gml_adam_loop(g, g, B, win, nw, iters, lr, history, flow_out, as_stream(stream));
+}
+
+int gml_dep_select(int nw, int H, int W, int patch, int slide, const int* row_box, const int* col_box, const double* events,
+                   int64_t n_events, const int64_t* offsets, int canvas_h, int canvas_w, int thresholding, double event_thres, int* sel,
+                   int* count, void* scratch, size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(gml_windows_ok(nw), "ebos_gml_dep_select: %d windows", nw);
+  DepAxis ar, ac;
+  int rc;
+  EBOS_REQUIRE(H >= 3 && W >= 3, "ebos_gml_dep_select: bad image size %d x %d", H, W);
+  if ((rc = dep_axis(H, patch, slide, &ar)) != EBOS_OK || (rc = dep_axis(W, patch, slide, &ac)) != EBOS_OK) return rc;
+  EBOS_REQUIRE(row_box && col_box && sel && count, "ebos_gml_dep_select: NULL buffer");
+  EBOS_REQUIRE(!thresholding || ((events || n_events == 0) && n_events >= 0 && n_events < ((int64_t)1 << 31) && scratch),
+               "ebos_gml_dep_select: bad events or NULL scratch");
+  EBOS_REQUIRE(canvas_h >= 0 && canvas_w >= 0 && (int64_t)(canvas_h + 1) * (canvas_w + 1) < ((int64_t)1 << 31),
+               "ebos_gml_dep_select: bad canvas %d x %d", canvas_h, canvas_w);
+  const hipStream_t st = as_stream(stream);
+  const int G = ar.g * ac.g;
+  int* sat = static_cast<int*>(scratch);
+  const size_t ss = nw > 1 ? scratch_stride / sizeof(int) : 0;
+  if (thresholding) {
+    const size_t need = (size_t)(canvas_h + 1) * (canvas_w + 1) * sizeof(int);
+    if ((rc = gml_check_slices("ebos_gml_dep_select", nw, need, scratch_stride, scratch_bytes)) != EBOS_OK) return rc;
+    for (int b = 0; b < nw; ++b)
+      if (hipMemsetAsync(static_cast<char*>(scratch) + (size_t)b * scratch_stride, 0, need, st) != hipSuccess) {
+        set_error("ebos_gml_dep_select: memset failed");
+        return EBOS_ERR_LAUNCH;
+      }
+    // n_events: one window's count, or the largest count of the batch (it sizes the grid; `offsets` bound each window)
+    if (n_events > 0)
+      hipLaunchKernelGGL(gml_count_events, dim3(blocks_for(n_events), 1, nw), dim3(kGmlBlock), 0, st, n_events, offsets, events, canvas_h,
+                         canvas_w, sat, ss);
+    hipLaunchKernelGGL(gml_scan_rows, dim3(blocks_for(canvas_h), 1, nw), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat, ss);
+    hipLaunchKernelGGL(gml_scan_cols, dim3(blocks_for(canvas_w), 1, nw), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat, ss);
+  }
+  hipLaunchKernelGGL(gml_select, dim3(blocks_for(G), 1, nw), dim3(kGmlBlock), 0, st, ar.g, ac.g, row_box, col_box,
+                     thresholding ? sat : nullptr, ss, canvas_h, canvas_w, thresholding, event_thres, sel);
+  hipLaunchKernelGGL(gml_rank, dim3(1, 1, nw), dim3(kGmlBlock), 0, st, G, sel, count);
+  EBOS_CHECK_LAUNCH("ebos_gml_dep_select");
+  return EBOS_OK;
+}
+
+// the dependent solver's strides: the crops and the iteration buffers of a window live in its scratch slice
+GmlWin dep_win(int nw, const GmlGeom& g, size_t scratch_stride, size_t history_stride, size_t out) {
+  GmlWin win = {};
+  if (nw > 1) {
+    win.grad = win.field = win.scr = scratch_stride / sizeof(double);
+    win.x = (size_t)g.nd * g.gh * g.gw;
+    win.sel = (size_t)g.gh * g.gw;
+    win.hist = history_stride;
+    win.out = out;
+  }
+  return win;
+}
+
+int gml_dep_solve(int nw, int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                  const double* weights, const int* order, int n_terms, const double* gx, const double* gy, size_t grad_stride,
+                  const double* q, const double* we, const double* winv, const int* sel, double* x, int iters, double lr, double* history,
+                  size_t history_stride, double* flow_out, void* scratch, size_t scratch_stride, size_t scratch_bytes,
+                  ebos_stream_t stream) {
+  EBOS_REQUIRE(gml_windows_ok(nw), "ebos_gml_dep_solve: %d windows", nw);
+  GmlGeom g;
+  int rc = make_dep_geom(&g, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
+  if (rc != EBOS_OK) return rc;
+  EBOS_REQUIRE(gx && gy && q && winv && sel && x && scratch && (!g.has_we || we), "ebos_gml_dep_solve_f64: NULL buffer");
+  EBOS_REQUIRE(iters >= 0, "ebos_gml_dep_solve_f64: iters %d < 0", iters);
+  EBOS_REQUIRE(grad_stride == 0 || grad_stride == (size_t)H * W, "ebos_gml_dep_solve: gradient stride is neither 0 nor H W");
+  const int G = g.gh * g.gw;
+  const DepLayout D = dep_layout(g.H, g.W, G);
+  if ((rc = gml_check_slices("ebos_gml_dep_solve_f64", nw, D.total, scratch_stride, scratch_bytes)) != EBOS_OK) return rc;
+  const hipStream_t st = as_stream(stream);
+  GmlWin src = {};
+  if (nw > 1) {
+    src.grad = grad_stride;
+    src.field = (size_t)H * W;
+  }
+  const GmlWin win = dep_win(nw, g, scratch_stride, history_stride, 2 * (size_t)H * W);
+  GmlBufs B;
+  if ((rc = dep_bufs(g, W, xmin, ymin, D, static_cast<char*>(scratch), gx, gy, q, g.has_we ? we : nullptr, winv, x, sel, src, win.scr, nw,
+                     st, &B)) != EBOS_OK)
+    return rc;
+  return gml_adam_loop(g, dep_out_geom(g, H, W, xmin, ymin), B, win, nw, iters, lr, history, flow_out, st);
 }
 
 }  // namespace
@@ -1012,69 +1333,34 @@ size_t ebos_gml_scratch_bytes(int H, int W, int min_patch) {
   return std::max(ebos::gml_layout(H, W, G).total, 4 * ebos::gml_align(hw) + ebos::gml_align(8 * sizeof(double)));
 }
 
+size_t ebos_gml_scratch_bytes_batch(int H, int W, int min_patch, int n_windows) {
+  if (n_windows < 1 || n_windows > ebos::kGmlMaxWindows) return 0;
+  return (size_t)n_windows * ebos_gml_scratch_bytes(H, W, min_patch);
+}
+
 int ebos_gml_prepare_f64(int H, int W, const double* frame, int use_log, const double* pol, int no_polarity, const double* blur_taps,
                          int blur_radius, const double* weight_taps, int weight_radius, const double* inv_taps, int inv_radius,
                          double* gx, double* gy, double* q, double* we, double* winv, void* scratch, size_t scratch_bytes,
                          ebos_stream_t stream) {
-  using namespace ebos;
-  EBOS_REQUIRE(H >= 3 && W >= 3 && (int64_t)H * W < ((int64_t)1 << 31), "ebos_gml_prepare_f64: bad image size %d x %d", H, W);
-  EBOS_REQUIRE(frame && pol && gx && gy && q && winv && scratch, "ebos_gml_prepare_f64: NULL buffer");
-  EBOS_REQUIRE(!weight_taps == !we, "ebos_gml_prepare_f64: weight_taps and we go together");
-  EBOS_REQUIRE(blur_radius >= 0 && weight_radius >= 0 && inv_radius >= 0, "ebos_gml_prepare_f64: negative radius");
-  const int64_t n = (int64_t)H * W;
-  const size_t plane = gml_align((size_t)n * sizeof(double));
-  EBOS_REQUIRE(scratch_bytes >= 4 * plane + gml_align(8 * sizeof(double)), "ebos_gml_prepare_f64: scratch too small");
-  char* s = static_cast<char*>(scratch);
-  double* hist = reinterpret_cast<double*>(s);
-  double* absh = reinterpret_cast<double*>(s + plane);
-  double* t1 = reinterpret_cast<double*>(s + 2 * plane);
-  double* t2 = reinterpret_cast<double*>(s + 3 * plane);
-  double* sc = reinterpret_cast<double*>(s + 4 * plane);
-  const hipStream_t st = as_stream(stream);
-  const int nb = blocks_for(n);
-  hipLaunchKernelGGL(gml_frame_sobel, dim3(nb), dim3(kGmlBlock), 0, st, H, W, frame, use_log, gx, gy);
-  hipLaunchKernelGGL(gml_hist, dim3(nb), dim3(kGmlBlock), 0, st, n, pol, no_polarity, hist, absh);
-  EBOS_CHECK_LAUNCH("ebos_gml_prepare_f64");
-  int rc;
-  // cv2.GaussianBlur: the row filter (along columns) first, then the column filter; reflect-101 = boundary 1
-  if (blur_taps) {
-    if ((rc = ebos_gauss1d_f64(hist, t1, H, W, 1, blur_taps, blur_radius, 1, stream)) != EBOS_OK) return rc;
-    if ((rc = ebos_gauss1d_f64(t1, q, 1, H, W, blur_taps, blur_radius, 1, stream)) != EBOS_OK) return rc;
-  } else {
-    if (hipMemcpyAsync(q, hist, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      set_error("ebos_gml_prepare_f64: copy failed");
-      return EBOS_ERR_LAUNCH;
-    }
-  }
-  if (weight_taps) {
-    if ((rc = ebos_gauss1d_f64(absh, t1, H, W, 1, weight_taps, weight_radius, 1, stream)) != EBOS_OK) return rc;
-    if ((rc = ebos_gauss1d_f64(t1, we, 1, H, W, weight_taps, weight_radius, 1, stream)) != EBOS_OK) return rc;
-    hipLaunchKernelGGL(gml_mul, dim3(nb), dim3(kGmlBlock), 0, st, n, we, q);
-  }
-  hipLaunchKernelGGL(gml_reduce, dim3(1), dim3(kGmlBlock), 0, st, n, q, 0, sc);
-  hipLaunchKernelGGL(gml_scale_by, dim3(nb), dim3(kGmlBlock), 0, st, n, q, sc);
-  if (inv_taps) {
-    // scipy gaussian_filter(|hist|, 10): axis 0, then axis 1, mode 'reflect' = boundary 0
-    if ((rc = ebos_gauss1d_f64(absh, t1, 1, H, W, inv_taps, inv_radius, 0, stream)) != EBOS_OK) return rc;
-    if ((rc = ebos_gauss1d_f64(t1, t2, H, W, 1, inv_taps, inv_radius, 0, stream)) != EBOS_OK) return rc;
-    hipLaunchKernelGGL(gml_reduce, dim3(1), dim3(kGmlBlock), 0, st, n, t2, 1, sc + 1);
-    hipLaunchKernelGGL(gml_winv, dim3(nb), dim3(kGmlBlock), 0, st, n, t2, sc + 1, winv);
-  } else {
-    hipLaunchKernelGGL(gml_fill, dim3(nb), dim3(kGmlBlock), 0, st, n, winv, 1.0);
-  }
-  EBOS_CHECK_LAUNCH("ebos_gml_prepare_f64");
-  return EBOS_OK;
+  return ebos::gml_prepare(1, H, W, frame, 0, use_log, pol, no_polarity, blur_taps, blur_radius, weight_taps, weight_radius, inv_taps,
+                           inv_radius, gx, gy, q, we, winv, scratch, scratch_bytes, stream);
+}
+
+int ebos_gml_prepare_batch_f64(int n_windows, int H, int W, const double* frame, int64_t frame_stride, int use_log, const double* pol,
+                               int no_polarity, const double* blur_taps, int blur_radius, const double* weight_taps, int weight_radius,
+                               const double* inv_taps, int inv_radius, double* gx, double* gy, double* q, double* we, double* winv,
+                               void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(frame_stride >= 0, "ebos_gml_prepare_batch_f64: negative frame stride");
+  return ebos::gml_prepare(n_windows, H, W, frame, (size_t)frame_stride, use_log, pol, no_polarity, blur_taps, blur_radius, weight_taps,
+                           weight_radius, inv_taps, inv_radius, gx, gy, q, we, winv, scratch, scratch_bytes, stream);
 }
 
 int ebos_gml_normalize_f64(int64_t n, double* q, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
-  using namespace ebos;
-  EBOS_REQUIRE(n > 0 && q && scratch && scratch_bytes >= sizeof(double), "ebos_gml_normalize_f64: bad arguments");
-  const hipStream_t st = as_stream(stream);
-  double* sc = static_cast<double*>(scratch);
-  hipLaunchKernelGGL(gml_reduce, dim3(1), dim3(kGmlBlock), 0, st, n, q, 0, sc);
-  hipLaunchKernelGGL(gml_scale_by, dim3(blocks_for(n)), dim3(kGmlBlock), 0, st, n, q, sc);
-  EBOS_CHECK_LAUNCH("ebos_gml_normalize_f64");
-  return EBOS_OK;
+  return ebos::gml_normalize(1, n, q, scratch, scratch_bytes, stream);
+}
+
+int ebos_gml_normalize_batch_f64(int n_windows, int64_t n, double* q, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
+  return ebos::gml_normalize(n_windows, n, q, scratch, scratch_bytes, stream);
 }
 
 int ebos_gml_objective_f64(int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags, const double* weights,
@@ -1094,9 +1380,10 @@ int ebos_gml_objective_f64(int H, int W, int patch, int n_dim, int xmin, int xma
   }
   GmlBufs B = make_bufs(L, static_cast<char*>(scratch), gx, gy, q, we, winv, const_cast<double*>(x));
   const hipStream_t st = as_stream(stream);
-  if ((rc = gml_forward_backward(g, B, parts, st)) != EBOS_OK) return rc;
+  const GmlWin win = {};
+  if ((rc = gml_forward_backward(g, B, win, 1, parts, st)) != EBOS_OK) return rc;
   AdamArgs a = {};
-  hipLaunchKernelGGL(gml_adam, dim3(blocks_for((int64_t)n_dim * G)), dim3(kGmlBlock), 0, st, g, B, a, grad);
+  hipLaunchKernelGGL(gml_adam, dim3(blocks_for((int64_t)n_dim * G)), dim3(kGmlBlock), 0, st, g, B, win, a, grad);
   EBOS_CHECK_LAUNCH("ebos_gml_objective_f64");
   return EBOS_OK;
 }
@@ -1105,43 +1392,20 @@ int ebos_gml_solve_scale_f64(int H, int W, int patch, int n_dim, int xmin, int x
                              const int* order, int n_terms, const double* gx, const double* gy, const double* q, const double* we,
                              const double* winv, double* x, int iters, double lr, double* history, double* flow_out, void* scratch,
                              size_t scratch_bytes, ebos_stream_t stream) {
-  using namespace ebos;
-  GmlGeom g;
-  int rc = make_geom(&g, H, W, patch, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
-  if (rc != EBOS_OK) return rc;
-  EBOS_REQUIRE(gx && gy && q && winv && x && scratch && (!g.has_we || we), "ebos_gml_solve_scale_f64: NULL buffer");
-  EBOS_REQUIRE(iters >= 0, "ebos_gml_solve_scale_f64: iters %d < 0", iters);
-  const int G = g.gh * g.gw;
-  const GmlLayout L = gml_layout(H, W, G);
-  if (scratch_bytes < L.total) {
-    set_error("ebos_gml_solve_scale_f64: scratch too small (%zu < %zu)", scratch_bytes, L.total);
-    return EBOS_ERR_SCRATCH;
-  }
-  GmlBufs B = make_bufs(L, static_cast<char*>(scratch), gx, gy, q, we, winv, x);
-  const hipStream_t st = as_stream(stream);
-  const int64_t np = (int64_t)n_dim * G;
-  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.m, 0.0);
-  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.v, 0.0);
-  AdamArgs a;
-  a.lr = lr;
-  a.beta1 = 0.9;
-  a.beta2 = 0.999;
-  a.eps = 1e-8;
-  a.step = 1;
-  for (int it = 0; it < iters; ++it) {
-    if ((rc = gml_forward_backward(g, B, history ? history + 4 * (size_t)it : nullptr, st)) != EBOS_OK) return rc;
-    const double t = (double)(it + 1);
-    a.step_size = lr / (1.0 - pow(a.beta1, t));
-    a.bc2_sqrt = pow(1.0 - pow(a.beta2, t), 0.5);
-    hipLaunchKernelGGL(gml_adam, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, g, B, a, nullptr);
-    EBOS_CHECK_LAUNCH("ebos_gml_solve_scale_f64: adam");
-  }
-  if (flow_out) {
-    hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, g, B.x, B.S);
-    hipLaunchKernelGGL(gml_flow_out, dim3(blocks_for(gml_npix(g))), dim3(kGmlBlock), 0, st, g, B.S, flow_out);
-    EBOS_CHECK_LAUNCH("ebos_gml_solve_scale_f64: flow");
-  }
-  return EBOS_OK;
+  return ebos::gml_solve_scale(1, H, W, patch, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms, gx, gy, 0, q, we, winv, x,
+                               iters, lr, history, 0, flow_out, scratch, 0, scratch_bytes, stream);
+}
+
+int ebos_gml_solve_scale_batch_f64(int n_windows, int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                                   const double* weights, const int* order, int n_terms, const double* gx, const double* gy,
+                                   int64_t grad_stride, const double* q, const double* we, const double* winv, double* x, int iters,
+                                   double lr, double* history, int64_t history_stride, double* flow_out, void* scratch,
+                                   size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(grad_stride >= 0 && history_stride >= 0, "ebos_gml_solve_scale_batch_f64: negative stride");
+  EBOS_REQUIRE(!history || n_windows == 1 || history_stride >= 4 * (int64_t)iters, "ebos_gml_solve_scale_batch_f64: history rows overlap");
+  return ebos::gml_solve_scale(n_windows, H, W, patch, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms, gx, gy,
+                               (size_t)grad_stride, q, we, winv, x, iters, lr, history, (size_t)history_stride, flow_out, scratch,
+                               scratch_stride, scratch_bytes, stream);
 }
 
 }  // extern "C"
@@ -1159,49 +1423,39 @@ size_t ebos_gml_dep_scratch_bytes(int H, int W, int patch, int slide, int xmin, 
   return std::max(std::max(prep, solve), sel);
 }
 
+size_t ebos_gml_dep_scratch_bytes_batch(int H, int W, int patch, int slide, int xmin, int xmax, int ymin, int ymax, int canvas_h,
+                                        int canvas_w, int n_windows) {
+  if (n_windows < 1 || n_windows > ebos::kGmlMaxWindows) return 0;
+  return (size_t)n_windows * ebos_gml_dep_scratch_bytes(H, W, patch, slide, xmin, xmax, ymin, ymax, canvas_h, canvas_w);
+}
+
 int ebos_gml_dep_select(int H, int W, int patch, int slide, const int* row_box, const int* col_box, const double* events, int64_t n_events,
                         int canvas_h, int canvas_w, int thresholding, double event_thres, int* sel, int* count, void* scratch,
                         size_t scratch_bytes, ebos_stream_t stream) {
-  using namespace ebos;
-  DepAxis ar, ac;
-  int rc;
-  EBOS_REQUIRE(H >= 3 && W >= 3, "ebos_gml_dep_select: bad image size %d x %d", H, W);
-  if ((rc = dep_axis(H, patch, slide, &ar)) != EBOS_OK || (rc = dep_axis(W, patch, slide, &ac)) != EBOS_OK) return rc;
-  EBOS_REQUIRE(row_box && col_box && sel && count, "ebos_gml_dep_select: NULL buffer");
-  EBOS_REQUIRE(!thresholding || ((events || n_events == 0) && n_events >= 0 && n_events < ((int64_t)1 << 31) && scratch),
-               "ebos_gml_dep_select: bad events or NULL scratch");
-  EBOS_REQUIRE(canvas_h >= 0 && canvas_w >= 0 && (int64_t)(canvas_h + 1) * (canvas_w + 1) < ((int64_t)1 << 31),
-               "ebos_gml_dep_select: bad canvas %d x %d", canvas_h, canvas_w);
-  const hipStream_t st = as_stream(stream);
-  const int G = ar.g * ac.g;
-  int* sat = static_cast<int*>(scratch);
-  if (thresholding) {
-    const size_t need = (size_t)(canvas_h + 1) * (canvas_w + 1) * sizeof(int);
-    if (scratch_bytes < need) {
-      set_error("ebos_gml_dep_select: scratch too small (%zu < %zu)", scratch_bytes, need);
-      return EBOS_ERR_SCRATCH;
-    }
-    if (hipMemsetAsync(sat, 0, need, st) != hipSuccess) {
-      set_error("ebos_gml_dep_select: memset failed");
-      return EBOS_ERR_LAUNCH;
-    }
-    if (n_events > 0) hipLaunchKernelGGL(gml_count_events, dim3(blocks_for(n_events)), dim3(kGmlBlock), 0, st, n_events, events, canvas_h,
-                                         canvas_w, sat);
-    hipLaunchKernelGGL(gml_scan_rows, dim3(blocks_for(canvas_h)), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat);
-    hipLaunchKernelGGL(gml_scan_cols, dim3(blocks_for(canvas_w)), dim3(kGmlBlock), 0, st, canvas_h, canvas_w, sat);
-  }
-  hipLaunchKernelGGL(gml_select, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, ar.g, ac.g, row_box, col_box, thresholding ? sat : nullptr,
-                     canvas_h, canvas_w, thresholding, event_thres, sel);
-  hipLaunchKernelGGL(gml_rank, dim3(1), dim3(kGmlBlock), 0, st, G, sel, count);
-  EBOS_CHECK_LAUNCH("ebos_gml_dep_select");
-  return EBOS_OK;
+  return ebos::gml_dep_select(1, H, W, patch, slide, row_box, col_box, events, n_events, nullptr, canvas_h, canvas_w, thresholding,
+                              event_thres, sel, count, scratch, 0, scratch_bytes, stream);
+}
+
+int ebos_gml_dep_select_batch(int n_windows, int H, int W, int patch, int slide, const int* row_box, const int* col_box,
+                              const double* events, const int64_t* event_offsets, int64_t max_events, int canvas_h, int canvas_w,
+                              int thresholding, double event_thres, int* sel, int* count, void* scratch, size_t scratch_stride,
+                              size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(!thresholding || event_offsets, "ebos_gml_dep_select_batch: NULL event offsets");
+  return ebos::gml_dep_select(n_windows, H, W, patch, slide, row_box, col_box, events, max_events, event_offsets, canvas_h, canvas_w,
+                              thresholding, event_thres, sel, count, scratch, scratch_stride, scratch_bytes, stream);
 }
 
 int ebos_gml_dep_init_f64(int gh, int gw, int n_dim, const int* sel, const double* draws, double* x, ebos_stream_t stream) {
+  return ebos_gml_dep_init_batch_f64(1, gh, gw, n_dim, sel, draws, x, stream);
+}
+
+int ebos_gml_dep_init_batch_f64(int n_windows, int gh, int gw, int n_dim, const int* sel, const double* draws, double* x,
+                                ebos_stream_t stream) {
   using namespace ebos;
-  EBOS_REQUIRE(gh >= 1 && gw >= 1 && n_dim >= 1 && n_dim <= 4 && sel && x, "ebos_gml_dep_init_f64: bad arguments");
+  EBOS_REQUIRE(gml_windows_ok(n_windows) && gh >= 1 && gw >= 1 && n_dim >= 1 && n_dim <= 4 && sel && x,
+               "ebos_gml_dep_init_f64: bad arguments");
   const int G = gh * gw;
-  hipLaunchKernelGGL(gml_dep_init, dim3(blocks_for(G)), dim3(kGmlBlock), 0, as_stream(stream), G, n_dim, sel, draws, x);
+  hipLaunchKernelGGL(gml_dep_init, dim3(blocks_for(G), 1, n_windows), dim3(kGmlBlock), 0, as_stream(stream), G, n_dim, sel, draws, x);
   EBOS_CHECK_LAUNCH("ebos_gml_dep_init_f64");
   return EBOS_OK;
 }
@@ -1222,13 +1476,14 @@ int ebos_gml_dep_objective_f64(int H, int W, int patch, int slide, int n_dim, in
     return EBOS_ERR_SCRATCH;
   }
   const hipStream_t st = as_stream(stream);
+  const GmlWin win = {};
   GmlBufs B;
   if ((rc = dep_bufs(g, W, xmin, ymin, D, static_cast<char*>(scratch), gx, gy, q, g.has_we ? we : nullptr, winv, const_cast<double*>(x),
-                     sel, st, &B)) != EBOS_OK)
+                     sel, win, 0, 1, st, &B)) != EBOS_OK)
     return rc;
-  if ((rc = gml_forward_backward(g, B, parts, st)) != EBOS_OK) return rc;
+  if ((rc = gml_forward_backward(g, B, win, 1, parts, st)) != EBOS_OK) return rc;
   AdamArgs a = {};
-  hipLaunchKernelGGL(gml_adam, dim3(blocks_for((int64_t)n_dim * G)), dim3(kGmlBlock), 0, st, g, B, a, grad);
+  hipLaunchKernelGGL(gml_adam, dim3(blocks_for((int64_t)n_dim * G)), dim3(kGmlBlock), 0, st, g, B, win, a, grad);
   EBOS_CHECK_LAUNCH("ebos_gml_dep_objective_f64");
   return EBOS_OK;
 }
@@ -1237,47 +1492,20 @@ int ebos_gml_dep_solve_f64(int H, int W, int patch, int slide, int n_dim, int xm
                            const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
                            const double* we, const double* winv, const int* sel, double* x, int iters, double lr, double* history,
                            double* flow_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
-  using namespace ebos;
-  GmlGeom g;
-  int rc = make_dep_geom(&g, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms);
-  if (rc != EBOS_OK) return rc;
-  EBOS_REQUIRE(gx && gy && q && winv && sel && x && scratch && (!g.has_we || we), "ebos_gml_dep_solve_f64: NULL buffer");
-  EBOS_REQUIRE(iters >= 0, "ebos_gml_dep_solve_f64: iters %d < 0", iters);
-  const int G = g.gh * g.gw;
-  const DepLayout D = dep_layout(g.H, g.W, G);
-  if (scratch_bytes < D.total) {
-    set_error("ebos_gml_dep_solve_f64: scratch too small (%zu < %zu)", scratch_bytes, D.total);
-    return EBOS_ERR_SCRATCH;
-  }
-  const hipStream_t st = as_stream(stream);
-  GmlBufs B;
-  if ((rc = dep_bufs(g, W, xmin, ymin, D, static_cast<char*>(scratch), gx, gy, q, g.has_we ? we : nullptr, winv, x, sel, st, &B)) !=
-      EBOS_OK)
-    return rc;
-  const int64_t np = (int64_t)n_dim * G;
-  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.m, 0.0);
-  hipLaunchKernelGGL(gml_fill, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, np, B.v, 0.0);
-  AdamArgs a;
-  a.lr = lr;
-  a.beta1 = 0.9;
-  a.beta2 = 0.999;
-  a.eps = 1e-8;
-  a.step = 1;
-  for (int it = 0; it < iters; ++it) {
-    if ((rc = gml_forward_backward(g, B, history ? history + 4 * (size_t)it : nullptr, st)) != EBOS_OK) return rc;
-    const double t = (double)(it + 1);
-    a.step_size = lr / (1.0 - pow(a.beta1, t));
-    a.bc2_sqrt = pow(1.0 - pow(a.beta2, t), 0.5);
-    hipLaunchKernelGGL(gml_adam, dim3(blocks_for(np)), dim3(kGmlBlock), 0, st, g, B, a, nullptr);
-    EBOS_CHECK_LAUNCH("ebos_gml_dep_solve_f64: adam");
-  }
-  if (flow_out) {
-    const GmlGeom o = dep_out_geom(g, H, W, xmin, ymin);
-    if (!g.vel) hipLaunchKernelGGL(gml_sobel, dim3(blocks_for(G)), dim3(kGmlBlock), 0, st, o, B.x, B.S);
-    hipLaunchKernelGGL(gml_flow_out, dim3(blocks_for(gml_npix(o))), dim3(kGmlBlock), 0, st, o, B.S, flow_out);
-    EBOS_CHECK_LAUNCH("ebos_gml_dep_solve_f64: flow");
-  }
-  return EBOS_OK;
+  return ebos::gml_dep_solve(1, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms, gx, gy, 0, q, we, winv,
+                             sel, x, iters, lr, history, 0, flow_out, scratch, 0, scratch_bytes, stream);
+}
+
+int ebos_gml_dep_solve_batch_f64(int n_windows, int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax,
+                                 int flags, const double* weights, const int* order, int n_terms, const double* gx, const double* gy,
+                                 int64_t grad_stride, const double* q, const double* we, const double* winv, const int* sel, double* x,
+                                 int iters, double lr, double* history, int64_t history_stride, double* flow_out, void* scratch,
+                                 size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream) {
+  EBOS_REQUIRE(grad_stride >= 0 && history_stride >= 0, "ebos_gml_dep_solve_batch_f64: negative stride");
+  EBOS_REQUIRE(!history || n_windows == 1 || history_stride >= 4 * (int64_t)iters, "ebos_gml_dep_solve_batch_f64: history rows overlap");
+  return ebos::gml_dep_solve(n_windows, H, W, patch, slide, n_dim, xmin, xmax, ymin, ymax, flags, weights, order, n_terms, gx, gy,
+                             (size_t)grad_stride, q, we, winv, sel, x, iters, lr, history, (size_t)history_stride, flow_out, scratch,
+                             scratch_stride, scratch_bytes, stream);
 }
 
 }  // extern "C"

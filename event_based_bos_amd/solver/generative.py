@@ -16,6 +16,11 @@ one per patch, laid out by a reshape, so that p_x and p_y do not start at zero);
 the coarser result; a scale's result is the parameters after its last step (the reference's ``best_x`` aliases the leaf tensor);
 the cached histogram is divided by its norm again at every scale when there are no event weights.
 
+``estimate_batch(windows, frames=None, background=None, max_batch=None) -> [B, 2, H, W]`` solves several windows per launch
+(``ebos_gml_*_batch_f64``: the window is the grid's z extent, so a batch issues the launches of one window).  It is defined as
+equal, bit for bit, to ``estimate`` on the windows in order, the draws from numpy's global RandomState and the solver's state
+afterwards included; the per-window results are in ``histories`` and ``params_per_scale_batch``.
+
 Not ported, because they do not change the result: the per-patch ``crop_event`` loop of ``run_estimation_per_scale`` (its mask is
 unused by pyramid2) and the visualisation calls (``visualize_evolution``, ``make_video``, ``visualize_scipy_history``).
 Out of scope, raising ``NotImplementedError``: the angle model, the direct-velocity model (``poisson_model: false``),
@@ -25,7 +30,7 @@ configuration error (``ValueError``; the reference raises KeyError).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -134,6 +139,8 @@ class GenerativeMixin(object):
         self.cost_func = _History(cost.keys())
         self.params_per_scale = {}
         self.iter_cnt = 0
+        self.histories = []                # estimate_batch: cost_func.get_history() of every window of the last call
+        self.params_per_scale_batch = []   # estimate_batch: params_per_scale of every window of the last call
 
     # ------------------------------------------------------------------ helpers
     def _gml_weights(self):
@@ -226,6 +233,160 @@ class GenerativeMixin(object):
             self.cost_func.history[k] = list(h[:, 1 + TERMS.index(k)])
         self.params_per_scale = {s: v.cpu().numpy() for s, v in self.params_per_scale.items()}
         self.iter_cnt += 1
+        return flow.cpu().numpy()
+
+    # ------------------------------------------------------------------ estimate_batch
+    _gml_who = "generative solver"
+
+    def _gml_batch_args(self, windows, frames, background, max_batch):
+        """The argument checks of ``estimate_batch``, before any GPU work -> (windows, frames, max_batch): ``frames`` is None (the
+        kept background), one frame for every window, or a list of one frame per window."""
+        who = self._gml_who
+        windows = list(windows)
+        n = len(windows)
+        if max_batch is None:
+            max_batch = max(n, 1)
+        if int(max_batch) != max_batch or max_batch < 1:
+            raise ValueError(f"{who}: max_batch {max_batch!r} < 1")
+        mi = self._gml_cfg.get("model_image", "current")
+        H, W = (int(v) for v in self.orig_image_shape)
+        if mi == "background":
+            if self._gml_frame is not None or n == 0:
+                return windows, None, int(max_batch)
+            if background is None:
+                raise ValueError(f"{who}: model_image 'background' needs background= on the first window")
+            frames = background
+        elif frames is None:
+            if n == 0:
+                return windows, None, int(max_batch)
+            raise ValueError(f"{who}: model_image {mi!r} needs frame=" + (" (for its shape)" if mi == "black" else ""))
+        if not isinstance(frames, (list, tuple)) and len(np.shape(frames)) == 3:
+            frames = list(frames)
+        if isinstance(frames, (list, tuple)):
+            if mi == "background":
+                raise ValueError(f"{who}: background= is one frame")
+            if len(frames) != n:
+                raise ValueError(f"{who}: {len(frames)} frames for {n} windows")
+            each = list(frames)
+        else:
+            each = [frames]
+        for f in each:
+            if tuple(np.shape(f)) != (H, W):
+                raise ValueError(f"{who}: frame shape {tuple(np.shape(f))} != image shape {(H, W)}")
+        return windows, (each if isinstance(frames, (list, tuple)) else frames), int(max_batch)
+
+    def _gml_batch_frames(self, frames, lo: int, hi: int):
+        """The model images of windows [lo, hi) -> (tensor [H, W] or [b, H, W], elements between windows); keeps the last one as
+        ``estimate`` keeps its frame."""
+        mi = self._gml_cfg.get("model_image", "current")
+        H, W = (int(v) for v in self.orig_image_shape)
+        if frames is None:
+            return self._gml_frame, 0
+        if mi == "black":
+            self._gml_set_frame(np.zeros((H, W), dtype=np.float64))
+            return self._gml_frame, 0
+        if not isinstance(frames, list):
+            self._gml_set_frame(frames)
+            return self._gml_frame, 0
+        stack = torch.stack([to_gpu(f, dtype=torch.float64) for f in frames[lo:hi]]).contiguous()
+        self._gml_frame = stack[-1].clone()
+        return stack, H * W
+
+    def _gml_batch_prepare(self, lib, evs, frame_t, frame_stride: int, scratch, nbytes: int):
+        """``ebos_gml_prepare_batch_f64`` of the windows ``evs`` (GPU tensors) -> (gx, gy, q, we, winv), each [b, H, W] (gx, gy
+        [H, W] when the model image is shared)."""
+        gml = self._gml_cfg
+        H, W = (int(v) for v in self.orig_image_shape)
+        dev, b = frame_t.device, len(evs)
+        pol = torch.stack([self._gml_imager._accumulate(ev, 1.0, _hip.SPLAT_POLARITY, EPS_NUMPY, torch.float64)[0]
+                           for ev in evs]).contiguous()   # [b, 2, H, W]
+        d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
+        ng = b if frame_stride else 1
+        gx, gy, q, winv = d(ng, H, W), d(ng, H, W), d(b, H, W), d(b, H, W)
+        use_we = _flag(gml, "weight_loss_by_event_hist")
+        we = d(b, H, W) if use_we else None
+        blur = cv_gaussian_taps(gml["iwe_sigma"]).to(dev) if gml.get("iwe_sigma") else None
+        wtap = cv_gaussian_taps(gml["weight_sigma"]).to(dev) if use_we else None
+        itap = scipy_gaussian_taps(10).to(dev) if _flag(gml, "weight_loss_by_inverse_event_hist") else None
+        rad = lambda t: 0 if t is None else (t.numel() - 1) // 2
+        check(lib.ebos_gml_prepare_batch_f64(b, H, W, ptr(frame_t), frame_stride, int(_flag(gml, "use_log_intensity")), ptr(pol),
+                                             int(_flag(gml, "no_polarity")), ptr(blur), rad(blur), ptr(wtap), rad(wtap), ptr(itap),
+                                             rad(itap), ptr(gx), ptr(gy), ptr(q), ptr(we), ptr(winv), ptr(scratch), nbytes,
+                                             stream_ptr(dev)), "ebos_gml_prepare_batch_f64")
+        return gx, gy, q, we, winv
+
+    def _gml_history(self, h: np.ndarray) -> dict:
+        """One window's history rows [iters, 4] in the shape ``cost_func.get_history()`` returns."""
+        out = {"loss": list(h[:, 0])}
+        out.update({k: list(h[:, 1 + TERMS.index(k)]) for k in self._gml_cost})
+        return out
+
+    def estimate_batch(self, windows, frames=None, background=None, max_batch: Optional[int] = None) -> np.ndarray:
+        """``estimate`` of every window of ``windows`` (a sequence of event arrays), several windows per launch -> [B, 2, H, W].
+
+        Equal to ``estimate(windows[i], frame=frames[i], background=background)`` for i = 0 .. B - 1 in order, bit for bit: the
+        flows, the histories (``histories``, one dict per window), the parameters (``params_per_scale_batch``), the draws from
+        numpy's global RandomState, ``iter_cnt`` and the kept background; ``cost_func`` and ``params_per_scale`` hold the last
+        window's values.  ``frames``: one per window, or one frame for all, or None where ``model_image`` allows it.
+        ``max_batch`` splits the list into consecutive batches of at most that many windows (a 720 x 1280 window holds about
+        100 MB on the device); the default solves all windows at once."""
+        windows, frames, max_batch = self._gml_batch_args(windows, frames, background, max_batch)
+        H, W = (int(v) for v in self.orig_image_shape)
+        flows, self.histories, self.params_per_scale_batch = [np.zeros((0, 2, H, W), dtype=np.float64)], [], []
+        for lo in range(0, len(windows), max_batch):
+            hi = min(lo + max_batch, len(windows))
+            flows.append(self._gml_solve_batch(windows[lo:hi], *self._gml_batch_frames(frames, lo, hi)))
+            self.iter_cnt += hi - lo
+        return np.concatenate(flows)
+
+    def _gml_solve_batch(self, windows: Sequence, frame_t: torch.Tensor, frame_stride: int) -> np.ndarray:
+        """One batch: every scale of every window, one launch per pass.  Appends to ``histories`` / ``params_per_scale_batch``."""
+        lib = _hip.require_gpu()
+        H, W = (int(v) for v in self.orig_image_shape)
+        dev, gml, n, b = frame_t.device, self._gml_cfg, H * W, len(windows)
+        evs = [to_gpu(ev, device=dev, dtype=torch.float64) for ev in windows]
+        d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
+        use_we = _flag(gml, "weight_loss_by_event_hist")
+        stride = int(lib.ebos_gml_scratch_bytes(H, W, PATCHES[-1]))
+        nbytes = int(lib.ebos_gml_scratch_bytes_batch(H, W, PATCHES[-1], b))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _hip.on_device(dev):
+            sp = stream_ptr(dev)
+            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes)
+            weights, order, n_terms = self._gml_weights()
+            w_t = torch.from_numpy(weights).to(dev)
+            o_t = torch.from_numpy(order).to(dev)
+            flags = (_hip.GML_NO_POLARITY if _flag(gml, "no_polarity") else 0) | (_hip.GML_EVENT_WEIGHTS if use_we else 0)
+            iters = [self._gml_n_iter // (FINEST_SCALE - s + 1) for s in range(1, FINEST_SCALE)]
+            rows = max(sum(iters), 1)
+            hist = d(b, rows, 4)
+            flow = d(b, 2, H, W)
+            xmin, xmax, ymin, ymax = self._gml_roi
+            x, row, per_scale = None, 0, {}
+            for s, p in enumerate(PATCHES, start=1):
+                gh, gw = grid_shape((H, W), p)
+                if x is None:   # window by window, as successive estimate calls draw
+                    x = torch.from_numpy(np.stack([self._gml_initial(gh, gw) for _ in range(b)])).to(dev)
+                else:
+                    x = F.interpolate(x, size=[gh, gw], mode="bilinear", align_corners=False).contiguous()
+                if s > 1 and not use_we:
+                    check(lib.ebos_gml_normalize_batch_f64(b, n, ptr(q), ptr(scratch), nbytes, sp), "ebos_gml_normalize_batch_f64")
+                it = iters[s - 1]
+                check(lib.ebos_gml_solve_scale_batch_f64(b, H, W, p, self._gml_n_dim, xmin, xmax, ymin, ymax, flags, ptr(w_t), ptr(o_t),
+                                                         n_terms, ptr(gx), ptr(gy), n if frame_stride else 0, ptr(q), ptr(we),
+                                                         ptr(winv), ptr(x), it, LR, ptr(hist[0, row:]), rows * 4,
+                                                         ptr(flow) if s == len(PATCHES) else None, ptr(scratch), stride, nbytes, sp),
+                      "ebos_gml_solve_scale_batch_f64")
+                row += it
+                per_scale[s] = x
+        h = hist[:, :row].cpu().numpy()   # the one read-back of the batch's histories
+        per_scale = {s: v.cpu().numpy() for s, v in per_scale.items()}
+        for i in range(b):
+            self.histories.append(self._gml_history(h[i]))
+            self.params_per_scale_batch.append({s: v[i] for s, v in per_scale.items()})
+        self.cost_func.clear_history()
+        self.cost_func.history.update(self._gml_history(h[-1]))
+        self.params_per_scale = dict(self.params_per_scale_batch[-1])
         return flow.cpu().numpy()
 
     def _gml_initial(self, gh: int, gw: int) -> np.ndarray:

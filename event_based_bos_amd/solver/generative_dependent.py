@@ -18,13 +18,18 @@ selected patch in row-major order); the velocity model starts at zero; the resul
 reference's ``best_x`` aliases the leaf tensor).  Per window the host reads back the selection count (to draw the initial values),
 then the loss history and the flow.
 
+``estimate_batch(windows, frames=None, background=None, max_batch=None) -> [B, 2, H, W]`` solves several windows per launch
+(``ebos_gml_dep_*_batch*``), bit for bit equal to ``estimate`` on the windows in order: the selection counts of a batch are read
+back once, then the initial values are drawn window by window.  Per window: ``histories``, ``params_batch``,
+``estimate_indices_batch``.
+
 Not ported: the visualisation calls.  Raising ``NotImplementedError``: the angle model, ``sobel_ksize: 5``, optimizers other than
 Adam, cost terms other than diff_norm / image_gradient / flow_norm_pxy.  ``model_image: black`` is a ``ValueError`` (the reference
 never sets its frame).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Sequence, Tuple
 
 import numpy as np
 import torch
@@ -93,6 +98,8 @@ class GenerativeDependentMixin(GenerativeMixin):
         self._dep_dev = {}
         self._dep_sel = None
         self._dep_x = None
+        self.params_batch = []             # estimate_batch: the final parameter grid of every window of the last call
+        self.estimate_indices_batch = []   # estimate_batch: the selected patches of every window of the last call
 
     # ------------------------------------------------------------------ results of the last window
     @property
@@ -189,6 +196,82 @@ class GenerativeDependentMixin(GenerativeMixin):
             self.cost_func.history[k] = list(h[:, 1 + ("diff_norm", "image_gradient", "flow_norm_pxy").index(k)])
         self._dep_sel, self._dep_x = sel, x
         self.iter_cnt += 1
+        return flow.cpu().numpy()
+
+
+    # ------------------------------------------------------------------ estimate_batch
+    _gml_who = "generative dependent solver"
+
+    def estimate_batch(self, windows, frames=None, background=None, max_batch=None) -> np.ndarray:
+        self.params_batch, self.estimate_indices_batch = [], []
+        return GenerativeMixin.estimate_batch(self, windows, frames=frames, background=background, max_batch=max_batch)
+
+    estimate_batch.__doc__ = GenerativeMixin.estimate_batch.__doc__.replace("``params_per_scale_batch``",
+                                                                            "``params_batch``, ``estimate_indices_batch``")
+
+    def _gml_solve_batch(self, windows: Sequence, frame_t: torch.Tensor, frame_stride: int) -> np.ndarray:
+        """One batch: selection (one read-back of the counts), the draws in window order, the Adam loop, one launch per pass."""
+        lib = _hip.require_gpu()
+        H, W = (int(v) for v in self.orig_image_shape)
+        dev, gml, b = frame_t.device, self._gml_cfg, len(windows)
+        p, s = self._dep_patch, self._dep_slide
+        gh, gw = self.patch_image_size
+        nd, G = self._gml_n_dim, gh * gw
+        xmin, xmax, ymin, ymax = self._gml_roi
+        evs = [to_gpu(ev, device=dev, dtype=torch.float64).reshape(-1, 4).contiguous() for ev in windows]
+        counts = [int(ev.shape[0]) for ev in evs]
+        d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
+        use_we = _flag(gml, "weight_loss_by_event_hist")
+        hc, wc = self._dep_canvas if self._dep_thresholding else (0, 0)
+        stride = int(lib.ebos_gml_dep_scratch_bytes(H, W, p, s, xmin, xmax, ymin, ymax, hc, wc))
+        nbytes = int(lib.ebos_gml_dep_scratch_bytes_batch(H, W, p, s, xmin, xmax, ymin, ymax, hc, wc, b))
+        if stride == 0 or nbytes == 0:
+            raise ValueError("generative dependent solver: invalid geometry")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rb, cb = self._dep_box_tensors(dev)
+        sel = torch.empty(b, gh, gw, dtype=torch.int32, device=dev)
+        count = torch.zeros(b, dtype=torch.int32, device=dev)
+        with _hip.on_device(dev):
+            sp = stream_ptr(dev)
+            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes)
+            ev_all = torch.cat(evs) if self._dep_thresholding else None
+            offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
+            check(lib.ebos_gml_dep_select_batch(b, H, W, p, s, ptr(rb), ptr(cb), ptr(ev_all), ptr(offsets), max(counts), hc, wc,
+                                                int(self._dep_thresholding), self._dep_thres, ptr(sel), ptr(count), ptr(scratch),
+                                                stride, nbytes, sp), "ebos_gml_dep_select_batch")
+            n_sel = [int(v) for v in count.cpu().numpy()]   # read-back 1 of the batch: how many initial values each window draws
+            draws = None if self._gml_velocity else np.zeros((b, G), dtype=np.float64)
+            for i, ns in enumerate(n_sel):   # window by window, as successive estimate calls draw (and fail)
+                if ns == 0:
+                    raise ValueError("generative dependent solver: no patch selected (the reference cannot start from an empty x0)")
+                if draws is not None:
+                    np.random.random()   # len(self._initialize_velocity()): one draw, discarded
+                    draws[i, :ns] = np.random.random(ns) * 2. - 1
+            draws_t = None if draws is None else torch.from_numpy(draws).to(dev)
+            x = d(b, nd, gh, gw)
+            check(lib.ebos_gml_dep_init_batch_f64(b, gh, gw, nd, ptr(sel), ptr(draws_t), ptr(x), sp), "ebos_gml_dep_init_batch_f64")
+            weights, order, n_terms = self._gml_weights()
+            w_t = torch.from_numpy(weights).to(dev)
+            o_t = torch.from_numpy(order).to(dev)
+            flags = ((_hip.GML_NO_POLARITY if _flag(gml, "no_polarity") else 0) | (_hip.GML_EVENT_WEIGHTS if use_we else 0) |
+                     (_hip.GML_VELOCITY if self._gml_velocity else 0))
+            it = self._gml_n_iter
+            rows = max(it, 1)
+            hist = d(b, rows, 4)
+            flow = d(b, 2, H, W)
+            check(lib.ebos_gml_dep_solve_batch_f64(b, H, W, p, s, nd, xmin, xmax, ymin, ymax, flags, ptr(w_t), ptr(o_t), n_terms,
+                                                   ptr(gx), ptr(gy), H * W if frame_stride else 0, ptr(q), ptr(we), ptr(winv),
+                                                   ptr(sel), ptr(x), it, LR, ptr(hist), rows * 4, ptr(flow), ptr(scratch), stride,
+                                                   nbytes, sp), "ebos_gml_dep_solve_batch_f64")
+        h = hist[:, :it].cpu().numpy()   # read-back 2: the histories
+        sel_np, x_np = sel.cpu().numpy(), x.cpu().numpy()
+        for i in range(b):
+            self.histories.append(self._gml_history(h[i]))
+            self.params_batch.append(x_np[i])
+            self.estimate_indices_batch.append(np.nonzero(sel_np[i].reshape(-1))[0])
+        self.cost_func.clear_history()
+        self.cost_func.history.update(self._gml_history(h[-1]))
+        self._dep_sel, self._dep_x = sel[-1], x[-1]
         return flow.cpu().numpy()
 
 

@@ -1098,6 +1098,27 @@ int ebos_gml_solve_scale_f64(int H, int W, int patch, int n_dim, int xmin, int x
                              const double* winv, double* x, int iters, double lr, double* history, double* flow_out, void* scratch,
                              size_t scratch_bytes, ebos_stream_t stream);
 
+/* The window axis: n_windows (1 .. 65535) independent windows per call, one launch of every pass for all of them (the window is
+ * the grid's z extent).  Window b is computed by exactly the operations, in the order, of the single-window entry, which is the
+ * n_windows = 1 case of the same kernels: results are bit-identical to n_windows single calls.  Everything that differs per
+ * window is window-major and contiguous: pol [B, 2, H, W]; gx, gy, q, we, winv [B, H, W]; x [B, n_dim, gh, gw]; flow_out
+ * [B, 2, H, W]; history rows of window b at history + b * history_stride doubles (>= 4 iters).  frame_stride / grad_stride
+ * (elements between windows) is H W, or 0 for one model image shared by all windows (gx, gy are then [H, W], formed once).
+ * Geometry, cost weights, flags and iters are shared.  Scratch: ebos_gml_scratch_bytes_batch = n_windows slices of
+ * ebos_gml_scratch_bytes; the solve entries use slice b at scratch + b * scratch_stride bytes (a multiple of 256, at least one
+ * window's bytes); prepare and normalize lay their work planes out over the whole allocation. */
+size_t ebos_gml_scratch_bytes_batch(int H, int W, int min_patch, int n_windows);
+int ebos_gml_prepare_batch_f64(int n_windows, int H, int W, const double* frame, int64_t frame_stride, int use_log, const double* pol,
+                               int no_polarity, const double* blur_taps, int blur_radius, const double* weight_taps, int weight_radius,
+                               const double* inv_taps, int inv_radius, double* gx, double* gy, double* q, double* we, double* winv,
+                               void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_normalize_batch_f64(int n_windows, int64_t n, double* q, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_solve_scale_batch_f64(int n_windows, int H, int W, int patch, int n_dim, int xmin, int xmax, int ymin, int ymax, int flags,
+                                   const double* weights, const int* order, int n_terms, const double* gx, const double* gy,
+                                   int64_t grad_stride, const double* q, const double* we, const double* winv, double* x, int iters,
+                                   double lr, double* history, int64_t history_stride, double* flow_out, void* scratch,
+                                   size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------- *
  * Generative BOS solver, single scale (src/solver/patch_eklt_dependent.py, patch_eklt_dependent), float64.
  *
@@ -1130,6 +1151,25 @@ int ebos_gml_dep_solve_f64(int H, int W, int patch, int slide, int n_dim, int xm
                            const double* weights, const int* order, int n_terms, const double* gx, const double* gy, const double* q,
                            const double* we, const double* winv, const int* sel, double* x, int iters, double lr, double* history,
                            double* flow_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
+/* The window axis of the single-scale solver (see above; the same kernels, n_windows = 1 being the entries above).  sel
+ * [B, gh, gw], count [B] (read back once per batch), draws [B, gh gw] (window b uses its first count[b] values; NULL: all zero),
+ * x [B, n_dim, gh, gw].  The events of all windows are one concatenated [n, 4] array; event_offsets [B + 1] (device int64) bound
+ * each window's rows and max_events is the largest window's count.  Scratch: ebos_gml_dep_scratch_bytes_batch = n_windows slices
+ * of ebos_gml_dep_scratch_bytes, slice b at scratch + b * scratch_stride bytes. */
+size_t ebos_gml_dep_scratch_bytes_batch(int H, int W, int patch, int slide, int xmin, int xmax, int ymin, int ymax, int canvas_h,
+                                        int canvas_w, int n_windows);
+int ebos_gml_dep_select_batch(int n_windows, int H, int W, int patch, int slide, const int* row_box, const int* col_box,
+                              const double* events, const int64_t* event_offsets, int64_t max_events, int canvas_h, int canvas_w,
+                              int thresholding, double event_thres, int* sel, int* count, void* scratch, size_t scratch_stride,
+                              size_t scratch_bytes, ebos_stream_t stream);
+int ebos_gml_dep_init_batch_f64(int n_windows, int gh, int gw, int n_dim, const int* sel, const double* draws, double* x,
+                                ebos_stream_t stream);
+int ebos_gml_dep_solve_batch_f64(int n_windows, int H, int W, int patch, int slide, int n_dim, int xmin, int xmax, int ymin, int ymax,
+                                 int flags, const double* weights, const int* order, int n_terms, const double* gx, const double* gy,
+                                 int64_t grad_stride, const double* q, const double* we, const double* winv, const int* sel, double* x,
+                                 int iters, double lr, double* history, int64_t history_stride, double* flow_out, void* scratch,
+                                 size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,13 @@ With ``--method patch_eklt_dependent``, the single-scale solver (GenerativePatch
   hip_ms_per_iter       (window at n_iter 600 - window at n_iter 100) / 500;
   torch_gpu_ms_per_iter _gml_dep_ref.Model forward + backward + torch.optim.Adam step on the GPU, float64 (eager baseline);
   torch_gpu_window_ms   the same iteration times 600.
+
+With ``--batch B [B ...]`` (either method), only the window axis is measured, at n_iter 600 and both sizes:
+  sequential_window_ms  one ``estimate`` per window, host clock around a synchronised call (every repeat is kept: their spread is
+                        the margin a comparison has to clear);
+  batch[B].window_ms    ``estimate_batch`` of B windows (different event counts), divided by B; .ms_per_iter divides by the
+                        window's iterations as well.
+The kernel table of a batch comes from a run of its own: rocprofv3 --kernel-trace --stats -- python tools/run_gml.py --batch B.
 """
 import argparse
 import json
@@ -190,13 +197,64 @@ def bench_dep_size(H, W):
     return out
 
 
+def batch_windows(H, W, n):
+    """n windows over one frame: different seeds, different event counts (2 per pixel, down to ~1.5)."""
+    return frame_image(H, W, 1), [synth_events(2 * H * W - (i % 4) * (H * W // 6), H, W, 2 + i) for i in range(n)]
+
+
+def bench_batch_size(method, H, W, batches, reps=3, n_iter=600):
+    import event_based_bos_amd as ebos
+    dep = method == "patch_eklt_dependent"
+    cls = ebos.solver.GenerativePatchDependent if dep else ebos.solver.GenerativePatchPyramid
+    solv = cls((H, W), (H, W), {}, (dep_config if dep else config)(H, W, n_iter))
+    frame, windows = batch_windows(H, W, max(batches))
+    iters = n_iter if dep else sum(n_iter // (5 - s + 1) for s in range(1, 5))
+    out = {"method": method, "size": [H, W], "iterations": iters, "batch": {}}
+
+    def timed(fn, n):
+        np.random.seed(0)
+        fn()   # warm-up: code objects, allocations
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(n):
+            np.random.seed(0)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return ts
+
+    seq = timed(lambda: solv.estimate(windows[0], frame=frame), max(reps, 5))
+    out["sequential_window_ms"] = min(seq)
+    out["sequential_window_ms_all"] = seq
+    for b in batches:
+        ts = [t / b for t in timed(lambda: solv.estimate_batch(windows[:b], frames=frame), reps)]
+        out["batch"][str(b)] = {"window_ms": min(ts), "window_ms_all": ts, "ms_per_iter": min(ts) / iters,
+                                "vs_sequential": min(seq) / min(ts)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, metavar="B",
+                    help="measure estimate_batch at these batch sizes beside the sequential window (nothing else)")
+    ap.add_argument("--sizes", type=int, nargs="+", default=(720, 1280, 260, 346), metavar="N", help="--batch: H W [H W ...]")
+    ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_gml.py measures on the GPU"
+    if args.batch:
+        res = {"sizes": []}
+        for H, W in zip(args.sizes[0::2], args.sizes[1::2]):
+            r = bench_batch_size(args.method, H, W, sorted(set(args.batch)), args.reps)
+            res["sizes"].append(r)
+            print(json.dumps(r), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     if args.method == "patch_eklt_dependent":
         res = {"sizes": []}
         for H, W in ((720, 1280), (260, 346)):

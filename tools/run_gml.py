@@ -6,6 +6,7 @@ BOS scene with a known displacement field.
     python tools/run_gml.py --size 128 160 --n_iter 120 --json out.json
     python tools/run_gml.py --config_file tests/golden/config_hot_plate1.json # the REFERENCE's configs/hot_plate1.yaml, as it is
     python tools/run_gml.py --method patch_eklt_dependent                     # the single-scale solver, the YAML's patch_eklt block
+    python tools/run_gml.py --batch 8                                         # 8 windows of the scene through estimate_batch
 
 The scene: a textured frame L, a potential phi (two Gaussian bumps) and its gradient d = grad phi as the displacement; events are
 drawn at pixels with probability proportional to |grad L . d|, with the sign of grad L . d as polarity.  Reported: the loss at
@@ -60,6 +61,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent"),
                     help="the solver when no --config_file is given")
+    ap.add_argument("--batch", type=int, default=0, metavar="B",
+                    help="also solve B windows of the scene (different event seeds and counts) with estimate_batch: per-window time "
+                         "beside the sequential window's, and whether window 0 equals the sequential result bit for bit")
     ap.add_argument("--json", default=None, help="also write the result here")
     args = ap.parse_args()
 
@@ -102,6 +106,20 @@ def main():
            "loss_first": float(h["loss"][0]), "loss_last": float(h["loss"][-1]), "window_ms": 1e3 * t_window,
            "ms_per_iteration": 1e3 * t_window / max(n_it, 1), "cosine_roi": cos,
            "EPE": float(err["EPE"]), "AE": float(err["AE"])}
+    if args.batch > 0:
+        n_ev = args.events or 2 * H * W
+        windows = [events] + [scene(H, W, n_ev - (i % 4) * (n_ev // 8), args.seed + i)[1] for i in range(1, args.batch)]
+        np.random.seed(args.seed)
+        solv.estimate_batch(windows, frames=frame, background=frame)   # warm-up
+        torch.cuda.synchronize()
+        np.random.seed(args.seed)
+        t0 = time.perf_counter()
+        flows = solv.estimate_batch(windows, frames=frame, background=frame)
+        t_batch = time.perf_counter() - t0
+        res.update({"batch": args.batch, "batch_window_ms": 1e3 * t_batch / args.batch,
+                    "batch_ms_per_iteration": 1e3 * t_batch / args.batch / max(n_it, 1),
+                    "batch_vs_sequential": t_window / (t_batch / args.batch),
+                    "batch_window0_bit_identical": bool(np.array_equal(flows[0], flow))})
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:
