@@ -15,7 +15,8 @@ tub-rip/event_based_bos:
     flow_error           the reference's flow-error metrics (EPE, NPE, AE), batched, on the GPU
     poisson              the reference's Poisson integration of a flow (and its uint8 picture), batched, on fp64 matrix cores
     frame_flow           the reference's frame-based flow (cv2.calcOpticalFlowFarneback, FrameFlowEstimator), batched
-    data_loader          raw-column event store (the CCS raw_events layout) feeding EventPlan.build_raw
+    frame_warp           the reference loader's frame warp (cv2.warpPerspective) and the driver's crop, batched, one launch
+    data_loader          raw-column event store (the CCS raw_events layout) feeding EventPlan.build_raw; FrameStore, the frame half
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -25,6 +26,8 @@ from ._hip import HipUnavailableError, load_library  # noqa: F401
 from .warp import MotionModelKeyError, Warp  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
 from .event_plan import EventPlan, SlabBatch  # noqa: F401
-from . import costs, data_loader, event_filters, flow_error, frame_flow, fusion, ops, poisson, solver, types, utils  # noqa: F401
+from .data_loader import FrameStore, RawEventStore  # noqa: F401
+from .frame_warp import validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
+from . import costs, data_loader, event_filters, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils  # noqa: F401
 
 __version__ = "0.1.0"

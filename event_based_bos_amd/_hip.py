@@ -239,6 +239,7 @@ SIGNATURES = {
     "ebos_gml_dep_select_batch": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _D, _P, _P, _P, _Z, _Z, _P]),
     "ebos_gml_dep_init_batch_f64": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "ebos_gml_dep_solve_batch_f64": (_I, [_I] * 11 + [_P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _D, _P, _L, _P, _P, _Z, _Z, _P]),
+    "ebos_warp_perspective": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
 }
 
 
@@ -248,6 +249,7 @@ FILTER_STATUS_OUT_OF_SENSOR, FILTER_STATUS_CLIPPED = 0, 1
 FLOW_ERROR_F32, FLOW_ERROR_F64, FLOW_ERROR_CLAMP_AE = 0, 1, 1
 POISSON_F32, POISSON_F64 = 0, 1
 FARNEBACK_U8, FARNEBACK_F32, FARNEBACK_F64 = 0, 1, 2
+WARP_U8, WARP_F32 = 0, 1
 
 
 class EventSource(C.Structure):

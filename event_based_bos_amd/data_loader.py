@@ -1,4 +1,5 @@
-"""Event ingest for the hot path: a raw-column event store.
+"""Ingest for the hot path: a raw-column event store and a frame store, the two halves of the reference's
+co-capture loader (src/data_loader/ccs.py, ``CcsDataLoader``).
 
 The reference reads CCS recordings from HDF5 (``raw_events/{x: int16, y: int16, t: int32 us, p: bool}``,
 src/data_loader/ccs.py:57-66) and hands every window to the solver as a float64 ``[n, 4]`` array
@@ -13,11 +14,20 @@ expands it with the same fp64 time arithmetic.
     plan = store.plan(i0, i1, (720, 1280), "first")      # fast path: raw columns -> device -> EventPlan
 
 Index helpers follow the reference loader: ``index_to_time`` (:319-330), ``time_to_index`` = searchsorted - 1 (:343-356).
+
+``FrameStore`` is the frame half (:36-47, :136-156, :332-343, :359-396): the camera frames, their trigger timestamps and the
+homography that maps them into the event view, under the reference's method names.  ``load_image`` returns what the reference
+returns; ``load_images`` uploads a batch of raw frames once and warps and crops them in one launch (frame_warp).
+
+    frames = FrameStore("frames.npy", "trigger_events.txt", "homography.txt", (720, 1280))
+    i = frames.time_to_image_index(t)
+    batch, ts = frames.load_images(range(i, i + 8), roi=config["common_params"])      # device [8, h, w]
 """
 from __future__ import annotations
 
 import logging
-from typing import Dict, Tuple, Union
+import os
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -150,6 +160,198 @@ class RawEventStore(object):
 
     def time_to_index(self, time: float) -> int:
         return int(np.searchsorted(self._times(), time)) - 1
+
+
+# file name suffixes that count as camera frames in a frame directory (the set the reference's loader accepts)
+_FRAME_SUFFIXES = frozenset((".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp", ".dng", ".mpo"))
+
+
+def list_frame_files(directory: str) -> list:
+    """The frame files of ``directory`` in name order: regular entries whose suffix, in any letter case, is an image suffix."""
+    names = sorted(n for n in os.listdir(directory) if os.path.splitext(n)[1].lower() in _FRAME_SUFFIXES)
+    return [os.path.join(directory, n) for n in names]
+
+
+def _trigger_rows(path: str):
+    """The integer records of a trigger text file and their column layout: "old" = whitespace-separated (t, id, polarity),
+    "new" = comma-separated (polarity, id, t).  The separator of the first record decides."""
+    with open(path) as f:
+        lines = [ln for ln in (raw.strip() for raw in f) if ln and not ln.startswith("#")]
+    if not lines:
+        raise ValueError(f"{path} holds no trigger records")
+    comma = "," in lines[0]
+    if comma:
+        logger.info(f"{path}: comma-separated trigger records (polarity, id, t)")
+    try:
+        rows = np.array([[int(v) for v in (ln.split(",") if comma else ln.split())] for ln in lines], dtype=np.int64)
+    except ValueError as err:
+        raise ValueError(f"{path}: trigger records must be three integers a line ({err})") from None
+    return rows, "new" if comma else "old"
+
+
+def read_trigger_timestamps(source, layout: str = "auto") -> np.ndarray:
+    """Trigger records -> the integer microsecond stamps of the POSITIVE edges (what the reference's loader keeps of its
+    ``trigger_events.txt``).
+
+    A path is a text file of three integers a line in either of the two layouts the reference reads: whitespace-separated
+    (t, id, polarity) or comma-separated (polarity, id, t).  An [n, 3] integer array is taken in the layout ``layout`` names
+    ("old" or "new"; "auto" = "old"); a 1-D integer array holds the positive edges' stamps already."""
+    if layout not in ("auto", "old", "new"):
+        raise ValueError(f"layout must be 'auto', 'old' or 'new', got {layout!r}")
+    if isinstance(source, (str, os.PathLike)):
+        rows, found = _trigger_rows(str(source))
+        if layout not in ("auto", found):
+            raise ValueError(f"{source} is in the {found!r} layout, not {layout!r}")
+        layout = found
+    else:
+        rows = np.asarray(source)
+        if not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError(f"trigger records must be integers (microseconds), got {rows.dtype}")
+        if rows.ndim == 1:
+            return rows
+        layout = "old" if layout == "auto" else layout
+    if rows.ndim != 2 or rows.shape[1] != 3:
+        raise ValueError(f"trigger records must be [n, 3], got {rows.shape}")
+    t_col, p_col = (0, 2) if layout == "old" else (2, 0)
+    return rows[rows[:, p_col] == 1, t_col]
+
+
+def _read_image(path: str) -> np.ndarray:
+    """A frame file as a grey uint8 [Hs, Ws] array (what ``cv2.imread(path, IMREAD_GRAYSCALE)`` hands the reference's loader; a
+    colour file goes through PIL's own luma conversion)."""
+    try:
+        from PIL import Image
+    except ImportError as err:
+        raise ImportError("reading frame files needs PIL (Pillow); pass the frames as an [N, Hs, Ws] array or .npy instead") from err
+    with Image.open(path) as im:
+        return np.asarray(im.convert("L"), dtype=np.uint8)
+
+
+class FrameStore(object):
+    """The frame half of ``CcsDataLoader``.
+
+    Args:
+        frames ... an [N, Hs, Ws] uint8 / float32 array, a ``.npy`` / ``.npz`` path holding one (``.npz``: key ``frames``, or its
+            only array), or a directory of image files (sorted; the reference's suffix list; read with PIL).
+        timestamps ... the trigger file (either text format) or an array, see ``read_trigger_timestamps``; seconds = stamps / 1e6.
+        homography ... None (frames are returned as they are), a text file (``np.loadtxt``) or a 3 x 3 array: camera -> event view.
+        sensor_size ... (height, width) of the event sensor: the size warped frames have.  Required with a homography.
+    """
+    def __init__(self, frames, timestamps, homography=None, sensor_size: Optional[Tuple[int, int]] = None,
+                 timestamp_layout: str = "auto"):
+        self._files, self._stack = None, None
+        if isinstance(frames, (str, os.PathLike)):
+            frames = str(frames)
+            if os.path.isdir(frames):
+                self._files = list_frame_files(frames)
+            elif frames.lower().endswith(".npz"):
+                with np.load(frames) as f:
+                    keys = list(f.keys())
+                    if "frames" not in keys and len(keys) != 1:
+                        raise ValueError(f"{frames} holds {keys}: expected the key 'frames' or a single array")
+                    self._stack = f["frames" if "frames" in keys else keys[0]]
+            elif frames.lower().endswith(".npy"):
+                self._stack = np.load(frames)
+            else:
+                raise ValueError(f"{frames} is neither a directory of image files nor a .npy / .npz stack")
+        elif isinstance(frames, np.ndarray):
+            self._stack = frames
+        else:
+            raise ValueError(f"frames must be an [N, Hs, Ws] array, a .npy / .npz path or a directory, got {type(frames).__name__}")
+        if self._stack is not None:
+            if self._stack.ndim != 3 or self._stack.dtype not in (np.uint8, np.float32):
+                raise ValueError(f"the frame stack must be [N, Hs, Ws] uint8 or float32, got {self._stack.shape} {self._stack.dtype}")
+            self._stack = np.ascontiguousarray(self._stack)
+        self.timestamps = read_trigger_timestamps(timestamps, timestamp_layout) / 1e6
+        self.homography = None
+        if homography is not None:
+            h = np.loadtxt(homography) if isinstance(homography, (str, os.PathLike)) else np.asarray(homography, dtype=np.float64)
+            if h.shape != (3, 3) or not np.isfinite(h).all():
+                raise ValueError(f"the homography must be a finite 3 x 3 matrix, got shape {h.shape}")
+            if sensor_size is None:
+                raise ValueError("sensor_size (height, width) is required with a homography")
+            self.homography = np.ascontiguousarray(h, dtype=np.float64)
+        self._HEIGHT, self._WIDTH = (None, None) if sensor_size is None else (int(sensor_size[0]), int(sensor_size[1]))
+        if sensor_size is not None and (self._HEIGHT < 1 or self._WIDTH < 1):
+            raise ValueError(f"sensor_size must be positive, got {sensor_size}")
+        self._pinned = None
+
+    @property
+    def warp_frame(self) -> bool:
+        return self.homography is not None
+
+    @property
+    def num_images(self) -> int:
+        return len(self._files) if self._stack is None else len(self._stack)
+
+    def image_index_to_time(self, index: int) -> float:
+        return self.timestamps[index]
+
+    def time_to_image_index(self, time: float) -> int:
+        return int(np.searchsorted(self.timestamps, time)) - 1
+
+    # ------------------------------------------------------------------ frames
+    def _raw(self, index: int) -> np.ndarray:
+        return self._stack[index] if self._stack is not None else _read_image(self._files[index])
+
+    def _check_index(self, index) -> int:
+        """0 .. num_images - 1.  Stricter than the reference, whose ``load_image`` only asserts ``index < len`` and so takes -1 for
+        the last frame: ``time_to_image_index`` answers -1 for a time before the first frame, and loading the LAST frame for it
+        would be a silent error.  (``image_index_to_time`` indexes the timestamps as the reference does, negative indices included.)"""
+        if int(index) != index or not 0 <= index < self.num_images:
+            raise IndexError(f"image index {index} outside 0 .. {self.num_images - 1}")
+        return int(index)
+
+    def load_image(self, index: int) -> Tuple[np.ndarray, float]:
+        """(image, timestamp) as src/data_loader/ccs.py:373-396: the frame, warped to the sensor's (height, width) where a
+        homography is set (that runs on the GPU), as a numpy array."""
+        from . import frame_warp
+
+        index = self._check_index(index)
+        image, timestamp = self._raw(index), self.timestamps[index]
+        if self.warp_frame:
+            image = frame_warp.warp_perspective(image, self.homography, (self._WIDTH, self._HEIGHT))
+        return image, timestamp
+
+    def pin(self) -> "FrameStore":
+        """Hold every raw frame in one page-locked stack (a directory is read once): later batches upload as plain asynchronous
+        copies from it."""
+        if self._pinned is None:
+            _hip.require_gpu()
+            if self._stack is None:
+                self._stack = np.stack([_read_image(f) for f in self._files])
+            self._pinned = torch.from_numpy(self._stack).pin_memory()
+        return self
+
+    def load_images(self, indices: Sequence[int], roi=None, device="cuda") -> Tuple[torch.Tensor, np.ndarray]:
+        """(device [B, h, w], timestamps [B]): the raw frames uploaded once, then warped and cropped by ONE launch; no host
+        synchronisation.  ``roi``: the driver's ``common_params`` (dict with xmin, xmax = rows and ymin, ymax = columns) or that
+        4-tuple; frame b equals ``validate_image(load_image(indices[b])[0], roi)``, and like ``validate_image`` a ``roi`` with an odd
+        number of rows or columns raises ``AssertionError``."""
+        from . import frame_warp
+
+        idx = [self._check_index(i) for i in indices]
+        if not idx:
+            raise ValueError("indices holds no frame")
+        first = self._raw(idx[0])
+        H, W = (self._HEIGHT, self._WIDTH) if self.warp_frame else first.shape
+        rect = frame_warp._check_roi(roi, H, W)
+        if roi is not None:
+            frame_warp.check_even_crop(rect[1] - rect[0], rect[3] - rect[2], rect)
+        _hip.require_gpu()
+        dev = torch.device(device)
+        contiguous = idx == list(range(idx[0], idx[0] + len(idx)))
+        if self._pinned is not None:
+            host = self._pinned[idx[0]:idx[0] + len(idx)] if contiguous else self._pinned[torch.as_tensor(idx)].pin_memory()
+        elif self._stack is not None:
+            host = torch.from_numpy(self._stack[idx[0]:idx[0] + len(idx)] if contiguous else self._stack[idx])
+        else:
+            host = torch.from_numpy(np.stack([first] + [self._raw(i) for i in idx[1:]]))
+        raw = host.to(dev, non_blocking=True)
+        ts = self.timestamps[idx]
+        if not self.warp_frame:
+            return raw[:, rect[0]:rect[1], rect[2]:rect[3]], ts
+        return frame_warp.warp_perspective_batch(raw, self.homography, (W, H), roi=rect), ts
 
 
 collections = {RawEventStore.NAME: RawEventStore}

@@ -1171,6 +1171,38 @@ int ebos_gml_dep_solve_batch_f64(int n_windows, int H, int W, int patch, int sli
                                  int iters, double lr, double* history, int64_t history_stride, double* flow_out, void* scratch,
                                  size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Perspective warp of camera frames into the event view: cv2.warpPerspective(src, M, (W, H), flags, BORDER_CONSTANT, border_value)
+ * as the reference's co-capture loader applies it to every frame (src/data_loader/ccs.py:373-396), for B frames in one launch,
+ * with the driver's validate_image crop (bos_event.py:25-39) fused in.  The arithmetic is OpenCV's classic fixed-point path
+ * (4.5 - 4.10) as tests/_warp_ref.py restates it: M inverted in double on the host unless EBOS_WARP_INVERSE_MAP (closed-form
+ * cofactors, one reciprocal); per pixel the double coordinates from the origin column of its block, 32 / W, round half to even,
+ * 5 fraction bits (the clamp is fmin / fmax: a NaN coordinate, inf * 0 where 32 / W overflows, becomes INT_MAX, outside every
+ * source); uint8: 15-bit weights, (sum + 16384) >> 15; float32: float weights, accumulated left to right; a tap outside
+ * the source is border_value (uint8: rounded and saturated).  It restates that algorithm and is not checked against OpenCV.
+ * No atomics, no scratch, no host synchronisation: a frame's bits do not depend on B, a pixel's bits not on the rectangle.
+ *
+ * dtype: EBOS_WARP_U8 / _F32, the element type of src and out.  src: device [B, Hs, Ws] (element strides src_sb, src_sr; unit
+ * columns).  M: HOST doubles, one row-major 3 x 3 shared by the batch (m_stride 0) or one per frame (m_stride 9; then 32 frames
+ * per launch); they travel as launch arguments, 72 bytes in the shared case.  Destination H rows x W columns; only rows
+ * [xmin, xmax) and columns [ymin, ymax) (the reference's common_params names) are computed: pixel (row y, column x) of frame b
+ * goes to out[b out_sb + (y - xmin) out_sr + (x - ymin)].
+ * flags: EBOS_WARP_INTER_NEAREST or EBOS_WARP_INTER_LINEAR, optionally | EBOS_WARP_INVERSE_MAP; anything else is
+ * EBOS_ERR_UNSUPPORTED.  Bad sizes (Hs, Ws <= 32767; H, W <= 65535), strides, rectangle, a non-finite border value, a matrix that
+ * is singular, not finite or beyond 1e100 in magnitude: EBOS_ERR_INVALID_ARG, before anything is launched.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum ebos_warp_dtype {
+  EBOS_WARP_U8 = 0,
+  EBOS_WARP_F32 = 1
+} ebos_warp_dtype;
+#define EBOS_WARP_INTER_NEAREST 0
+#define EBOS_WARP_INTER_LINEAR 1
+#define EBOS_WARP_INVERSE_MAP 16
+
+int ebos_warp_perspective(int dtype, int B, int Hs, int Ws, const void* src, int64_t src_sb, int64_t src_sr, const double* M,
+                          int64_t m_stride, int H, int W, int flags, double border_value, int xmin, int xmax, int ymin, int ymax,
+                          void* out, int64_t out_sb, int64_t out_sr, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

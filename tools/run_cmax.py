@@ -40,7 +40,7 @@ def synthetic_window(cfg):
     x = (pts[:, None, 0] + t * flow[:, None, 0]).reshape(-1)
     y = (pts[:, None, 1] + t * flow[:, None, 1]).reshape(-1)
     # raw sensor events sit on integer pixels -- what the reference's loaders hand out (src/data_loader/ccs.py:57-66 reads the int16
-    # columns; `data.warp` there warps the FRAMES with a homography, ccs.py:85-86,152-153; src/utils/event_utils.py:242-266 truncates
+    # columns; `data.warp` there warps the FRAMES with a homography, ccs.py:85-86,152-153 (here: frame_warp / FrameStore); src/utils/event_utils.py:242-266 truncates
     # undistorted coordinates to int32).  --fractional keeps the sub-pixel coordinates (events rectified with a sub-pixel map).
     # (On integer pixels the variance has a local optimum at zero flow -- an event that sits on a pixel centre is not smeared --: the
     # 2-DoF Adam loop of the reference's YAML, started at zero, stays there on this synthetic window; the run then times the loop.)
