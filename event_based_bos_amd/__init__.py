@@ -17,6 +17,7 @@ tub-rip/event_based_bos:
     frame_flow           the reference's frame-based flow (cv2.calcOpticalFlowFarneback, FrameFlowEstimator), batched
     frame_warp           the reference loader's frame warp (cv2.warpPerspective) and the driver's crop, batched, one launch
     data_loader          raw-column event store (the CCS raw_events layout) feeding EventPlan.build_raw; FrameStore, the frame half
+    evaluation           the reference driver's per-frame evaluation of a recording: the plan, the batched window ingest, the evaluator
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -28,6 +29,8 @@ from .event_image_converter import EventImageConverter  # noqa: F401
 from .event_plan import EventPlan, SlabBatch  # noqa: F401
 from .data_loader import FrameStore, RawEventStore  # noqa: F401
 from .frame_warp import validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
-from . import costs, data_loader, event_filters, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils  # noqa: F401
+from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingEvaluator, plan_evaluation,  # noqa: F401
+                         window_ingest_raw_batch)
+from . import costs, data_loader, evaluation, event_filters, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils  # noqa: F401
 
 __version__ = "0.1.0"

@@ -240,6 +240,8 @@ SIGNATURES = {
     "ebos_gml_dep_init_batch_f64": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "ebos_gml_dep_solve_batch_f64": (_I, [_I] * 11 + [_P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _D, _P, _L, _P, _P, _Z, _Z, _P]),
     "ebos_warp_perspective": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
+    "ebos_window_ingest_scratch_bytes": (_Z, [_I] * 8),
+    "ebos_window_ingest_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 12 + [_P] * 6 + [_Z, _P]),
 }
 
 

@@ -302,6 +302,15 @@ class FrameStore(object):
             raise IndexError(f"image index {index} outside 0 .. {self.num_images - 1}")
         return int(index)
 
+    def image_shape(self, index: int) -> Tuple[int, int]:
+        """(rows, columns) of what ``load_image(index)`` returns, without warping anything."""
+        index = self._check_index(index)
+        if self.warp_frame:
+            return self._HEIGHT, self._WIDTH
+        if self._stack is not None:
+            return tuple(int(v) for v in self._stack.shape[1:])
+        return tuple(int(v) for v in self._raw(index).shape)
+
     def load_image(self, index: int) -> Tuple[np.ndarray, float]:
         """(image, timestamp) as src/data_loader/ccs.py:373-396: the frame, warped to the sensor's (height, width) where a
         homography is set (that runs on the GPU), as a numpy array."""

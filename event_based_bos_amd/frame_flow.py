@@ -21,7 +21,7 @@ float64); there is no CPU computation -- without a GPU the calls raise ``HipUnav
 from __future__ import annotations
 
 import logging
-from typing import Optional
+from typing import Sequence, Optional
 
 import numpy as np
 import torch
@@ -213,6 +213,41 @@ class FrameFlowEstimator(object):
         e = f"{method} is not supported"
         logger.error(e)
         raise NotImplementedError(e)
+
+    def estimate_batch(self, method: str, frame0, frames, first: Sequence[int], second: Sequence[int], config: dict) -> torch.Tensor:
+        """``estimate(method, frame0, frames[first[b]], frames[second[b]], config)`` for every pair b, on the device -> float32
+        [B, 2, H + pads, W + pads] without a host synchronisation.  ``frames``: [n, H, W] (numpy or torch; a crop view is read in
+        place), every distinct frame once; ``frame0``: the background [H, W], read by ``opencv_flow_two_steps`` only.  One Farneback
+        chain for all pairs; two-step: the background against every distinct frame in one chain, one ``poisson_image`` of those
+        flows, then the pairs' pictures against each other."""
+        if method not in ("opencv_flow", "opencv_flow_two_steps"):
+            return self.estimate(method, frame0, None, None, config)   # (raises as ``estimate`` does)
+        params = config["params_opencv_flow"]
+        p, pads = _params_of(params), _pads(params)
+        _check_frames(frames, "frames", 3)
+        if len(first) != len(second) or len(first) == 0:
+            raise ValueError(f"first ({len(first)}) and second ({len(second)}) must name the same, non-zero number of pairs")
+        fr = _upload(frames, frames.device if isinstance(frames, torch.Tensor) and frames.is_cuda else None)
+        dev = fr.device
+        i1, i2 = torch.as_tensor(list(first), device=dev), torch.as_tensor(list(second), device=dev)
+        n, H, W = (int(v) for v in fr.shape)
+        if method == "opencv_flow":
+            full, roi = _padded_out(len(first), H, W, pads, dev)
+            _launch(fr[i1], fr[i2], p, roi, tuple(roi.stride()))
+            return full
+        from .poisson import poisson_image
+
+        _check_frames(frame0, "frame0", 2)
+        if tuple(frame0.shape) != (H, W) or _dtype_of(frame0) != _dtype_of(fr):
+            raise ValueError(f"frame0 {tuple(frame0.shape)} {frame0.dtype} differs from the frames {(H, W)} {fr.dtype}")
+        f0 = _upload(frame0, dev)
+        full, roi = _padded_out(n, H, W, pads, dev)
+        _launch(f0[None].contiguous(), fr.contiguous(), p, roi, tuple(roi.stride()))
+        pics = poisson_image(full)                                   # [n, Hf, Wf] uint8
+        Hf, Wf = (int(v) for v in pics.shape[1:])
+        out = torch.empty((len(first), 2, Hf, Wf), dtype=torch.float32, device=dev)
+        _launch(pics[i1], pics[i2], p, out, tuple(out.stride()))
+        return out
 
     def opencv_farneback_two_step(self, frame0, frame1, frame2, params_opencv_flow):
         """The background frame0 against frame1 and frame2 (one batch, frame0 shared), both flows integrated to their uint8

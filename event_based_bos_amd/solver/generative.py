@@ -292,14 +292,17 @@ class GenerativeMixin(object):
         self._gml_frame = stack[-1].clone()
         return stack, H * W
 
-    def _gml_batch_prepare(self, lib, evs, frame_t, frame_stride: int, scratch, nbytes: int):
+    def _gml_batch_prepare(self, lib, evs, frame_t, frame_stride: int, scratch, nbytes: int, pol=None):
         """``ebos_gml_prepare_batch_f64`` of the windows ``evs`` (GPU tensors) -> (gx, gy, q, we, winv), each [b, H, W] (gx, gy
-        [H, W] when the model image is shared)."""
+        [H, W] when the model image is shared).  ``pol``: the windows' polarity images [b, 2, H, W] float64 where they exist already
+        (``estimate_batch_prepared``); ``evs`` is then not read."""
         gml = self._gml_cfg
         H, W = (int(v) for v in self.orig_image_shape)
-        dev, b = frame_t.device, len(evs)
-        pol = torch.stack([self._gml_imager._accumulate(ev, 1.0, _hip.SPLAT_POLARITY, EPS_NUMPY, torch.float64)[0]
-                           for ev in evs]).contiguous()   # [b, 2, H, W]
+        dev = frame_t.device
+        if pol is None:
+            pol = torch.stack([self._gml_imager._accumulate(ev, 1.0, _hip.SPLAT_POLARITY, EPS_NUMPY, torch.float64)[0]
+                               for ev in evs]).contiguous()   # [b, 2, H, W]
+        b = int(pol.shape[0])
         d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
         ng = b if frame_stride else 1
         gx, gy, q, winv = d(ng, H, W), d(ng, H, W), d(b, H, W), d(b, H, W)
@@ -339,12 +342,43 @@ class GenerativeMixin(object):
             self.iter_cnt += hi - lo
         return np.concatenate(flows)
 
-    def _gml_solve_batch(self, windows: Sequence, frame_t: torch.Tensor, frame_stride: int) -> np.ndarray:
-        """One batch: every scale of every window, one launch per pass.  Appends to ``histories`` / ``params_per_scale_batch``."""
+    def estimate_batch_prepared(self, prepared, frames=None, background=None, max_batch: Optional[int] = None,
+                                device_out: bool = False):
+        """``estimate_batch`` of windows whose event side is on the device already: ``prepared`` is an
+        ``evaluation.PreparedWindows`` (``pol`` [B, 2, H, W] float64 of ``ebos_window_ingest_raw_batch``).  The upload of the events
+        and the polarity splat of every window are skipped; ``pol`` goes straight into ``ebos_gml_prepare_batch_f64``.  Everything
+        else is ``estimate_batch``: the flows, ``histories``, the parameters, the draws from numpy's global RandomState,
+        ``iter_cnt``, the kept background and ``max_batch`` -- bit for bit what ``estimate_batch`` gives on the same windows handed
+        over as arrays.  ``device_out``: return the flows as a device tensor instead of a numpy array."""
+        H, W = (int(v) for v in self.orig_image_shape)
+        pol = prepared.pol
+        if not (isinstance(pol, torch.Tensor) and pol.is_cuda and pol.dtype == torch.float64 and pol.dim() == 4
+                and tuple(pol.shape[1:]) == (2, H, W)):
+            raise ValueError(f"{self._gml_who}: prepared.pol must be a device float64 [B, 2, {H}, {W}] tensor")
+        n = int(pol.shape[0])
+        _, frames, max_batch = self._gml_batch_args([None] * n, frames, background, max_batch)
+        self._gml_prepared_reset()
+        flows = []
+        for lo in range(0, n, max_batch):
+            hi = min(lo + max_batch, n)
+            frame_t, frame_stride = self._gml_batch_frames(frames, lo, hi)
+            flows.append(self._gml_solve_batch(prepared.slice(lo, hi), frame_t, frame_stride, prepared=True, device_out=device_out))
+            self.iter_cnt += hi - lo
+        if device_out:
+            return torch.cat(flows) if flows else torch.zeros((0, 2, H, W), dtype=torch.float64, device=pol.device)
+        return np.concatenate([np.zeros((0, 2, H, W), dtype=np.float64)] + flows)
+
+    def _gml_prepared_reset(self) -> None:
+        self.histories, self.params_per_scale_batch = [], []
+
+    def _gml_solve_batch(self, windows, frame_t: torch.Tensor, frame_stride: int, prepared: bool = False, device_out: bool = False):
+        """One batch: every scale of every window, one launch per pass.  Appends to ``histories`` / ``params_per_scale_batch``.
+        ``prepared``: ``windows`` is a ``PreparedWindows`` (its ``pol`` replaces the upload and the splat)."""
         lib = _hip.require_gpu()
         H, W = (int(v) for v in self.orig_image_shape)
         dev, gml, n, b = frame_t.device, self._gml_cfg, H * W, len(windows)
-        evs = [to_gpu(ev, device=dev, dtype=torch.float64) for ev in windows]
+        pol = windows.pol.to(dev).contiguous() if prepared else None
+        evs = None if prepared else [to_gpu(ev, device=dev, dtype=torch.float64) for ev in windows]
         d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
         use_we = _flag(gml, "weight_loss_by_event_hist")
         stride = int(lib.ebos_gml_scratch_bytes(H, W, PATCHES[-1]))
@@ -352,7 +386,7 @@ class GenerativeMixin(object):
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _hip.on_device(dev):
             sp = stream_ptr(dev)
-            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes)
+            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes, pol=pol)
             weights, order, n_terms = self._gml_weights()
             w_t = torch.from_numpy(weights).to(dev)
             o_t = torch.from_numpy(order).to(dev)
@@ -387,7 +421,7 @@ class GenerativeMixin(object):
         self.cost_func.clear_history()
         self.cost_func.history.update(self._gml_history(h[-1]))
         self.params_per_scale = dict(self.params_per_scale_batch[-1])
-        return flow.cpu().numpy()
+        return flow if device_out else flow.cpu().numpy()
 
     def _gml_initial(self, gh: int, gw: int) -> np.ndarray:
         """x0 of the coarsest scale from numpy's global RandomState, as run_estimation_per_scale draws it."""

@@ -209,8 +209,16 @@ class GenerativeDependentMixin(GenerativeMixin):
     estimate_batch.__doc__ = GenerativeMixin.estimate_batch.__doc__.replace("``params_per_scale_batch``",
                                                                             "``params_batch``, ``estimate_indices_batch``")
 
-    def _gml_solve_batch(self, windows: Sequence, frame_t: torch.Tensor, frame_stride: int) -> np.ndarray:
-        """One batch: selection (one read-back of the counts), the draws in window order, the Adam loop, one launch per pass."""
+    def _gml_prepared_reset(self) -> None:
+        GenerativeMixin._gml_prepared_reset(self)
+        self.params_batch, self.estimate_indices_batch = [], []
+
+    def _gml_solve_batch(self, windows, frame_t: torch.Tensor, frame_stride: int, prepared: bool = False, device_out: bool = False):
+        """One batch: selection (one read-back of the counts), the draws in window order, the Adam loop, one launch per pass.
+        ``prepared``: ``windows`` is a ``PreparedWindows``; its ``pol`` replaces the upload and the splat.  The event thresholding
+        of the selection counts events inside each patch's box from the event list itself (``ebos_gml_dep_select_batch``); with
+        ``do_event_thresholding`` the prepared path therefore keeps that event path and hands it the windows' kept events, built
+        on the device from the raw columns (``PreparedWindows.events``) -- the same list ``preprocess`` yields."""
         lib = _hip.require_gpu()
         H, W = (int(v) for v in self.orig_image_shape)
         dev, gml, b = frame_t.device, self._gml_cfg, len(windows)
@@ -218,8 +226,12 @@ class GenerativeDependentMixin(GenerativeMixin):
         gh, gw = self.patch_image_size
         nd, G = self._gml_n_dim, gh * gw
         xmin, xmax, ymin, ymax = self._gml_roi
-        evs = [to_gpu(ev, device=dev, dtype=torch.float64).reshape(-1, 4).contiguous() for ev in windows]
-        counts = [int(ev.shape[0]) for ev in evs]
+        pol = windows.pol.to(dev).contiguous() if prepared else None
+        if prepared:
+            evs = [windows.events(i).to(dev).reshape(-1, 4).contiguous() for i in range(b)] if self._dep_thresholding else []
+        else:
+            evs = [to_gpu(ev, device=dev, dtype=torch.float64).reshape(-1, 4).contiguous() for ev in windows]
+        counts = [int(ev.shape[0]) for ev in evs] if evs else [0] * b
         d = lambda *sh: torch.empty(*sh, dtype=torch.float64, device=dev)
         use_we = _flag(gml, "weight_loss_by_event_hist")
         hc, wc = self._dep_canvas if self._dep_thresholding else (0, 0)
@@ -233,7 +245,7 @@ class GenerativeDependentMixin(GenerativeMixin):
         count = torch.zeros(b, dtype=torch.int32, device=dev)
         with _hip.on_device(dev):
             sp = stream_ptr(dev)
-            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes)
+            gx, gy, q, we, winv = self._gml_batch_prepare(lib, evs, frame_t, frame_stride, scratch, nbytes, pol=pol)
             ev_all = torch.cat(evs) if self._dep_thresholding else None
             offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
             check(lib.ebos_gml_dep_select_batch(b, H, W, p, s, ptr(rb), ptr(cb), ptr(ev_all), ptr(offsets), max(counts), hc, wc,
@@ -272,7 +284,7 @@ class GenerativeDependentMixin(GenerativeMixin):
         self.cost_func.clear_history()
         self.cost_func.history.update(self._gml_history(h[-1]))
         self._dep_sel, self._dep_x = sel[-1], x[-1]
-        return flow.cpu().numpy()
+        return flow if device_out else flow.cpu().numpy()
 
 
 def make_dependent_class(base, name: str = "GenerativePatchDependent"):

@@ -56,6 +56,13 @@ def crop_event(events: NUMPY_TORCH, x0: int, x1: int, y0: int, y1: int) -> NUMPY
     return events[mask]
 
 
+def remove_event(events: NUMPY_TORCH, x0: int, x1: int, y0: int, y1: int) -> NUMPY_TORCH:
+    """The complement of ``crop_event``: the events outside rows [x0, x1) x columns [y0, y1), order kept (the driver's
+    ``remove_nose``).  src/utils/event_utils.py:133-153."""
+    mask = (x0 <= events[..., 0]) & (events[..., 0] < x1) & (y0 <= events[..., 1]) & (events[..., 1] < y1)
+    return events[~mask]
+
+
 from .event_filters import (EventFilter, background_activity_filter, continuous_background_activity_filter,  # noqa: E402,F401
                             hot_pixel_filter)
 from .flow_error import calculate_flow_error_numpy, calculate_flow_error_tensor, flow_error_batch  # noqa: E402,F401

@@ -1203,6 +1203,28 @@ int ebos_warp_perspective(int dtype, int B, int Hs, int Ws, const void* src, int
                           int64_t m_stride, int H, int W, int flags, double border_value, int xmin, int xmax, int ymin, int ymax,
                           void* out, int64_t out_sb, int64_t out_sr, ebos_stream_t stream);
 
+/* ---- several solver windows' event side in one launch, from the raw sensor columns (csrc/window_ingest.hip) -----------------
+ * col / row int16, t int32 (t_is_64 = 0) or int64 ticks, pol uint8: device columns of n_total events (RawEventStore.load_raw).
+ * ranges: device int64 [B, 2], window b = events [begin, end) of the columns; ranges may overlap or be empty and are clamped to
+ * [0, n_total]; max_len: an upper bound of end - begin known on the host (it only sizes the grid).  An event is kept when it lies
+ * inside the CROP rectangle (has_roi: rows [xmin, xmax), columns [ymin, ymax), the solver's filter parameters) and outside the
+ * removal rectangle (has_remove: rows [rm_x0, rm_x1), columns [rm_y0, rm_y1)).  Outputs, all overwritten:
+ *   pol_out   double [B, 2, H, W]  events per pixel with p != 0 (channel 0) and p == 0 (channel 1): the float64 polarity image
+ *                                  of the kept events (EBOS_SPLAT_POLARITY on integer pixels, whose weights are 1, 0, 0, 0);
+ *   mask_out  uint8  [B, H, W]     1 where a kept event fell;
+ *   count_out int64  [B]           kept events;  tmin_out / tmax_out double [B]: their first / last time, ticks /
+ *                                  ticks_per_second in float64 (0 for a window that keeps nothing).
+ * Counts are integers (LDS, then integer atomics); no floating-point atomic: every run gives the same bits.
+ * scratch: ebos_window_ingest_scratch_bytes(B, H, W, has_roi, xmin, xmax, ymin, ymax) bytes, 256-byte aligned.  Two launches.
+ * B <= 65535, H * W < 2^31 - 1, else EBOS_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------- */
+size_t ebos_window_ingest_scratch_bytes(int B, int H, int W, int has_roi, int xmin, int xmax, int ymin, int ymax);
+int ebos_window_ingest_raw_batch(const int16_t* col, const int16_t* row, const void* t, int t_is_64, const uint8_t* pol,
+                                 int64_t n_total, double ticks_per_second, const int64_t* ranges, int B, int64_t max_len, int H,
+                                 int W, int has_roi, int xmin, int xmax, int ymin, int ymax, int has_remove, int rm_x0, int rm_x1,
+                                 int rm_y0, int rm_y1, double* pol_out, uint8_t* mask_out, int64_t* count_out, double* tmin_out,
+                                 double* tmax_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
