@@ -1,9 +1,10 @@
 """``estimate_batch`` of the generative solvers on the GPU (csrc/gml.hip ``ebos_gml_*_batch*``): several windows per launch.
 
-The single-window path is pinned to the reference by golden_gml.npz / golden_gml_dep.npz (tests/test_gpu_gml.py,
-tests/test_gpu_gml_dep.py) and is not the code under test here.  ``estimate_batch`` is defined as equal to ``estimate`` on the
-windows in order, and a batched pass runs the single-window body on the view of its window, so everything is compared with
-``np.array_equal``: no tolerance, no excluded case.  ``n_iter`` is shortened (two runs of this package are compared, so the
+``estimate`` is the batch driver at one window; tests/test_gpu_gml.py and tests/test_gpu_gml_dep.py pin it, and with it the driver
+at B = 1, to the reference's golden_gml.npz / golden_gml_dep.npz and to the torch restatement.  This file compares the driver at
+B > 1 (and ``estimate_batch`` at B = 1) with that: ``estimate_batch`` is defined as equal to ``estimate`` on the windows in order,
+and a batched pass runs the single-window body on the view of its window, so everything is compared with ``np.array_equal``: no
+tolerance, no excluded case.  ``n_iter`` is shortened (two runs of this package are compared, so the
 fixture's length is not needed).  Two cases go through ``estimate_batch`` against the fixture itself, with the existing bounds.
 """
 import os
