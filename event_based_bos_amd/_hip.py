@@ -133,6 +133,10 @@ SIGNATURES = {
     "ebos_bin_events_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ebos_plan_lean_scratch_bytes": (_Z, [_L, _I, _I, _I, _I]),
     "ebos_plan_lean": (_I, [_I, _P, _P, _P, _P, _D, _L, _I, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P, _P, _Z, _P]),
+    "ebos_plan_lean_batch_scratch_bytes": (_Z, [_P, _I, _I, _I, _I, _I]),
+    "ebos_plan_lean_batch": (_I, [_P, _P, _P, _I, _D, _L, _P, _I, _I, _D, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ebos_plan_parts_batch": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "ebos_plan_facts_batch": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P, _L, _P, _P]),
     "ebos_plan_compact_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P]),
     "ebos_plan_compact_frac_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "ebos_iwe_dense_f32": (_I, [_P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P]),

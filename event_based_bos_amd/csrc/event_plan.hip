@@ -8,6 +8,8 @@
 //   - all events of one image tile contiguous (LDS-privatised IWE tile per workgroup),
 //   - all events of one source pixel contiguous (flow reads broadcast; the backward pass
 //     pre-reduces d_flow across the wavefront and issues one atomic per pixel run).
+#include <algorithm>
+
 #include "common.h"
 
 namespace ebos {
@@ -456,9 +458,8 @@ compact_canon_hot_kernel(const int32_t* __restrict__ key_offsets, int tile_px, c
 // (and for which the parts fit the 2 x tiles budget) -- if that beats one part per tile by 20 % or more.  A uniform
 // window keeps one part per tile, while a window whose events sit in a few tiles (a schlieren object in front of a
 // static background) spreads those tiles over the otherwise idle CUs.  One workgroup; runs once per plan.
-__global__ void __launch_bounds__(1024)
-plan_parts_kernel(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px, int n_items, int n_cu, int fixed_events,
-                  int32_t* __restrict__ part_table) {
+__device__ __forceinline__ void plan_parts_body(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px, int n_items, int n_cu,
+                                                int fixed_events, int32_t* __restrict__ part_table) {
   __shared__ long long red[1024 / kWave];
   __shared__ long long s_bcast;
   __shared__ int s_max;
@@ -564,11 +565,29 @@ plan_parts_kernel(const int32_t* __restrict__ key_offsets, int n_tiles, int tile
   }
 }
 
+__global__ void __launch_bounds__(1024)
+plan_parts_kernel(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px, int n_items, int n_cu, int fixed_events,
+                  int32_t* __restrict__ part_table) {
+  plan_parts_body(key_offsets, n_tiles, tile_px, n_items, n_cu, fixed_events, part_table);
+}
+// several plans of one geometry, a workgroup each (ebos_plan_parts_batch): the price of a work item is per window (it follows the
+// window's event count, EventPlan's part_fixed_events) and travels with the launch
+constexpr int kPartsBatch = 64;
+struct PartsBatch {
+  int fixed_events[kPartsBatch];
+};
+__global__ void __launch_bounds__(1024)
+plan_parts_batch_kernel(const int32_t* __restrict__ key_offsets, int64_t key_stride, int n_tiles, int tile_px, int n_items, int n_cu,
+                        PartsBatch fixed, int32_t* __restrict__ part_table, int64_t part_stride) {
+  plan_parts_body(key_offsets + (int64_t)blockIdx.x * key_stride, n_tiles, tile_px, n_items, n_cu, fixed.fixed_events[blockIdx.x],
+                  part_table + (int64_t)blockIdx.x * part_stride);
+}
+
 // The build's one read-back as ONE small kernel (ebos_plan_facts): (outside the image, fractional sources, work items in use,
 // events of the fullest tile) side by side -- gathered with torch ops they were four launches and a copy (~20 us of a 0.3 ms build)
-__global__ void __launch_bounds__(256) plan_facts_kernel(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px,
-                                                         const int32_t* __restrict__ counts, const int32_t* __restrict__ part_table,
-                                                         int32_t* __restrict__ facts) {
+__device__ __forceinline__ void plan_facts_body(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px,
+                                                const int32_t* __restrict__ counts, const int32_t* __restrict__ part_table,
+                                                int32_t* __restrict__ facts) {
   __shared__ int s_max;
   if (threadIdx.x == 0) s_max = 0;
   __syncthreads();
@@ -583,6 +602,20 @@ __global__ void __launch_bounds__(256) plan_facts_kernel(const int32_t* __restri
     facts[2] = part_table ? part_table[n_tiles] : 0;
     facts[3] = s_max;
   }
+}
+__global__ void __launch_bounds__(256) plan_facts_kernel(const int32_t* __restrict__ key_offsets, int n_tiles, int tile_px,
+                                                         const int32_t* __restrict__ counts, const int32_t* __restrict__ part_table,
+                                                         int32_t* __restrict__ facts) {
+  plan_facts_body(key_offsets, n_tiles, tile_px, counts, part_table, facts);
+}
+// (ebos_plan_facts_batch: a workgroup per plan, facts [B, 4])
+__global__ void __launch_bounds__(256) plan_facts_batch_kernel(const int32_t* __restrict__ key_offsets, int64_t key_stride, int n_tiles,
+                                                               int tile_px, const int32_t* __restrict__ counts,
+                                                               const int32_t* __restrict__ part_table, int64_t part_stride,
+                                                               int32_t* __restrict__ facts) {
+  const int64_t w = blockIdx.x;
+  plan_facts_body(key_offsets + w * key_stride, n_tiles, tile_px, counts ? counts + 2 * w : nullptr,
+                  part_table ? part_table + w * part_stride : nullptr, facts + 4 * w);
 }
 
 template <typename T>
@@ -681,6 +714,41 @@ int ebos_plan_facts(const int32_t* key_offsets, int H, int W, int tile_h, int ti
   const int n_tiles = ((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w);
   plan_facts_kernel<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(key_offsets, n_tiles, tile_h * tile_w, counts, part_table, facts);
   EBOS_CHECK_LAUNCH("ebos_plan_facts");
+  return EBOS_OK;
+}
+
+int ebos_plan_parts_batch(const int32_t* key_offsets, int64_t key_stride, int n_windows, int H, int W, int tile_h, int tile_w, int n_cu,
+                          const int32_t* fixed_events, int32_t* part_table, int64_t part_stride, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(key_offsets && part_table && fixed_events, "ebos_plan_parts_batch: NULL buffer");
+  EBOS_REQUIRE(n_windows >= 1 && H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && n_cu >= 1, "ebos_plan_parts_batch: bad sizes");
+  const int n_tiles = ((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w);
+  EBOS_REQUIRE(key_stride >= (int64_t)n_tiles * tile_h * tile_w + 1 && part_stride >= 5 * (int64_t)n_tiles + 1,
+               "ebos_plan_parts_batch: strides shorter than a window's arrays");
+  for (int w = 0; w < n_windows; ++w) EBOS_REQUIRE(fixed_events[w] >= 0, "ebos_plan_parts_batch: fixed_events[%d] < 0", w);
+  for (int first = 0; first < n_windows; first += kPartsBatch) {
+    const int nw = std::min(kPartsBatch, n_windows - first);
+    PartsBatch fixed{};
+    for (int k = 0; k < nw; ++k) fixed.fixed_events[k] = fixed_events[first + k];
+    plan_parts_batch_kernel<<<dim3(nw), dim3(1024), 0, as_stream(stream)>>>(key_offsets + (int64_t)first * key_stride, key_stride, n_tiles,
+                                                                            tile_h * tile_w, 2 * n_tiles, n_cu, fixed,
+                                                                            part_table + (int64_t)first * part_stride, part_stride);
+  }
+  EBOS_CHECK_LAUNCH("ebos_plan_parts_batch");
+  return EBOS_OK;
+}
+
+int ebos_plan_facts_batch(const int32_t* key_offsets, int64_t key_stride, int n_windows, int H, int W, int tile_h, int tile_w,
+                          const int32_t* counts, const int32_t* part_table, int64_t part_stride, int32_t* facts, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(key_offsets && facts, "ebos_plan_facts_batch: NULL buffer");
+  EBOS_REQUIRE(n_windows >= 1 && H > 0 && W > 0 && tile_h > 0 && tile_w > 0, "ebos_plan_facts_batch: bad sizes");
+  const int n_tiles = ((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w);
+  EBOS_REQUIRE(key_stride >= (int64_t)n_tiles * tile_h * tile_w + 1 && (part_table == nullptr || part_stride >= 5 * (int64_t)n_tiles + 1),
+               "ebos_plan_facts_batch: strides shorter than a window's arrays");
+  plan_facts_batch_kernel<<<dim3(n_windows), dim3(256), 0, as_stream(stream)>>>(key_offsets, key_stride, n_tiles, tile_h * tile_w, counts,
+                                                                               part_table, part_stride, facts);
+  EBOS_CHECK_LAUNCH("ebos_plan_facts_batch");
   return EBOS_OK;
 }
 

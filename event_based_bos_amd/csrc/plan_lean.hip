@@ -204,9 +204,34 @@ __device__ __forceinline__ int32_t block_exclusive_scan(int32_t v, int32_t* s_wa
 
 // (eight waves per SIMD = TWO workgroups per CU: with 72 - 80 VGPRs a CU held one, and its load phase -- 60 % of a workgroup's time,
 // tools/stamp_plan_lean.py -- overlapped with nothing: 1536 workgroups ran as six rounds of 256)
-template <int SRC>
+// What the staging pass works on: ONE window, which is the whole launch (StageOne: ebos_plan_lean -- the grid is the window's chunks, read
+// where they are used as this kernel always did) or a stretch of the flattened grid of a batch (StageMany, further down).  The pass
+// sits at its register budget, so the body stays IN the kernel -- instantiated once per kind of launch -- and only the small view of
+// the window is a function of the arguments.
+struct StageOne {
+  LeanIn in;
+  int64_t n;
+  LeanGeom g;
+  LeanScratch sc;
+  struct View {
+    LeanIn in;
+    int64_t n;
+    LeanGeom g;
+    LeanScratch sc;
+    __device__ __forceinline__ unsigned index() const { return blockIdx.x; }
+    __device__ __forceinline__ unsigned count() const { return gridDim.x; }
+  };
+  __device__ __forceinline__ View view() const { return View{in, n, g, sc}; }
+};
+
+template <int SRC, typename Args>
 __global__ void __launch_bounds__(kLeanBlock, 8)
-lean_stage_kernel(LeanIn in, int64_t n, LeanGeom g, LeanScratch sc) {
+lean_stage_kernel(Args args) {
+  const typename Args::View v = args.view();
+  const LeanIn in = v.in;
+  const int64_t n = v.n;
+  const LeanGeom g = v.g;
+  const LeanScratch sc = v.sc;
   typedef typename StageT<SRC>::type stamp_t;
   extern __shared__ int32_t s_mem[];
   int32_t* s_hist = s_mem;                                                          // [n_bins] counts, then exclusive offsets
@@ -215,10 +240,10 @@ lean_stage_kernel(LeanIn in, int64_t n, LeanGeom g, LeanScratch sc) {
   __shared__ int32_t s_wave[kLeanBlock / kWave + 1];
   EBOS_LSTAMP(0, 0);
   for (int b = threadIdx.x; b < g.n_bins; b += kLeanBlock) s_hist[b] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *sc.ticket = 0u;   // (K1 counts its workgroups; it is a later launch)
+  if (v.index() == 0 && threadIdx.x == 0) *sc.ticket = 0u;   // (K1 counts its workgroups; it is a later launch)
   __syncthreads();
   constexpr int kPer = kChunk / kLeanBlock;
-  const int64_t base = (int64_t)blockIdx.x * g.chunk;
+  const int64_t base = (int64_t)v.index() * g.chunk;
   const int64_t chunk_end = min(n, base + g.chunk);
   double lo = 1.0e308 * 10.0, hi = -1.0e308 * 10.0;  // +-inf
   int bad = 0, frac = 0;
@@ -264,7 +289,7 @@ lean_stage_kernel(LeanIn in, int64_t n, LeanGeom g, LeanScratch sc) {
       s_hist[b0 + j] = run;
       // (4-byte stores a table row apart: the bin sort reads a bin's 1536 entries as 96 lines instead of 1536, and it is the pass that
       // is bound by the number of its requests)
-      sc.tab[(int64_t)(b0 + j) * gridDim.x + blockIdx.x] = (unsigned)run | ((unsigned)c << kTabShift);
+      sc.tab[(int64_t)(b0 + j) * v.count() + v.index()] = (unsigned)run | ((unsigned)c << kTabShift);
       run += c;
     }
   __syncthreads();
@@ -305,10 +330,21 @@ lean_stage_kernel(LeanIn in, int64_t n, LeanGeom g, LeanScratch sc) {
       bad += s_bad[k];
       frac += s_frac[k];
     }
-    sc.partial[blockIdx.x] = ChunkPartial{lo, hi, bad, frac};
+    sc.partial[v.index()] = ChunkPartial{lo, hi, bad, frac};
   }
   EBOS_LSTAMP(0, 5);
 }
+
+// Where a workgroup stands in the grid of ITS window: the launch's own grid for a single window, a row of the grid for a window of a batch
+struct WholeGrid {
+  __device__ __forceinline__ unsigned index() const { return blockIdx.x; }
+  __device__ __forceinline__ unsigned count() const { return gridDim.x; }
+};
+struct GridPart {
+  unsigned idx, cnt;
+  __device__ __forceinline__ unsigned index() const { return idx; }
+  __device__ __forceinline__ unsigned count() const { return cnt; }
+};
 
 // one workgroup (1024 threads): bin totals -> bin_base (exclusive, + total); tile totals -> grp_offsets (groups of 4 slots,
 // exclusive); key_offsets[n_keys] = events kept; tminmax (seconds) for the caller.  The totals are read with agent-scope loads: the
@@ -368,12 +404,13 @@ __device__ __forceinline__ void lean_scan_bins_block(const LeanGeom& g, const Le
 
 // K1: events per bin = sums of the table's rows, a wave per bin (sixteen bins per workgroup); workgroup 0 also folds the chunks' time
 // partials and counts; the last workgroup to finish scans the totals
-__global__ void __launch_bounds__(kLeanBlock)
-lean_totals_kernel(LeanGeom g, int n_chunks, LeanScratch sc, int32_t* __restrict__ counts, int32_t* __restrict__ grp_offsets,
-                   int32_t* __restrict__ key_offsets, int64_t n_keys, double ticks_per_second, int raw, double* __restrict__ tminmax) {
+template <typename Grid>
+__device__ __forceinline__ void lean_totals_body(const LeanGeom& g, int n_chunks, const LeanScratch& sc, int32_t* __restrict__ counts,
+                                                 int32_t* __restrict__ grp_offsets, int32_t* __restrict__ key_offsets, int64_t n_keys,
+                                                 double ticks_per_second, int raw, double* __restrict__ tminmax, const Grid grid) {
   __shared__ int s_is_last;
   {
-    const int bin = blockIdx.x * (kLeanBlock / kWave) + (int)(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
+    const int bin = grid.index() * (kLeanBlock / kWave) + (int)(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
     if (bin < g.n_bins) {
       const unsigned* __restrict__ row = sc.tab + (int64_t)bin * n_chunks;
       int32_t acc = 0;
@@ -393,7 +430,7 @@ lean_totals_kernel(LeanGeom g, int n_chunks, LeanScratch sc, int32_t* __restrict
       }
     }
   }
-  if (blockIdx.x == 0) {
+  if (grid.index() == 0) {
     double lo = 1.0e308 * 10.0, hi = -1.0e308 * 10.0;
     int bad = 0, frac = 0;
     for (int c = threadIdx.x; c < n_chunks; c += kLeanBlock) {
@@ -437,7 +474,7 @@ lean_totals_kernel(LeanGeom g, int n_chunks, LeanScratch sc, int32_t* __restrict
   if (threadIdx.x == 0) {
     typedef __attribute__((address_space(1))) unsigned gu32_;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned n_wg = gridDim.x;
+    const unsigned n_wg = grid.count();
     s_is_last = __hip_atomic_fetch_add((gu32_*)sc.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_wg - 1u;
   }
   __syncthreads();
@@ -450,6 +487,12 @@ lean_totals_kernel(LeanGeom g, int n_chunks, LeanScratch sc, int32_t* __restrict
   }
   __syncthreads();
   lean_scan_bins_block(g, sc, grp_offsets, key_offsets, n_keys, ticks_per_second, raw, tminmax);
+}
+
+__global__ void __launch_bounds__(kLeanBlock)
+lean_totals_kernel(LeanGeom g, int n_chunks, LeanScratch sc, int32_t* __restrict__ counts, int32_t* __restrict__ grp_offsets,
+                   int32_t* __restrict__ key_offsets, int64_t n_keys, double ticks_per_second, int raw, double* __restrict__ tminmax) {
+  lean_totals_body(g, n_chunks, sc, counts, grp_offsets, key_offsets, n_keys, ticks_per_second, raw, tminmax, WholeGrid{});
 }
 
 // what the bin sort needs to turn a staged timestamp into dt (fp64, exactly as events_to_soa_kernel / raw_to_soa_kernel, event_plan.hip)
@@ -600,9 +643,11 @@ __device__ __forceinline__ void lean_gather(const LeanScratch& sc, const LeanGeo
 }
 
 // one workgroup per bin: counting sort of the bin's segment by pixel -> key_offsets of the band, cpix / cdt at their final slots
-__global__ void __launch_bounds__(kSortBlock)
-lean_bin_sort_kernel(LeanGeom g, LeanScratch sc, const int32_t* __restrict__ grp_offsets, int32_t* __restrict__ key_offsets,
-                     uint16_t* __restrict__ cpix, float* __restrict__ cdt, int pix_cap, int sort_cap, int n_chunks, LeanTime tc) {
+// (a workgroup of ONE window's grid: blockIdx.x in lean_bin_sort_kernel and in lean_bin_sort_batch_kernel, whose blockIdx.y is the
+// window -- the placement below is the same in both)
+__device__ __forceinline__ void lean_bin_sort_body(const LeanGeom& g, const LeanScratch& sc, const int32_t* __restrict__ grp_offsets,
+                                                   int32_t* __restrict__ key_offsets, uint16_t* __restrict__ cpix, float* __restrict__ cdt,
+                                                   int pix_cap, int sort_cap, int n_chunks, const LeanTime& tc) {
   // sort_cap: events of one bin staged in LDS, TWICE (6 B each: as they arrive from the gather, then sorted by pixel); a larger bin
   // (lean_layout leaves most bins of a window beyond ~10 k events per tile larger, on purpose) is gathered once for its histogram and
   // once per chunk of whole pixels, 2 x sort_cap events of the whole staging area at a time
@@ -873,6 +918,41 @@ lean_bin_sort_kernel(LeanGeom g, LeanScratch sc, const int32_t* __restrict__ grp
   }
 }
 
+__global__ void __launch_bounds__(kSortBlock)
+lean_bin_sort_kernel(LeanGeom g, LeanScratch sc, const int32_t* __restrict__ grp_offsets, int32_t* __restrict__ key_offsets,
+                     uint16_t* __restrict__ cpix, float* __restrict__ cdt, int pix_cap, int sort_cap, int n_chunks, LeanTime tc) {
+  lean_bin_sort_body(g, sc, grp_offsets, key_offsets, cpix, cdt, pix_cap, sort_cap, n_chunks, tc);
+}
+
+// the sections of one window's scratch (bytes from its base), from the sizes lean_layout picks: on the host for the launches of
+// ebos_plan_lean, on the device by every workgroup of a batch (the window's sizes travel, not its seven pointers)
+struct LeanSections {
+  size_t off_base, off_tm, off_partial, off_px, off_t, total;
+};
+__host__ __device__ __forceinline__ LeanSections lean_sections(int n_bins, int n_chunks, int chunk) {
+  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  LeanSections S;
+  S.off_base = align((size_t)n_bins * n_chunks * 4);
+  S.off_tm = S.off_base + align((size_t)(n_bins + 1) * 4);
+  S.off_partial = S.off_tm + 256;
+  S.off_px = S.off_partial + align((size_t)n_chunks * sizeof(ChunkPartial));
+  S.off_t = S.off_px + align((size_t)n_chunks * chunk * 2);
+  S.total = S.off_t + align((size_t)n_chunks * chunk * 8);   // (sized for 8-byte timestamps: the query does not know the source)
+  return S;
+}
+__host__ __device__ __forceinline__ LeanScratch lean_scratch_at(char* base, const LeanSections& S) {
+  return LeanScratch{reinterpret_cast<unsigned*>(base), reinterpret_cast<int32_t*>(base + S.off_base),
+                     reinterpret_cast<unsigned long long*>(base + S.off_tm), reinterpret_cast<unsigned*>(base + S.off_tm + 64),
+                     reinterpret_cast<ChunkPartial*>(base + S.off_partial), reinterpret_cast<uint16_t*>(base + S.off_px),
+                     base + S.off_t};
+}
+// the bin sort's LDS split for `sub` row bands per tile: pixels of a band (+ a row), events staged at once
+__host__ __device__ __forceinline__ void lean_sort_caps(int th, int tw, int sub, int& pix_cap, int& sort_cap) {
+  pix_cap = ((th + sub - 1) / sub + 1) * tw;
+  const long long room = (long long)kSortLds - (long long)pix_cap * 8;
+  sort_cap = room > 0 ? (int)(room / 12) & ~1 : 0;   // (two staging buffers: arrival order, sorted by pixel)
+}
+
 struct LeanLayout {
   int n_chunks, chunk, sub, n_bins, pix_cap, sort_cap;
   size_t off_base, off_tm, off_partial, off_px, off_t, total;
@@ -902,20 +982,118 @@ inline LeanLayout lean_layout(int64_t n, int H, int W, int th, int tw) {
   for (int sub = 1;; sub *= 2) {
     if (sub > th) sub = th;
     L.sub = sub;
-    L.pix_cap = ((th + sub - 1) / sub + 1) * tw;
-    const long long room = (long long)kSortLds - (long long)L.pix_cap * 8;
-    L.sort_cap = room > 0 ? (int)(room / 12) & ~1 : 0;   // (two staging buffers: arrival order, sorted by pixel)
+    lean_sort_caps(th, tw, sub, L.pix_cap, L.sort_cap);
     if (sub == th || ((double)n / ((double)n_tiles * sub) <= kBinFill * L.sort_cap)) break;
   }
   L.n_bins = n_tiles * L.sub;
-  auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  L.off_base = align((size_t)L.n_bins * L.n_chunks * 4);
-  L.off_tm = L.off_base + align((size_t)(L.n_bins + 1) * 4);
-  L.off_partial = L.off_tm + 256;
-  L.off_px = L.off_partial + align((size_t)L.n_chunks * sizeof(ChunkPartial));
-  L.off_t = L.off_px + align((size_t)L.n_chunks * L.chunk * 2);
-  L.total = L.off_t + align((size_t)L.n_chunks * L.chunk * 8);   // (sized for 8-byte timestamps: the query does not know the source)
+  const LeanSections S = lean_sections(L.n_bins, L.n_chunks, L.chunk);
+  L.off_base = S.off_base, L.off_tm = S.off_tm, L.off_partial = S.off_partial, L.off_px = S.off_px, L.off_t = S.off_t, L.total = S.total;
   return L;
+}
+
+// ---- several windows per launch (ebos_plan_lean_batch) -------------------------------------------------------------------------
+// The windows are ranges [begin, begin + n) of ONE set of columns.  What differs between them is what lean_layout derives from n
+// (chunk length, chunks, row bands per tile) and where their outputs lie; a window's descriptor holds those, and every workgroup
+// derives the rest -- geometry, scratch sections, LDS split -- with the functions the single-window entry uses on the host.  The
+// descriptors travel in the kernel argument segment (like FwdBatch, iwe_tile_core.h): no table to upload, nothing to keep alive.
+struct LeanWin {
+  int64_t begin;         // first event of the window in the columns
+  int64_t scratch_off;   // its scratch (bytes from the batch's; 256-byte aligned)
+  int64_t slot_off;      // its first slot of cpix / cdt (a multiple of 8: 16-byte aligned in both)
+  int32_t n;             // events
+  int32_t chunk0;        // first of its chunks in the flattened grid of the staging pass
+  int32_t n_chunks, chunk, sub;   // lean_layout(n)
+  int32_t reserved;
+};
+constexpr int kLeanBatch = 64;   // windows per set of three launches
+struct LeanBatch {
+  LeanWin w[kLeanBatch];
+};
+static_assert(sizeof(LeanBatch) <= 3072, "the batch travels in the kernel argument segment");
+struct LeanBatchOut {   // window w: key_offsets + w * key_stride, grp_offsets + w * grp_stride, counts + 2 w, tminmax + 2 w (nullable)
+  int32_t* key_offsets;
+  int32_t* grp_offsets;
+  uint16_t* cpix;
+  float* cdt;
+  int32_t* counts;
+  double* tminmax;
+  char* scratch;
+  int64_t key_stride, grp_stride;
+  int first;   // index of the set's first window in the batch
+};
+// the columns of a window: the batch's, from its first event on (raw sources only)
+__device__ __forceinline__ LeanIn lean_window_in(const LeanIn& in, int wide, int64_t begin) {
+  return LeanIn{nullptr, in.col + begin, in.row + begin,
+                wide ? static_cast<const void*>(static_cast<const int64_t*>(in.t) + begin)
+                     : static_cast<const void*>(static_cast<const int32_t*>(in.t) + begin),
+                in.ticks_per_second};
+}
+__device__ __forceinline__ LeanGeom lean_window_geom(LeanGeom g, const LeanWin& w) {
+  g.sub = w.sub, g.n_bins = g.n_tiles * w.sub, g.chunk = w.chunk;
+  return g;
+}
+__device__ __forceinline__ LeanScratch lean_window_scratch(const LeanBatchOut& o, const LeanGeom& g, const LeanWin& w) {
+  return lean_scratch_at(o.scratch + w.scratch_off, lean_sections(g.n_bins, w.n_chunks, w.chunk));
+}
+
+// K0 of a batch (lean_stage_kernel<SRC, StageMany>): the grid is the windows' chunks one after the other (windows of a recording differ
+// several-fold in size: no window is padded to the largest); a workgroup finds its window ONCE, by bisection of the chunks' prefix
+// table (uniform: scalar work)
+struct StageMany {
+  LeanBatch b;
+  int n_windows, wide;
+  LeanIn in;
+  LeanGeom g0;
+  LeanBatchOut o;
+  struct View {
+    LeanIn in;
+    int64_t n;
+    LeanGeom g;
+    LeanScratch sc;
+    unsigned idx, cnt;
+    __device__ __forceinline__ unsigned index() const { return idx; }
+    __device__ __forceinline__ unsigned count() const { return cnt; }
+  };
+  __device__ __forceinline__ View view() const {
+    int lo = 0, hi = n_windows - 1;
+    while (lo < hi) {   // the last window whose first chunk is not beyond this one (every window has a chunk: chunk0 strictly ascends)
+      const int mid = (lo + hi + 1) >> 1;
+      if ((unsigned)b.w[mid].chunk0 <= blockIdx.x) lo = mid;
+      else hi = mid - 1;
+    }
+    const LeanWin w = b.w[lo];
+    const LeanGeom g = lean_window_geom(g0, w);
+    return View{lean_window_in(in, wide, w.begin), (int64_t)w.n, g, lean_window_scratch(o, g, w), blockIdx.x - (unsigned)w.chunk0,
+                (unsigned)w.n_chunks};
+  }
+};
+static_assert(sizeof(StageMany) <= 3584, "the batch travels in the kernel argument segment");
+
+// K1 of a batch: blockIdx.y = window, blockIdx.x = the window's workgroup (the grid is as wide as the window of most bins needs)
+__global__ void __launch_bounds__(kLeanBlock)
+lean_totals_batch_kernel(LeanBatch b, LeanGeom g0, LeanBatchOut o, int64_t n_keys, double ticks_per_second) {
+  const LeanWin w = b.w[blockIdx.y];
+  const LeanGeom g = lean_window_geom(g0, w);
+  const unsigned n_wg = (unsigned)((g.n_bins + kLeanBlock / kWave - 1) / (kLeanBlock / kWave));
+  if (blockIdx.x >= n_wg) return;
+  const int64_t wi = o.first + (int64_t)blockIdx.y;
+  lean_totals_body(g, w.n_chunks, lean_window_scratch(o, g, w), o.counts + 2 * wi, o.grp_offsets + wi * o.grp_stride,
+                   o.key_offsets + wi * o.key_stride, n_keys, ticks_per_second, 1, o.tminmax ? o.tminmax + 2 * wi : nullptr,
+                   GridPart{blockIdx.x, n_wg});
+}
+
+// K3 of a batch: blockIdx.y = window; blockIdx.x -> bin exactly as in lean_bin_sort_kernel (the grid's width is a multiple of 8, so a
+// workgroup's XCD is blockIdx.x & 7 in every row of the grid)
+__global__ void __launch_bounds__(kSortBlock)
+lean_bin_sort_batch_kernel(LeanBatch b, LeanGeom g0, LeanBatchOut o, LeanTime tc) {
+  const LeanWin w = b.w[blockIdx.y];
+  const LeanGeom g = lean_window_geom(g0, w);
+  if (blockIdx.x >= 8u * (unsigned)((g.n_bins + 7) / 8)) return;
+  const int64_t wi = o.first + (int64_t)blockIdx.y;
+  int pix_cap, sort_cap;
+  lean_sort_caps(g.th, g.tw, g.sub, pix_cap, sort_cap);
+  lean_bin_sort_body(g, lean_window_scratch(o, g, w), o.grp_offsets + wi * o.grp_stride, o.key_offsets + wi * o.key_stride,
+                     o.cpix + w.slot_off, o.cdt + w.slot_off, pix_cap, sort_cap, w.n_chunks, tc);
 }
 
 }  // namespace
@@ -962,10 +1140,7 @@ int ebos_plan_lean(int source, const void* events, const int16_t* col, const int
   }
   hipStream_t s = as_stream(stream);
   char* base = reinterpret_cast<char*>(scratch);
-  LeanScratch sc{reinterpret_cast<unsigned*>(base), reinterpret_cast<int32_t*>(base + L.off_base),
-                 reinterpret_cast<unsigned long long*>(base + L.off_tm), reinterpret_cast<unsigned*>(base + L.off_tm + 64),
-                 reinterpret_cast<ChunkPartial*>(base + L.off_partial),
-                 reinterpret_cast<uint16_t*>(base + L.off_px), base + L.off_t};
+  const LeanScratch sc = lean_scratch_at(base, lean_sections(L.n_bins, L.n_chunks, L.chunk));
   const bool small = H <= 65536 && W <= 65536;
   const LeanGeom g{H, W, tile_h, tile_w, tiles_x, n_tiles, L.sub, L.n_bins, L.chunk,
                    small ? (unsigned)(0x100000000ull / (unsigned)tile_h) + 1u : 0u, small ? (unsigned)(0x100000000ull / (unsigned)tile_w) + 1u : 0u};
@@ -977,12 +1152,12 @@ int ebos_plan_lean(int source, const void* events, const int16_t* col, const int
   bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(lean_bin_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kSortLds) == hipSuccess;
 #define EBOS_LEAN_ATTR(SRC)                                                                                                  \
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(lean_stage_kernel<SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(lean_stage_kernel<SRC, StageOne>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                  (int)lds_stage) == hipSuccess
 #define EBOS_LEAN(SRC)                                                                                                       \
   do {                                                                                                                       \
     EBOS_LEAN_ATTR(SRC);                                                                                                     \
-    if (ok) lean_stage_kernel<SRC><<<dim3(L.n_chunks), dim3(kLeanBlock), lds_stage, s>>>(in, n, g, sc);                      \
+    if (ok) lean_stage_kernel<SRC, StageOne><<<dim3(L.n_chunks), dim3(kLeanBlock), lds_stage, s>>>(StageOne{in, n, g, sc});  \
   } while (0)
   if (source == SRC_AOS_F32) EBOS_LEAN(SRC_AOS_F32);
   else if (source == SRC_AOS_F64) EBOS_LEAN(SRC_AOS_F64);
@@ -1000,6 +1175,101 @@ int ebos_plan_lean(int source, const void* events, const int16_t* col, const int
   lean_bin_sort_kernel<<<dim3(8 * ((L.n_bins + 7) / 8)), dim3(kSortBlock), lds_sort, s>>>(g, sc, grp_offsets, key_offsets, cpix, cdt, L.pix_cap, L.sort_cap,
                                                                           L.n_chunks, tc);
   EBOS_CHECK_LAUNCH("ebos_plan_lean");
+  return EBOS_OK;
+}
+
+size_t ebos_plan_lean_batch_scratch_bytes(const int64_t* ranges, int n_windows, int H, int W, int tile_h, int tile_w) {
+  if (ranges == nullptr || n_windows < 1 || H <= 0 || W <= 0 || tile_h <= 0 || tile_w <= 0) return 0;
+  size_t total = 0;
+  for (int w = 0; w < n_windows; ++w) {
+    const int64_t n = ranges[2 * w + 1] - ranges[2 * w];
+    if (n < 0) return 0;
+    total += ebos::lean_layout(n, H, W, tile_h, tile_w).total;   // (a multiple of 256: every window's sections stay aligned)
+  }
+  return total;
+}
+
+int ebos_plan_lean_batch(const int16_t* col, const int16_t* row, const void* t, int t_is_64, double ticks_per_second, int64_t n_total,
+                         const int64_t* ranges, int n_windows, int ref_mode, double ref_fraction, int normalize_t, int H, int W,
+                         int tile_h, int tile_w, int32_t* key_offsets, int64_t key_stride, int32_t* grp_offsets, int64_t grp_stride,
+                         uint16_t* cpix, float* cdt, const int64_t* slot_offsets, int32_t* counts, double* tminmax, void* scratch,
+                         size_t scratch_bytes, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(n_windows >= 1 && n_total >= 0 && ranges && slot_offsets, "ebos_plan_lean_batch: no windows / NULL host table");
+  EBOS_REQUIRE(H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && tile_h <= 256 && tile_w <= 256, "ebos_plan_lean_batch: bad sizes (tiles up to 256 x 256)");
+  EBOS_REQUIRE(ref_mode >= 0 && ref_mode <= 2, "ebos_plan_lean_batch: ref_mode must be FIRST / LAST / FRACTION");
+  EBOS_REQUIRE(col && row && t && ticks_per_second > 0.0, "ebos_plan_lean_batch: NULL event columns");
+  EBOS_REQUIRE(key_offsets && grp_offsets && cpix && cdt && counts && scratch, "ebos_plan_lean_batch: NULL output / scratch");
+  const int tiles_y = (H + tile_h - 1) / tile_h, tiles_x = (W + tile_w - 1) / tile_w, n_tiles = tiles_y * tiles_x;
+  const int64_t n_keys = (int64_t)n_tiles * tile_h * tile_w;
+  EBOS_REQUIRE(key_stride >= n_keys + 1 && grp_stride >= n_tiles + 1, "ebos_plan_lean_batch: strides shorter than a window's arrays");
+  // every window checked before anything is launched: the call builds all of them or none
+  size_t need = 0;
+  for (int w = 0; w < n_windows; ++w) {
+    const int64_t b = ranges[2 * w], e = ranges[2 * w + 1], n = e - b;
+    EBOS_REQUIRE(b >= 0 && e >= b && e <= n_total && n < (int64_t)1 << 31, "ebos_plan_lean_batch: window %d = [%lld, %lld) outside the %lld events",
+                 w, (long long)b, (long long)e, (long long)n_total);
+    EBOS_REQUIRE(slot_offsets[w] >= 0 && slot_offsets[w] % 8 == 0 && slot_offsets[w + 1] - slot_offsets[w] >= n + 3 * (int64_t)n_tiles + 4,
+                 "ebos_plan_lean_batch: window %d: slots must start on a multiple of 8 and hold n + 3 tiles + 4", w);
+    const LeanLayout L = lean_layout(n, H, W, tile_h, tile_w);
+    if (L.n_bins > kMaxBins || L.sort_cap < 64) {
+      set_error("ebos_plan_lean_batch: %d bins / %d pixels per band exceed what this build sorts in LDS", L.n_bins, L.pix_cap);
+      return EBOS_ERR_UNSUPPORTED;
+    }
+    need += L.total;
+  }
+  if (scratch_bytes < need) {
+    set_error("ebos_plan_lean_batch: scratch too small (%zu < %zu)", scratch_bytes, need);
+    return EBOS_ERR_SCRATCH;
+  }
+  hipStream_t s = as_stream(stream);
+  const int source = t_is_64 ? SRC_RAW64 : SRC_RAW32;
+  const bool small = H <= 65536 && W <= 65536;
+  const LeanGeom g0{H, W, tile_h, tile_w, tiles_x, n_tiles, 1, n_tiles, 8,
+                    small ? (unsigned)(0x100000000ull / (unsigned)tile_h) + 1u : 0u, small ? (unsigned)(0x100000000ull / (unsigned)tile_w) + 1u : 0u};
+  const LeanIn in{nullptr, col, row, t, ticks_per_second};
+  const LeanTime tc{source, ref_mode, normalize_t, ref_fraction, ticks_per_second};
+  const size_t stamp_bytes = t_is_64 ? 8 : 4;
+  bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(lean_bin_sort_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kSortLds) == hipSuccess;
+  size_t scratch_off = 0;
+  for (int first = 0; first < n_windows && ok; first += kLeanBatch) {
+    const int nw = std::min(kLeanBatch, n_windows - first);
+    LeanBatch b{};
+    int chunks = 0, max_bins = 0;
+    size_t lds_stage = 0, lds_sort = 0;
+    for (int k = 0; k < nw; ++k) {
+      const int w = first + k;
+      const int64_t n = ranges[2 * w + 1] - ranges[2 * w];
+      const LeanLayout L = lean_layout(n, H, W, tile_h, tile_w);
+      b.w[k] = LeanWin{ranges[2 * w], (int64_t)scratch_off, slot_offsets[w], (int32_t)n, chunks, L.n_chunks, L.chunk, L.sub, 0};
+      scratch_off += L.total;
+      chunks += L.n_chunks;
+      max_bins = std::max(max_bins, L.n_bins);
+      lds_stage = std::max(lds_stage, (size_t)((L.n_bins + 1) & ~1) * 4 + (size_t)L.chunk * (stamp_bytes + 2));
+      lds_sort = std::max(lds_sort, (size_t)(2 * L.pix_cap) * 4 + (size_t)L.sort_cap * 12);
+    }
+    const LeanBatchOut o{key_offsets, grp_offsets, cpix, cdt, counts, tminmax, reinterpret_cast<char*>(scratch), key_stride, grp_stride, first};
+    const StageMany many{b, nw, t_is_64 ? 1 : 0, in, g0, o};
+    if (t_is_64) {
+      ok = hipFuncSetAttribute(reinterpret_cast<const void*>(lean_stage_kernel<SRC_RAW64, StageMany>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds_stage) == hipSuccess;
+      if (ok) lean_stage_kernel<SRC_RAW64, StageMany><<<dim3(chunks), dim3(kLeanBlock), lds_stage, s>>>(many);
+    } else {
+      ok = hipFuncSetAttribute(reinterpret_cast<const void*>(lean_stage_kernel<SRC_RAW32, StageMany>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds_stage) == hipSuccess;
+      if (ok) lean_stage_kernel<SRC_RAW32, StageMany><<<dim3(chunks), dim3(kLeanBlock), lds_stage, s>>>(many);
+    }
+    if (!ok) break;
+    lean_totals_batch_kernel<<<dim3((max_bins + kLeanBlock / kWave - 1) / (kLeanBlock / kWave), nw), dim3(kLeanBlock), 0, s>>>(
+        b, g0, o, n_keys, ticks_per_second);
+    lean_bin_sort_batch_kernel<<<dim3(8 * ((max_bins + 7) / 8), nw), dim3(kSortBlock), lds_sort, s>>>(b, g0, o, tc);
+  }
+  if (!ok) {
+    set_error("ebos_plan_lean_batch: cannot reserve LDS for the staging pass / the bin sort");
+    return EBOS_ERR_LAUNCH;
+  }
+  EBOS_CHECK_LAUNCH("ebos_plan_lean_batch");
   return EBOS_OK;
 }
 

@@ -149,6 +149,22 @@ class RawEventStore(object):
         return EventPlan.build_raw(col, row, t, pol, image_size, direction, normalize_t, tile, self.TICKS_PER_SECOND,
                                    deferred=deferred, emit=emit)
 
+    def plans(self, windows, image_size: Tuple[int, int], direction="first", normalize_t: bool = True, tile="auto", device="cuda",
+              deferred: bool = True) -> list:
+        """The lean plans of several (start_index, end_index) windows in one set of launches: the batched sibling of ``plan(...,
+        emit="compact")``, ``EventPlan.build_raw_batch``.  The stretch of the recording from the first window's start to the last
+        one's end is uploaded ONCE (windows of a recording follow or overlap each other; events between far-apart windows travel
+        along), and every window is a range of it.  Plan k equals ``plan(*windows[k], ..., emit="compact")`` bit for bit."""
+        windows = [(int(a), int(b)) for a, b in windows]
+        if not windows:
+            return []
+        for a, b in windows:
+            self._check(a, b)
+        lo, hi = min(a for a, _ in windows), max(b for _, b in windows)
+        col, row, t, pol = self.load_raw(lo, hi, device)
+        return EventPlan.build_raw_batch(col, row, t, pol, [(a - lo, b - lo) for a, b in windows], image_size, direction, normalize_t,
+                                         tile, self.TICKS_PER_SECOND, deferred=deferred)
+
     # ------------------------------------------------------------------ index <-> time
     def _times(self) -> np.ndarray:
         if self._time_cache is None:

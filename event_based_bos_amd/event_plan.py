@@ -13,8 +13,9 @@ and every objective evaluation afterwards is one fused kernel over 12-16 B/event
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass, fields
-from typing import Optional, Tuple, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch.utils import _pytree
@@ -125,6 +126,42 @@ def part_fixed_events(n_events: int, n_tiles: int, n_cu: int) -> int:
     if 2 * n_tiles <= n_cu:
         return PART_FIXED_EVENTS
     return int(min(65536, max(PART_FIXED_EVENTS, 6.5e10 / max(int(n_events), 1))))
+
+
+class PlanBatchLayout(NamedTuple):
+    """Where the plans of ``EventPlan.build_raw_batch`` lie in the batch's buffers (elements, not bytes)."""
+    n_tiles: int
+    n_keys: int
+    key_stride: int                 # window w: key_offsets [n_keys + 1] at w * key_stride
+    grp_stride: int                 # grp_offsets [n_tiles + 1] at w * grp_stride
+    part_stride: int                # part_table [5 n_tiles + 1] at w * part_stride
+    capacities: Tuple[int, ...]     # slots of cpix / cdt per window: the single build's n + 3 n_tiles + 8
+    slot_offsets: Tuple[int, ...]   # [B + 1]: first slot of every window, and the slots of the batch
+
+
+PLAN_BATCH_ALIGN = 64   # elements: every window's arrays start on 128 bytes (u16 pixels) / 256 bytes (int32, f32) -- the tile-private
+#                         kernels read 16-byte vectors, ebos_plan_lean_batch asks for slots on a multiple of 8
+
+
+def plan_batch_layout(lengths: Sequence[int], image_size: Tuple[int, int], tile: Tuple[int, int]) -> PlanBatchLayout:
+    """Offsets and capacities of the windows of a batched plan build from their event counts and the tile grid (host arithmetic only:
+    the lengths are known before anything runs, so nothing on the device sizes anything).  A window holds exactly what the single
+    build allocates for it -- empty windows included --, rounded up to ``PLAN_BATCH_ALIGN`` elements so that the next one is aligned."""
+    H, W = int(image_size[0]), int(image_size[1])
+    th, tw = int(tile[0]), int(tile[1])
+    if H <= 0 or W <= 0 or th <= 0 or tw <= 0:
+        raise ValueError("plan_batch_layout: image and tile sizes must be positive")
+    n_tiles = ((H + th - 1) // th) * ((W + tw - 1) // tw)
+    n_keys = n_tiles * th * tw
+    up = lambda v: (v + PLAN_BATCH_ALIGN - 1) // PLAN_BATCH_ALIGN * PLAN_BATCH_ALIGN   # noqa: E731
+    caps, offs = [], [0]
+    for n in lengths:
+        n = int(n)
+        if n < 0:
+            raise ValueError("plan_batch_layout: a window cannot hold a negative number of events")
+        caps.append(n + 3 * n_tiles + 8)
+        offs.append(offs[-1] + up(caps[-1]))
+    return PlanBatchLayout(n_tiles, n_keys, up(n_keys + 1), up(n_tiles + 1), up(5 * n_tiles + 1), tuple(caps), tuple(offs))
 
 
 @dataclass
@@ -349,6 +386,94 @@ class EventPlan:
         if tile is not None:
             plan = plan.bin(tile, deferred=deferred)  # int16 columns: integer coordinates by construction
         return plan
+
+    @staticmethod
+    def build_raw_batch(col: torch.Tensor, row: torch.Tensor, t: torch.Tensor, pol: torch.Tensor, ranges: Sequence[Tuple[int, int]],
+                        image_size: Tuple[int, int], direction: Union[str, float] = "first", normalize_t: bool = True,
+                        tile: Tuple[int, int] = DEFAULT_TILE, ticks_per_second: float = 1e6, deferred: bool = True) -> List["EventPlan"]:
+        """The lean plans (``emit="compact"``) of several windows of one recording in one set of launches (``ebos_plan_lean_batch``,
+        ``ebos_plan_parts_batch``): ``ranges`` are half-open index ranges [begin, end) into the raw columns -- they may overlap and
+        come in any order.  Plan k holds what ``build_raw(col[b:e], row[b:e], t[b:e], pol[b:e], ..., emit="compact")`` holds for
+        range k, bit for bit: every window has its own reference time and normalisation.  The plans' tensors are views into the
+        batch's buffers (``plan_batch_layout``), which live as long as any of the plans; ``record_stream`` works as on a single plan.
+        ``deferred=False``: ONE read-back for all windows fills ``n_dropped``, the work items in use and the fullest tile.
+        An empty range gives a plan without events (the window-by-window route raises IndexError for it, as ``build_raw`` does).
+        A tile outside the LDS sort (``ebos_plan_lean_batch`` answers EBOS_ERR_UNSUPPORTED) is built window by window instead."""
+        if isinstance(tile, str):
+            if tile != "auto":
+                raise ValueError("tile must be a (tile_h, tile_w) pair or 'auto'")
+            tile = choose_tile(image_size)
+        if tile is None:
+            raise ValueError("EventPlan.build_raw_batch builds binned (lean) plans: tile must be a (tile_h, tile_w) pair or 'auto'")
+        lib = _hip.require_gpu()
+        n_total = int(t.shape[0])
+        for name, v, dts in (("col", col, (torch.int16,)), ("row", row, (torch.int16,)), ("t", t, (torch.int32, torch.int64)),
+                             ("pol", pol, (torch.bool, torch.uint8))):
+            if v.dim() != 1 or v.shape[0] != n_total or v.dtype not in dts:
+                raise ValueError(f"EventPlan.build_raw_batch: {name} must be a 1-D tensor of {n_total} elements, dtype in {dts}; "
+                                 f"got {tuple(v.shape)} {v.dtype}")
+            if not v.is_cuda:
+                raise _hip.HipUnavailableError(f"EventPlan.build_raw_batch: {name} must be on the GPU")
+        ranges = [(int(b), int(e)) for b, e in ranges]
+        for b, e in ranges:
+            if not 0 <= b <= e <= n_total:
+                raise IndexError(f"EventPlan.build_raw_batch: range [{b}, {e}) outside the {n_total} events")
+        if not ranges:
+            return []
+        col, row, t = col.contiguous(), row.contiguous(), t.contiguous()
+        H, W = int(image_size[0]), int(image_size[1])
+        th, tw = int(tile[0]), int(tile[1])
+
+        def one_by_one():
+            return [EventPlan.build_raw(col[b:e], row[b:e], t[b:e], pol[b:e], (H, W), direction, normalize_t, (th, tw), ticks_per_second,
+                                        deferred=deferred, emit="compact") for b, e in ranges]
+
+        if th > 256 or tw > 256:
+            return one_by_one()
+        ref_mode, frac = parse_direction(direction)
+        dev, B = t.device, len(ranges)
+        lay = plan_batch_layout([e - b for b, e in ranges], (H, W), (th, tw))
+        n_tiles, n_keys = lay.n_tiles, lay.n_keys
+        c_ranges = (C.c_int64 * (2 * B))(*[v for r in ranges for v in r])
+        c_slots = (C.c_int64 * (B + 1))(*lay.slot_offsets)
+        nbytes = int(lib.ebos_plan_lean_batch_scratch_bytes(c_ranges, B, H, W, th, tw))
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        key_all = torch.empty((B, lay.key_stride), dtype=torch.int32, device=dev)
+        grp_all = torch.empty((B, lay.grp_stride), dtype=torch.int32, device=dev)
+        part_all = torch.empty((B, lay.part_stride), dtype=torch.int32, device=dev)
+        cpix_all = torch.empty(lay.slot_offsets[-1], dtype=torch.int16, device=dev)
+        cdt_all = torch.empty(lay.slot_offsets[-1], dtype=torch.float32, device=dev)
+        counts_all = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        n_cu = _n_cu(dev)
+        c_fixed = (C.c_int32 * B)(*[part_fixed_events(e - b, n_tiles, n_cu) for b, e in ranges])
+        with _hip.on_device(dev):
+            rc = lib.ebos_plan_lean_batch(ptr(col), ptr(row), ptr(t), int(t.dtype == torch.int64), float(ticks_per_second), n_total,
+                                          c_ranges, B, ref_mode, frac, int(normalize_t), H, W, th, tw, ptr(key_all), lay.key_stride,
+                                          ptr(grp_all), lay.grp_stride, ptr(cpix_all), ptr(cdt_all), c_slots, ptr(counts_all), None,
+                                          ptr(scratch), nbytes, stream_ptr())
+            if rc == -3:  # EBOS_ERR_UNSUPPORTED (nothing was launched): geometry outside the LDS sort
+                return one_by_one()
+            check(rc, "ebos_plan_lean_batch")
+            check(lib.ebos_plan_parts_batch(ptr(key_all), lay.key_stride, B, H, W, th, tw, n_cu, c_fixed, ptr(part_all), lay.part_stride,
+                                            stream_ptr()), "ebos_plan_parts_batch")
+            facts = None
+            if not deferred:  # the one host read-back of the batch: (outside the image, fractional, work items in use, fullest tile) x B
+                f_dev = torch.empty((B, 4), dtype=torch.int32, device=dev)
+                check(lib.ebos_plan_facts_batch(ptr(key_all), lay.key_stride, B, H, W, th, tw, ptr(counts_all), ptr(part_all),
+                                                lay.part_stride, ptr(f_dev), stream_ptr()), "ebos_plan_facts_batch")
+                facts = f_dev.tolist()
+        plans = []
+        bound = dt_bound_for(direction, normalize_t)
+        for w, (b, e) in enumerate(ranges):
+            n = e - b
+            dropped, used, fullest = (0, None, None) if facts is None else (facts[w][0], facts[w][2], facts[w][3])
+            o, cap = lay.slot_offsets[w], lay.capacities[w]
+            plan = EventPlan(None, None, None, None, (H, W), n - dropped, n, (th, tw), key_all[w, :n_keys + 1], None, dropped,
+                             grp_all[w, :n_tiles + 1], cpix_all[o:o + cap], cdt_all[o:o + cap], part_all[w, :5 * n_tiles + 1], bound)
+            plan.__dict__["_counts"], plan.__dict__["_deferred"], plan.__dict__["_parts_used"] = counts_all[w], bool(deferred), used
+            plan.__dict__["_fullest_tile"] = fullest
+            plans.append(plan)
+        return plans
 
     def bin(self, tile: Tuple[int, int] = DEFAULT_TILE, deferred: bool = False) -> "EventPlan":
         """Counting-sort the plan by source pixel, tile-major (ebos_bin_events_f32).

@@ -27,6 +27,9 @@ filters' masks chained on the device, one compaction, one host read-back of the 
 CROP.  The BAF time map of BAF_continuous_update carries over the windows of one ``run`` call in list order and starts from
 zero at every call.  A window solved again after a resident fallback reuses the events it was filtered to the first time.
 
+With ``batch_ingest=True`` the plans of a group are built in one batched call (``RawEventStore.plans``) instead of one by one; the
+flag is ignored when BAF / HOT filters are configured, and the results are the same bits either way.
+
 With ``poisson=True`` the Poisson integration the reference's visualizer runs on every window's flow (``poisson``) is computed for
 all windows of a ``run`` in one batched call on the device and kept in ``poisson_images``; it is read back together with the flows.
 """
@@ -75,7 +78,7 @@ RESIDENT_TILES = ((32, 32), (32, 64), (45, 80))   # the tiles with resident kern
 
 class WindowPipeline(object):
     def __init__(self, solver: ContrastMaximization, n_concurrent: Optional[int] = None, device="cuda", resident: Optional[bool] = None,
-                 poisson: bool = False):
+                 poisson: bool = False, batch_ingest: bool = False):
         # the patch-flow solver, or the 2-DoF Adam loop of the reference's shipped YAML (configs/hot_plate1.yaml:47,70)
         self.two_dof = solver.motion_model in ("2d-translation", "rigid-optical-flow")
         if solver.motion_model != "dense-flow" and not (self.two_dof and solver.opt_method == "Adam"):
@@ -97,6 +100,12 @@ class WindowPipeline(object):
         self.filters = EventFilter(solver.orig_image_shape, dict(section, parameters={
             k: v for k, v in (section.get("parameters") or {}).items() if k not in ("xmin", "xmax", "ymin", "ymax")})) \
             if section.get("filters") else None
+        # batch_ingest: the plans of a group of windows are built by ONE ``RawEventStore.plans`` call on the ingest stream (one upload of
+        # the group's stretch of the recording, three build launches, one work-item launch) instead of window by window; the group's
+        # solver streams then all wait for one event, the end of the group's build.  Same plans bit for bit, so the same flows.  Ignored
+        # when BAF / HOT filters are configured: every window's plan is sized by the count its filter reads back.  Off by default:
+        # the per-window events of the default path let a window's solve start as soon as ITS plan is ready.
+        self.batch_ingest = bool(batch_ingest)
         self.lib = _hip.require_gpu()
         self.histories: List[List[float]] = []
         # poisson: ``run`` also integrates every window's dense flow (the visualizer's poisson_reconstruct(flow[1], flow[0], zeros),
@@ -263,6 +272,14 @@ class WindowPipeline(object):
 
             def ingest_group(group, filtered=None):   # one event per window: a window's stream waits for ITS plan, not for the group's last one
                 plans, ready, kept = [], [], []
+                if self.batch_ingest and self.filters is None:
+                    s = self.solver
+                    with torch.cuda.stream(ingest):
+                        plans = [self._check_plan(p) for p in store.plans(group, s.orig_image_shape, s.warp_direction, True, tile=self.tile,
+                                                                           device=self.device, deferred=True)]
+                        ev = torch.cuda.Event()
+                        ev.record(ingest)
+                    return plans, [ev] * len(plans), [None] * len(plans)
                 with torch.cuda.stream(ingest):
                     for k, wnd in enumerate(group):
                         plan, f = self._ingest(store, wnd, None if filtered is None else filtered[k])

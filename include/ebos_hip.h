@@ -270,6 +270,31 @@ int ebos_plan_lean(int source, const void* events, const int16_t* col, const int
                    int tile_h, int tile_w, int32_t* key_offsets, int32_t* grp_offsets, uint16_t* cpix, float* cdt,
                    int64_t capacity_slots, int32_t* counts, double* tminmax, void* scratch, size_t scratch_bytes,
                    ebos_stream_t stream);
+/* The lean plans of SEVERAL windows of one recording in one set of launches.  col / row / t (int32, or int64 with t_is_64): the
+ * device columns of n_total raw events; ranges: HOST int64 [n_windows, 2], window w = events [begin, end) of the columns -- ranges
+ * may overlap, be empty and come in any order.  Every window is built exactly as ebos_plan_lean builds events [begin, end) on their
+ * own -- its own reference time and normalisation, the same bits in every output -- into shared buffers:
+ *     key_offsets + w * key_stride  [n_keys + 1]      grp_offsets + w * grp_stride  [tiles + 1]      counts + 2 w      tminmax + 2 w
+ *     cpix / cdt + slot_offsets[w]: slot_offsets HOST int64 [n_windows + 1], ascending, each a multiple of 8 (16-byte aligned
+ *         slots), slot_offsets[w + 1] - slot_offsets[w] >= n_w + 3 tiles + 4.
+ * An empty window leaves key_offsets and grp_offsets zero, counts zero and tminmax undefined.  The stage, totals and bin-sort passes
+ * run once for every 64 windows (the windows' descriptors travel in the kernel arguments); the staging pass's grid is the windows'
+ * chunks one after the other, so no window is padded to the largest.  The host-only size query takes the same ranges: the sum of
+ * ebos_plan_lean_scratch_bytes over the windows.  Returns EBOS_ERR_UNSUPPORTED -- before anything is launched -- when ANY window's
+ * geometry is outside the LDS sort (as ebos_plan_lean would for it): build the windows one by one then. */
+size_t ebos_plan_lean_batch_scratch_bytes(const int64_t* ranges, int n_windows, int H, int W, int tile_h, int tile_w);
+int ebos_plan_lean_batch(const int16_t* col, const int16_t* row, const void* t, int t_is_64, double ticks_per_second, int64_t n_total,
+                         const int64_t* ranges, int n_windows, int ref_mode, double ref_fraction, int normalize_t, int H, int W,
+                         int tile_h, int tile_w, int32_t* key_offsets, int64_t key_stride, int32_t* grp_offsets, int64_t grp_stride,
+                         uint16_t* cpix, float* cdt, const int64_t* slot_offsets, int32_t* counts, double* tminmax, void* scratch,
+                         size_t scratch_bytes, ebos_stream_t stream);
+/* ebos_plan_parts / ebos_plan_facts for n_windows plans of one geometry laid out as above, one launch each (a workgroup per plan;
+ * parts: one launch per 64 plans): part_table + w * part_stride [5 tiles + 1]; fixed_events: HOST int32 [n_windows], the per-item
+ * fixed work of each window; counts [n_windows, 2] (nullable), facts [n_windows, 4] (device; one copy reads them all back). */
+int ebos_plan_parts_batch(const int32_t* key_offsets, int64_t key_stride, int n_windows, int H, int W, int tile_h, int tile_w, int n_cu,
+                          const int32_t* fixed_events, int32_t* part_table, int64_t part_stride, ebos_stream_t stream);
+int ebos_plan_facts_batch(const int32_t* key_offsets, int64_t key_stride, int n_windows, int H, int W, int tile_h, int tile_w,
+                          const int32_t* counts, const int32_t* part_table, int64_t part_stride, int32_t* facts, ebos_stream_t stream);
 /* Compact plan: the 6 B/event layout of the tile-private kernels, valid when every source coordinate is a
  * non-negative integer (frac_count == 0; camera events always are).  Per tile t the events occupy the groups
  * [grp_offsets[t], grp_offsets[t+1]) of 4 slots (16-byte vector loads, tiles start on a group boundary):

@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--tile", type=int, nargs=2, default=None, help="source tile of the window plans (default: the one that fills the GPU with one window)")
     ap.add_argument("--blur", type=float, default=0.0, help="iwe.blur_sigma")
     ap.add_argument("--two-dof", action="store_true", help="the 2-DoF Adam loop (configs/hot_plate1.yaml:47,70 of the reference) instead of the patch flow")
+    ap.add_argument("--batch-ingest", action="store_true", help="also time WindowPipeline(batch_ingest=True) (resident), alternating with the default in the same rounds")
     a = ap.parse_args()
     a.halo = a.halo if a.halo == "auto" else int(a.halo)
     H, W = a.size
@@ -74,6 +75,22 @@ def main():
         res[tag + "_fallbacks"] = len(pipe.resident_fallbacks)
         if a.repeat > 1:
             res[tag + "_all"] = [round(t, 2) for t in times]
+    if a.batch_ingest:   # the group's plans by one batched build against the default's per-window builds, alternating, same process
+        for nc in a.nc:
+            pipes = {False: ebos.solver.WindowPipeline(solver, n_concurrent=nc), True: ebos.solver.WindowPipeline(solver, n_concurrent=nc, batch_ingest=True)}
+            times = {False: [], True: []}
+            for flag in (False, True):
+                pipes[flag].run(store, windows)
+            for _ in range(max(a.repeat, 3)):
+                for flag in (False, True):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pipes[flag].run(store, windows)
+                    torch.cuda.synchronize()
+                    times[flag].append((time.perf_counter() - t0) / a.windows * 1e3)
+            for flag, tag in ((False, "default"), (True, "batch_ingest")):
+                res[f"ingest_{nc}_{tag}_ms_per_window"] = {"best": round(min(times[flag]), 4), "spread": round(max(times[flag]) - min(times[flag]), 4),
+                                                           "all": [round(t, 3) for t in times[flag]]}
     print(json.dumps(res))
 
 

@@ -2,6 +2,11 @@
 """Wall-clock of EventPlan.build / build_raw per window (host + device, synchronised), after warm-up.
 
     python tools/bench_plan_build.py [--events 10000000] [--height 720 --width 1280]
+    python tools/bench_plan_build.py --batch 8 --events 400000 --height 720 --width 1280 [--out profiles/plan_batch_bench.json]
+
+``--batch K``: K consecutive windows of ``--events`` events of one recording (raw columns on the device), deferred lean builds:
+the per-window wall time of K single builds in a loop against ONE ``EventPlan.build_raw_batch`` of the same windows -- same process,
+alternating, after warm-up; best, median and spread (max - min) over ``--reps`` rounds of each.
 """
 import argparse
 import json
@@ -29,12 +34,65 @@ def timed(fn, reps=5):
     return float(np.median(out))
 
 
+def bench_batch(a):
+    """Loop of deferred single builds against one batched build of the same K windows, alternating in one process."""
+    H, W, n, K = a.height, a.width, a.events, a.batch
+    rs = np.random.RandomState(0)
+    tile = ebos.event_plan.choose_tile((H, W))
+    raw = [torch.from_numpy(rs.randint(0, W, n * K).astype(np.int16)).cuda(), torch.from_numpy(rs.randint(0, H, n * K).astype(np.int16)).cuda(),
+           torch.from_numpy((np.sort(rs.randint(0, 8333 * K, n * K)) + 10_000_000).astype(np.int32)).cuda(),
+           torch.from_numpy(rs.randint(0, 2, n * K).astype(np.uint8)).cuda()]
+    ranges = [(k * n, (k + 1) * n) for k in range(K)]
+    slices = [tuple(c[b:e] for c in raw) for b, e in ranges]
+
+    def loop():
+        return [ebos.EventPlan.build_raw(*sl, (H, W), "first", True, tile=tile, deferred=True, emit="compact") for sl in slices]
+
+    def batch():
+        return ebos.EventPlan.build_raw_batch(*raw, ranges, (H, W), "first", True, tile=tile, deferred=True)
+
+    # the same plans, at the sizes timed
+    for p1, pb in zip(loop(), batch()):
+        used = int(p1.grp_offsets[-1]) * 4
+        same = (torch.equal(p1.key_offsets, pb.key_offsets) and torch.equal(p1.grp_offsets, pb.grp_offsets) and
+                torch.equal(p1.cpix[:used], pb.cpix[:used]) and torch.equal(p1.cdt[:used].view(torch.int32), pb.cdt[:used].view(torch.int32)) and
+                torch.equal(p1.part_table, pb.part_table))
+        if not same:
+            raise SystemExit("bench_plan_build: the batched plans differ from the single builds")
+    for _ in range(3):
+        loop(), batch()
+    torch.cuda.synchronize()
+    times = {"loop": [], "batch": []}
+    for _ in range(a.reps):
+        for name, fn in (("loop", loop), ("batch", batch)):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3 / K)
+    res = {"windows": K, "events_per_window": n, "image": [H, W], "tile": list(tile), "reps": a.reps, "unit": "ms per window (host + device)"}
+    for name, v in times.items():
+        res[name] = {"best": round(min(v), 4), "median": round(float(np.median(v)), 4), "spread": round(max(v) - min(v), 4)}
+    res["gain"] = bool(res["batch"]["best"] < res["loop"]["best"] - res["loop"]["spread"])   # below the loop's best by more than its spread
+    res["gain_over_median_spread"] = bool(res["batch"]["best"] < res["loop"]["best"] - (res["loop"]["median"] - res["loop"]["best"]))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        rows = json.load(open(a.out)) if os.path.exists(a.out) else []
+        rows.append(res)
+        json.dump(rows, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--events", type=int, default=10_000_000)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--batch", type=int, default=0, help="K > 0: K windows of --events events, loop of single builds against one batched build")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None, help="--batch: append the result to this JSON list")
     a = ap.parse_args()
+    if a.batch > 0:
+        return bench_batch(a)
     H, W, n = a.height, a.width, a.events
     rs = np.random.RandomState(0)
     col = rs.randint(0, W, n).astype(np.int16)
