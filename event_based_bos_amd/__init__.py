@@ -18,6 +18,7 @@ tub-rip/event_based_bos:
     frame_warp           the reference loader's frame warp (cv2.warpPerspective) and the driver's crop, batched, one launch
     data_loader          raw-column event store (the CCS raw_events layout) feeding EventPlan.build_raw; FrameStore, the frame half
     evaluation           the reference driver's per-frame evaluation of a recording: the plan, the batched window ingest, the evaluator
+    visualizer           the reference visualizer's pictures (colour-coded flow, event picture, density picture), batched
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -31,6 +32,6 @@ from .data_loader import FrameStore, RawEventStore  # noqa: F401
 from .frame_warp import validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
 from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingEvaluator, plan_evaluation,  # noqa: F401
                          window_ingest_raw_batch)
-from . import costs, data_loader, evaluation, event_filters, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils  # noqa: F401
+from . import costs, data_loader, evaluation, event_filters, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

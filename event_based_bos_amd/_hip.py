@@ -246,6 +246,11 @@ SIGNATURES = {
     "ebos_warp_perspective": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
     "ebos_window_ingest_scratch_bytes": (_Z, [_I] * 8),
     "ebos_window_ingest_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 12 + [_P] * 6 + [_Z, _P]),
+    "ebos_viz_reduce_f64": (_I, [_I, _I, _I, _P, _I, _D, _P, _P]),
+    "ebos_viz_flow_rgb_u8": (_I, [_I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _I, _D, _P, _P]),
+    "ebos_viz_hsv2rgb_u8": (_I, [_L, _P, _P, _P]),
+    "ebos_viz_mask_close_u8": (_I, [_I, _I, _I, _P, _L, _P, _P]),
+    "ebos_viz_gray_u8": (_I, [_I, _I, _I, _I, _I, _P, _L, _P, _L, _D, _P, _L, _P, _P]),
 }
 
 
@@ -256,12 +261,22 @@ FLOW_ERROR_F32, FLOW_ERROR_F64, FLOW_ERROR_CLAMP_AE = 0, 1, 1
 POISSON_F32, POISSON_F64 = 0, 1
 FARNEBACK_U8, FARNEBACK_F32, FARNEBACK_F64 = 0, 1, 2
 WARP_U8, WARP_F32 = 0, 1
+VIZ_MAX_FIELDS = 8
+VIZ_FLOW, VIZ_FLOW_PAIR, VIZ_SCALAR = 0, 1, 2
+VIZ_MASK_MULTIPLY, VIZ_MASK_BLACK, VIZ_MASK_WHITE = 1, 2, 4
+VIZ_GRAY_EVENT, VIZ_GRAY_IWE, VIZ_GRAY_CENTER = 0, 1, 2
 
 
 class EventSource(C.Structure):
     """``ebos_event_source`` of include/ebos_hip.h (same field order): the window an event filter reads."""
     _fields_ = [("kind", _I), ("layout", _I)] + [(k, _P) for k in ("events", "col", "row", "t", "pol")] + \
                [("ticks_per_second", _D), ("n", _L)]
+
+
+class VizField(C.Structure):
+    """``ebos_viz_field`` of include/ebos_hip.h (same field order): one scalar ``ebos_viz_reduce_f64`` computes per window."""
+    _fields_ = [(k, _P) for k in ("x", "y", "x2", "y2", "mask")] + [(k, _L) for k in ("sb", "sb2", "mask_sb")] + \
+               [("kind", _I), ("reserved", _I)]
 
 
 class CmaxPatchProblem(C.Structure):

@@ -28,7 +28,7 @@ SOURCES = ["errors.cpp", "warp_kernels.hip", "splat_kernels.hip", "event_plan.hi
            "iwe_tiled_45x80x16.hip", "iwe_tiled_32x32x16.hip", "iwe_tiled_32x32x8.hip",
            "cmax_resident_45x80.hip", "cmax_resident_32x32.hip", "cmax_resident_32x64.hip",
            "cmax_resident_45x80_2dof.hip", "cmax_resident_32x32_2dof.hip", "cmax_resident_32x64_2dof.hip",
-           "event_filters.hip", "flow_error.hip", "poisson.hip", "gml.hip", "farneback.hip", "frame_warp.hip", "window_ingest.hip"]
+           "event_filters.hip", "flow_error.hip", "poisson.hip", "gml.hip", "farneback.hip", "frame_warp.hip", "window_ingest.hip", "visualize.hip"]
 
 # -munsafe-fp-atomics: hardware global_atomic_add_f32/f64 and ds_add_f32 instead of CAS loops.
 HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-fPIC",
@@ -55,6 +55,8 @@ def _needs_rebuild(target: str, deps: List[str]) -> bool:
 # sink-insts-to-avoid-spills puts those computations back next to their uses: 41 -> 7 spilled VGPRs.
 _RESIDENT_FLAGS = ["-mllvm", "-sink-insts-to-avoid-spills=1"]
 PER_FILE_FLAGS = {f"cmax_resident_{t}{p}.hip": _RESIDENT_FLAGS for t in ("45x80", "32x32", "32x64") for p in ("", "_2dof")}
+# visualize.hip: the float32 HSV -> RGB arithmetic is compared with its numpy restatement bit for bit: no fused multiply-adds.
+PER_FILE_FLAGS["visualize.hip"] = ["-ffp-contract=off"]
 
 
 def _compile(src: str, extra: List[str]) -> str:

@@ -16,7 +16,10 @@ of steps into the solver's polarity images, the event masks of the masked error 
 straight from the raw sensor columns; the generative solvers take them through ``estimate_batch_prepared``.  Any other registered
 solver is driven window by window through ``preprocess`` + ``estimate``.
 
-Out of scope: ``method: openpiv`` / ``estimation_method: openpiv``, the visualizer's pictures and videos.
+``run(pictures=True)`` also draws the driver's ten pictures per step (bos_event.py:202-207) on the device, batched
+(``visualizer.render_step_batch``), and writes them under ``save_dir`` in the driver's order and under its file names.
+
+Out of scope: ``method: openpiv`` / ``estimation_method: openpiv``, the visualizer's videos.
 """
 from __future__ import annotations
 
@@ -283,6 +286,7 @@ class EvaluationResult(object):
     flows: Optional[list] = None           # on request: per step (estimation, reference flow) device tensors
     poisson: Optional[list] = None         # on request: per step (P of the scaled estimate, P of the reference flow) device tensors
     files: dict = field(default_factory=dict)
+    pictures: Optional[list] = None        # with pictures=True: per step {name: uint8 numpy picture} as written
 
     @property
     def statistics(self) -> dict:
@@ -314,6 +318,7 @@ class RecordingEvaluator(object):
         self.remove = NOSE_RECT if bool(config["data"].get("remove_nose", False)) else None
         self.prepared_path = hasattr(solver, "estimate_batch_prepared")
         self.flow_estimator = frame_flow.FrameFlowEstimator(None)
+        self._picture_writer = None
 
     # ------------------------------------------------------------------ frames and the frame-based flow
     def _load_frames(self, indices: Sequence[int]):
@@ -373,11 +378,21 @@ class RecordingEvaluator(object):
         return save_line(self.solver, i_frame, d, name, self.save_dir)
 
     # ------------------------------------------------------------------ run
-    def run(self, max_batch: int = 8, poisson: bool = False, keep_flows: bool = False) -> EvaluationResult:
+    def run(self, max_batch: int = 8, poisson: bool = False, keep_flows: bool = False, pictures: bool = False) -> EvaluationResult:
+        """``pictures``: also render the driver's ten pictures of every step (``visualizer.render_step_batch``: one more
+        ``window_ingest_raw_batch`` call for the unfiltered events between the two frames, then a fixed number of launches per
+        batch) and write them, ``pred_flow<i>.npy`` and ``color_wheel.png`` under ``save_dir`` (default: the solver's
+        visualizer's directory, else the working directory) as the reference names them.  Needs PIL.  Off: nothing changes."""
         if int(max_batch) != max_batch or max_batch < 1:
             raise ValueError(f"max_batch {max_batch!r} < 1")
         plan = plan_evaluation(self.config, self.events, self.frames)
-        result = EvaluationResult(flows=[] if keep_flows else None, poisson=[] if poisson else None)
+        result = EvaluationResult(flows=[] if keep_flows else None, poisson=[] if poisson else None, pictures=[] if pictures else None)
+        self._picture_writer = None
+        if pictures:
+            from .visualizer import Visualizer
+
+            where = self.save_dir if self.save_dir is not None else getattr(self.solver.visualizer, "save_dir", "./")
+            self._picture_writer = Visualizer(tuple(self.solver.orig_image_shape), save=True, save_dir=where)
         todo = []
         for s in plan:
             if s.run:
@@ -394,6 +409,39 @@ class RecordingEvaluator(object):
             self._run_batch(todo[lo:lo + int(max_batch)], full0, result, poisson)
         return result
 
+    def _ingest_unfiltered(self, steps: Sequence[EvalStep]) -> torch.Tensor:
+        """The events between the two frames of every step, un-cropped (the driver's ``batch_for_gt``, nose removed when asked)
+        -> their polarity counts [B, 2, H, W], one launch."""
+        lo, hi = min(s.gt_range[0] for s in steps), max(s.gt_range[1] for s in steps)
+        cols = self.events.load_raw(lo, hi)
+        ranges = [(s.gt_range[0] - lo, s.gt_range[1] - lo) for s in steps]
+        H, W = (int(v) for v in self.solver.orig_image_shape)
+        return window_ingest_raw_batch(cols, ranges, (H, W), None, self.remove, self.events.TICKS_PER_SECOND).pol
+
+    def _draw(self, steps, est, gt, mask, filter_pol, period, result: EvaluationResult) -> None:
+        """The pictures of a batch: rendered at once, read back once per picture kind, written step by step in the driver's order."""
+        from .visualizer import PICTURES, color_wheel, render_step_batch
+
+        viz, solver = self._picture_writer, self.solver
+        scale = torch.tensor([s.gt_time_scale for s in steps], dtype=torch.float64, device=est.device) / period.to(est.device)
+        pred = est.double() * scale[:, None, None, None]
+        pics = render_step_batch(pred, gt, mask, filter_pol, self._ingest_unfiltered(steps), getattr(solver, "pad", 0),
+                                 getattr(solver, "iwe_visualize_max_scale", 50))
+        host = {k: v.cpu().numpy() for k, v in pics.items()}
+        flows = pred.cpu().numpy()
+        wheel = color_wheel(int(pred.shape[2]), pred.device).cpu().numpy()
+        for b, _ in enumerate(steps):
+            for name in PICTURES:
+                if name == "pred_flow":
+                    viz.save_array(flows[b], "pred_flow")          # (visualize_optical_flow(save_flow=True): the .npy, same number)
+                viz.visualize_image(host[name][b], file_prefix=name)
+                if name == "flow_comparison_gt":
+                    viz._show_or_save_image(wheel, fixed_file_name="color_wheel")
+                listed = getattr(solver, "sequential_video_list", None)
+                if listed is not None and not name.startswith("flow_comparison") and name not in listed:
+                    listed.append(name)
+            result.pictures.append({name: host[name][b] for name in PICTURES})
+
     def _run_batch(self, steps: Sequence[EvalStep], full0: torch.Tensor, result: EvaluationResult, poisson: bool) -> None:
         c = self.common
         full, pos = self._load_frames([s.i1 for s in steps] + [s.i2 for s in steps])
@@ -403,9 +451,11 @@ class RecordingEvaluator(object):
             prepared = self._ingest(steps)
             est = self.solver.estimate_batch_prepared(prepared, frames=[full[k] for k in k1], background=full0,
                                                       max_batch=len(steps), device_out=True)
-            mask, period = prepared.mask, prepared.period
+            mask, period, filter_pol = prepared.mask, prepared.period, prepared.pol
         else:
-            est, mask, period = self._solve_sequential(steps, gt, full, k1, full0)
+            est, mask, period, filter_pol = self._solve_sequential(steps, gt, full, k1, full0)
+        if result.pictures is not None:
+            self._draw(steps, est, gt, mask, filter_pol, period, result)
         roi = (slice(None), slice(None), slice(c["xmin"], c["xmax"]), slice(c["ymin"], c["ymax"]))
         plain, _ = flow_error.flow_error_batch(gt[roi], est[roi])
         masked, _ = flow_error.flow_error_batch(gt[roi], est[roi], event_mask=mask[roi[0], roi[2], roi[3]][:, None])
@@ -439,7 +489,7 @@ class RecordingEvaluator(object):
 
         solver = self.solver
         im0 = full0.cpu().numpy()
-        ests, masks, periods = [], [], []
+        ests, masks, periods, pols = [], [], [], []
         for b, s in enumerate(steps):
             self.events._check(*s.gt_range)
             batch = self.events.load_event(*s.est_range)
@@ -451,7 +501,11 @@ class RecordingEvaluator(object):
             ev = torch.as_tensor(filtered, dtype=torch.float64).to(gt.device)
             masks.append(solver.orig_imager.create_eventmask(ev).reshape(tuple(solver.orig_image_shape)).to(torch.uint8))
             periods.append(float(period))
-        return torch.stack(ests), torch.stack(masks), torch.tensor(periods, dtype=torch.float64, device=gt.device)
+            if self._picture_writer is not None:
+                pols.append(self._picture_writer.imager.create_image_from_events_tensor(ev, method="polarity", sigma=0)
+                            .reshape(2, *solver.orig_image_shape))
+        return (torch.stack(ests), torch.stack(masks), torch.tensor(periods, dtype=torch.float64, device=gt.device),
+                torch.stack(pols) if pols else None)
 
 
 # ------------------------------------------------------------------------------------------------ a synthetic recording

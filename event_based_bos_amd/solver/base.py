@@ -2,8 +2,10 @@
 
 Kept from the reference: the constructor signature, ``preprocess(events) -> (events, time_period)``,
 ``estimate(events, *args, **kwargs) -> np.ndarray [2, H, W]`` and the owned helpers ``orig_imager`` /
-``crop_imager`` / ``orig_warper`` / ``crop_warper`` (always ``normalize_t=True``, :98-100).  Visualisation is outside the
-accelerated path; the driver's evaluation calls ``calculate_flow_error`` / ``save_flow_error_as_text``
+``crop_imager`` / ``orig_warper`` / ``crop_warper`` (always ``normalize_t=True``, :98-100).  The driver's picture calls
+(``visualize_original_sequential`` / ``visualize_flows`` / ``visualize_pred_sequential`` / ``visualize_gt_sequential``, :208-287) are
+composed over ``visualize_module`` exactly as the reference composes them: ``visualizer.Visualizer`` of this package renders on the
+GPU, the reference's own ``Visualizer`` works there too.  The driver's evaluation calls ``calculate_flow_error`` / ``save_flow_error_as_text``
 (:289-353) are here, on the GPU metrics of ``flow_error``.  ``preprocess`` runs the reference's
 filter pipeline (src/solver/base.py:108-139): CROP to the region of interest, then the filters ``solver.filter.filters``
 lists ("BAF", "HOT": ``event_filters.EventFilter`` on the GPU, the BAF time map carried from window to window when
@@ -18,7 +20,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .. import costs, event_filters, event_image_converter, flow_error, warp
+from .. import _hip, costs, event_filters, event_image_converter, flow_error, warp
 from .._staging import to_gpu
 
 logger = logging.getLogger(__name__)
@@ -52,6 +54,8 @@ class SolverBase(object):
         self.roi = self._roi_from_config(self.slv_config)
         self.filter_set = self._filter_from_config(self.orig_image_shape, self.slv_config)
         self.previous_best = None
+        self.iwe_visualize_max_scale = self.slv_config.get("max_scale", 50)
+        self._viz_imager = event_image_converter.EventImageConverter(self.orig_image_shape)   # (the reference's orig_imager: no padding)
 
     @staticmethod
     def _filter_from_config(image_shape, cfg: dict) -> Optional[event_filters.EventFilter]:
@@ -89,6 +93,52 @@ class SolverBase(object):
 
     def estimate(self, events, *args, **kwargs) -> np.ndarray:
         raise NotImplementedError
+
+    # ------------------------------------------------------------------ pictures (src/solver/base.py:154-287)
+    def create_clipped_image(self, events, max_scale=50):
+        """255 - uint8(clip(max_scale IWE, 0, 255)) of the un-padded bilinear vote of ``events`` [n, 4], ``outer_padding`` pixels
+        cropped from every side -> uint8 numpy [H - 2 pad, W - 2 pad] (:154-174; rendered by csrc/visualize.hip)."""
+        from ..visualizer import clipped_iwe_picture
+
+        assert events.shape[-1] <= 4, "this function is for events"
+        ev = to_gpu(events, dtype=torch.float64)
+        iwe = self._viz_imager._accumulate(ev, 1.0, _hip.SPLAT_BILINEAR, event_image_converter.EPS_NUMPY, torch.float64)
+        return clipped_iwe_picture(iwe.reshape(1, *self.orig_image_shape), max_scale, self.pad)[0].cpu().numpy()
+
+    def _listed(self, prefix: str) -> None:
+        if prefix not in self.sequential_video_list:
+            self.sequential_video_list.append(prefix)
+
+    def visualize_original_sequential(self, orig_events, filter_events):
+        """The event picture of ``orig_events`` ("original") and the clipped IWE of ``filter_events`` ("original_filter"), :208-227."""
+        self.visualizer.visualize_event(orig_events, file_prefix="original")
+        self._listed("original")
+        clipped_iwe = self.create_clipped_image(filter_events, max_scale=self.iwe_visualize_max_scale)
+        self.visualizer.visualize_image(clipped_iwe, file_prefix="original_filter")
+        self._listed("original_filter")
+
+    def visualize_pred_sequential(self, events, flow):
+        """"pred_flow" (+ its .npy), "pred_flow_poisson" and "pred_masked" of the prediction ``flow`` [2, H, W], :229-250."""
+        self.visualizer.visualize_optical_flow(flow[0], flow[1], visualize_color_wheel=False, file_prefix="pred_flow", save_flow=True)
+        self._listed("pred_flow")
+        self.visualizer.visualize_poisson_integration(flow, file_prefix="pred_flow_poisson")
+        self._listed("pred_flow_poisson")
+        self.visualizer.visualize_optical_flow_on_event_mask(flow, events, file_prefix="pred_masked", mask_color="black", mask_morph=True)
+        self._listed("pred_masked")
+
+    def visualize_gt_sequential(self, events, gt_flow):
+        """"gt_flow", "gt_flow_poisson" and "gt_masked" of the reference flow ``gt_flow`` [2, H, W], :252-273."""
+        self.visualizer.visualize_optical_flow(gt_flow[0], gt_flow[1], visualize_color_wheel=False, file_prefix="gt_flow", save_flow=False)
+        self._listed("gt_flow")
+        self.visualizer.visualize_poisson_integration(gt_flow, file_prefix="gt_flow_poisson")
+        self._listed("gt_flow_poisson")
+        self.visualizer.visualize_optical_flow_on_event_mask(gt_flow, events, file_prefix="gt_masked", mask_color="black", mask_morph=True)
+        self._listed("gt_masked")
+
+    def visualize_flows(self, pred_flow, gt_flow) -> None:
+        """"flow_comparison_pred" and "flow_comparison_gt" on one scale (+ the colour wheel), :276-287."""
+        self.visualizer.visualize_optical_flow_pred_and_gt(pred_flow, gt_flow, pred_file_prefix="flow_comparison_pred",
+                                                           gt_file_prefix="flow_comparison_gt")
 
     def calculate_flow_error(self, pred_disp, gt_flow, timescale: float = 1.0, events=None, roi: Optional[dict] = None) -> dict:
         """Flow error of one window (src/solver/base.py:289-318): ``flow_error.calculate_flow_error_numpy(gt_flow[None],

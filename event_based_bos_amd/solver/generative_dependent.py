@@ -24,7 +24,7 @@ back once, then the initial values are drawn window by window.  Per window: ``hi
 ``estimate_indices_batch``.  ``estimate`` is a batch of one window.  The host driver is ``GenerativeMixin``'s (generative.py);
 this module adds the solver's event staging and scratch size, its steps after the prepare pass, and its record fields.
 
-Not ported: the visualisation calls.  Raising ``NotImplementedError``: the angle model, ``sobel_ksize: 5``, optimizers other than
+Not ported: the solver's own loss-video calls (the driver's pictures: ``SolverBase.visualize_*``).  Raising ``NotImplementedError``: the angle model, ``sobel_ksize: 5``, optimizers other than
 Adam, cost terms other than diff_norm / image_gradient / flow_norm_pxy.  ``model_image: black`` is a ``ValueError`` (the reference
 never sets its frame).
 """

@@ -1250,6 +1250,68 @@ int ebos_window_ingest_raw_batch(const int16_t* col, const int16_t* row, const v
                                  int rm_y0, int rm_y1, double* pol_out, uint8_t* mask_out, int64_t* count_out, double* tmin_out,
                                  double* tmax_out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * The visualizer's pictures for B windows per launch (csrc/visualize.hip; reference: src/visualizer.py, src/solver/base.py:154-287).
+ * Every plane is a device array of H W contiguous doubles (uint8 for masks) per window; window b of a plane starts sb elements
+ * (mask_sb bytes) after window b - 1, so the two components of a [B, 2, H, W] flow are x = flow, y = flow + H W, sb = 2 H W.
+ * Outputs are contiguous.  B <= 65535.  No floating-point atomics, no scratch: every run gives the same bits, and a window's
+ * bits do not depend on the batch it is in.  The 8-bit HSV -> RGB step restates OpenCV's cvtColor(COLOR_HSV2RGB) on uint8
+ * (hue 0 - 180, float32 sector arithmetic, round half to even) as tests/_viz_ref.py does; it is not checked against OpenCV.
+ *
+ * ebos_viz_reduce_f64: out[b, k] (device double [B, n_fields], overwritten) = the scalar field k's picture is normalised by.
+ *   EBOS_VIZ_FLOW       max over pixels of sqrt(x^2 + y^2)^ord, NaN and +-inf components counted as 0; with a mask both
+ *                       components are multiplied by (mask != 0) first (max_color_on_mask).
+ *   EBOS_VIZ_FLOW_PAIR  the larger of that for (x, y) and for (x2, y2): the shared scale of visualize_optical_flow_pred_and_gt.
+ *   EBOS_VIZ_SCALAR     max |x| (standardize_image_center); NaN entries are passed over.
+ *   ord 0.5 is sqrt(sqrt(.)), ord 1 is sqrt(.), anything else pow.  fields: a HOST array of 1 .. EBOS_VIZ_MAX_FIELDS
+ *   descriptors (it travels as a launch argument).  One memset node and one launch.
+ * ebos_viz_flow_rgb_u8: color_optical_flow.  H = uint8((atan2(y, x) + pi) 180 / pi / 2), S = 255, V = uint8(255 mag / scale[b
+ *   scale_stride]), HSV -> RGB; out uint8 [B, H, W, 3].  The casts truncate (NaN -> 0).  scale <= 0 (an all-zero flow) gives
+ *   black.  mask (or NULL) with mask_mode: EBOS_VIZ_MASK_MULTIPLY multiplies the flow by (mask != 0) before anything else;
+ *   EBOS_VIZ_MASK_BLACK / _WHITE paints the pixels with mask == 0 (Image.composite of visualize_optical_flow_on_event_mask).
+ * ebos_viz_hsv2rgb_u8: the colour stage alone on n interleaved uint8 HSV pixels -> n RGB pixels.
+ * ebos_viz_mask_close_u8: cv2.morphologyEx(mask != 0, MORPH_CLOSE, 3 x 3 MORPH_CROSS) with the default border (outside pixels
+ *   never win the dilation and never lose the erosion); out uint8 [B, H, W] of 0 / 1, not aliasing mask.
+ * ebos_viz_gray_u8: out uint8 [B, H - 2 pad, W - 2 pad], the inside of the H x W planes.
+ *   EBOS_VIZ_GRAY_EVENT   clip(20 (a - b) + max_scale, 0, 255): a, b the positive and negative event counts, max_scale the
+ *                         background colour, 127 in the reference (visualize_event)
+ *   EBOS_VIZ_GRAY_IWE     255 - uint8(clip(max_scale (a + b), 0, 255)), b may be NULL (create_clipped_image; pad = outer_padding)
+ *   EBOS_VIZ_GRAY_CENTER  uint8(a / scale[b scale_stride] 127 + 128); scale <= 0 (an all-zero field) gives 128
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_VIZ_MAX_FIELDS 8
+#define EBOS_VIZ_FLOW 0
+#define EBOS_VIZ_FLOW_PAIR 1
+#define EBOS_VIZ_SCALAR 2
+#define EBOS_VIZ_MASK_MULTIPLY 1
+#define EBOS_VIZ_MASK_BLACK 2
+#define EBOS_VIZ_MASK_WHITE 4
+#define EBOS_VIZ_GRAY_EVENT 0
+#define EBOS_VIZ_GRAY_IWE 1
+#define EBOS_VIZ_GRAY_CENTER 2
+
+typedef struct ebos_viz_field {
+  const double* x;       /* first component, or the scalar field */
+  const double* y;
+  const double* x2;      /* EBOS_VIZ_FLOW_PAIR: the second flow */
+  const double* y2;
+  const uint8_t* mask;   /* EBOS_VIZ_FLOW: optional */
+  int64_t sb;            /* window stride of x, y (elements) */
+  int64_t sb2;           /* ... of x2, y2 */
+  int64_t mask_sb;
+  int kind;
+  int reserved;
+} ebos_viz_field;
+
+int ebos_viz_reduce_f64(int B, int H, int W, const ebos_viz_field* fields, int n_fields, double ord, double* out,
+                        ebos_stream_t stream);
+int ebos_viz_flow_rgb_u8(int B, int H, int W, const double* x, const double* y, int64_t sb, const double* scale,
+                         int64_t scale_stride, const uint8_t* mask, int64_t mask_sb, int mask_mode, double ord, uint8_t* out,
+                         ebos_stream_t stream);
+int ebos_viz_hsv2rgb_u8(int64_t n, const uint8_t* hsv, uint8_t* rgb, ebos_stream_t stream);
+int ebos_viz_mask_close_u8(int B, int H, int W, const uint8_t* mask, int64_t mask_sb, uint8_t* out, ebos_stream_t stream);
+int ebos_viz_gray_u8(int mode, int B, int H, int W, int pad, const double* a, int64_t a_sb, const double* b, int64_t b_sb,
+                     double max_scale, const double* scale, int64_t scale_stride, uint8_t* out, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
     python tools/run_eval.py --config_file tests/golden/config_hot_plate1.json --events recording.npz --frames frames/ \
         --triggers trigger_events.txt [--homography homography.txt] [--max-batch 8] [--height H --width W] [--out out/]
-    python tools/run_eval.py --synthetic [--n-iter 60]
+    python tools/run_eval.py --synthetic [--n-iter 60] [--pictures]
 
 ``--config_file`` is a JSON (or, where PyYAML is installed, YAML) file with the reference's keys; a file with an "input" section
 (tests/golden/config_hot_plate1.json) is read from there and propagated.  ``--synthetic`` builds a small recording in a temporary
@@ -62,6 +62,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--out", default=None, help="directory of the three text files (default: a temporary directory)")
     ap.add_argument("--poisson", action="store_true")
+    ap.add_argument("--pictures", action="store_true", help="also write the driver's ten pictures per step under --out (needs PIL)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n-iter", type=int, default=60, help="--synthetic: Adam iterations")
     args = ap.parse_args(argv)
@@ -89,8 +90,11 @@ def main(argv=None) -> int:
                                  (cfg["data"]["height"], cfg["data"]["width"]) if args.homography else None)
     cfg = ebos.utils.propagate_config(cfg)
     solv = build_solver(ebos, cfg)
-    result = RecordingEvaluator(cfg, events, frames, solv, save_dir=out).run(max_batch=args.max_batch, poisson=args.poisson)
+    result = RecordingEvaluator(cfg, events, frames, solv, save_dir=out).run(max_batch=args.max_batch, poisson=args.poisson,
+                                                                              pictures=args.pictures)
     print(f"{len(result.steps)} steps evaluated, {len(result.skipped)} skipped; text files in {out}")
+    if args.pictures:
+        print(f"  {sum(f.endswith('.png') for f in os.listdir(out))} pictures and {sum(f.endswith('.npy') for f in os.listdir(out))} flows written")
     for name, stats in result.statistics.items():
         for k, s in stats.items():
             print(f"  {name:13s} {k:5s} mean {s['mean']:.6g}  std {s['std']:.6g}  min {s['min']:.6g}  max {s['max']:.6g}  n {s['n_data']}")
