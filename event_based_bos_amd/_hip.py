@@ -251,6 +251,12 @@ SIGNATURES = {
     "ebos_viz_hsv2rgb_u8": (_I, [_L, _P, _P, _P]),
     "ebos_viz_mask_close_u8": (_I, [_I, _I, _I, _P, _L, _P, _P]),
     "ebos_viz_gray_u8": (_I, [_I, _I, _I, _I, _I, _P, _L, _P, _L, _D, _P, _L, _P, _P]),
+    "ebos_event_voxel_f64": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P]),
+    "ebos_event_voxel_normalize_scratch_bytes": (_Z, [_I]),
+    "ebos_event_voxel_normalize_f64": (_I, [_I, _L, _P, _P, _Z, _P]),
+    "ebos_event_volume_f64": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
+    "ebos_event_volume_f32": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
+    "ebos_event_voxel_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 9 + [_P] * 4),
 }
 
 
@@ -265,6 +271,7 @@ VIZ_MAX_FIELDS = 8
 VIZ_FLOW, VIZ_FLOW_PAIR, VIZ_SCALAR = 0, 1, 2
 VIZ_MASK_MULTIPLY, VIZ_MASK_BLACK, VIZ_MASK_WHITE = 1, 2, 4
 VIZ_GRAY_EVENT, VIZ_GRAY_IWE, VIZ_GRAY_CENTER = 0, 1, 2
+EVENT_VOLUME_OUT_OF_BOUNDS, EVENT_VOLUME_DEGENERATE_SPAN = 1, 2   # flags ebos_event_volume_* leaves in status[0]
 
 
 class EventSource(C.Structure):

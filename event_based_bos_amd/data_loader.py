@@ -34,6 +34,7 @@ import torch
 
 from . import _hip
 from .event_plan import EventPlan
+from .event_voxel import event_voxel_batch
 
 logger = logging.getLogger(__name__)
 
@@ -164,6 +165,29 @@ class RawEventStore(object):
         col, row, t, pol = self.load_raw(lo, hi, device)
         return EventPlan.build_raw_batch(col, row, t, pol, [(a - lo, b - lo) for a, b in windows], image_size, direction, normalize_t,
                                          tile, self.TICKS_PER_SECOND, deferred=deferred)
+
+    def voxels(self, ranges, n_bins: int, image_size: Tuple[int, int], roi=None, signed: bool = True, normalize: bool = False,
+               device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+        """The event voxel grids (``create_event_voxel``) of several (start_index, end_index) windows in one set of launches:
+        ``event_voxel.event_voxel_batch`` with the sensor column as x and the row as y, so a plane of a grid is an image.  As in
+        ``plans``, the stretch of the recording the windows cover is uploaded once.  Returns (grids float64 [B, n_bins, H, W] -- the
+        ``roi`` crop with one --, valid int32 [B]); unlike ``load_event``, an empty window is allowed: its grid is zero, its
+        ``valid`` 0."""
+        windows = [(int(a), int(b)) for a, b in ranges]
+        n = len(self)
+        for a, b in windows:
+            if not 0 <= a <= n or not 0 <= b <= n:
+                raise IndexError(f"Specified {a} to {b} index, but there are only {n} events.")
+        windows = [(a, max(a, b)) for a, b in windows]
+        if not windows:
+            raise ValueError("ranges holds no window")
+        lo, hi = min(a for a, _ in windows), max(b for _, b in windows)
+        if hi > lo:
+            cols = self.load_raw(lo, hi, device)
+        else:   # nothing but empty windows: no event to upload
+            cols = tuple(torch.empty(0, dtype=d, device=device) for d in (torch.int16, torch.int16, torch.int32, torch.uint8))
+        return event_voxel_batch(cols, [(a - lo, b - lo) for a, b in windows], n_bins, image_size, roi, signed, normalize,
+                                 self.TICKS_PER_SECOND)
 
     # ------------------------------------------------------------------ index <-> time
     def _times(self) -> np.ndarray:

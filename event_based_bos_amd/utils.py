@@ -7,7 +7,8 @@ over the whole event array per patch, only to count -- is replaced by ``EventPla
 The reference's event filters are re-exported from ``event_filters`` under their names, as src/utils/__init__.py:2 does, and
 its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does, and its Poisson integration and
 ``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does, and ``bos_optical_flow`` and
-``pad_to_same_resolution`` from ``frame_flow``, as src/utils/__init__.py:34-42 does.
+``pad_to_same_resolution`` from ``frame_flow``, as src/utils/__init__.py:34-42 does, and the two time-resolved event representations,
+``create_event_voxel`` and ``generate_discretized_event_volume``, from ``event_voxel``, as src/utils/__init__.py:4,7 does.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -69,3 +70,4 @@ from .flow_error import calculate_flow_error_numpy, calculate_flow_error_tensor,
 from .poisson import (poisson_image, poisson_reconstruct, poisson_reconstruct_batch,  # noqa: E402,F401
                       standardize_image_center)
 from .frame_flow import bos_optical_flow, pad_to_same_resolution  # noqa: E402,F401
+from .event_voxel import create_event_voxel, generate_discretized_event_volume  # noqa: E402,F401

@@ -1312,6 +1312,54 @@ int ebos_viz_mask_close_u8(int B, int H, int W, const uint8_t* mask, int64_t mas
 int ebos_viz_gray_u8(int mode, int B, int H, int W, int pad, const double* a, int64_t a_sb, const double* b, int64_t b_sb,
                      double max_scale, const double* scale, int64_t scale_stride, uint8_t* out, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Time-resolved event representations (csrc/event_voxel.hip; reference: src/utils/event_utils.py:291-440).  All buffers are device
+ * memory, outputs are contiguous and overwritten.  Every addend of a voxel is the reference's addend bit for bit (no fused
+ * multiply-add, the reference's order of operations); the order in which the float atomics add them is free.  Taps whose weight
+ * is exactly zero are skipped.
+ *
+ * ebos_event_voxel_f64: create_event_voxel.  x (the width direction), y, pol, t: n doubles each; out double [C, H, W].
+ *   t_norm = (C - 1) (t - t[0]) / (t[n - 1] - t[0]); x0, y0, t0 truncated towards zero; the eight corners {x0, x0 + 1} x {y0, y0 + 1}
+ *   x {t0, t0 + 1} inside the grid get ((pol (1 - |xl - x|)) (1 - |yl - y|)) (1 - |tl - t_norm|).  status (device int): 1, or 0
+ *   when t[n - 1] - t[0] is zero or not finite -- the grid is then all zero (the reference divides by zero there).  One memset
+ *   node and one launch.
+ * ebos_event_voxel_normalize_f64: B grids of n voxels each, in place: the non-zero voxels v become (v - mean) / std with their
+ *   mean and unbiased std, v - mean when std is not > 0; a grid without a non-zero voxel is left alone.  scratch:
+ *   ebos_event_voxel_normalize_scratch_bytes(B) bytes (the partial moments), 8-byte aligned.  One reduction launch, one map
+ *   launch, nothing read back.
+ * ebos_event_volume_f64 / _f32: generate_discretized_event_volume.  events [n, 4] = (x = row, y = column, t, p) contiguous;
+ *   out [T, X, Y] in the events' type; nb = T / 2, t_scaled = (t - tmin) ((1 / (tmax - tmin)) (nb - 1)) (torch's tensor
+ *   __rdiv__), tmin / tmax reduced on the device; bin floor(ts + 1e-8) gets floor(ts) + 1 - ts, bin ceil(ts - 1e-8) gets
+ *   ts - floor(ts + 1e-8), + nb for p < 0, pixel x Y + y of the truncated coordinates.  status: device int64 [4]; status[0] holds
+ *   the flags below afterwards (0: fine), status[1 .. 2] are the keys of the time range.  A vote outside the volume (what the
+ *   reference asserts against) is not made and sets EBOS_EVENT_VOLUME_OUT_OF_BOUNDS; tmax == tmin leaves the volume zero and
+ *   sets EBOS_EVENT_VOLUME_DEGENERATE_SPAN.  T >= 2.  Three memset nodes and two launches.
+ * ebos_event_voxel_raw_batch: the voxel grids of B windows of a recording from its raw columns (col / row int16, t int32 or,
+ *   t_is_64, int64 ticks, pol uint8: n_total events, RawEventStore.load_raw), x = col, y = row, t = ticks / ticks_per_second in
+ *   float64, pol = +-1 (signed_pol) or 0 / 1.  ranges: device int64 [B, 2], window b = events [begin, end), clamped to
+ *   [0, n_total]; they may overlap, be empty and come in any order; max_len: an upper bound of end - begin known on the host (it
+ *   sizes the grid).  has_roi: only events in rows [xmin, xmax) x columns [ymin, ymax) are kept, the grid is the crop (H = xmax -
+ *   xmin, W = ymax - ymin) and the coordinates are shifted by its origin -- crop_event first, then create_event_voxel.  A window's
+ *   time bounds are those of its first and last kept event, read from the time-sorted column.  out double [B, C, H, W];
+ *   valid int [B]: 0 and an all-zero grid for a window that keeps fewer than two events or spans no time; bounds int64 [B, 2]:
+ *   the indices of the first and last kept event (-1, -1 where valid is 0).  One memset node and two launches, whatever B is.
+ *   B <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_VOXEL_NORM_PARTIALS 256
+#define EBOS_EVENT_VOLUME_OUT_OF_BOUNDS 1
+#define EBOS_EVENT_VOLUME_DEGENERATE_SPAN 2
+
+int ebos_event_voxel_f64(const double* x, const double* y, const double* pol, const double* t, int64_t n, int C, int H, int W,
+                         double* out, int* status, ebos_stream_t stream);
+size_t ebos_event_voxel_normalize_scratch_bytes(int B);
+int ebos_event_voxel_normalize_f64(int B, int64_t n, double* grid, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_event_volume_f64(const double* events, int64_t n, int T, int X, int Y, double* out, int64_t* status, ebos_stream_t stream);
+int ebos_event_volume_f32(const float* events, int64_t n, int T, int X, int Y, float* out, int64_t* status, ebos_stream_t stream);
+int ebos_event_voxel_raw_batch(const int16_t* col, const int16_t* row, const void* t, int t_is_64, const uint8_t* pol, int64_t n_total,
+                               double ticks_per_second, const int64_t* ranges, int B, int64_t max_len, int C, int H, int W,
+                               int has_roi, int xmin, int xmax, int ymin, int ymax, int signed_pol, double* out, int* valid,
+                               int64_t* bounds, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,220 @@
+"""GPU checks of the event voxel kernels (csrc/event_voxel.hip) against tests/_voxel_ref.py, the numpy restatement that
+tests/test_voxel.py pins to the reference's own arrays.
+
+The kernels compute every addend of a voxel as the reference does (fp contract off, the reference's order of operations), so the
+addends are bit-equal and only their order of summation differs: per voxel |gpu - ref| <= 2 k u sum|w| (k addends, u = 2^-53, or
+2^-24 for the float32 volume), and a voxel nothing votes into is exactly 0.  All cases are a 12 x 16 sensor with about 2000 events
+(eight workgroups of events, four partials in the normaliser); nothing here depends on a larger size -- the indices are 64-bit
+throughout, and a grid beyond 2^31 voxels would need 16 GiB.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import _voxel_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+G = np.load(os.path.join(HERE, "golden", "golden_voxel.npz"))
+SHAPE = tuple(int(v) for v in G["shape"])
+VOL = tuple(int(v) for v in G["vol_size"])
+C, H, W = SHAPE
+ROI = (2, 10, 3, 13)
+N_OUTSIDE = 300          # leading events of the recording that lie outside ROI: more than one workgroup's scan step
+_cache = {}
+
+
+def case(c):
+    return tuple(G[f"{c}_{k}"] for k in ("x", "y", "pol", "t"))
+
+
+def ref_case(c):
+    if c not in _cache:
+        _cache[c] = R.create_event_voxel(*case(c), SHAPE)
+    return _cache[c]
+
+
+def within_bound(got, ref, u=2.0 ** -53):
+    want, k, sabs = ref
+    got = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else got
+    assert got.shape == want.shape and got.dtype == want.dtype
+    err, bound = np.abs(got.astype(np.float64) - want.astype(np.float64)), R.error_bound(k, sabs, u)
+    worst = (err / np.where(bound > 0, bound, 1.0)).max()
+    print(f"max |gpu - ref| {err.max():.3e}, worst share of the bound {worst:.3f}, {int((k == 0).sum())} voxels without a vote")
+    assert (got[k == 0] == 0).all()
+    assert (err <= bound).all(), (float(err.max()), int((err > bound).sum()))
+
+
+def recording():
+    """Raw columns of 2000 events on the 12 x 16 sensor, the first N_OUTSIDE of them in row 0 (outside ROI), as a store."""
+    if "store" not in _cache:
+        from event_based_bos_amd import RawEventStore
+
+        rs = np.random.RandomState(4201)
+        n = 2000
+        cols = {"x": rs.randint(0, W, n).astype(np.int16), "y": rs.randint(0, H, n).astype(np.int16),
+                "t": (1_000_000 + np.cumsum(rs.randint(1, 20, n))).astype(np.int32), "p": rs.randint(0, 2, n).astype(bool)}
+        cols["y"][:N_OUTSIDE] = 0
+        _cache["store"] = RawEventStore(cols)
+    return _cache["store"]
+
+
+@pytest.mark.parametrize("c", ["int", "frac", "pos"])
+def test_voxel_grid_matches_the_restatement(c):
+    from event_based_bos_amd.utils import create_event_voxel
+
+    x, y, pol, t = case(c)
+    got = create_event_voxel(x, y, pol, t, SHAPE)
+    assert isinstance(got, np.ndarray)
+    within_bound(got, ref_case(c))
+    dev = create_event_voxel(*(torch.from_numpy(a).cuda() for a in (x, y, pol, t)), SHAPE)
+    assert dev.is_cuda and dev.dtype == torch.float64
+    within_bound(dev, ref_case(c))
+    if c == "int":   # CPU tensors come back as CPU tensors; float32 and integer columns are staged to float64
+        host = create_event_voxel(torch.from_numpy(x).float(), torch.from_numpy(y).long(), torch.from_numpy(pol).int(), torch.from_numpy(t), SHAPE)
+        assert not host.is_cuda and host.dtype == torch.float64
+        within_bound(host, ref_case(c))
+
+
+@pytest.mark.parametrize("c,u", [("vol", 2.0 ** -53), ("vol32", 2.0 ** -24)])
+def test_event_volume_matches_the_restatement(c, u):
+    from event_based_bos_amd.utils import generate_discretized_event_volume
+
+    ev = G[f"{c}_events"]
+    ref = R.generate_discretized_event_volume(ev, VOL)
+    got = generate_discretized_event_volume(ev, VOL)
+    assert isinstance(got, np.ndarray) and got.dtype == ev.dtype
+    within_bound(got, ref, u)
+    dev = generate_discretized_event_volume(torch.from_numpy(ev).cuda(), VOL)
+    assert dev.is_cuda and dev.dtype == torch.from_numpy(ev).dtype
+    within_bound(dev, ref, u)
+
+
+def test_normalised_grid():
+    from event_based_bos_amd import _hip, event_voxel as V
+
+    x, y, pol, t = (torch.from_numpy(a).cuda() for a in case("pos"))
+    assert set(G["pos_pol"]) == {1.0}                      # one polarity: nothing cancels, no voxel is left out
+    raw = V.create_event_voxel(x, y, pol, t, SHAPE)
+    own = raw.clone()
+    V._normalize_(own.unsqueeze(0), _hip.require_gpu())    # the normaliser on the GPU's own un-normalised grid
+    want = R.normalize_voxel(raw.cpu().numpy())
+    for name, got in (("normaliser alone", own), ("normalize=True", V.create_event_voxel(x, y, pol, t, SHAPE, normalize=True))):
+        got = got.cpu().numpy()
+        assert np.array_equal(got != 0, want != 0), name
+        err = np.linalg.norm(got - want) / np.linalg.norm(want)
+        print(f"{name}: rel-L2 {err:.3e}")
+        assert err <= 1e-12, name
+    # nothing non-zero: unchanged; one voxel (std NaN) and equal voxels (std 0): centred only; B grids, each on its own
+    grids = torch.zeros((4, 5, 12, 16), dtype=torch.float64, device="cuda")
+    grids[1, 4, 11, 15] = 5.0
+    grids[2, 0, 0, 0] = grids[2, 3, 2, 1] = 2.5
+    grids[3] = raw
+    V._normalize_(grids, _hip.require_gpu())
+    assert (grids[:3] == 0).all()
+    assert np.linalg.norm(grids[3].cpu().numpy() - want) / np.linalg.norm(want) <= 1e-12
+
+
+@pytest.mark.parametrize("t_dtype", [np.int32, np.int64])
+def test_batch_of_windows(t_dtype):
+    from event_based_bos_amd import RawEventStore, create_event_voxel
+
+    store = recording()
+    if t_dtype == np.int64:
+        store = RawEventStore({**store.event_data, "t": store.event_data["t"].astype(np.int64) + (1 << 33)})
+    ranges = [(800, 2000), (0, 1200), (500, 500), (700, 701)]        # two that overlap, out of order; one empty; a single event
+    grids, valid = store.voxels(ranges, C, (H, W))
+    assert grids.shape == (4, C, H, W) and grids.dtype == torch.float64 and grids.is_cuda
+    assert valid.tolist() == [1, 1, 0, 0]
+    assert (grids[2:] == 0).all()
+    for b, (i0, i1) in enumerate(ranges[:2]):
+        ev = store.load_event(i0, i1)
+        ref = R.voxel_of_events(ev, C, (H, W))
+        within_bound(grids[b], ref)
+        within_bound(create_event_voxel(ev[:, 1], ev[:, 0], 2.0 * ev[:, 3] - 1.0, ev[:, 2], SHAPE), ref)   # the single call on load_event
+    # the polarity itself as the weight (one sign: nothing cancels); every window normalised on its own
+    plain, _ = store.voxels(ranges, C, (H, W), signed=False)
+    within_bound(plain[1], R.voxel_of_events(store.load_event(0, 1200), C, (H, W), signed=False))
+    normed, ok = store.voxels(ranges, C, (H, W), signed=False, normalize=True)
+    assert ok.tolist() == [1, 1, 0, 0] and (normed[2:] == 0).all()
+    for b in (0, 1):
+        want = R.normalize_voxel(plain[b].cpu().numpy())
+        assert np.array_equal(normed[b].cpu().numpy() != 0, want != 0)
+        assert np.linalg.norm(normed[b].cpu().numpy() - want) / np.linalg.norm(want) <= 1e-12
+    # windows that share one timestamp span nothing
+    flat = RawEventStore({**store.event_data, "t": np.full(len(store), 7, dtype=t_dtype)})
+    g, v = flat.voxels([(0, 100)], C, (H, W))
+    assert v.tolist() == [0] and (g == 0).all()
+    g, v = store.voxels([(5, 5), (9, 3)], C, (H, W))                   # nothing but empty windows
+    assert v.tolist() == [0, 0] and (g == 0).all()
+
+
+def test_batch_with_a_region_of_interest():
+    from event_based_bos_amd.utils import create_event_voxel, crop_event
+
+    store = recording()
+    x0, x1, y0, y1 = ROI
+    # the first skips the N_OUTSIDE dropped events to find its first time; the second keeps nothing; the third keeps one event
+    one = next(i for i in range(N_OUTSIDE, 2000) if len(crop_event(store.load_event(i, i + 1), *ROI)) == 1)
+    ranges = [(0, 1200), (0, N_OUTSIDE), (one - 3 if one >= N_OUTSIDE + 3 else one, one + 1), (900, 2000)]
+    kept_third = len(crop_event(store.load_event(*ranges[2]), *ROI))
+    grids, valid = store.voxels(ranges, C, (H, W), roi={"xmin": x0, "xmax": x1, "ymin": y0, "ymax": y1})
+    assert grids.shape == (4, C, x1 - x0, y1 - y0)
+    assert valid.tolist() == [1, 0, int(kept_third >= 2), 1]
+    assert (grids[1] == 0).all()
+    for b in (0, 3):
+        ev = crop_event(store.load_event(*ranges[b]), *ROI)
+        assert 2 <= len(ev) < ranges[b][1] - ranges[b][0]
+        ref = R.voxel_of_events(ev, C, (x1 - x0, y1 - y0), origin=(x0, y0))
+        within_bound(grids[b], ref)
+        within_bound(create_event_voxel(ev[:, 1] - y0, ev[:, 0] - x0, 2.0 * ev[:, 3] - 1.0, ev[:, 2], (C, x1 - x0, y1 - y0)), ref)
+    if kept_third < 2:
+        assert (grids[2] == 0).all()
+
+
+def test_degenerate_time_span_raises():
+    from event_based_bos_amd.utils import create_event_voxel, generate_discretized_event_volume
+
+    x, y, pol, t = case("int")
+    with pytest.raises(ValueError, match="span no time"):
+        create_event_voxel(x, y, pol, np.full_like(t, 0.25), SHAPE)
+    with pytest.raises(ValueError, match="span no time"):
+        create_event_voxel(x[:1], y[:1], pol[:1], t[:1], SHAPE, normalize=True)
+    with pytest.raises(ValueError, match="span no time"):
+        create_event_voxel(*(torch.from_numpy(a).cuda() for a in (x, y, pol, np.full_like(t, np.nan))), SHAPE)
+    ev = G["vol_events"].copy()
+    ev[:, 2] = 0.5
+    with pytest.raises(ValueError, match="one timestamp"):
+        generate_discretized_event_volume(ev, VOL)
+    # the reference's bounds assertions
+    for col, value in ((0, H), (1, -1.0), (1, W)):
+        ev = G["vol_events"].copy()
+        ev[17, col] = value
+        with pytest.raises(ValueError, match="outside the volume"):
+            generate_discretized_event_volume(ev, VOL)
+
+
+def test_contention_on_one_address():
+    """20 events on one pixel, two bins: every vote of a plane lands on one address."""
+    from event_based_bos_amd.utils import create_event_voxel
+
+    rs = np.random.RandomState(4301)
+    n = 20
+    x, y = np.full(n, 7.0), np.full(n, 5.0)
+    pol = np.where(np.arange(n) % 3 == 0, -1.0, 1.0)
+    t = np.sort(rs.uniform(0.0, 1.0, n))
+    ref = R.create_event_voxel(x, y, pol, t, (2, H, W))
+    # (the last event sits on bin 1 exactly, so bin 0 takes n - 1 votes and bin 1 all n; the restatement also counts the
+    # zero-weight taps on the three neighbouring pixels, which add nothing)
+    assert ref[1][0, 5, 7] == n - 1 and ref[1][1, 5, 7] == n
+    assert np.argwhere(ref[0] != 0).tolist() == np.argwhere(ref[2] > 0).tolist() == [[0, 5, 7], [1, 5, 7]]
+    within_bound(create_event_voxel(x, y, pol, t, (2, H, W)), ref)
+    xf, yf = x + 0.37, y + 0.61                                # eight addresses, twenty votes each
+    ref = R.create_event_voxel(xf, yf, pol, t, (2, H, W))
+    assert sorted(set(ref[1].ravel())) == [0, n - 1, n] and (ref[1] > 0).sum() == 8
+    within_bound(create_event_voxel(xf, yf, pol, t, (2, H, W)), ref)
