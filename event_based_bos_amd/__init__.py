@@ -20,6 +20,7 @@ tub-rip/event_based_bos:
     evaluation           the reference driver's per-frame evaluation of a recording: the plan, the batched window ingest, the evaluator
     visualizer           the reference visualizer's pictures (colour-coded flow, event picture, density picture), batched
     event_voxel          the reference's event voxel grid and discretised event volume; the voxel grids of a batch of raw windows
+    flow_voxel           the reference's time-aware flow: upwind / Burgers / bilinear flow voxels of one flow or a batch, and their mean
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -34,6 +35,7 @@ from .frame_warp import validate_image, warp_perspective, warp_perspective_batch
 from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingEvaluator, plan_evaluation,  # noqa: F401
                          window_ingest_raw_batch)
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
-from . import costs, data_loader, evaluation, event_filters, event_voxel, flow_error, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
+from .flow_voxel import flow_voxel_batch  # noqa: F401
+from . import costs, data_loader, evaluation, event_filters, event_voxel, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

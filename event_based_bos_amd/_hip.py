@@ -257,6 +257,17 @@ SIGNATURES = {
     "ebos_event_volume_f64": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
     "ebos_event_volume_f32": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
     "ebos_event_voxel_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 9 + [_P] * 4),
+    "ebos_flow_voxel_halo_cap": (_I, []),
+    "ebos_flow_voxel_advect_f32": (_I, [_I] * 5 + [_P, _P, _I, _I, _D, _I, _I, _P]),
+    "ebos_flow_voxel_advect_f64": (_I, [_I] * 5 + [_P, _P, _I, _I, _D, _I, _I, _P]),
+    "ebos_flow_upwind_step_f32": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_upwind_step_f64": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_burgers_step_f32": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_burgers_step_f64": (_I, [_I, _I, _I, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_voxel_propagate_bilinear_f32": (_I, [_I] * 4 + [_P, _P, _I, _I, _D, _I, _D, _P]),
+    "ebos_flow_voxel_propagate_bilinear_f64": (_I, [_I] * 4 + [_P, _P, _I, _I, _D, _I, _D, _P]),
+    "ebos_flow_voxel_truncate_mean_f32": (_I, [_I, _I, _I, _P, _P, _P]),
+    "ebos_flow_voxel_truncate_mean_f64": (_I, [_I, _I, _I, _P, _P, _P]),
 }
 
 
@@ -272,6 +283,8 @@ VIZ_FLOW, VIZ_FLOW_PAIR, VIZ_SCALAR = 0, 1, 2
 VIZ_MASK_MULTIPLY, VIZ_MASK_BLACK, VIZ_MASK_WHITE = 1, 2, 4
 VIZ_GRAY_EVENT, VIZ_GRAY_IWE, VIZ_GRAY_CENTER = 0, 1, 2
 EVENT_VOLUME_OUT_OF_BOUNDS, EVENT_VOLUME_DEGENERATE_SPAN = 1, 2   # flags ebos_event_volume_* leaves in status[0]
+FLOW_UPWIND, FLOW_BURGERS, FLOW_SAME = 0, 1, 2
+FLOW_ROUTE_AUTO, FLOW_ROUTE_FUSED, FLOW_ROUTE_STEPS = 0, 1, 2
 
 
 class EventSource(C.Structure):

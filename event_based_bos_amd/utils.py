@@ -8,7 +8,8 @@ The reference's event filters are re-exported from ``event_filters`` under their
 its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does, and its Poisson integration and
 ``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does, and ``bos_optical_flow`` and
 ``pad_to_same_resolution`` from ``frame_flow``, as src/utils/__init__.py:34-42 does, and the two time-resolved event representations,
-``create_event_voxel`` and ``generate_discretized_event_volume``, from ``event_voxel``, as src/utils/__init__.py:4,7 does.
+``create_event_voxel`` and ``generate_discretized_event_volume``, from ``event_voxel``, as src/utils/__init__.py:4,7 does, and the
+time-aware flow (``construct_dense_flow_voxel_*`` and the functions around it) from ``flow_voxel``, as src/utils/__init__.py:19-33 does.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -71,3 +72,7 @@ from .poisson import (poisson_image, poisson_reconstruct, poisson_reconstruct_ba
                       standardize_image_center)
 from .frame_flow import bos_optical_flow, pad_to_same_resolution  # noqa: E402,F401
 from .event_voxel import create_event_voxel, generate_discretized_event_volume  # noqa: E402,F401
+from .flow_voxel import (construct_dense_flow_voxel_numpy, construct_dense_flow_voxel_torch,  # noqa: E402,F401
+                         convert_flow_per_bin_to_flow_per_sec, flow_voxel_batch, inviscid_burger_flow_to_voxel_numpy,
+                         inviscid_burger_flow_to_voxel_torch, propagate_flow_to_voxel_numpy, propagate_flow_to_voxel_torch,
+                         truncate_voxel_flow_numpy, upwind_flow_to_voxel_numpy, upwind_flow_to_voxel_torch)

@@ -1360,6 +1360,58 @@ int ebos_event_voxel_raw_batch(const int16_t* col, const int16_t* row, const voi
                                int has_roi, int xmin, int xmax, int ymin, int ymax, int signed_pol, double* out, int* valid,
                                int64_t* bounds, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Time-aware flow (csrc/flow_voxel.hip; reference: src/utils/flow_utils.py:68-702): a dense flow at t0 becomes a flow per time
+ * bin.  All buffers are device memory and contiguous, outputs are overwritten and never alias inputs.  flow[.., 0, :, :] moves
+ * along the rows (H), flow[.., 1, :, :] along the columns.  Every operation is rounded on its own and in the reference's order
+ * (no fused multiply-add): the advection kernels reproduce the reference bit for bit; NaN propagates as through np.maximum.
+ *
+ * ebos_flow_upwind_step_* / ebos_flow_burgers_step_*: one step of upwind_flow_to_voxel / inviscid_burger_flow_to_voxel on
+ *   B flows [B, 2, H, W] -> out [B, 2, H, W].  dt != 0; a negative dt steps the negated flow and negates the result.  The upwind
+ *   step divides u_dx and u_dy by dx and v_dx and v_dy by dy, the Burgers step u_dy by dx and v_dx by dy, as the reference does.
+ *   One launch.  B <= 32767.
+ * ebos_flow_voxel_advect_*: construct_dense_flow_voxel for scheme EBOS_FLOW_UPWIND / _BURGERS / _SAME: flow [B, 2, H, W] ->
+ *   out [B, T, 2, H, W].  Bin t0_index is the input, bin t0_index - s is s steps with dt = -1 / T, bin t0_index + s is s steps
+ *   with +1 / T (dx = dy = 1); _SAME copies the input into every bin.  has_clamp: every stored value is min(max(v, -clamp),
+ *   clamp); the steps themselves run on unclamped values.  wrap_last (the reference's torch Burgers constructor, whose backward
+ *   loop runs one step too far and stores it in bin -1): when t0_index == T - 1 the chain takes t0_index + 1 backward steps and
+ *   the last one replaces bin T - 1; otherwise nothing changes, because the forward chain overwrites that bin.  route:
+ *   EBOS_FLOW_ROUTE_AUTO takes one launch for the whole voxel (a 32 x 32 tile with its halo in LDS, all steps there) when
+ *   neither direction needs more than ebos_flow_voxel_halo_cap() steps and one launch per step otherwise; _FUSED / _STEPS force
+ *   either (_FUSED beyond the cap is an error).  The two routes store identical bits.
+ * ebos_flow_voxel_propagate_bilinear_*: propagate_flow_to_voxel(.., "bilinear") for B flows and T time offsets: out [B, T, 2,
+ *   H, W], bin t with dt = (t - t_offset) / denominator in double when denominator > 0, else dt (T = 1 then serves the
+ *   stand-alone function).  Pixel (i, j) votes both flow components into cells (x1, y1), (x1 + 1, y1), (x1, y1 + 1), (x1 + 1,
+ *   y1 + 1) of (x, y) = (i + u dt, j + v dt), x1 = floor(x + 1e-8), with the weights (1 - fx)(1 - fy), (1 - fx) fy, fx (1 - fy),
+ *   fx fy in that order (the reference's order); a vote outside the image adds value * 0 to cell 0.  Float atomics: the addends
+ *   are the reference's, their order is free.  One memset node, one launch, one more launch with a clamp.  B * T <= 65535.
+ * ebos_flow_voxel_truncate_mean_*: truncate_voxel_flow(.., "mean"): voxel [T, 2, H, W] -> out double [2, H, W] =
+ *   sum_t(flow * mask) / (sum_t(mask) + 1e-6), mask = (u u + v v > 0), the bins added in index order.  One launch.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_FLOW_UPWIND 0
+#define EBOS_FLOW_BURGERS 1
+#define EBOS_FLOW_SAME 2
+#define EBOS_FLOW_ROUTE_AUTO 0
+#define EBOS_FLOW_ROUTE_FUSED 1
+#define EBOS_FLOW_ROUTE_STEPS 2
+#define EBOS_FLOW_VOXEL_HALO_CAP 8
+
+int ebos_flow_voxel_halo_cap(void);
+int ebos_flow_voxel_advect_f32(int scheme, int B, int T, int H, int W, const float* flow, float* out, int t0_index, int has_clamp,
+                               double clamp, int wrap_last, int route, ebos_stream_t stream);
+int ebos_flow_voxel_advect_f64(int scheme, int B, int T, int H, int W, const double* flow, double* out, int t0_index, int has_clamp,
+                               double clamp, int wrap_last, int route, ebos_stream_t stream);
+int ebos_flow_upwind_step_f32(int B, int H, int W, const float* flow, float* out, double dt, double dx, double dy, ebos_stream_t stream);
+int ebos_flow_upwind_step_f64(int B, int H, int W, const double* flow, double* out, double dt, double dx, double dy, ebos_stream_t stream);
+int ebos_flow_burgers_step_f32(int B, int H, int W, const float* flow, float* out, double dt, double dx, double dy, ebos_stream_t stream);
+int ebos_flow_burgers_step_f64(int B, int H, int W, const double* flow, double* out, double dt, double dx, double dy, ebos_stream_t stream);
+int ebos_flow_voxel_propagate_bilinear_f32(int B, int T, int H, int W, const float* flow, float* out, int t_offset, int denominator,
+                                           double dt, int has_clamp, double clamp, ebos_stream_t stream);
+int ebos_flow_voxel_propagate_bilinear_f64(int B, int T, int H, int W, const double* flow, double* out, int t_offset, int denominator,
+                                           double dt, int has_clamp, double clamp, ebos_stream_t stream);
+int ebos_flow_voxel_truncate_mean_f32(int T, int H, int W, const float* voxel, double* out, ebos_stream_t stream);
+int ebos_flow_voxel_truncate_mean_f64(int T, int H, int W, const double* voxel, double* out, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
