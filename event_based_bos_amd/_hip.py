@@ -268,6 +268,17 @@ SIGNATURES = {
     "ebos_flow_voxel_propagate_bilinear_f64": (_I, [_I] * 4 + [_P, _P, _I, _I, _D, _I, _D, _P]),
     "ebos_flow_voxel_truncate_mean_f32": (_I, [_I, _I, _I, _P, _P, _P]),
     "ebos_flow_voxel_truncate_mean_f64": (_I, [_I, _I, _I, _P, _P, _P]),
+    "ebos_flow_voxel_advect_adjoint_workspace": (_L, [_I] * 8),
+    "ebos_flow_upwind_step_adjoint_f32": (_I, [_I, _I, _I, _P, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_upwind_step_adjoint_f64": (_I, [_I, _I, _I, _P, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_burgers_step_adjoint_f32": (_I, [_I, _I, _I, _P, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_burgers_step_adjoint_f64": (_I, [_I, _I, _I, _P, _P, _P, _D, _D, _D, _P]),
+    "ebos_flow_voxel_advect_adjoint_f32": (_I, [_I] * 5 + [_P, _P, _P, _P, _I, _I, _D, _I, _I, _P, _P]),
+    "ebos_flow_voxel_advect_adjoint_f64": (_I, [_I] * 5 + [_P, _P, _P, _P, _I, _I, _D, _I, _I, _P, _P]),
+    "ebos_flow_voxel_propagate_bilinear_adjoint_f32": (_I, [_I] * 4 + [_P, _P, _P, _P, _I, _I, _D, _I, _D, _P]),
+    "ebos_flow_voxel_propagate_bilinear_adjoint_f64": (_I, [_I] * 4 + [_P, _P, _P, _P, _I, _I, _D, _I, _D, _P]),
+    "ebos_flow_voxel_clamp_f32": (_I, [_L, _P, _P, _D, _P]),
+    "ebos_flow_voxel_clamp_f64": (_I, [_L, _P, _P, _D, _P]),
 }
 
 

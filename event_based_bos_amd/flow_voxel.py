@@ -14,6 +14,13 @@ expressions in its order with every operation rounded on its own, so a step and 
 float32 and float64; the bilinear votes are the reference's addends, summed by float atomics in a free order.  numpy in, numpy out;
 a tensor comes back on its device (a CUDA tensor without any host synchronisation).
 
+``flow_voxel_batch`` and the ``_torch`` functions are differentiable with respect to the flow, as the reference's torch expressions are
+(kernels: csrc/flow_voxel_grad.hip): a flow that requires grad, with grad mode on, gives a result with a ``grad_fn`` whose backward is
+the hand-written adjoint -- torch's rules, half the gradient on each side of a tie of ``maximum`` / ``minimum``, none through ``sign``
+and ``floor``, the clamp's bounds included -- gathered without atomics, so two runs give the same bits.  With a clamp the unclamped
+voxel is kept for the backward (the steps run on unclamped values).  ``out=`` cannot be combined with such a flow (``ValueError``);
+a second derivative raises.  Any other input takes the plain path and its result is what it was.
+
 Reference kinks, each either kept or replaced:
 
 kept
@@ -120,8 +127,18 @@ def flow_voxel_batch(flows: torch.Tensor, time_bin: int, scheme: str = "upwind",
         raise ValueError("flows must be on the GPU")
     if clamp is not None and math.isnan(float(clamp)):
         raise ValueError("clamp must be a number")
-    suffix = _hip.suffix(flows.dtype)
-    lib = _hip.require_gpu()
+    _hip.suffix(flows.dtype)
+    if B * T > 65535 and scheme == "bilinear":
+        raise ValueError(f"{B} flows x {T} bins: at most 65535 bins per call")
+    if B > 32767 and scheme != "bilinear":
+        raise ValueError(f"{B} flows: at most 32767 per call")
+    wrap = bool(torch_burgers_wrap) and scheme == "burgers"
+    if flows.requires_grad and torch.is_grad_enabled():
+        if out is not None:
+            raise ValueError("out= cannot be filled for flows that require grad: the voxel has to be a new tensor of the graph")
+        if scheme == "bilinear":
+            return _BilinearVoxel.apply(flows, T, t0, T, 0.0, clamp)
+        return _AdvectVoxel.apply(flows, T, scheme, t0, clamp, wrap)
     dev = flows.device
     src = flows.detach().contiguous()
     with _hip.on_device(dev):
@@ -132,19 +149,135 @@ def flow_voxel_batch(flows: torch.Tensor, time_bin: int, scheme: str = "upwind",
         lo, hi = src.data_ptr(), src.data_ptr() + src.numel() * src.element_size()
         if out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * out.element_size():
             raise ValueError("out must not overlap the flows' memory: the bins are written while the flows are still read")
-        has_clamp, c = int(clamp is not None), float(clamp if clamp is not None else 0.0)
         if scheme == "bilinear":
-            if B * T > 65535:
-                raise ValueError(f"{B} flows x {T} bins: at most 65535 bins per call")
-            check(getattr(lib, "ebos_flow_voxel_propagate_bilinear_" + suffix)(B, T, H, W, ptr(src), ptr(out), t0, T, 0.0,
-                                                                               has_clamp, c, stream_ptr(dev)), "ebos_flow_voxel_propagate_bilinear")
+            _launch_bilinear(src, out, t0, T, 0.0, clamp)
         else:
-            if B > 32767:
-                raise ValueError(f"{B} flows: at most 32767 per call")
-            route = _hip.FLOW_ROUTE_AUTO if _FORCE_ROUTE is None else _FORCE_ROUTE
-            wrap = int(bool(torch_burgers_wrap) and scheme == "burgers")
-            check(getattr(lib, "ebos_flow_voxel_advect_" + suffix)(_ADVECT[scheme], B, T, H, W, ptr(src), ptr(out), t0, has_clamp, c, wrap,
-                                                                   route, stream_ptr(dev)), "ebos_flow_voxel_advect")
+            _launch_advect(src, out, scheme, t0, clamp, wrap)
+    return out
+
+
+def _launch_advect(src: torch.Tensor, out: torch.Tensor, scheme: str, t0: int, clamp, wrap: bool) -> None:
+    """out [B, T, 2, H, W] = the voxel of src [B, 2, H, W], on the current device."""
+    B, T, _, H, W = (int(v) for v in out.shape)
+    route = _hip.FLOW_ROUTE_AUTO if _FORCE_ROUTE is None else _FORCE_ROUTE
+    check(getattr(_hip.require_gpu(), "ebos_flow_voxel_advect_" + _hip.suffix(src.dtype))(
+        _ADVECT[scheme], B, T, H, W, ptr(src), ptr(out), t0, int(clamp is not None), float(clamp if clamp is not None else 0.0), int(wrap), route,
+        stream_ptr(src.device)), "ebos_flow_voxel_advect")
+
+
+def _launch_bilinear(src: torch.Tensor, out: torch.Tensor, t_offset: int, denominator: int, dt: float, clamp) -> None:
+    """out [B, T, 2, H, W]: bin t is src [B, 2, H, W] carried along itself for (t - t_offset) / denominator, or for dt with denominator 0."""
+    B, T, _, H, W = (int(v) for v in out.shape)
+    check(getattr(_hip.require_gpu(), "ebos_flow_voxel_propagate_bilinear_" + _hip.suffix(src.dtype))(
+        B, T, H, W, ptr(src), ptr(out), t_offset, denominator, float(dt), int(clamp is not None), float(clamp if clamp is not None else 0.0),
+        stream_ptr(src.device)), "ebos_flow_voxel_propagate_bilinear")
+
+
+def _clamped_copy(raw: torch.Tensor, clamp) -> torch.Tensor:
+    out = torch.empty_like(raw)
+    check(getattr(_hip.require_gpu(), "ebos_flow_voxel_clamp_" + _hip.suffix(raw.dtype))(raw.numel(), ptr(raw), ptr(out), float(clamp),
+                                                                                         stream_ptr(raw.device)), "ebos_flow_voxel_clamp")
+    return out
+
+
+# The backward with respect to the flow (csrc/flow_voxel_grad.hip).  The steps of a chain run on unclamped values and the clamp comes
+# last, so with a clamp the forward keeps the unclamped voxel -- the chain's intermediates, and what the clamp's mask is taken from --
+# and returns a clamped copy.  Double backward is not supported: once_differentiable raises on it.
+class _AdvectVoxel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, T, scheme, t0, clamp, wrap):
+        src = flows.detach().contiguous()
+        B, _, H, W = (int(v) for v in src.shape)
+        keep = scheme != "same"
+        with _hip.on_device(src.device):
+            out = torch.empty((B, T, 2, H, W), dtype=src.dtype, device=src.device)
+            _launch_advect(src, out, scheme, t0, None if keep else clamp, wrap)
+            raw = out if keep else None
+            if keep and clamp is not None:
+                out = _clamped_copy(raw, clamp)
+        ctx.save_for_backward(src, raw)
+        ctx.meta = (T, scheme, t0, clamp, wrap)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        src, raw = ctx.saved_tensors
+        T, scheme, t0, clamp, wrap = ctx.meta
+        lib = _hip.require_gpu()
+        B, _, H, W = (int(v) for v in src.shape)
+        g = g.contiguous()
+        route = _hip.FLOW_ROUTE_AUTO if _FORCE_ROUTE is None else _FORCE_ROUTE
+        with _hip.on_device(src.device):
+            d = torch.empty_like(src)
+            n = int(lib.ebos_flow_voxel_advect_adjoint_workspace(_ADVECT[scheme], B, T, H, W, t0, int(wrap), route))
+            if n < 0:
+                raise RuntimeError("ebos_flow_voxel_advect_adjoint_workspace: " + lib.ebos_last_error().decode("utf-8", "replace"))
+            ws = torch.empty(n, dtype=src.dtype, device=src.device) if n else None
+            check(getattr(lib, "ebos_flow_voxel_advect_adjoint_" + _hip.suffix(src.dtype))(
+                _ADVECT[scheme], B, T, H, W, ptr(src), ptr(raw), ptr(g), ptr(d), t0, int(clamp is not None),
+                float(clamp if clamp is not None else 0.0), int(wrap), route, ptr(ws), stream_ptr(src.device)), "ebos_flow_voxel_advect_adjoint")
+        return d, None, None, None, None, None
+
+
+class _BilinearVoxel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, T, t_offset, denominator, dt, clamp):
+        src = flows.detach().contiguous()
+        B, _, H, W = (int(v) for v in src.shape)
+        with _hip.on_device(src.device):
+            out = torch.empty((B, T, 2, H, W), dtype=src.dtype, device=src.device)
+            _launch_bilinear(src, out, t_offset, denominator, dt, None)
+            raw = out if clamp is not None else None
+            if clamp is not None:
+                out = _clamped_copy(raw, clamp)
+        ctx.save_for_backward(src, raw)
+        ctx.meta = (T, t_offset, denominator, dt, clamp)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        src, raw = ctx.saved_tensors
+        T, t_offset, denominator, dt, clamp = ctx.meta
+        B, _, H, W = (int(v) for v in src.shape)
+        g = g.contiguous()
+        with _hip.on_device(src.device):
+            d = torch.empty_like(src)
+            check(getattr(_hip.require_gpu(), "ebos_flow_voxel_propagate_bilinear_adjoint_" + _hip.suffix(src.dtype))(
+                B, T, H, W, ptr(src), ptr(raw), ptr(g), ptr(d), t_offset, denominator, float(dt), int(clamp is not None),
+                float(clamp if clamp is not None else 0.0), stream_ptr(src.device)), "ebos_flow_voxel_propagate_bilinear_adjoint")
+        return d, None, None, None, None, None
+
+
+class _Step(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flows, name, dt, dx, dy):
+        src = flows.detach().contiguous()
+        ctx.save_for_backward(src)
+        ctx.meta = (name, dt, dx, dy)
+        return _launch_step(name, src, dt, dx, dy)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (src,) = ctx.saved_tensors
+        name, dt, dx, dy = ctx.meta
+        B, _, H, W = (int(v) for v in src.shape)
+        g = g.contiguous()
+        with _hip.on_device(src.device):
+            d = torch.empty_like(src)
+            check(getattr(_hip.require_gpu(), f"ebos_flow_{name}_step_adjoint_" + _hip.suffix(src.dtype))(
+                B, H, W, ptr(src), ptr(g), ptr(d), dt, dx, dy, stream_ptr(src.device)), f"ebos_flow_{name}_step_adjoint")
+        return d, None, None, None, None
+
+
+def _launch_step(name: str, src: torch.Tensor, dt: float, dx: float, dy: float) -> torch.Tensor:
+    B, _, H, W = (int(v) for v in src.shape)
+    with _hip.on_device(src.device):
+        out = torch.empty_like(src)
+        check(getattr(_hip.require_gpu(), f"ebos_flow_{name}_step_" + _hip.suffix(src.dtype))(B, H, W, ptr(src), ptr(out), dt, dx, dy,
+                                                                                            stream_ptr(src.device)), f"ebos_flow_{name}_step")
     return out
 
 
@@ -192,18 +325,17 @@ def _step(name: str, flow, dt: float, dx, dy, kind: str):
         raise ValueError(f"dt, dx and dy must be numbers, got {dt!r}, {dx!r}, {dy!r}")
     if min(int(v) for v in flow.shape) < 1:
         raise ValueError(f"flow must not be empty, got {tuple(flow.shape)}")
-    lib = _hip.require_gpu()
+    _hip.require_gpu()
     dev = flow.device if kind == _staging.GPU else None
-    src = _staging.to_gpu(flow, dev, torch.float64 if kind == _staging.NUMPY else None).detach().contiguous()
+    src = _staging.to_gpu(flow, dev, torch.float64 if kind == _staging.NUMPY else None)
     if src.dim() == 3:
         src = src[None]
-    B, _, H, W = (int(v) for v in src.shape)
-    if B > 32767:
-        raise ValueError(f"{B} flows: at most 32767 per call")
-    with _hip.on_device(src.device):
-        out = torch.empty_like(src)
-        check(getattr(lib, f"ebos_flow_{name}_step_" + _hip.suffix(src.dtype))(B, H, W, ptr(src), ptr(out), float(dt), float(dx), float(dy),
-                                                                              stream_ptr(src.device)), f"ebos_flow_{name}_step")
+    if int(src.shape[0]) > 32767:
+        raise ValueError(f"{int(src.shape[0])} flows: at most 32767 per call")
+    if src.requires_grad and torch.is_grad_enabled():
+        out = _Step.apply(src, name, float(dt), float(dx), float(dy))
+    else:
+        out = _launch_step(name, src.detach().contiguous(), float(dt), float(dx), float(dy))
     return _staging.back(out.squeeze(), kind)
 
 
@@ -263,13 +395,16 @@ def _propagate(flow_0, dt: float, method: str, kind: str):
     _, H, W = (int(v) for v in flow_0.shape)
     if min(H, W) < 1:
         raise ValueError(f"flow_0 must not be empty, got {tuple(flow_0.shape)}")
-    lib = _hip.require_gpu()
+    _hip.require_gpu()
     dev = flow_0.device if kind == _staging.GPU else None
-    src = _staging.to_gpu(flow_0, dev, torch.float64 if kind == _staging.NUMPY else None).detach().contiguous()
-    with _hip.on_device(src.device):
-        out = torch.empty_like(src)
-        check(getattr(lib, "ebos_flow_voxel_propagate_bilinear_" + _hip.suffix(src.dtype))(1, 1, H, W, ptr(src), ptr(out), 0, 0, float(dt), 0, 0.0,
-                                                                                         stream_ptr(src.device)), "ebos_flow_voxel_propagate_bilinear")
+    src = _staging.to_gpu(flow_0, dev, torch.float64 if kind == _staging.NUMPY else None)
+    if src.requires_grad and torch.is_grad_enabled():
+        out = _BilinearVoxel.apply(src[None], 1, 0, 0, float(dt), None)[0, 0]
+    else:
+        src = src.detach().contiguous()
+        with _hip.on_device(src.device):
+            out = torch.empty_like(src)
+            _launch_bilinear(src[None], out[None, None], 0, 0, float(dt), None)
     return _staging.back(out.squeeze(), kind)
 
 

@@ -1412,6 +1412,48 @@ int ebos_flow_voxel_propagate_bilinear_f64(int B, int T, int H, int W, const dou
 int ebos_flow_voxel_truncate_mean_f32(int T, int H, int W, const float* voxel, double* out, ebos_stream_t stream);
 int ebos_flow_voxel_truncate_mean_f64(int T, int H, int W, const double* voxel, double* out, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Backward of the time-aware flow with respect to the flow at t0 (csrc/flow_voxel_grad.hip).  Every kernel gathers, in a fixed
+ * order and without atomics: two runs give the same bits.  The derivative rules are torch's: maximum(x, 0) and minimum(x, 0) pass
+ * half the gradient each where x == 0, sign() and floor() none; a clamp passes the gradient where -clamp <= x <= clamp.
+ *
+ * ebos_flow_upwind_step_adjoint_* / ebos_flow_burgers_step_adjoint_*: flow [B, 2, H, W] is the input of the step with (dt, dx, dy),
+ *   grad_out the gradient of its output -> grad_in the gradient of its input.  One launch.
+ * ebos_flow_voxel_advect_adjoint_*: the arguments of ebos_flow_voxel_advect_* with voxel [B, T, 2, H, W] = its UNCLAMPED output
+ *   (not read for _SAME, may be NULL) and grad_voxel the gradient of the (clamped, if has_clamp) voxel -> grad_flow [B, 2, H, W].
+ *   The bins are the intermediates of the chain; the walk goes from the outer bins towards t0 and adds each bin's upstream
+ *   gradient as it passes.  Routes as in the forward: one launch with a tile (32 x 32 for float, 24 x 24 for double), its halo and the
+ *   running gradient in LDS, or one launch per step through workspace, which holds
+ *   ebos_flow_voxel_advect_adjoint_workspace(..) elements (0: not needed, may be NULL; -1: bad arguments).
+ * ebos_flow_voxel_propagate_bilinear_adjoint_*: the arguments of ebos_flow_voxel_propagate_bilinear_* with voxel = its unclamped
+ *   output (read with has_clamp only) and grad_voxel -> grad_flow: per source pixel the four weights times the gradient at its four
+ *   cells plus the part through the position (d fx / d flow[0] = dt, d fy / d flow[1] = dt), summed over the bins in index order.
+ * ebos_flow_voxel_clamp_*: out[i] = min(max(in[i], -clamp), clamp), NaN kept; out of place, for the clamped copy of a kept voxel.
+ * ---------------------------------------------------------------------------------------- */
+int64_t ebos_flow_voxel_advect_adjoint_workspace(int scheme, int B, int T, int H, int W, int t0_index, int wrap_last, int route);
+int ebos_flow_upwind_step_adjoint_f32(int B, int H, int W, const float* flow, const float* grad_out, float* grad_in, double dt, double dx,
+                                      double dy, ebos_stream_t stream);
+int ebos_flow_upwind_step_adjoint_f64(int B, int H, int W, const double* flow, const double* grad_out, double* grad_in, double dt, double dx,
+                                      double dy, ebos_stream_t stream);
+int ebos_flow_burgers_step_adjoint_f32(int B, int H, int W, const float* flow, const float* grad_out, float* grad_in, double dt, double dx,
+                                       double dy, ebos_stream_t stream);
+int ebos_flow_burgers_step_adjoint_f64(int B, int H, int W, const double* flow, const double* grad_out, double* grad_in, double dt, double dx,
+                                       double dy, ebos_stream_t stream);
+int ebos_flow_voxel_advect_adjoint_f32(int scheme, int B, int T, int H, int W, const float* flow, const float* voxel, const float* grad_voxel,
+                                       float* grad_flow, int t0_index, int has_clamp, double clamp, int wrap_last, int route, float* workspace,
+                                       ebos_stream_t stream);
+int ebos_flow_voxel_advect_adjoint_f64(int scheme, int B, int T, int H, int W, const double* flow, const double* voxel, const double* grad_voxel,
+                                       double* grad_flow, int t0_index, int has_clamp, double clamp, int wrap_last, int route, double* workspace,
+                                       ebos_stream_t stream);
+int ebos_flow_voxel_propagate_bilinear_adjoint_f32(int B, int T, int H, int W, const float* flow, const float* voxel, const float* grad_voxel,
+                                                   float* grad_flow, int t_offset, int denominator, double dt, int has_clamp, double clamp,
+                                                   ebos_stream_t stream);
+int ebos_flow_voxel_propagate_bilinear_adjoint_f64(int B, int T, int H, int W, const double* flow, const double* voxel, const double* grad_voxel,
+                                                   double* grad_flow, int t_offset, int denominator, double dt, int has_clamp, double clamp,
+                                                   ebos_stream_t stream);
+int ebos_flow_voxel_clamp_f32(int64_t n, const float* in, float* out, double clamp, ebos_stream_t stream);
+int ebos_flow_voxel_clamp_f64(int64_t n, const double* in, double* out, double clamp, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

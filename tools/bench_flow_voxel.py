@@ -2,6 +2,7 @@
 """Timing of the flow voxels (event_based_bos_amd/flow_voxel.py, csrc/flow_voxel.hip).
 
     python tools/bench_flow_voxel.py [--out profiles/flow_voxel_bench.json] [--rounds 5] [--reps 20]
+    python tools/bench_flow_voxel.py --backward [--out profiles/flow_voxel_backward_bench.json]
 
 Per shape (260 x 346, 720 x 1280), ``time_bin`` (5, 15), batch (1, 8), scheme (upwind, burgers) and dtype (float32, float64), with t0 in
 the middle: ``flow_voxel_batch`` on device tensors against the restatement of the reference's constructor (tests/_flow_voxel_ref.py:
@@ -13,6 +14,12 @@ the rounds and their spread (min, max) are kept.  A difference counts as a gain 
 overlap; ``intervals_overlap`` says so per row.  ``copy_share`` is the time a device-to-device copy at the measured rate needs for
 the bytes the chain must move (read 2 H W, write 2 T H W elements per flow), divided by the kernel's time: 1.0 is a kernel as fast as
 a copy of its output.
+
+``--backward`` times forward plus backward per voxel instead (csrc/flow_voxel_grad.hip): 260 x 346 and 720 x 1280, ``time_bin`` 5 and
+17, batch 1 and 8, the four schemes, float32 and float64, against eager torch on the same GPU running the restatement of the
+reference's expressions under autograd (tests/_flow_voxel_grad_ref.py), in the same process and in alternating rounds.  ``min`` is the
+best round, [min, max] the spread.  ``relative_difference`` is max|kernel - eager| / max|eager| of the two gradients, reported and not
+judged here (tests/test_gpu_flow_voxel_grad.py does that against the CPU).
 """
 import argparse
 import json
@@ -26,6 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _flow_voxel_ref as R  # noqa: E402
+import _flow_voxel_grad_ref as GR  # noqa: E402
 from event_based_bos_amd import _hip  # noqa: E402
 from event_based_bos_amd import flow_voxel as FV  # noqa: E402
 
@@ -110,13 +118,63 @@ def rows(rounds, reps, rate):
     return out
 
 
+def backward_rows(rounds, reps):
+    out = []
+    rs = np.random.RandomState(1)
+    for H, W in SHAPES:
+        for dtype in (torch.float32, torch.float64):
+            for B in BATCHES:
+                flows = torch.from_numpy(rs.uniform(-3.0, 3.0, (B, 2, H, W))).cuda().to(dtype).requires_grad_()
+                for T in (5, 17):
+                    up = torch.from_numpy(rs.standard_normal((B, T, 2, H, W))).cuda().to(dtype)
+                    for scheme in ("upwind", "burgers", "same", "bilinear"):
+                        def kernel(route=None):
+                            flows.grad = None
+                            FV._FORCE_ROUTE = route
+                            try:
+                                FV.flow_voxel_batch(flows, T, scheme, "middle").backward(up)
+                            finally:
+                                FV._FORCE_ROUTE = None
+                            return flows.grad
+
+                        def eager():
+                            flows.grad = None
+                            GR.voxel_torch(flows, T, scheme, "middle").backward(up)
+                            return flows.grad
+
+                        got, want = kernel(), eager()
+                        scale = float(want.abs().max())
+                        worst = float((got - want).abs().max()) / scale
+                        row = {"shape": [H, W], "dtype": str(dtype).split(".")[-1], "B": B, "time_bin": T, "scheme": scheme,
+                               "unit": "us per voxel, forward + backward", "relative_difference": worst}
+                        calls = {"kernel": kernel, "eager_torch": eager}
+                        if scheme in ("upwind", "burgers"):
+                            calls["per_step_route"] = lambda: kernel(_hip.FLOW_ROUTE_STEPS)
+                        row.update(compare(calls, rounds, reps, per=B))
+                        row["speedup_of_best"] = row["eager_torch"]["min"] / row["kernel"]["min"]
+                        print(json.dumps(row), flush=True)
+                        out.append(row)
+                        del got, want
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flow_voxel_bench.json"))
+    ap.add_argument("--backward", action="store_true", help="time forward + backward against eager autograd instead of the forward")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "flow_voxel_backward_bench.json" if args.backward else "flow_voxel_bench.json")
     assert torch.cuda.is_available(), "bench_flow_voxel needs a GPU"
+    if args.backward:
+        res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps,
+               "method": "device events around a loop of forward + backward calls; alternating rounds; median and [min, max] over the rounds",
+               "rows": backward_rows(args.rounds, args.reps)}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        json.dump(res, open(args.out, "w"), indent=1)
+        return
     rate = copy_rate(args.rounds, args.reps)
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "copy_bytes_per_us": rate,
            "method": "device events around a loop of calls; alternating rounds; median and [min, max] over the rounds"}
