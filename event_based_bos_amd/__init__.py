@@ -21,6 +21,8 @@ tub-rip/event_based_bos:
     visualizer           the reference visualizer's pictures (colour-coded flow, event picture, density picture), batched
     event_voxel          the reference's event voxel grid and discretised event volume; the voxel grids of a batch of raw windows
     flow_voxel           the reference's time-aware flow: upwind / Burgers / bilinear flow voxels of one flow or a batch, and their mean
+    time_bins, warp_voxel   the time-aware warp: every event displaced by the flow of its own time bin of a flow voxel
+                         (Warp.warp_event(.., "dense-flow-voxel"), EventPlan.build(.., time_bin=T).iwe_voxel / contrast_voxel)
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -36,6 +38,7 @@ from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingE
                          window_ingest_raw_batch)
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
 from .flow_voxel import flow_voxel_batch  # noqa: F401
+from .ops import time_bins, warp_voxel  # noqa: F401
 from . import costs, data_loader, evaluation, event_filters, event_voxel, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -94,6 +94,8 @@ _P, _I, _L, _D, _Z, _F = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t,
 _WARP = [_P, _P, _P, _I, _D, _I, _L, _L, _I, _I, _I, _P, _P, _P]
 _WARP_BWD = [_P, _P, _I, _D, _I, _P, _L, _L, _I, _I, _I, _P, _P]
 _W2 = [_P, _P, _P, _I, _D, _I, _P, _L, _P, _P]
+_WARP_VOXEL = [_P, _P, _P, _I, _D, _I, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P]
+_WARP_VOXEL_BWD = [_P, _P, _I, _D, _I, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P]
 _W2_BWD = [_P, _P, _I, _D, _I, _P, _P, _L, _P, _P]
 _SPLAT = [_P, _P, _D, _I, _D, _L, _L, _I, _I, _I, _I, _P, _P]
 _SPLAT_BWD = [_P, _P, _D, _D, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P]
@@ -279,6 +281,15 @@ SIGNATURES = {
     "ebos_flow_voxel_propagate_bilinear_adjoint_f64": (_I, [_I] * 4 + [_P, _P, _P, _P, _I, _I, _D, _I, _D, _P]),
     "ebos_flow_voxel_clamp_f32": (_I, [_L, _P, _P, _D, _P]),
     "ebos_flow_voxel_clamp_f64": (_I, [_L, _P, _P, _D, _P]),
+    "ebos_event_time_bins_f32": (_I, [_P, _P, _L, _L, _I, _P, _P]),
+    "ebos_event_time_bins_f64": (_I, [_P, _P, _L, _L, _I, _P, _P]),
+    "ebos_warp_voxel_f32": (_I, _WARP_VOXEL),
+    "ebos_warp_voxel_f64": (_I, _WARP_VOXEL),
+    "ebos_warp_voxel_bwd_f32": (_I, _WARP_VOXEL_BWD),
+    "ebos_warp_voxel_bwd_f64": (_I, _WARP_VOXEL_BWD),
+    "ebos_iwe_voxel_f32": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "ebos_iwe_voxel_tiled_f32": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "ebos_iwe_voxel_bwd_f32": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
 }
 
 

@@ -1,0 +1,568 @@
+// warp_voxel.hip -- the time-aware warp for gfx950 / CDNA4: every event is displaced by the flow of ITS OWN time bin of a
+// flow voxel [T, 2, H, W] (construct_dense_flow_voxel_* of flow_voxel.hip), materialised (A3 with a bin) and fused with the
+// bilinear IWE and its backward (iwe_fused.hip with a bin).
+//
+//   bin      tau = (t - tmin) / (tmax - tmin) in float64 whatever the event type; k = min((int)(tau * T), T - 1); tmax == tmin -> 0
+//   warp     i = trunc(x) * row_stride + trunc(y);  x' = x - dt * V[k][0][i];  y' = y - dt * V[k][1][i];  t' = dt;  p' = p
+//            (dt and the operation order exactly as warp_kernels.hip: src/warp.py:283-287, 330-337, no FMA contraction)
+//   fused    iwe_dense_kernel / iwe_dense_tiled_kernel / iwe_dense_bwd_kernel of iwe_fused.hip with the gather
+//            V[(k * 2 + c) * H * W + lin] and the bins as one more SoA stream (1 B/event)
+//
+// Every kernel reads a bin as min(bins[i], T - 1): a bins array that was made for another T cannot index outside the voxel.
+// Dead and padding slots never gather.
+#include <type_traits>
+
+#include "common.h"
+
+namespace ebos {
+namespace {
+
+// ---- AoS helpers (as warp_kernels.hip) -----------------------------------------------------------
+template <typename T>
+struct Vec4;
+template <>
+struct Vec4<float> {
+  using type = float4;
+};
+template <>
+struct Vec4<double> {
+  using type = double4;
+};
+template <typename T>
+__device__ __forceinline__ typename Vec4<T>::type load_event(const T* base, int64_t i) {
+  return reinterpret_cast<const typename Vec4<T>::type*>(base)[i];
+}
+template <typename T>
+__device__ __forceinline__ void store_event(T* base, int64_t i, typename Vec4<T>::type v) {
+  reinterpret_cast<typename Vec4<T>::type*>(base)[i] = v;
+}
+
+template <typename T>
+__device__ __forceinline__ T event_dt(T t, const TimeBase<T>& tb, int normalize_t) {
+#pragma clang fp contract(off)
+  T dt = t - tb.ref;                    // src/warp.py:283
+  if (normalize_t) dt = dt / tb.period;  // :284-287
+  return dt;
+}
+
+// source-pixel linear index of src/warp.py:334 (trunc toward zero, flattened bounds as torch.gather)
+template <typename T>
+__device__ __forceinline__ bool source_index(T x, T y, int row_stride, int64_t hw, int64_t* lin) {
+  const T lim = T(1e15);
+  if (!(x > -lim && x < lim && y > -lim && y < lim)) return false;  // NaN / Inf
+  const int64_t l = static_cast<int64_t>(x) * row_stride + static_cast<int64_t>(y);
+  *lin = l;
+  return l >= 0 && l < hw;
+}
+
+__device__ __forceinline__ int clamp_bin(uint8_t b, int T) { return min((int)b, T - 1); }
+
+// ---- the bin rule, in float64 --------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256)
+time_bins_kernel(const T* __restrict__ events, const T* __restrict__ tminmax, int64_t n, int nbins,
+                 uint8_t* __restrict__ bins) {
+#pragma clang fp contract(off)
+  const int64_t row = blockIdx.y;
+  const T* ev = events + row * n * 4;
+  uint8_t* out = bins + row * n;
+  const double tmin = (double)tminmax[2 * row], tmax = (double)tminmax[2 * row + 1];  // float -> double is exact
+  const double span = tmax - tmin;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    int k = 0;
+    if (span > 0.0) {
+      const double tau = ((double)ev[4 * i + 2] - tmin) / span;
+      const double s = tau * (double)nbins;
+      if (s >= (double)nbins) k = nbins - 1;  // t == tmax (and anything later, were tminmax not this window's)
+      else if (s > 0.0) k = (int)s;           // NaN and negatives stay in bin 0
+    }
+    out[i] = (uint8_t)k;
+  }
+}
+
+// ---- materialised warp, forward ------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256)
+warp_voxel_kernel(const T* __restrict__ events, const T* __restrict__ voxel, const T* __restrict__ tminmax, int ref_mode,
+                  double ref_fraction, int normalize_t, int64_t n, int nbins, int H, int W, int row_stride,
+                  const uint8_t* __restrict__ bins, T* __restrict__ warped, int32_t* oob_count) {
+#pragma clang fp contract(off)
+  const int64_t row = blockIdx.y;
+  const int64_t hw = (int64_t)H * W;
+  const T* ev = events + row * n * 4;
+  const T* vx = voxel + row * nbins * 2 * hw;
+  const uint8_t* bn = bins + row * n;
+  T* out = warped + row * n * 4;
+  const TimeBase<T> tb = time_base(tminmax + 2 * row, ref_mode, ref_fraction);
+  int bad = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    auto e = load_event(ev, i);
+    const T dt = event_dt(e.z, tb, normalize_t);
+    int64_t lin;
+    if (source_index(e.x, e.y, row_stride, hw, &lin)) {
+      const T* f0 = vx + (int64_t)clamp_bin(bn[i], nbins) * 2 * hw;
+      const T u = f0[lin], v = f0[hw + lin];
+      const T du = dt * u, dv = dt * v;  // separate roundings: mul, then sub (src/warp.py:335-336)
+      e.x = e.x - du;
+      e.y = e.y - dv;
+    } else {
+      ++bad;
+    }
+    e.z = dt;
+    store_event(out, i, e);
+  }
+  if (oob_count != nullptr && bad) atomicAdd(oob_count, bad);
+}
+
+// ---- materialised warp, backward: d_voxel[k][c][src] += -dt * d_warped[c] ------------------------
+template <typename T>
+__global__ void __launch_bounds__(256)
+warp_voxel_bwd_kernel(const T* __restrict__ events, const T* __restrict__ tminmax, int ref_mode, double ref_fraction,
+                      int normalize_t, const T* __restrict__ d_warped, int64_t n, int nbins, int H, int W, int row_stride,
+                      const uint8_t* __restrict__ bins, T* d_voxel) {
+  const int64_t row = blockIdx.y;
+  const int64_t hw = (int64_t)H * W;
+  const T* ev = events + row * n * 4;
+  const T* dw = d_warped + row * n * 4;
+  const uint8_t* bn = bins + row * n;
+  T* gv = d_voxel + row * nbins * 2 * hw;
+  const TimeBase<T> tb = time_base(tminmax + 2 * row, ref_mode, ref_fraction);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const auto e = load_event(ev, i);
+    const auto g = load_event(dw, i);
+    const T dt = event_dt(e.z, tb, normalize_t);
+    int64_t lin;
+    if (source_index(e.x, e.y, row_stride, hw, &lin)) {
+      T* g0 = gv + (int64_t)clamp_bin(bn[i], nbins) * 2 * hw;
+      atomic_add(&g0[lin], -dt * g.x);
+      atomic_add(&g0[hw + lin], -dt * g.y);
+    }
+  }
+}
+
+// ---- fused warp + IWE ----------------------------------------------------------------------------
+constexpr float kEps = 1e-6f;  // src/event_image_converter.py:586
+
+// Warped footprint in SOURCE-PIXEL-RELATIVE coordinates (iwe_fused.hip: the float arithmetic only ever sees the fraction of
+// the source coordinate plus the displacement, so its rounding error does not grow with the image size).
+struct Taps {
+  int R, C;      // top-left tap, padded image coordinates
+  float fr, fc;  // fractional offsets
+  bool ok;       // finite
+};
+__device__ __forceinline__ Taps warped_taps(float ex, float ey, float dx, float dy, int pad_h, int pad_w) {
+  const int rs = (int)ex, cs = (int)ey;
+  const float lx = (ex - (float)rs) + dx, ly = (ey - (float)cs) + dy;
+  const float r0 = floorf(lx + kEps), c0 = floorf(ly + kEps);
+  Taps t;
+  t.fr = lx - r0;
+  t.fc = ly - c0;
+  t.ok = (r0 > -1e9f) && (r0 < 1e9f) && (c0 > -1e9f) && (c0 < 1e9f);
+  t.R = t.ok ? rs + (int)r0 + pad_h : -4;
+  t.C = t.ok ? cs + (int)c0 + pad_w : -4;
+  return t;
+}
+
+// general forward: any event order, four global float atomics per event
+__global__ void __launch_bounds__(256)
+iwe_voxel_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
+                 const float* __restrict__ weight, const uint8_t* __restrict__ bins, int64_t n,
+                 const float* __restrict__ voxel, int nbins, int H, int W, int row_stride, int pad_h, int pad_w, float* iwe) {
+  const int64_t hw = (int64_t)H * W;
+  const int h = H + 2 * pad_h, w = W + 2 * pad_w;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float ex = x[i], ey = y[i], edt = dt[i];
+    if (!(ex > -1e9f && ex < 1e9f && ey > -1e9f && ey < 1e9f)) continue;
+    const int64_t lin = (int64_t)(int)ex * row_stride + (int)ey;
+    if (lin < 0 || lin >= hw) continue;  // torch.gather would raise (src/warp.py:334-336): dropped
+    const float* f0 = voxel + (int64_t)clamp_bin(bins[i], nbins) * 2 * hw;
+    const Taps f = warped_taps(ex, ey, -edt * f0[lin], -edt * f0[hw + lin], pad_h, pad_w);
+    const float wv = weight ? weight[i] : 1.0f;
+    const bool r0 = f.R >= 0 && f.R < h, r1 = f.R + 1 >= 0 && f.R + 1 < h;
+    const bool c0 = f.C >= 0 && f.C < w, c1 = f.C + 1 >= 0 && f.C + 1 < w;
+    const int64_t base = (int64_t)f.R * w + f.C;
+    const float a = 1.0f - f.fr, b = 1.0f - f.fc;
+    if (r0 && c0) atomic_add(&iwe[base], a * b * wv);
+    if (r1 && c0) atomic_add(&iwe[base + w], f.fr * b * wv);
+    if (r0 && c1) atomic_add(&iwe[base + 1], a * f.fc * wv);
+    if (r1 && c1) atomic_add(&iwe[base + w + 1], f.fr * f.fc * wv);
+  }
+}
+
+// tiled forward: LDS-privatised IWE tile per workgroup (iwe_dense_tiled_kernel with the bins as a fourth SoA stream; the
+// accumulator rule -- f64 wherever tile + halo fits the LDS in doubles -- and the spill path beyond the halo are the same)
+constexpr int kTiledBlock = 1024;
+
+template <int TH, int TW, int HALO, typename ACC>
+__global__ void __launch_bounds__(kTiledBlock)
+iwe_voxel_tiled_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ dts,
+                       const float* __restrict__ weight, const uint8_t* __restrict__ bins,
+                       const int32_t* __restrict__ key_offsets, const float* __restrict__ voxel, int nbins, int H, int W,
+                       int tiles_x, int splits, int pad_h, int pad_w, float* iwe) {
+  constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
+  extern __shared__ double s_raw[];  // [LH][LW] of ACC
+  ACC* s_img = reinterpret_cast<ACC*>(s_raw);
+
+  const int tile = blockIdx.x / splits, part = blockIdx.x - tile * splits;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int32_t beg = key_offsets[tile * (TH * TW)], end = key_offsets[(tile + 1) * (TH * TW)];
+  if (beg == end) return;
+  int32_t chunk = (end - beg + splits - 1) / splits;
+  chunk = (chunk + kWave - 1) & ~(kWave - 1);
+  const int32_t my_beg = beg + part * chunk;
+  const int32_t my_end = min(end, my_beg + chunk);
+  if (my_beg >= my_end) return;
+
+  for (int i = threadIdx.x; i < LH * LW; i += kTiledBlock) s_img[i] = ACC(0);
+  __syncthreads();
+
+  const int64_t hw = (int64_t)H * W;
+  const int h = H + 2 * pad_h, w = W + 2 * pad_w;
+  // LDS cell (0,0) <-> un-padded image pixel (oy, ox); padded pixel (oy + pad_h, ox + pad_w)
+  const int oy = ty * TH - HALO, ox = tx * TW - HALO;
+
+  // kUnroll events in flight per thread: the coalesced SoA loads (bins among them) first, then the voxel gathers, then the LDS atomics
+  constexpr int kUnroll = 8;
+  for (int32_t base = my_beg + threadIdx.x; base < my_end; base += kTiledBlock * kUnroll) {
+    float ex[kUnroll], ey[kUnroll], edt[kUnroll], wv[kUnroll], fu[kUnroll], fv[kUnroll];
+    int kb[kUnroll];
+#pragma unroll
+    for (int k = 0; k < kUnroll; ++k) {
+      const int32_t i = base + k * kTiledBlock;
+      const bool live = i < my_end;
+      ex[k] = live ? xs[i] : -1.0f;  // -1 marks a dead slot
+      ey[k] = live ? ys[i] : 0.0f;
+      edt[k] = live ? dts[i] : 0.0f;
+      kb[k] = live ? clamp_bin(bins[i], nbins) : 0;
+      wv[k] = (live && weight) ? weight[i] : 1.0f;
+      if (!live) wv[k] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < kUnroll; ++k) {
+      const int32_t i = base + k * kTiledBlock;
+      const int64_t lin = (int64_t)(int)ex[k] * W + (int)ey[k];  // binned events have a valid source pixel
+      const bool live = i < my_end && lin >= 0 && lin < hw;
+      const float* f0 = voxel + (int64_t)kb[k] * 2 * hw;
+      fu[k] = live ? f0[lin] : 0.0f;
+      fv[k] = live ? f0[hw + lin] : 0.0f;
+      if (!live) wv[k] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < kUnroll; ++k) {
+      const int32_t i = base + k * kTiledBlock;
+      if (i >= my_end) break;
+      const Taps f = warped_taps(ex[k], ey[k], -edt[k] * fu[k], -edt[k] * fv[k], 0, 0);  // un-padded coordinates
+      const float fr = f.fr, fc = f.fc;
+      const float a = 1.0f - fr, b = 1.0f - fc;
+      const float w00 = a * b * wv[k], w10 = fr * b * wv[k], w01 = a * fc * wv[k], w11 = fr * fc * wv[k];
+      const int rl = f.R - oy, cl = f.C - ox;  // LDS cell of the top-left tap
+      if (f.ok && rl >= 0 && rl < LH - 1 && cl >= 0 && cl < LW - 1) {
+        ACC* p = &s_img[rl * LW + cl];
+        atomic_add(p, (ACC)w00);
+        atomic_add(p + LW, (ACC)w10);
+        atomic_add(p + 1, (ACC)w01);
+        atomic_add(p + LW + 1, (ACC)w11);
+      } else if (f.ok) {
+        // beyond the halo: straight to the image, so any displacement stays exact
+        const int R = f.R + pad_h, C = f.C + pad_w;
+        const bool rr0 = R >= 0 && R < h, rr1 = R + 1 >= 0 && R + 1 < h;
+        const bool cc0 = C >= 0 && C < w, cc1 = C + 1 >= 0 && C + 1 < w;
+        const int64_t gb = (int64_t)R * w + C;
+        if (rr0 && cc0) atomic_add(&iwe[gb], w00);
+        if (rr1 && cc0) atomic_add(&iwe[gb + w], w10);
+        if (rr0 && cc1) atomic_add(&iwe[gb + 1], w01);
+        if (rr1 && cc1) atomic_add(&iwe[gb + w + 1], w11);
+      }
+    }
+  }
+  __syncthreads();
+
+  // flush: consecutive lanes -> consecutive columns of one image row
+  const int gy0 = oy + pad_h, gx0 = ox + pad_w;
+  for (int i = threadIdx.x; i < LH * LW; i += kTiledBlock) {
+    const float v = (float)s_img[i];
+    if (v == 0.0f) continue;
+    const int rl = i / LW, cl = i - rl * LW;
+    const int R = gy0 + rl, C = gx0 + cl;
+    if (R >= 0 && R < h && C >= 0 && C < w) atomic_add(&iwe[(int64_t)R * w + C], v);
+  }
+}
+
+template <int TH, int TW, int HALO>
+struct TileAcc {  // f64 when it fits the LDS, else f32
+  static constexpr bool kF64 = (size_t)(TH + 2 * HALO) * (TW + 2 * HALO) * sizeof(double) <= 160 * 1024;
+  using type = typename std::conditional<kF64, double, float>::type;
+};
+
+template <int TH, int TW, int HALO>
+int launch_voxel_tiled(const float* xs, const float* ys, const float* dts, const float* weight, const uint8_t* bins,
+                       const int32_t* key_offsets, const float* voxel, int nbins, int H, int W, int splits, int pad_h,
+                       int pad_w, float* iwe, hipStream_t s) {
+  constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
+  using ACC = typename TileAcc<TH, TW, HALO>::type;
+  constexpr size_t lds = (size_t)LH * LW * sizeof(ACC);
+  static_assert(lds <= 160 * 1024, "tile + halo must fit the 160 KiB LDS of a CDNA4 CU");
+  const int tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
+  auto kern = iwe_voxel_tiled_kernel<TH, TW, HALO, ACC>;
+  if (lds > 64 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      set_error("ebos_iwe_voxel_tiled: cannot reserve %zu B of LDS", lds);
+      return EBOS_ERR_LAUNCH;
+    }
+  }
+  kern<<<dim3((unsigned)(tiles_y * tiles_x * splits)), dim3(kTiledBlock), lds, s>>>(
+      xs, ys, dts, weight, bins, key_offsets, voxel, nbins, H, W, tiles_x, splits, pad_h, pad_w, iwe);
+  return EBOS_OK;
+}
+
+// ---- fused backward ------------------------------------------------------------------------------
+struct GradImage {
+  const float* g;
+  float a, c;  // G = a * g + c inside the valid region
+  int h, w, lo;
+  __device__ __forceinline__ float at(int R, int C) const {
+    if (R < lo || R >= h - lo || C < lo || C >= w - lo) return 0.0f;
+    return a * g[(int64_t)R * w + C] + c;
+  }
+};
+
+template <bool SORTED>
+__global__ void __launch_bounds__(256)
+iwe_voxel_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
+                     const float* __restrict__ weight, const uint8_t* __restrict__ bins, int64_t n,
+                     const float* __restrict__ voxel, int nbins, int H, int W, int row_stride, int pad_h, int pad_w,
+                     const float* __restrict__ g_image, const float* __restrict__ affine, int g_lo, float* d_voxel,
+                     float* __restrict__ d_weight) {
+  const int64_t hw = (int64_t)H * W;
+  GradImage G;
+  G.g = g_image;
+  G.a = affine ? affine[0] : 1.0f;
+  G.c = affine ? affine[1] : 0.0f;
+  G.h = H + 2 * pad_h;
+  G.w = W + 2 * pad_w;
+  G.lo = g_lo;
+  const int lane = threadIdx.x & (kWave - 1);
+  // whole waves iterate together so that the shuffles below see all 64 lanes
+  const int64_t n_round = (n + kWave - 1) / kWave * kWave;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_round; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t key = -1;  // k * H * W + lin names the pair of d_voxel cells this event adds to
+    int kb = 0;
+    float gx = 0.0f, gy = 0.0f;
+    if (i < n) {
+      const float ex = x[i], ey = y[i], edt = dt[i];
+      int64_t lin = -1;
+      if (ex > -1e9f && ex < 1e9f && ey > -1e9f && ey < 1e9f) {
+        lin = (int64_t)(int)ex * row_stride + (int)ey;
+        if (lin < 0 || lin >= hw) lin = -1;
+      }
+      if (lin >= 0) {
+        kb = clamp_bin(bins[i], nbins);
+        const float* f0 = voxel + (int64_t)kb * 2 * hw;
+        const Taps f = warped_taps(ex, ey, -edt * f0[lin], -edt * f0[hw + lin], pad_h, pad_w);
+        const float g00 = G.at(f.R, f.C), g10 = G.at(f.R + 1, f.C);
+        const float g01 = G.at(f.R, f.C + 1), g11 = G.at(f.R + 1, f.C + 1);
+        const float wv = weight ? weight[i] : 1.0f;
+        const float a = 1.0f - f.fr, b = 1.0f - f.fc;
+        const float dx = wv * (b * (g10 - g00) + f.fc * (g11 - g01));  // dL/dx'
+        const float dy = wv * (a * (g01 - g00) + f.fr * (g11 - g10));  // dL/dy'
+        gx = -edt * dx;                                                // dL/dV[k][0][src]
+        gy = -edt * dy;
+        key = (int64_t)kb * hw + lin;
+        if (d_weight) d_weight[i] = a * b * g00 + f.fr * b * g10 + a * f.fc * g01 + f.fr * f.fc * g11;
+      } else if (d_weight) {
+        d_weight[i] = 0.0f;
+      }
+    }
+    const int64_t cell = key >= 0 ? key + (int64_t)kb * hw : 0;  // (k * 2 + 0) * H * W + lin
+    if (SORTED) {
+      // events of one source pixel are contiguous, in whatever order of their bins: the segmented wave reduction keys on
+      // (bin, pixel), so a run is a stretch of neighbours that add to the same cells -- one atomic pair per run
+      const int64_t prev = __shfl_up(key, 1, kWave);
+      const bool head = (lane == 0) || (prev != key);
+      const unsigned long long heads = __ballot(head);
+      const int run = __popcll(heads & (~0ull >> (63 - lane)));  // number of heads at or below this lane
+#pragma unroll
+      for (int off = 1; off < kWave; off <<= 1) {
+        const float ox_ = __shfl_down(gx, off, kWave);
+        const float oy_ = __shfl_down(gy, off, kWave);
+        const int orun = __shfl_down(run, off, kWave);
+        if (lane + off < kWave && orun == run) {
+          gx += ox_;
+          gy += oy_;
+        }
+      }
+      if (head && key >= 0) {
+        atomic_add(&d_voxel[cell], gx);
+        atomic_add(&d_voxel[cell + hw], gy);
+      }
+    } else if (key >= 0) {
+      atomic_add(&d_voxel[cell], gx);
+      atomic_add(&d_voxel[cell + hw], gy);
+    }
+  }
+}
+
+bool ref_mode_ok(int m) { return m >= EBOS_REF_FIRST && m <= EBOS_REF_TIMEBASE; }
+bool bins_ok(int T) { return T >= 1 && T <= 255; }
+
+template <typename T>
+int time_bins_impl(const T* events, const T* tminmax, int64_t b, int64_t n, int nbins, uint8_t* bins, ebos_stream_t stream) {
+  EBOS_REQUIRE(tminmax != nullptr, "ebos_event_time_bins: tminmax is NULL");
+  EBOS_REQUIRE((events && bins) || n == 0, "ebos_event_time_bins: NULL events/bins");
+  EBOS_REQUIRE(bins_ok(nbins), "ebos_event_time_bins: T = %d is outside [1, 255]", nbins);
+  EBOS_REQUIRE(b >= 1 && b <= 65535 && n >= 0, "ebos_event_time_bins: bad sizes b=%lld n=%lld", (long long)b, (long long)n);
+  if (n == 0) return EBOS_OK;
+  dim3 grid(stream_grid(n, 256), (unsigned)b);
+  time_bins_kernel<T><<<grid, dim3(256), 0, as_stream(stream)>>>(events, tminmax, n, nbins, bins);
+  EBOS_CHECK_LAUNCH("ebos_event_time_bins");
+  return EBOS_OK;
+}
+
+template <typename T>
+int warp_voxel_impl(const T* events, const T* voxel, const T* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                    int64_t b, int64_t n, int nbins, int H, int W, int row_stride, const uint8_t* bins, T* warped,
+                    int32_t* oob_count, ebos_stream_t stream) {
+  EBOS_REQUIRE(voxel && tminmax, "ebos_warp_voxel: NULL voxel/tminmax");
+  EBOS_REQUIRE((events && warped && bins) || n == 0, "ebos_warp_voxel: NULL events/warped/bins");
+  EBOS_REQUIRE(ref_mode_ok(ref_mode), "ebos_warp_voxel: bad ref_mode %d", ref_mode);
+  EBOS_REQUIRE(bins_ok(nbins), "ebos_warp_voxel: T = %d is outside [1, 255]", nbins);
+  EBOS_REQUIRE(b >= 1 && b <= 65535 && n >= 0 && H > 0 && W > 0 && row_stride > 0,
+               "ebos_warp_voxel: bad sizes b=%lld n=%lld H=%d W=%d stride=%d", (long long)b, (long long)n, H, W, row_stride);
+  if (n == 0) return EBOS_OK;
+  dim3 grid(stream_grid(n, 256), (unsigned)b);
+  warp_voxel_kernel<T><<<grid, dim3(256), 0, as_stream(stream)>>>(events, voxel, tminmax, ref_mode, ref_fraction, normalize_t, n,
+                                                                  nbins, H, W, row_stride, bins, warped, oob_count);
+  EBOS_CHECK_LAUNCH("ebos_warp_voxel");
+  return EBOS_OK;
+}
+
+template <typename T>
+int warp_voxel_bwd_impl(const T* events, const T* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                        const T* d_warped, int64_t b, int64_t n, int nbins, int H, int W, int row_stride,
+                        const uint8_t* bins, T* d_voxel, ebos_stream_t stream) {
+  EBOS_REQUIRE(tminmax && d_voxel, "ebos_warp_voxel_bwd: NULL tminmax/d_voxel");
+  EBOS_REQUIRE((events && d_warped && bins) || n == 0, "ebos_warp_voxel_bwd: NULL events/d_warped/bins");
+  EBOS_REQUIRE(ref_mode_ok(ref_mode), "ebos_warp_voxel_bwd: bad ref_mode %d", ref_mode);
+  EBOS_REQUIRE(bins_ok(nbins), "ebos_warp_voxel_bwd: T = %d is outside [1, 255]", nbins);
+  EBOS_REQUIRE(b >= 1 && b <= 65535 && n >= 0 && H > 0 && W > 0 && row_stride > 0, "ebos_warp_voxel_bwd: bad sizes");
+  if (n == 0) return EBOS_OK;
+  dim3 grid(stream_grid(n, 256), (unsigned)b);
+  warp_voxel_bwd_kernel<T><<<grid, dim3(256), 0, as_stream(stream)>>>(events, tminmax, ref_mode, ref_fraction, normalize_t,
+                                                                      d_warped, n, nbins, H, W, row_stride, bins, d_voxel);
+  EBOS_CHECK_LAUNCH("ebos_warp_voxel_bwd");
+  return EBOS_OK;
+}
+
+}  // namespace
+}  // namespace ebos
+
+extern "C" {
+
+int ebos_event_time_bins_f32(const float* events, const float* tminmax, int64_t b, int64_t n, int T, uint8_t* bins,
+                             ebos_stream_t stream) {
+  return ebos::time_bins_impl<float>(events, tminmax, b, n, T, bins, stream);
+}
+int ebos_event_time_bins_f64(const double* events, const double* tminmax, int64_t b, int64_t n, int T, uint8_t* bins,
+                             ebos_stream_t stream) {
+  return ebos::time_bins_impl<double>(events, tminmax, b, n, T, bins, stream);
+}
+
+int ebos_warp_voxel_f32(const float* events, const float* voxel, const float* tminmax, int ref_mode, double ref_fraction,
+                        int normalize_t, int64_t b, int64_t n, int T, int H, int W, int row_stride, const uint8_t* bins,
+                        float* warped, int32_t* oob_count, ebos_stream_t stream) {
+  return ebos::warp_voxel_impl<float>(events, voxel, tminmax, ref_mode, ref_fraction, normalize_t, b, n, T, H, W, row_stride,
+                                      bins, warped, oob_count, stream);
+}
+int ebos_warp_voxel_f64(const double* events, const double* voxel, const double* tminmax, int ref_mode, double ref_fraction,
+                        int normalize_t, int64_t b, int64_t n, int T, int H, int W, int row_stride, const uint8_t* bins,
+                        double* warped, int32_t* oob_count, ebos_stream_t stream) {
+  return ebos::warp_voxel_impl<double>(events, voxel, tminmax, ref_mode, ref_fraction, normalize_t, b, n, T, H, W, row_stride,
+                                       bins, warped, oob_count, stream);
+}
+int ebos_warp_voxel_bwd_f32(const float* events, const float* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                            const float* d_warped, int64_t b, int64_t n, int T, int H, int W, int row_stride,
+                            const uint8_t* bins, float* d_voxel, ebos_stream_t stream) {
+  return ebos::warp_voxel_bwd_impl<float>(events, tminmax, ref_mode, ref_fraction, normalize_t, d_warped, b, n, T, H, W,
+                                          row_stride, bins, d_voxel, stream);
+}
+int ebos_warp_voxel_bwd_f64(const double* events, const double* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                            const double* d_warped, int64_t b, int64_t n, int T, int H, int W, int row_stride,
+                            const uint8_t* bins, double* d_voxel, ebos_stream_t stream) {
+  return ebos::warp_voxel_bwd_impl<double>(events, tminmax, ref_mode, ref_fraction, normalize_t, d_warped, b, n, T, H, W,
+                                           row_stride, bins, d_voxel, stream);
+}
+
+int ebos_iwe_voxel_f32(const float* x, const float* y, const float* dt, const float* weight, const uint8_t* bins, int64_t n,
+                       const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w, float* iwe,
+                       ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(voxel && iwe, "ebos_iwe_voxel: NULL voxel/iwe");
+  EBOS_REQUIRE((x && y && dt && bins) || n == 0, "ebos_iwe_voxel: NULL event buffer");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(n >= 0 && H > 0 && W > 0 && row_stride > 0 && pad_h >= 0 && pad_w >= 0, "ebos_iwe_voxel: bad sizes");
+  if (n == 0) return EBOS_OK;
+  iwe_voxel_kernel<<<dim3(stream_grid(n, 256)), dim3(256), 0, as_stream(stream)>>>(x, y, dt, weight, bins, n, voxel, T, H, W,
+                                                                                   row_stride, pad_h, pad_w, iwe);
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel");
+  return EBOS_OK;
+}
+
+int ebos_iwe_voxel_tiled_f32(const float* xs, const float* ys, const float* dts, const float* weight, const uint8_t* bins,
+                             const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                             int tile_w, int halo, int splits, int pad_h, int pad_w, float* iwe, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(voxel && iwe && key_offsets, "ebos_iwe_voxel_tiled: NULL voxel/iwe/key_offsets");
+  EBOS_REQUIRE((xs && ys && dts && bins) || n == 0, "ebos_iwe_voxel_tiled: NULL event buffer");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel_tiled: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(n >= 0 && H > 0 && W > 0 && pad_h >= 0 && pad_w >= 0 && splits >= 1 && splits <= 64,
+               "ebos_iwe_voxel_tiled: bad sizes (splits=%d)", splits);
+  if (n == 0) return EBOS_OK;
+  hipStream_t s = as_stream(stream);
+  int rc = EBOS_ERR_UNSUPPORTED;
+#define EBOS_VOXEL_TILED_CASE(TH, TW, HL)                                                                            \
+  if (tile_h == TH && tile_w == TW && halo == HL)                                                                    \
+    rc = launch_voxel_tiled<TH, TW, HL>(xs, ys, dts, weight, bins, key_offsets, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
+  EBOS_VOXEL_TILED_CASE(64, 64, 32)
+  EBOS_VOXEL_TILED_CASE(32, 64, 32)
+  EBOS_VOXEL_TILED_CASE(32, 32, 32)
+  EBOS_VOXEL_TILED_CASE(16, 64, 32)
+  EBOS_VOXEL_TILED_CASE(64, 64, 16)
+  EBOS_VOXEL_TILED_CASE(32, 32, 16)
+  EBOS_VOXEL_TILED_CASE(32, 32, 8)
+  EBOS_VOXEL_TILED_CASE(64, 64, 64)
+  EBOS_VOXEL_TILED_CASE(32, 64, 48)
+#undef EBOS_VOXEL_TILED_CASE
+  if (rc == EBOS_ERR_UNSUPPORTED) {
+    set_error("ebos_iwe_voxel_tiled: no kernel built for tile %dx%d halo %d (see ebos_tiled_config)", tile_h, tile_w, halo);
+    return rc;
+  }
+  if (rc != EBOS_OK) return rc;
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel_tiled");
+  return EBOS_OK;
+}
+
+int ebos_iwe_voxel_bwd_f32(const float* x, const float* y, const float* dt, const float* weight, const uint8_t* bins,
+                           int64_t n, const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w,
+                           const float* g_image, const float* affine, int g_lo, int sorted, float* d_voxel, float* d_weight,
+                           ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(voxel && g_image && d_voxel, "ebos_iwe_voxel_bwd: NULL voxel/g_image/d_voxel");
+  EBOS_REQUIRE((x && y && dt && bins) || n == 0, "ebos_iwe_voxel_bwd: NULL event buffer");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel_bwd: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(n >= 0 && H > 0 && W > 0 && row_stride > 0 && pad_h >= 0 && pad_w >= 0 && g_lo >= 0,
+               "ebos_iwe_voxel_bwd: bad sizes");
+  if (n == 0) return EBOS_OK;
+  dim3 grid(stream_grid(n, 256)), block(256);
+  hipStream_t s = as_stream(stream);
+  if (sorted)
+    iwe_voxel_bwd_kernel<true><<<grid, block, 0, s>>>(x, y, dt, weight, bins, n, voxel, T, H, W, row_stride, pad_h, pad_w,
+                                                      g_image, affine, g_lo, d_voxel, d_weight);
+  else
+    iwe_voxel_bwd_kernel<false><<<grid, block, 0, s>>>(x, y, dt, weight, bins, n, voxel, T, H, W, row_stride, pad_h, pad_w,
+                                                       g_image, affine, g_lo, d_voxel, d_weight);
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel_bwd");
+  return EBOS_OK;
+}
+
+}  // extern "C"

@@ -184,6 +184,8 @@ class EventPlan:
     cdt: Optional[torch.Tensor] = None           # compact plan: f32 dt, NaN in padding slots
     part_table: Optional[torch.Tensor] = None    # adaptive work items (ebos_plan_parts): int32 [5 tiles + 1]
     dt_bound: Optional[float] = None             # max |dt| over the events as known on the host (dt_bound_for), else None
+    bins: Optional[torch.Tensor] = None          # time-aware plan: uint8 [n] time bin of each planned event (ops.time_bins)
+    time_bin: Optional[int] = None               # time-aware plan: the number of bins T the bins were made for
 
     @property
     def binned(self) -> bool:
@@ -292,16 +294,24 @@ class EventPlan:
     @staticmethod
     def build(events: torch.Tensor, image_size: Tuple[int, int], direction: Union[str, float] = "first",
               normalize_t: bool = True, tile: Optional[Tuple[int, int]] = DEFAULT_TILE, emit: str = "full",
-              deferred: bool = False) -> "EventPlan":
+              deferred: bool = False, time_bin: Optional[int] = None) -> "EventPlan":
         """events: [n, 4] (x=row, y=col, t, p), float32 or float64, on the GPU.
 
         ``tile=None`` keeps the input (time) order: only the general global-atomic kernels apply;
         ``tile="auto"`` picks the tile-private configuration that fills the GPU best (``choose_tile``).
         ``emit="compact"``: the LEAN build (``ebos_plan_lean``) -- only the compact events and offsets the tile-private
         kernels read, built by a two-level counting sort in a third of the time; such a plan takes no per-event weights
-        (``plan.lean``).  Windows with fractional source coordinates fall back to the full build."""
+        (``plan.lean``).  Windows with fractional source coordinates fall back to the full build.
+        ``time_bin=T``: a time-aware plan -- the time bin of every event among T bins (``ops.time_bins``: float64, the window's own
+        time range) is computed once in input order and kept permuted like the events (``plan.bins``, ``plan.time_bin``) for
+        ``iwe_voxel`` / ``contrast_voxel``.  Needs ``emit="full"`` and ``deferred=False``, the standing of per-event weights."""
         if emit not in ("full", "compact"):
             raise ValueError("emit must be 'full' or 'compact'")
+        if time_bin is not None:
+            time_bin = ops.check_time_bins(time_bin)
+            if emit != "full" or deferred:
+                raise NotImplementedError('EventPlan.build: time_bin needs the SoA events and the permutation of emit="full" with '
+                                          "deferred=False (a lean, compact or deferred plan keeps neither)")
         if isinstance(tile, str):
             if tile != "auto":
                 raise ValueError("tile must be a (tile_h, tile_w) pair, None or 'auto'")
@@ -333,6 +343,8 @@ class EventPlan:
             check(fn(ptr(events), ptr(tmm), ref_mode, frac, int(normalize_t), n, ptr(x), ptr(y), ptr(dt), ptr(p),
                      stream_ptr()), "ebos_events_to_soa")
         plan = EventPlan(x, y, dt, p, (H, W), n, n, dt_bound=dt_bound_for(direction, normalize_t))
+        if time_bin is not None:
+            plan.bins, plan.time_bin = ops.time_bins(events[None], time_bin, tmm)[0], time_bin
         if tile is not None:
             plan = plan.bin(tile)
         return plan
@@ -341,11 +353,14 @@ class EventPlan:
     def build_raw(col: torch.Tensor, row: torch.Tensor, t: torch.Tensor, pol: torch.Tensor, image_size: Tuple[int, int],
                   direction: Union[str, float] = "first", normalize_t: bool = True,
                   tile: Optional[Tuple[int, int]] = DEFAULT_TILE, ticks_per_second: float = 1e6,
-                  deferred: bool = False, emit: str = "full") -> "EventPlan":
+                  deferred: bool = False, emit: str = "full", time_bin: Optional[int] = None) -> "EventPlan":
         """Plan of a window given as raw sensor columns on the GPU -- ``raw_events/{x, y, t, p}`` of the CCS
         recordings: col int16 (sensor x), row int16 (sensor y), t int32/int64 ticks, pol bool/uint8
         (src/data_loader/ccs.py:57-66).  Same plan, bit for bit, as ``build`` on the float64 [n, 4] array the
         reference's loader makes of the window (:289-297), without materialising that array (32 B/event) anywhere."""
+        if time_bin is not None:
+            raise NotImplementedError('EventPlan.build_raw: a time-aware plan (time_bin) is built from the event array: '
+                                      'EventPlan.build(events, ..., emit="full", time_bin=T)')
         if isinstance(tile, str):
             if tile != "auto":
                 raise ValueError("tile must be a (tile_h, tile_w) pair, None or 'auto'")
@@ -531,6 +546,12 @@ class EventPlan:
         frac_pending = bool(fractional > 0 and th <= 256 and tw <= 256)
         out = EventPlan(xs[:kept], ys[:kept], dts[:kept], ps[:kept], self.image_size, kept, self.n_input,
                         (th, tw), key_offsets, src_perm, self.n_dropped + dropped, grp_offsets, cpix, cdt, part_table, self.dt_bound)
+        if self.bins is not None:
+            if deferred:
+                raise NotImplementedError('a time-aware plan (time_bin) needs the host read-back of the build: deferred=False, emit="full"')
+            bins = torch.zeros(n_pad, dtype=torch.uint8, device=dev)  # permuted and padded like the other SoA arrays
+            bins[:kept] = self.bins[perm[:kept].long()]
+            out.bins, out.time_bin = bins[:kept], self.time_bin
         out.__dict__["_frac"] = None          # (grp_offsets, cpix, cdt, cfx, cfy) once built
         out.__dict__["_frac_pending"] = frac_pending
         out.__dict__["_counts"], out.__dict__["_deferred"] = counts, bool(deferred)
@@ -744,6 +765,29 @@ class EventPlan:
             return v if sign == 1.0 else v * sign
         v = ops.gradient_magnitude(self.iwe_dense(flow, pad=pad, halo=halo, splits=splits), omit_boundary)
         return v if sign == 1.0 else v * sign
+
+    # ------------------------------------------------------------------------------------------ time-aware warp
+    def iwe_voxel(self, voxel: torch.Tensor, pad: Tuple[int, int] = (0, 0), weight: Optional[torch.Tensor] = None,
+                  halo: Optional[int] = DEFAULT_HALO, splits: Optional[int] = None) -> torch.Tensor:
+        """Fused time-aware warp + bilinear IWE on a plan built with ``time_bin=T``: voxel [T, 2, H, W] -> iwe
+        [H + 2 pad_h, W + 2 pad_w]; every event is displaced by the flow of its own time bin (``plan.bins``).  Differentiable
+        with respect to the voxel and the weights.  A binned plan whose (tile, halo) is a built ``ebos_tiled_config`` takes the
+        tiled kernel (LDS tile + halo, spill path beyond it: exact for any displacement), anything else -- ``halo=None``, an
+        un-binned plan -- the general global-atomic kernel.  ``halo="auto"`` means the default built halo here."""
+        return _FusedIweVoxel.apply(voxel, weight, self, (int(pad[0]), int(pad[1])), _voxel_halo(self, halo), self.resolve_splits(splits))
+
+    def contrast_voxel(self, voxel: torch.Tensor, cost: str = "image_variance", omit_boundary: bool = False,
+                       pad: Tuple[int, int] = (0, 0), halo: Optional[int] = DEFAULT_HALO,
+                       splits: Optional[int] = None) -> torch.Tensor:
+        """Contrast of the time-aware IWE under ``voxel`` (0-d tensor, raw contrast), differentiable with respect to the voxel:
+        the value and gradient of ``cost(iwe_voxel(voxel))`` through the existing cost kernels.  For ``image_variance`` the
+        gradient 2 (IWE - mean) / (M - 1) is folded into the backward event kernel as an affine map of the IWE (no d_iwe image)."""
+        if cost not in ("image_variance", "gradient_magnitude"):
+            raise KeyError(f"unknown contrast cost {cost!r}")
+        pad2, halo, splits = (int(pad[0]), int(pad[1])), _voxel_halo(self, halo), self.resolve_splits(splits)
+        if cost == "image_variance":
+            return _FusedVarianceVoxel.apply(voxel, self, pad2, bool(omit_boundary), halo, splits)
+        return ops.gradient_magnitude(_FusedIweVoxel.apply(voxel, None, self, pad2, halo, splits), omit_boundary)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1109,6 +1153,128 @@ class _FusedIweDense(torch.autograd.Function):
                                         splits=splits)
         d_weight = _unpermute(plan, d_w).to(wdt) if need_w else None
         return (d_flow.to(fdt) if ctx.needs_input_grad[0] else None), d_weight, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# time-aware warp on a plan: the flow of an event's own time bin
+# ----------------------------------------------------------------------------------------------
+_TILED_CONFIGS = None
+
+
+def _voxel_halo(plan: EventPlan, halo) -> Optional[int]:
+    """The built halo the tiled voxel kernel runs with, or None for the general kernel: ``"auto"`` is the default built halo."""
+    global _TILED_CONFIGS
+    if halo is None or not plan.binned:
+        return None
+    halo = DEFAULT_HALO if halo == "auto" else _max_halo(int(halo))
+    if _TILED_CONFIGS is None:
+        _TILED_CONFIGS = set(_hip.tiled_configs())
+    return halo if (plan.tile[0], plan.tile[1], halo) in _TILED_CONFIGS else None
+
+
+def _check_voxel(plan: EventPlan, voxel: torch.Tensor) -> torch.Tensor:
+    H, W = plan.image_size
+    if plan.bins is None:
+        raise ValueError('the plan holds no time bins: build it with EventPlan.build(..., emit="full", time_bin=T)')
+    if voxel.dim() != 4 or tuple(voxel.shape[1:]) != (2, H, W):
+        raise ValueError(f"voxel must be [T, 2, {H}, {W}], got {tuple(voxel.shape)}")
+    if voxel.shape[0] != plan.time_bin:
+        raise ValueError(f"the plan's bins were made for time_bin={plan.time_bin}, the voxel has {voxel.shape[0]} bins")
+    if voxel.device != plan.device:
+        raise _hip.HipUnavailableError(f"voxel is on {voxel.device}, the event plan on {plan.device}")
+    return voxel.to(torch.float32).contiguous()
+
+
+def _launch_iwe_voxel(plan: EventPlan, vox32: torch.Tensor, weight, pad, halo, splits) -> torch.Tensor:
+    lib = _hip.require_gpu()
+    _refuse_deferred(plan, "iwe_voxel")
+    H, W = plan.image_size
+    T = int(vox32.shape[0])
+    iwe = torch.zeros((H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
+    with _hip.on_device(plan.device):
+        if halo is not None:
+            check(lib.ebos_iwe_voxel_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(weight), ptr(plan.bins), ptr(plan.key_offsets),
+                                               plan.n, ptr(vox32), T, H, W, plan.tile[0], plan.tile[1], int(halo), max(1, splits),
+                                               pad[0], pad[1], ptr(iwe), stream_ptr()), "ebos_iwe_voxel_tiled")
+        else:
+            check(lib.ebos_iwe_voxel_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(weight), ptr(plan.bins), plan.n, ptr(vox32), T,
+                                         H, W, W, pad[0], pad[1], ptr(iwe), stream_ptr()), "ebos_iwe_voxel")
+    return iwe
+
+
+def _launch_voxel_bwd(plan: EventPlan, vox32, weight_p, pad, g_image, affine, g_lo, want_dweight, var_moments=None, upstream=None,
+                      sorted_: Optional[bool] = None):
+    """d_voxel [T, 2, H, W] (and d_weight in plan order).  ``var_moments`` / ``upstream``: the variance's gradient as the affine
+    map of ``g_image`` = the IWE (``ebos_image_variance_affine_f32``).  ``sorted_``: None = what the plan is."""
+    lib = _hip.require_gpu()
+    _refuse_deferred(plan, "iwe_voxel backward")
+    H, W = plan.image_size
+    T = int(vox32.shape[0])
+    d_w = torch.empty(plan.n, dtype=torch.float32, device=plan.device) if want_dweight else None
+    if var_moments is not None:
+        affine = torch.empty(2, dtype=torch.float32, device=plan.device)
+        with _hip.on_device(plan.device):
+            check(lib.ebos_image_variance_affine_f32(ptr(var_moments), ptr(upstream), 1, ptr(affine), stream_ptr()),
+                  "ebos_image_variance_affine")
+    d_voxel = torch.zeros((T, 2, H, W), dtype=torch.float32, device=plan.device)
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_voxel_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(weight_p), ptr(plan.bins), plan.n, ptr(vox32), T,
+                                         H, W, W, pad[0], pad[1], ptr(g_image), ptr(affine), g_lo,
+                                         int(plan.binned if sorted_ is None else sorted_), ptr(d_voxel), ptr(d_w), stream_ptr()),
+              "ebos_iwe_voxel_bwd")
+    return d_voxel, d_w
+
+
+class _FusedIweVoxel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, voxel, weight, plan, pad, halo, splits):
+        vox32 = _check_voxel(plan, voxel)
+        wp = _plan_weight(plan, weight)
+        iwe = _launch_iwe_voxel(plan, vox32, wp, pad, halo, splits)
+        ctx.save_for_backward(vox32, wp if wp is not None else torch.empty(0))
+        ctx.meta = (plan, pad, voxel.dtype, weight.dtype if weight is not None else None)
+        return iwe if voxel.dtype == torch.float32 else iwe.to(voxel.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        vox32, wp = ctx.saved_tensors
+        plan, pad, vdt, wdt = ctx.meta
+        wp = wp if wdt is not None else None
+        need_w = wdt is not None and ctx.needs_input_grad[1]
+        d_voxel, d_w = _launch_voxel_bwd(plan, vox32, wp, pad, g.to(torch.float32).contiguous(), None, 0, need_w)
+        d_weight = _unpermute(plan, d_w).to(wdt) if need_w else None
+        return (d_voxel.to(vdt) if ctx.needs_input_grad[0] else None), d_weight, None, None, None, None
+
+
+class _FusedVarianceVoxel(torch.autograd.Function):
+    """var(IWE(voxel)): the IWE by the fused time-aware kernel, the variance and its moments by the cost kernel; the backward
+    event kernel reads the IWE through the variance's affine map, so no d_iwe image is made."""
+
+    @staticmethod
+    def forward(ctx, voxel, plan, pad, omit, halo, splits):
+        lib = _hip.require_gpu()
+        vox32 = _check_voxel(plan, voxel)
+        iwe = _launch_iwe_voxel(plan, vox32, None, pad, halo, splits)
+        h, w = iwe.shape
+        out = torch.empty(1, dtype=torch.float32, device=plan.device)
+        moments = torch.empty((1, 2), dtype=torch.float64, device=plan.device)
+        nbytes = int(lib.ebos_cost_scratch_bytes(1))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
+        with _hip.on_device(plan.device):
+            check(lib.ebos_image_variance_f32(ptr(iwe), 1, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes,
+                                              stream_ptr()), "ebos_image_variance")
+        ctx.save_for_backward(vox32, iwe, moments)
+        ctx.meta = (plan, pad, int(omit), voxel.dtype)
+        return out[0].to(voxel.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        vox32, iwe, moments = ctx.saved_tensors
+        plan, pad, omit, vdt = ctx.meta
+        up = g.to(torch.float32).reshape(1).contiguous()
+        d_voxel, _ = _launch_voxel_bwd(plan, vox32, None, pad, iwe, None, omit, False, moments, up)
+        return d_voxel.to(vdt), None, None, None, None, None
 
 
 def _eager_ok(plan: EventPlan, flow: torch.Tensor, halo) -> bool:

@@ -102,6 +102,100 @@ def warp_dense(events: torch.Tensor, flow: torch.Tensor, ref_mode: int, ref_frac
 
 
 # ----------------------------------------------------------------------------------------------
+# time-aware warp: every event reads the flow of its own time bin of a flow voxel
+# ----------------------------------------------------------------------------------------------
+MAX_TIME_BINS = 255  # a bin is one uint8 per event
+
+
+def check_time_bins(T) -> int:
+    T = int(T)
+    if not 1 <= T <= MAX_TIME_BINS:
+        raise ValueError(f"a flow voxel has 1 to {MAX_TIME_BINS} time bins, got {T}")
+    return T
+
+
+def time_bins(events: torch.Tensor, T: int, tmm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """events [b, n, 4] -> the time bin of every event, uint8 [b, n]: ``k = min(int(tau * T), T - 1)`` with
+    ``tau = (t - tmin) / (tmax - tmin)`` per batch row, evaluated in float64 whatever the event dtype; ``tmax == tmin`` gives
+    bin 0.  ``tmm`` [b, 2] = ``time_range(events)`` if the caller already has it."""
+    if events.dim() != 3 or events.shape[-1] != 4:
+        raise ValueError(f"time_bins expects events [b,n,4], got {tuple(events.shape)}")
+    T = check_time_bins(T)
+    lib = _hip.require_gpu()
+    events = _cuda_contig(events, "events")
+    b, n, _ = events.shape
+    if tmm is None:
+        tmm = time_range(events)
+    tmm = _cuda_contig(tmm.to(events.dtype).reshape(b, 2), "tmm")
+    bins = torch.empty((b, n), dtype=torch.uint8, device=events.device)
+    with _hip.on_device(events.device):
+        fn = getattr(lib, "ebos_event_time_bins_" + suffix(events.dtype))
+        check(fn(ptr(events), ptr(tmm), b, n, T, ptr(bins), stream_ptr()), "ebos_event_time_bins")
+    return bins
+
+
+class _WarpVoxel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, events, voxel, ref_mode, ref_fraction, normalize_t, row_stride, oob, timebase, tmm, bins):
+        lib = _hip.require_gpu()
+        events = _cuda_contig(events, "events")
+        voxel = _cuda_contig(voxel, "voxel")
+        _same(events, voxel, "warp_voxel(events, voxel)")
+        b, n, _ = events.shape
+        T, H, W = voxel.shape[1], voxel.shape[-2], voxel.shape[-1]
+        if bins is None:  # the bins come from the window's own (min t, max t), whatever the reference time is
+            bins = time_bins(events, T, tmm)
+        bins = _cuda_contig(bins, "bins")
+        if timebase is not None:  # explicit (t_ref, period) per batch row
+            tmm = _cuda_contig(timebase.to(events.dtype).reshape(b, 2), "timebase")
+            ref_mode = _hip.REF_TIMEBASE
+        elif tmm is None:
+            tmm = time_range(events)
+        out = torch.empty_like(events)
+        with _hip.on_device(events.device):
+            fn = getattr(lib, "ebos_warp_voxel_" + suffix(events.dtype))
+            check(fn(ptr(events), ptr(voxel), ptr(tmm), ref_mode, ref_fraction, int(normalize_t), b, n, T, H, W,
+                     row_stride, ptr(bins), ptr(out), ptr(oob), stream_ptr()), "ebos_warp_voxel")
+        ctx.save_for_backward(events, tmm, bins)
+        ctx.meta = (ref_mode, ref_fraction, int(normalize_t), row_stride, tuple(voxel.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        events, tmm, bins = ctx.saved_tensors
+        ref_mode, ref_fraction, normalize_t, row_stride, vshape = ctx.meta
+        d_voxel = None
+        if ctx.needs_input_grad[1]:
+            lib = _hip.require_gpu()
+            g = _cuda_contig(g, "grad")
+            b, n, _ = events.shape
+            d_voxel = torch.zeros(vshape, dtype=events.dtype, device=events.device)
+            with _hip.on_device(events.device):
+                fn = getattr(lib, "ebos_warp_voxel_bwd_" + suffix(events.dtype))
+                check(fn(ptr(events), ptr(tmm), ref_mode, ref_fraction, normalize_t, ptr(g), b, n, vshape[1], vshape[-2],
+                         vshape[-1], row_stride, ptr(bins), ptr(d_voxel), stream_ptr()), "ebos_warp_voxel_bwd")
+        return None, d_voxel, None, None, None, None, None, None, None, None
+
+
+def warp_voxel(events: torch.Tensor, voxel: torch.Tensor, ref_mode: int, ref_fraction: float, normalize_t: bool,
+               row_stride: Optional[int] = None, oob: Optional[torch.Tensor] = None,
+               timebase: Optional[torch.Tensor] = None, tmm: Optional[torch.Tensor] = None,
+               bins: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """events [b, n, 4], voxel [b, T, 2, H, W] -> warped [b, n, 4]: ``warp_dense`` with every event reading the flow of its own
+    time bin (``time_bins``; ``bins`` uint8 [b, n] if the caller already has them).  The gradient goes to the voxel and to
+    nothing else.  ``timebase`` / ``tmm`` as in ``warp_dense``; the bins always come from the window's own time range."""
+    if events.dim() != 3 or events.shape[-1] != 4 or voxel.dim() != 5 or voxel.shape[2] != 2:
+        raise ValueError(f"warp_voxel expects events [b,n,4] and voxel [b,T,2,H,W], got {tuple(events.shape)}, {tuple(voxel.shape)}")
+    check_time_bins(voxel.shape[1])
+    if events.shape[0] != voxel.shape[0]:
+        raise ValueError("warp_voxel: batch sizes of events and voxel differ")
+    if bins is not None and (bins.dtype != torch.uint8 or tuple(bins.shape) != tuple(events.shape[:2])):
+        raise ValueError("warp_voxel: bins must be uint8 [b, n]")
+    stride = int(voxel.shape[-1] if row_stride is None else row_stride)
+    return _WarpVoxel.apply(events, voxel, int(ref_mode), float(ref_fraction), bool(normalize_t), stride, oob, timebase, tmm, bins)
+
+
+# ----------------------------------------------------------------------------------------------
 # A4  2-DoF warp
 # ----------------------------------------------------------------------------------------------
 class _Warp2Dof(torch.autograd.Function):

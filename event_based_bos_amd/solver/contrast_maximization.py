@@ -15,6 +15,12 @@ parameters, cost, cost_with_weight, outer_padding, iwe.{method, blur_sigma}, pat
 optimizer.{method (Adam | CG | BFGS | L-BFGS-B | TNC | SLSQP | grid | random | TPE | optuna + sampler), sampler, seed, n_iter, parameters.lr,
 options, graph, fused,
 refine_iters}.
+
+``time_aware: {time_bin, scheme: upwind | burgers, t0_location: first | middle, clamp}`` (optional, this build's; dense-flow only): the
+time-aware objective.  The dense flow is the flow at t0; ``flow_voxel_batch`` transports it into ``time_bin`` bins, every event is
+warped by the flow of its own bin (``EventPlan.contrast_voxel``) and the gradient comes back through the voxel's adjoint to the
+patch grid.  Such a solver runs the autograd loop (Adam or the scipy methods): ``fused``, ``resident`` and HIP-graph capture are off
+and ``loop_mode`` reports "autograd".  Without the block nothing changes.
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import costs, ops
+from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
 from ..event_plan import EventPlan
@@ -35,6 +42,25 @@ logger = logging.getLogger(__name__)
 
 CONTRAST_COSTS = ("image_variance", "gradient_magnitude")
 SCIPY_METHODS = ("CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")  # first-order methods of scipy.optimize.minimize
+
+
+def parse_time_aware(block) -> Optional[dict]:
+    """The ``time_aware`` block of the solver's configuration -> {time_bin, scheme, t0_location, clamp}, or None without one."""
+    if block is None:
+        return None
+    block = dict(block)
+    unknown = sorted(set(block) - {"time_bin", "scheme", "t0_location", "clamp"})
+    if unknown:
+        raise ValueError(f"time_aware: unknown key(s) {unknown}; it takes time_bin, scheme, t0_location, clamp")
+    if "time_bin" not in block:
+        raise ValueError("time_aware needs time_bin, the number of bins of the flow voxel")
+    out = {"time_bin": ops.check_time_bins(block["time_bin"]), "scheme": block.get("scheme", "upwind"),
+           "t0_location": block.get("t0_location", "middle"), "clamp": None if block.get("clamp") is None else float(block["clamp"])}
+    if out["scheme"] not in ("upwind", "burgers"):
+        raise ValueError(f"time_aware.scheme must be 'upwind' or 'burgers', got {out['scheme']!r}")
+    if out["t0_location"] not in ("first", "middle"):
+        raise ValueError(f"time_aware.t0_location must be 'first' or 'middle', got {out['t0_location']!r}")
+    return out
 
 
 def patch_grid_shape(image_size, patch_size, sliding_window):
@@ -125,10 +151,29 @@ class ContrastMaximizationMixin(object):
         self.loop_mode: Optional[str] = None
         self.loop_modes: List[str] = []   # ... of every pyramid scale of the last estimate, coarse to fine
         self.history: List[float] = []
+        # time_aware (module docstring): the flow is the flow at t0 of a voxel, every event reads its own bin; the autograd loop only
+        self.time_aware = parse_time_aware(cfg.get("time_aware"))
+        if self.time_aware is not None:
+            if self.motion_model != "dense-flow":
+                raise NotImplementedError(f"time_aware is defined for motion_model 'dense-flow', not {self.motion_model!r}")
+            self.use_graph = self.fused_loop = False
+            self.resident = False
 
     # ------------------------------------------------------------------ objective pieces
     def _contrast(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
         total = 0.0
+        if self.time_aware is not None:
+            ta = self.time_aware
+            voxel = flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0]
+            if self.blur_sigma > 0:
+                iwe = EventImageConverter._gaussian_blur3(plan.iwe_voxel(voxel, pad=(self.pad, self.pad), halo=self.halo), self.blur_sigma)
+                for name, wgt in self.contrast_terms.items():
+                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
+                    total = total + wgt * fn(iwe, self.omit_boundary)
+                return total
+            for name, wgt in self.contrast_terms.items():
+                total = total + wgt * plan.contrast_voxel(voxel, name, self.omit_boundary, pad=(self.pad, self.pad), halo=self.halo)
+            return total
         if self.blur_sigma > 0:
             iwe = plan.iwe_dense(flow, pad=(self.pad, self.pad), halo=self.halo)
             iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
@@ -157,8 +202,12 @@ class ContrastMaximizationMixin(object):
         # (a stream of sub-pixel rectified events is fractional window after window: once a window fell back, the lean
         # attempt -- its kernels and its read-back, ~0.3 ms of a 100 k-event window's build -- is skipped until a full build finds
         # integer coordinates again; either build is valid for either kind of window)
-        plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
-                               emit="full" if getattr(self, "_fractional_stream", False) else "compact")
+        if self.time_aware is not None:   # the bins travel with the SoA events of the full build
+            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
+                                   time_bin=self.time_aware["time_bin"])
+        else:
+            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
+                                   emit="full" if getattr(self, "_fractional_stream", False) else "compact")
         self._fractional_stream = plan.fractional
         self.history = []
         # The optimisation loops below call loss.backward() thousands of times on graphs of one or two nodes: with the autograd
@@ -261,6 +310,9 @@ class ContrastMaximizationMixin(object):
             self.history += loop.losses[:n_iter].cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
             return loop.theta
         self.fused = False
+        if self.time_aware is not None:
+            self.loop_mode = "autograd"
+            self.loop_modes.append("autograd")
         if self.opt_method in SCIPY_METHODS:
             if self.fused_loop and fused_loop.objective_supported(self.contrast_terms, self.flow_terms, self.blur_sigma, plan,
                                                                   self.halo):

@@ -80,6 +80,9 @@ class WindowPipeline(object):
     def __init__(self, solver: ContrastMaximization, n_concurrent: Optional[int] = None, device="cuda", resident: Optional[bool] = None,
                  poisson: bool = False, batch_ingest: bool = False):
         # the patch-flow solver, or the 2-DoF Adam loop of the reference's shipped YAML (configs/hot_plate1.yaml:47,70)
+        if getattr(solver, "time_aware", None) is not None:
+            raise NotImplementedError("WindowPipeline runs the native solver loops; a time_aware solver runs the autograd loop: "
+                                      "call its estimate() window by window")
         self.two_dof = solver.motion_model in ("2d-translation", "rigid-optical-flow")
         if solver.motion_model != "dense-flow" and not (self.two_dof and solver.opt_method == "Adam"):
             raise NotImplementedError("WindowPipeline drives the patch-flow (dense-flow) solver and the 2-DoF Adam loop")

@@ -14,6 +14,21 @@ Semantics kept from the reference:
   * ``direction`` must be a python ``float`` or one of first/middle/last/random/before/after (:245-262)
 On equal dtypes the warped coordinates are bit-identical to the reference (same operation order,
 no FMA contraction).
+
+The time-aware warp, ``motion_model="dense-flow-voxel"``.  The reference documents a voxel motion model
+("dense-flow-voxel-optimized", :199, 211) and ships without its branch (:223-228); here it is:
+  * motion = a flow voxel [(b,) T, 2, H, W] as ``construct_dense_flow_voxel_*`` returns it, channel 0 = rows, 1 <= T <= 255
+  * bin:  tau = (t - tmin) / (tmax - tmin) per batch row, ALWAYS in float64 (float32 times are widened exactly);
+    k = min(int(tau * T), T - 1);  tmax == tmin -> k = 0 for every event;  T == 1 -> every event in bin 0.
+    The bin does not depend on ``direction``.
+  * warp:  i = trunc(x) * image_size[1] + trunc(y);  x' = x - dt * V[k, 0, i],  y' = y - dt * V[k, 1, i],  t' = dt,  p' = p,
+    with dt exactly as in dense-flow (direction, ``normalize_t``, operation order in the element type, no FMA contraction)
+  * a source pixel outside [0, H * W) behaves as in dense-flow: the event passes through un-displaced, is counted, and
+    ``IndexError`` is raised under the same strict / deferred rules
+  * a wrong rank or channel count, T = 0 or T > 255 raise ``ValueError`` -- before ``HipUnavailableError``
+Out of scope: interpolating between neighbouring bins in time; ``flow_propagate_bin``, which stays accepted and ignored;
+gradients with respect to event coordinates or times (the gradient goes to the voxel alone).  The result is never lazy and
+never provenance-tagged.
 """
 from __future__ import annotations
 
@@ -32,6 +47,7 @@ from .types import FLOAT_TORCH, NUMPY_TORCH, is_numpy, is_torch
 logger = logging.getLogger(__name__)
 
 TRANSLATION_MODELS = ("2d-translation", "rigid-optical-flow")
+VOXEL_MODEL = "dense-flow-voxel"
 
 
 class MotionModelKeyError(Exception):
@@ -181,6 +197,8 @@ class Warp(object):
         if motion_model in TRANSLATION_MODELS:
             assert motion.shape[-1] == 2
             return self._warp_2dof(events, motion, ref_mode, frac, None, None)
+        if motion_model == VOXEL_MODEL:
+            return self._warp_dense(events, motion, ref_mode, frac, None, voxel=True)
         raise MotionModelKeyError(f"{motion_model = } not supported")
 
     def warp_event_now(self, events, motion, ref_mode, frac, direction) -> torch.Tensor:
@@ -230,17 +248,28 @@ class Warp(object):
             return True
         return (kind != GPU) if self.strict is None else bool(self.strict)
 
-    def _warp_dense(self, event, flow, ref_mode, frac, timebase) -> Tuple[NUMPY_TORCH, dict]:
+    @staticmethod
+    def _check_voxel(event, voxel) -> None:
+        """Argument errors of the time-aware warp: raised before anything asks for the GPU."""
+        if event.ndim not in (2, 3) or voxel.ndim != event.ndim + 2 or voxel.shape[-3] != 2 or event.shape[-1] != 4:
+            raise ValueError(f"dense-flow-voxel expects events [(b,) n, 4] and a voxel [(b,) T, 2, H, W], got "
+                             f"{tuple(event.shape)}, {tuple(voxel.shape)}")
+        ops.check_time_bins(voxel.shape[-4])
+
+    def _warp_dense(self, event, flow, ref_mode, frac, timebase, voxel: bool = False) -> Tuple[NUMPY_TORCH, dict]:
+        """The dense-flow warp; ``voxel``: ``flow`` is a flow voxel [(b,) T, 2, H, W] and every event reads its own time bin."""
         kind = kind_of(event)
         if kind == NUMPY:
             assert is_numpy(flow)
         else:
             assert is_torch(flow)
+        if voxel:
+            self._check_voxel(event, flow)
         ev = to_gpu(event)
         fl = to_gpu(flow, device=ev.device, dtype=ev.dtype)
         if ev.dim() == 2:
             ev, fl = ev[None], fl[None]
-        assert ev.dim() == fl.dim() - 1 == 3  # same shape contract as :312
+        assert ev.dim() == fl.dim() - (2 if voxel else 1) == 3  # same shape contract as :312
         strict = self._strict_for(kind)
         lazy = (not strict) and self.strict is None and os.environ.get("EBOS_STRICT", "") != "0" \
             and not torch.cuda.is_current_stream_capturing()
@@ -266,7 +295,14 @@ class Warp(object):
                     event._ebos_time_range = (event._version, tmm)
                 except AttributeError:
                     pass
-        warped = ops.warp_dense(ev, fl, ref_mode, frac, self.normalize_t, int(self.image_size[1]), oob, timebase, tmm)
+        if voxel:
+            if tmm is None:  # an explicit reference time: the bins still come from the window's own (min t, max t)
+                tmm = ops.time_range(ev)
+            bins = ops.time_bins(ev, fl.shape[1], tmm)
+            warped = ops.warp_voxel(ev, fl, ref_mode, frac, self.normalize_t, int(self.image_size[1]), oob, timebase,
+                                    None if timebase is not None else tmm, bins)
+        else:
+            warped = ops.warp_dense(ev, fl, ref_mode, frac, self.normalize_t, int(self.image_size[1]), oob, timebase, tmm)
         if strict and int(oob.item()) > 0:
             raise IndexError(f"{int(oob.item())} event(s) have a source pixel outside the flow field "
                              f"(index out of range in gather, src/warp.py:334-336)")
@@ -343,6 +379,15 @@ class Warp(object):
         ev = to_gpu(event)
         tb = self._timebase(ev if ev.dim() == 3 else ev[None], reference_time)
         return self._warp_dense(event, flow, _hip.REF_TIMEBASE, 0.0, tb)
+
+    def warp_event_from_optical_flow_voxel(self, event: NUMPY_TORCH, voxel: NUMPY_TORCH,
+                                           reference_time: FLOAT_TORCH) -> Tuple[NUMPY_TORCH, dict]:
+        """The time-aware warp (``"dense-flow-voxel"``) with an explicit reference time: the bins come from the window's own
+        time range, dt from ``reference_time``."""
+        self._check_voxel(event, voxel)
+        ev = to_gpu(event)
+        tb = self._timebase(ev if ev.dim() == 3 else ev[None], reference_time)
+        return self._warp_dense(event, voxel, _hip.REF_TIMEBASE, 0.0, tb, voxel=True)
 
     def warp_event_2dof_xy(self, event: NUMPY_TORCH, translation: NUMPY_TORCH, reference_time: FLOAT_TORCH,
                            time_period: Optional[FLOAT_TORCH] = None) -> Tuple[NUMPY_TORCH, dict]:

@@ -1454,6 +1454,66 @@ int ebos_flow_voxel_propagate_bilinear_adjoint_f64(int B, int T, int H, int W, c
 int ebos_flow_voxel_clamp_f32(int64_t n, const float* in, float* out, double clamp, ebos_stream_t stream);
 int ebos_flow_voxel_clamp_f64(int64_t n, const double* in, double* out, double clamp, ebos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Time-aware warp: every event is displaced by the flow of ITS OWN time bin of a flow voxel
+ *   (voxel [(b,) T, 2, H, W] as ebos_flow_voxel_advect_* / _propagate_bilinear_* write it, channel 0 = rows).
+ *   The reference documents the motion model ("dense-flow-voxel-optimized", src/warp.py:199, 211) and
+ *   ships without its branch (:223-228); this is A3 and the fused hot path with one more gather index.
+ *
+ * bin      tau = (t - tmin) / (tmax - tmin) evaluated in float64 whatever the event type (float32 times
+ *          are widened exactly);  k = min((int)(tau * T), T - 1);  tmax == tmin -> k = 0 for every event.
+ *          The bin does not depend on the reference time.  1 <= T <= 255 everywhere below.
+ * warp     i = trunc(x) * row_stride + trunc(y)
+ *          x' = x - dt * voxel[k][0][i];  y' = y - dt * voxel[k][1][i];  t' = dt;  p' = p
+ *          dt, the operation order, the rounding (no FMA contraction), the out-of-range rule and
+ *          *oob_count exactly as ebos_warp_dense_*.
+ * Every entry reads a bin as min(bins[i], T - 1), so a bins array made for another T never indexes
+ * outside the voxel.
+ *
+ * ebos_event_time_bins_*   events [b, n, 4], tminmax [b, 2] (ebos_time_range_*) -> bins [b, n] uint8.
+ * ebos_warp_voxel_*        the arguments of ebos_warp_dense_* plus T and bins [b, n]; voxel [b, T, 2, H, W].
+ * ebos_warp_voxel_bwd_*    d_voxel[k][c][i] += -dt * d_warped[..., c]  (accumulates; d_voxel [b, T, 2, H, W]).
+ * ---------------------------------------------------------------------------------------- */
+int ebos_event_time_bins_f32(const float* events, const float* tminmax, int64_t b, int64_t n, int T, uint8_t* bins,
+                             ebos_stream_t stream);
+int ebos_event_time_bins_f64(const double* events, const double* tminmax, int64_t b, int64_t n, int T, uint8_t* bins,
+                             ebos_stream_t stream);
+int ebos_warp_voxel_f32(const float* events, const float* voxel, const float* tminmax, int ref_mode, double ref_fraction,
+                        int normalize_t, int64_t b, int64_t n, int T, int H, int W, int row_stride, const uint8_t* bins,
+                        float* warped, int32_t* oob_count, ebos_stream_t stream);
+int ebos_warp_voxel_f64(const double* events, const double* voxel, const double* tminmax, int ref_mode, double ref_fraction,
+                        int normalize_t, int64_t b, int64_t n, int T, int H, int W, int row_stride, const uint8_t* bins,
+                        double* warped, int32_t* oob_count, ebos_stream_t stream);
+int ebos_warp_voxel_bwd_f32(const float* events, const float* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                            const float* d_warped, int64_t b, int64_t n, int T, int H, int W, int row_stride,
+                            const uint8_t* bins, float* d_voxel, ebos_stream_t stream);
+int ebos_warp_voxel_bwd_f64(const double* events, const double* tminmax, int ref_mode, double ref_fraction, int normalize_t,
+                            const double* d_warped, int64_t b, int64_t n, int T, int H, int W, int row_stride,
+                            const uint8_t* bins, double* d_voxel, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused hot path of the time-aware warp: the three entries of the dense-flow path with the gather
+ *   voxel[(k * 2 + c) * H * W + i] and the bins (uint8 [n], in the order of the events) as one more SoA stream.
+ *   x, y, dt, weight(nullable): SoA f32 [n];  voxel [T, 2, H, W];  iwe [h, w] with h = H + 2 pad_h ...
+ * ebos_iwe_voxel_f32        any event order; one global float atomic per tap.  Accumulates into iwe.
+ * ebos_iwe_voxel_tiled_f32  binned events: ebos_iwe_dense_tiled_f32's organisation, (tile_h, tile_w, halo)
+ *   configurations (ebos_tiled_config), LDS accumulator rule and spill path beyond the halo.  Accumulates into iwe.
+ * ebos_iwe_voxel_bwd_f32    g_image / affine / g_lo / d_weight as in ebos_iwe_dense_bwd_f32;
+ *   d_voxel[k][c][i] += -dt * dL/d(x', y')  (accumulates; d_voxel [T, 2, H, W]).  sorted != 0 promises that
+ *   events sharing a source pixel are contiguous; the wave's segmented reduction keys on (k, i), so the
+ *   result is right for any order of a pixel's events among its bins.
+ * ---------------------------------------------------------------------------------------- */
+int ebos_iwe_voxel_f32(const float* x, const float* y, const float* dt, const float* weight, const uint8_t* bins, int64_t n,
+                       const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w, float* iwe,
+                       ebos_stream_t stream);
+int ebos_iwe_voxel_tiled_f32(const float* xs, const float* ys, const float* dts, const float* weight, const uint8_t* bins,
+                             const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                             int tile_w, int halo, int splits, int pad_h, int pad_w, float* iwe, ebos_stream_t stream);
+int ebos_iwe_voxel_bwd_f32(const float* x, const float* y, const float* dt, const float* weight, const uint8_t* bins,
+                           int64_t n, const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w,
+                           const float* g_image, const float* affine, int g_lo, int sorted, float* d_voxel, float* d_weight,
+                           ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
