@@ -23,6 +23,8 @@ tub-rip/event_based_bos:
     flow_voxel           the reference's time-aware flow: upwind / Burgers / bilinear flow voxels of one flow or a batch, and their mean
     time_bins, warp_voxel   the time-aware warp: every event displaced by the flow of its own time bin of a flow voxel
                          (Warp.warp_event(.., "dense-flow-voxel"), EventPlan.build(.., time_bin=T).iwe_voxel / contrast_voxel)
+                         and its contrast maximisation as a native loop: EventPlan.variance_voxel_value_and_grad (pixel-owner
+                         backward into the voxel), solver.time_aware_loop.TimeAwarePatchLoop, solver block time_aware.native
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the

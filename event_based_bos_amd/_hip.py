@@ -290,6 +290,9 @@ SIGNATURES = {
     "ebos_iwe_voxel_f32": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ebos_iwe_voxel_tiled_f32": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "ebos_iwe_voxel_bwd_f32": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "ebos_iwe_voxel_owner_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "ebos_cmax_voxel_solve_f32": (_I, [_P, _I, _P]),
+    "ebos_cmax_voxel_gradient_f32": (_I, [_P, _P]),
 }
 
 
@@ -335,6 +338,21 @@ class CmaxPatchProblem(C.Structure):
                 [(k, _P) for k in ("moments", "upstream", "reg_partials", "upsample_scratch", "workspace")] +
                 [("workspace_bytes", _Z), ("losses", _P), ("losses_cap", _I), ("theta_mask", _P), ("grad_partials", _P),
                  ("grad_partials_bytes", _Z), ("blur_k0", _F), ("blur_k1", _F), ("blur_image", _P), ("cfx", _P), ("cfy", _P)])
+
+
+class CmaxVoxelProblem(C.Structure):
+    """``ebos_cmax_voxel_problem`` of include/ebos_hip.h (same field order)."""
+    _fields_ = ([(k, _P) for k in ("xs", "ys", "dts", "bins", "key_offsets")] + [("n", _L)] +
+                [(k, _I) for k in ("H", "W", "tile_h", "tile_w", "halo", "pad_h", "pad_w", "omit_boundary", "splits")] +
+                [(k, _I) for k in ("T", "scheme", "t0_index", "wrap_last", "route", "has_clamp")] + [("clamp", _D), ("owner_bwd", _I)] +
+                [(k, _I) for k in ("gh", "gw", "patch_h", "patch_w", "slide_h", "slide_w")] +
+                [(k, _F) for k in ("w_variance", "w_flow_norm", "w_image_gradient")] +
+                [(k, _D) for k in ("lr", "beta1", "beta2", "eps")] +
+                [(k, _P) for k in ("theta", "d_theta", "exp_avg", "exp_avg_sq", "step")] + [("steps_done", _I)] +
+                [(k, _P) for k in ("dense", "d_dense", "d_reg", "voxel", "voxel_clamped", "d_voxel", "iwe", "variance", "moments", "upstream",
+                                   "affine", "cost_scratch")] +
+                [("cost_scratch_bytes", _Z), ("reg_partials", _P), ("upsample_scratch", _P), ("adjoint_workspace", _P),
+                 ("adjoint_workspace_elems", _L), ("losses", _P), ("losses_cap", _I), ("theta_mask", _P)])
 
 
 class Cmax2dofProblem(C.Structure):

@@ -7,6 +7,8 @@
 //            (dt and the operation order exactly as warp_kernels.hip: src/warp.py:283-287, 330-337, no FMA contraction)
 //   fused    iwe_dense_kernel / iwe_dense_tiled_kernel / iwe_dense_bwd_kernel of iwe_fused.hip with the gather
 //            V[(k * 2 + c) * H * W + lin] and the bins as one more SoA stream (1 B/event)
+//   owner    iwe_voxel_owner_bwd_kernel: the backward for a binned plan, summed by the owner of each source pixel's run -- no
+//            atomics, every cell of d_voxel written, the same bits on every call
 //
 // Every kernel reads a bin as min(bins[i], T - 1): a bins array that was made for another T cannot index outside the voxel.
 // Dead and padding slots never gather.
@@ -403,6 +405,195 @@ iwe_voxel_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, c
   }
 }
 
+// ---- fused backward, pixel-owner form ------------------------------------------------------------
+// A cell d_voxel[k][c][i] receives addends only from events whose SOURCE pixel is i, and a binned plan keeps the events of one
+// source pixel in one run (key_offsets).  One lane per key walks its pixel's run and is the only writer of that pixel's 2 T cells:
+// no atomics, every cell written (zeros where nothing lands), the order of the additions fixed by the plan -> the same bits on
+// every call.  Keys of an overhanging tile's pixels outside the image own no cell.
+//   Runs are walked kOwnerChunk events at a time, in stages, so that a lane's loads are in flight together instead of one event's
+//   chain after the other: the events, then the voxel gathers, then the four taps of each, then the arithmetic.
+//   run <= kOwnerChunk   the addends stay in registers; each cell is stored once, the sum of the run's events of that bin in run order
+//   run <= kOwnerHot     the lane zeroes its cells and adds chunk after chunk, event by event (plain loads and stores of cells
+//                        nobody else touches)
+//   longer (a hot pixel) the whole wave walks the run 64 events at a time; per chunk and per bin present in it, a butterfly sum
+//                        over the lanes (a fixed tree), added to the bin's running sum, which lane (k mod 64) keeps in registers
+constexpr int kOwnerChunk = 8;
+constexpr int kOwnerHot = 64;
+constexpr int kOwnerSlots = 4;  // bins per lane of the hot path: 4 x 64 >= 255
+
+// the addend of iwe_voxel_bwd_kernel for one event of source pixel `lin` and bin `kb`
+__device__ __forceinline__ void owner_event_grad(const GradImage& G, const float* __restrict__ voxel, int64_t hw, int64_t lin, int kb,
+                                                 float ex, float ey, float edt, float wv, int pad_h, int pad_w, float* gx, float* gy) {
+  const float* f0 = voxel + (int64_t)kb * 2 * hw;
+  const Taps f = warped_taps(ex, ey, -edt * f0[lin], -edt * f0[hw + lin], pad_h, pad_w);
+  const float g00 = G.at(f.R, f.C), g10 = G.at(f.R + 1, f.C);
+  const float g01 = G.at(f.R, f.C + 1), g11 = G.at(f.R + 1, f.C + 1);
+  const float a = 1.0f - f.fr, b = 1.0f - f.fc;
+  const float dx = wv * (b * (g10 - g00) + f.fc * (g11 - g01));  // dL/dx'
+  const float dy = wv * (a * (g01 - g00) + f.fr * (g11 - g10));  // dL/dy'
+  *gx = -edt * dx;
+  *gy = -edt * dy;
+}
+
+// events [b0, b0 + cnt) of source pixel `lin`, cnt <= kOwnerChunk: their bins (-1 in the unused slots) and addends (0 there)
+__device__ __forceinline__ void owner_chunk(const GradImage& G, const float* __restrict__ x, const float* __restrict__ y,
+                                            const float* __restrict__ dt, const float* __restrict__ weight,
+                                            const uint8_t* __restrict__ bins, const float* __restrict__ voxel, int nbins, int64_t hw,
+                                            int64_t lin, int32_t b0, int cnt, int pad_h, int pad_w, int (&kb)[kOwnerChunk],
+                                            float (&gx)[kOwnerChunk], float (&gy)[kOwnerChunk]) {
+  float ex[kOwnerChunk], ey[kOwnerChunk], edt[kOwnerChunk], fu[kOwnerChunk], fv[kOwnerChunk];
+#pragma unroll
+  for (int j = 0; j < kOwnerChunk; ++j) {
+    const bool live = j < cnt;
+    const int32_t i = b0 + j;
+    kb[j] = live ? clamp_bin(bins[i], nbins) : -1;
+    ex[j] = live ? x[i] : 0.0f;
+    ey[j] = live ? y[i] : 0.0f;
+    edt[j] = live ? dt[i] : 0.0f;
+  }
+#pragma unroll
+  for (int j = 0; j < kOwnerChunk; ++j) {
+    const bool live = j < cnt;
+    const float* f0 = voxel + (int64_t)(live ? kb[j] : 0) * 2 * hw;
+    fu[j] = live ? f0[lin] : 0.0f;
+    fv[j] = live ? f0[hw + lin] : 0.0f;
+  }
+  float g00[kOwnerChunk], g10[kOwnerChunk], g01[kOwnerChunk], g11[kOwnerChunk], fr[kOwnerChunk], fc[kOwnerChunk];
+#pragma unroll
+  for (int j = 0; j < kOwnerChunk; ++j) {
+    const bool live = j < cnt;
+    const Taps f = warped_taps(ex[j], ey[j], -edt[j] * fu[j], -edt[j] * fv[j], pad_h, pad_w);
+    fr[j] = f.fr;
+    fc[j] = f.fc;
+    g00[j] = live ? G.at(f.R, f.C) : 0.0f;
+    g10[j] = live ? G.at(f.R + 1, f.C) : 0.0f;
+    g01[j] = live ? G.at(f.R, f.C + 1) : 0.0f;
+    g11[j] = live ? G.at(f.R + 1, f.C + 1) : 0.0f;
+  }
+#pragma unroll
+  for (int j = 0; j < kOwnerChunk; ++j) {
+    const float wv = (weight != nullptr && j < cnt) ? weight[b0 + j] : 1.0f;
+    const float a = 1.0f - fr[j], b = 1.0f - fc[j];
+    const float dx = wv * (b * (g10[j] - g00[j]) + fc[j] * (g11[j] - g01[j]));  // dL/dx'
+    const float dy = wv * (a * (g01[j] - g00[j]) + fr[j] * (g11[j] - g10[j]));  // dL/dy'
+    gx[j] = -edt[j] * dx;  // (an unused slot: edt = 0 and every g = 0)
+    gy[j] = -edt[j] * dy;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+iwe_voxel_owner_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
+                           const float* __restrict__ weight, const uint8_t* __restrict__ bins,
+                           const int32_t* __restrict__ key_offsets, int32_t n, const float* __restrict__ voxel, int nbins, int H,
+                           int W, int tile_h, int tile_w, int tiles_x, int64_t n_keys, int pad_h, int pad_w,
+                           const float* __restrict__ g_image, const float* __restrict__ affine, int g_lo, float* d_voxel) {
+  const int64_t hw = (int64_t)H * W;
+  GradImage G;
+  G.g = g_image;
+  G.a = affine ? affine[0] : 1.0f;
+  G.c = affine ? affine[1] : 0.0f;
+  G.h = H + 2 * pad_h;
+  G.w = W + 2 * pad_w;
+  G.lo = g_lo;
+  const int lane = threadIdx.x & (kWave - 1);
+  // every lane of a wave stays to the end (the hot path shuffles): a key beyond the table or outside the image owns nothing
+  const int64_t key = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t lin = -1;
+  int32_t beg = 0, end = 0;
+  if (key < n_keys) {
+    const int tile_px = tile_h * tile_w;
+    const int tile = (int)(key / tile_px), pit = (int)(key - (int64_t)tile * tile_px);
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int r = ty * tile_h + pit / tile_w, c = tx * tile_w + pit % tile_w;
+    if (r < H && c < W) {
+      lin = (int64_t)r * W + c;
+      beg = min(max(key_offsets[key], 0), n);  // a run never leaves the event arrays, whatever the table holds
+      end = min(max(key_offsets[key + 1], beg), n);
+    }
+  }
+  const int len = end - beg;
+  const bool hot = lin >= 0 && len > kOwnerHot;
+  if (lin >= 0 && !hot) {
+    float* cell = d_voxel + lin;
+    int kb[kOwnerChunk];
+    float gx[kOwnerChunk], gy[kOwnerChunk];
+    if (len <= kOwnerChunk) {
+      owner_chunk(G, x, y, dt, weight, bins, voxel, nbins, hw, lin, beg, len, pad_h, pad_w, kb, gx, gy);
+      for (int k = 0; k < nbins; ++k) {
+        float sx = 0.0f, sy = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kOwnerChunk; ++j)
+          if (kb[j] == k) {
+            sx += gx[j];
+            sy += gy[j];
+          }
+        cell[(int64_t)(2 * k) * hw] = sx;  // consecutive lanes: consecutive columns of one image row
+        cell[(int64_t)(2 * k + 1) * hw] = sy;
+      }
+    } else {
+      for (int k = 0; k < 2 * nbins; ++k) cell[(int64_t)k * hw] = 0.0f;
+      for (int32_t b0 = beg; b0 < end; b0 += kOwnerChunk) {
+        owner_chunk(G, x, y, dt, weight, bins, voxel, nbins, hw, lin, b0, min(kOwnerChunk, end - b0), pad_h, pad_w, kb, gx, gy);
+#pragma unroll
+        for (int j = 0; j < kOwnerChunk; ++j)
+          if (kb[j] >= 0) {
+            cell[(int64_t)(2 * kb[j]) * hw] += gx[j];
+            cell[(int64_t)(2 * kb[j] + 1) * hw] += gy[j];
+          }
+      }
+    }
+  }
+  // hot pixels of this wave, one after the other, all 64 lanes on each (every value that steers the loops is wave-uniform)
+  unsigned long long hot_lanes = __ballot(hot);
+  while (hot_lanes) {
+    const int src = __ffsll((long long)hot_lanes) - 1;
+    hot_lanes &= hot_lanes - 1;
+    const int64_t hlin = __shfl(lin, src, kWave);
+    const int32_t hbeg = __shfl(beg, src, kWave), hend = __shfl(end, src, kWave);
+    float ax[kOwnerSlots], ay[kOwnerSlots];  // lane l: the running sums of bins l, l + 64, l + 128, l + 192
+#pragma unroll
+    for (int s = 0; s < kOwnerSlots; ++s) ax[s] = ay[s] = 0.0f;
+    for (int32_t base = hbeg; base < hend; base += kWave) {
+      const int32_t i = base + lane;
+      const bool live = i < hend;
+      int kb = -1;
+      float gx = 0.0f, gy = 0.0f;
+      if (live) {
+        kb = clamp_bin(bins[i], nbins);
+        owner_event_grad(G, voxel, hw, hlin, kb, x[i], y[i], dt[i], weight ? weight[i] : 1.0f, pad_h, pad_w, &gx, &gy);
+      }
+      unsigned long long todo = __ballot(live);
+      while (todo) {  // one round per bin present in the chunk, in the order of the bins' first events
+        const int k = __shfl(kb, __ffsll((long long)todo) - 1, kWave);
+        const bool mine = live && kb == k;
+        todo &= ~__ballot(mine);
+        float sx = mine ? gx : 0.0f, sy = mine ? gy : 0.0f;
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {  // butterfly: the same tree, and the same total, in every lane
+          sx += __shfl_xor(sx, off, kWave);
+          sy += __shfl_xor(sy, off, kWave);
+        }
+        if (lane == (k & (kWave - 1))) {
+#pragma unroll
+          for (int s = 0; s < kOwnerSlots; ++s)
+            if (s == (k >> 6)) {
+              ax[s] += sx;
+              ay[s] += sy;
+            }
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < kOwnerSlots; ++s) {
+      const int k = s * kWave + lane;
+      if (k < nbins) {
+        d_voxel[(int64_t)(2 * k) * hw + hlin] = ax[s];
+        d_voxel[(int64_t)(2 * k + 1) * hw + hlin] = ay[s];
+      }
+    }
+  }
+}
+
 bool ref_mode_ok(int m) { return m >= EBOS_REF_FIRST && m <= EBOS_REF_TIMEBASE; }
 bool bins_ok(int T) { return T >= 1 && T <= 255; }
 
@@ -562,6 +753,28 @@ int ebos_iwe_voxel_bwd_f32(const float* x, const float* y, const float* dt, cons
     iwe_voxel_bwd_kernel<false><<<grid, block, 0, s>>>(x, y, dt, weight, bins, n, voxel, T, H, W, row_stride, pad_h, pad_w,
                                                        g_image, affine, g_lo, d_voxel, d_weight);
   EBOS_CHECK_LAUNCH("ebos_iwe_voxel_bwd");
+  return EBOS_OK;
+}
+
+int ebos_iwe_voxel_owner_bwd_f32(const float* xs, const float* ys, const float* dts, const float* weight, const uint8_t* bins,
+                                 const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                                 int tile_w, int pad_h, int pad_w, const float* g_image, const float* affine, int g_lo,
+                                 float* d_voxel, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(voxel && g_image && d_voxel, "ebos_iwe_voxel_owner_bwd: NULL voxel/g_image/d_voxel");
+  EBOS_REQUIRE(key_offsets, "ebos_iwe_voxel_owner_bwd: key_offsets is NULL (the kernel needs a binned plan)");
+  EBOS_REQUIRE((xs && ys && dts && bins) || n == 0, "ebos_iwe_voxel_owner_bwd: NULL event buffer");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel_owner_bwd: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(n >= 0 && n <= INT32_MAX && H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && pad_h >= 0 && pad_w >= 0 && g_lo >= 0,
+               "ebos_iwe_voxel_owner_bwd: bad sizes");
+  const int tiles_y = (H + tile_h - 1) / tile_h, tiles_x = (W + tile_w - 1) / tile_w;
+  const int64_t n_keys = (int64_t)tiles_y * tiles_x * tile_h * tile_w;
+  EBOS_REQUIRE(n_keys < INT32_MAX, "ebos_iwe_voxel_owner_bwd: %lld keys are more than a plan can hold", (long long)n_keys);
+  // (n == 0 still runs: every cell is written, with zeros)
+  iwe_voxel_owner_bwd_kernel<<<dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, as_stream(stream)>>>(
+      xs, ys, dts, weight, bins, key_offsets, (int32_t)n, voxel, T, H, W, tile_h, tile_w, tiles_x, n_keys, pad_h, pad_w, g_image,
+      affine, g_lo, d_voxel);
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel_owner_bwd");
   return EBOS_OK;
 }
 

@@ -789,6 +789,46 @@ class EventPlan:
             return _FusedVarianceVoxel.apply(voxel, self, pad2, bool(omit_boundary), halo, splits)
         return ops.gradient_magnitude(_FusedIweVoxel.apply(voxel, None, self, pad2, halo, splits), omit_boundary)
 
+    def variance_voxel_value_and_grad(self, voxel: torch.Tensor, omit_boundary: bool = False, pad: Tuple[int, int] = (0, 0),
+                                      halo="auto", upstream: float = 1.0,
+                                      out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(var(IWE(voxel)) [1] f32, ``upstream`` * d var / d voxel [T, 2, H, W] f32) without an autograd node: the forward kernel of
+        ``iwe_voxel``, the variance and its affine map, and the pixel-owner backward (``ebos_iwe_voxel_owner_bwd_f32``: no atomics,
+        every cell written, the same bits on every call).  ``out``: a caller-owned contiguous float32 [T, 2, H, W] on the plan's
+        device that is overwritten (it needs no clearing).  Needs a binned time-aware plan (``EventPlan.build(..,
+        emit="full", time_bin=T, tile=..)``): the errors of ``contrast_voxel`` otherwise, ``NotImplementedError`` on an un-binned one."""
+        lib = _hip.require_gpu()
+        vox32 = _check_voxel(self, voxel)
+        if not self.binned:
+            raise NotImplementedError("variance_voxel_value_and_grad walks the runs of a binned plan: build it with a tile "
+                                      "(contrast_voxel serves an un-binned one)")
+        _refuse_deferred(self, "variance_voxel_value_and_grad")
+        pad2 = (int(pad[0]), int(pad[1]))
+        H, W = self.image_size
+        T = int(vox32.shape[0])
+        dev = self.device
+        if out is None:
+            out = torch.empty((T, 2, H, W), dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (T, 2, H, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(T, 2, H, W)} on {dev}")
+        iwe = _launch_iwe_voxel(self, vox32, None, pad2, _voxel_halo(self, halo), self.resolve_splits(None))
+        h, w = iwe.shape
+        value = torch.empty(1, dtype=torch.float32, device=dev)
+        moments = torch.empty((1, 2), dtype=torch.float64, device=dev)
+        affine = torch.empty(2, dtype=torch.float32, device=dev)
+        up = torch.full((1,), float(upstream), dtype=torch.float32, device=dev)
+        nbytes = int(lib.ebos_cost_scratch_bytes(1))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _hip.on_device(dev):
+            check(lib.ebos_image_variance_f32(ptr(iwe), 1, h, w, int(bool(omit_boundary)), ptr(value), ptr(moments), ptr(scratch), nbytes,
+                                              stream_ptr()), "ebos_image_variance")
+            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), 1, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
+            check(lib.ebos_iwe_voxel_owner_bwd_f32(ptr(self.x), ptr(self.y), ptr(self.dt), None, ptr(self.bins), ptr(self.key_offsets),
+                                                   self.n, ptr(vox32), T, H, W, self.tile[0], self.tile[1], pad2[0], pad2[1], ptr(iwe),
+                                                   ptr(affine), int(bool(omit_boundary)), ptr(out), stream_ptr()),
+                  "ebos_iwe_voxel_owner_bwd")
+        return value, out
+
 
 # ----------------------------------------------------------------------------------------------
 def _build_lean(source: int, events, raw, image_size, direction, normalize_t, tile, ticks_per_second, deferred):

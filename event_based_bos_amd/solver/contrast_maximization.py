@@ -21,6 +21,13 @@ time-aware objective.  The dense flow is the flow at t0; ``flow_voxel_batch`` tr
 warped by the flow of its own bin (``EventPlan.contrast_voxel``) and the gradient comes back through the voxel's adjoint to the
 patch grid.  Such a solver runs the autograd loop (Adam or the scipy methods): ``fused``, ``resident`` and HIP-graph capture are off
 and ``loop_mode`` reports "autograd".  Without the block nothing changes.
+
+``time_aware.native: true`` (default false) runs the same objective as a fixed pipeline of HIP kernels instead
+(``solver/time_aware_loop.py``: one C call enqueues the whole Adam loop, the scipy methods evaluate value and gradient through it, at
+every pyramid scale): ``loop_mode`` reports "native", ``fused`` is True, ``history`` comes from the loop's losses, and without an
+explicit ``tile`` the plan takes a built tile of the time-aware forward kernel, (64, 64).  Its family is the variance contrast alone
+with optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``, Adam or a scipy method; the constructor raises
+``NotImplementedError`` naming the key that leaves it.
 """
 from __future__ import annotations
 
@@ -35,7 +42,7 @@ from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
 from ..event_plan import EventPlan
-from . import fused_loop
+from . import fused_loop, time_aware_loop
 from .base import SolverBase
 
 logger = logging.getLogger(__name__)
@@ -45,17 +52,22 @@ SCIPY_METHODS = ("CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")  # first-order method
 
 
 def parse_time_aware(block) -> Optional[dict]:
-    """The ``time_aware`` block of the solver's configuration -> {time_bin, scheme, t0_location, clamp}, or None without one."""
+    """The ``time_aware`` block of the solver's configuration -> {time_bin, scheme, t0_location, clamp}, plus ``native`` where the block
+    gives it (absent means false), or None without one."""
     if block is None:
         return None
     block = dict(block)
-    unknown = sorted(set(block) - {"time_bin", "scheme", "t0_location", "clamp"})
+    unknown = sorted(set(block) - {"time_bin", "scheme", "t0_location", "clamp", "native"})
     if unknown:
-        raise ValueError(f"time_aware: unknown key(s) {unknown}; it takes time_bin, scheme, t0_location, clamp")
+        raise ValueError(f"time_aware: unknown key(s) {unknown}; it takes time_bin, scheme, t0_location, clamp, native")
     if "time_bin" not in block:
         raise ValueError("time_aware needs time_bin, the number of bins of the flow voxel")
     out = {"time_bin": ops.check_time_bins(block["time_bin"]), "scheme": block.get("scheme", "upwind"),
            "t0_location": block.get("t0_location", "middle"), "clamp": None if block.get("clamp") is None else float(block["clamp"])}
+    if "native" in block:   # (returned as given; a block without the key parses to what it always did, and means false)
+        if not isinstance(block["native"], bool):
+            raise ValueError(f"time_aware.native must be true or false, got {block['native']!r}")
+        out["native"] = block["native"]
     if out["scheme"] not in ("upwind", "burgers"):
         raise ValueError(f"time_aware.scheme must be 'upwind' or 'burgers', got {out['scheme']!r}")
     if out["t0_location"] not in ("first", "middle"):
@@ -158,6 +170,22 @@ class ContrastMaximizationMixin(object):
                 raise NotImplementedError(f"time_aware is defined for motion_model 'dense-flow', not {self.motion_model!r}")
             self.use_graph = self.fused_loop = False
             self.resident = False
+            if self.time_aware.get("native", False):
+                self._check_native_time_aware()
+
+    def _check_native_time_aware(self) -> None:
+        """``time_aware.native``: the family of ``time_aware_loop.TimeAwarePatchLoop``, or NotImplementedError naming the key outside it."""
+        what = None
+        if set(self.contrast_terms) != {"image_variance"}:
+            what = f"cost / cost_with_weight: the contrast {sorted(self.contrast_terms)} (the variance contrast alone)"
+        elif not set(self.flow_terms) <= set(fused_loop.FLOW_TERMS):
+            what = f"cost_with_weight: {sorted(set(self.flow_terms) - set(fused_loop.FLOW_TERMS))} (flow_norm and image_gradient only)"
+        elif self.blur_sigma > 0:
+            what = f"iwe.blur_sigma: {self.blur_sigma} (the un-blurred IWE only)"
+        elif self.opt_method != "Adam" and self.opt_method not in SCIPY_METHODS:
+            what = f"optimizer.method: {self.opt_method!r} (Adam or one of {SCIPY_METHODS})"
+        if what is not None:
+            raise NotImplementedError("time_aware.native does not cover " + what + "; drop native to run the autograd loop")
 
     # ------------------------------------------------------------------ objective pieces
     def _contrast(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
@@ -237,6 +265,14 @@ class ContrastMaximizationMixin(object):
 
         if self.tile is not None:
             return self.tile
+        if self.time_aware is not None and self.time_aware.get("native", False):
+            # the native loop's forward is the tiled time-aware kernel: a tile it is built for with this halo, (64, 64) first
+            from .. import _hip
+
+            halo = 32 if self.halo == "auto" else self.halo
+            built = [(th, tw) for th, tw, hl in _hip.tiled_configs() if hl == halo]
+            if built:
+                return time_aware_loop.DEFAULT_TILE if time_aware_loop.DEFAULT_TILE in built else built[0]
         return choose_tile(self.orig_image_shape, 32 if self.halo == "auto" else self.halo)
 
     def pyramid_scales(self):
@@ -287,6 +323,8 @@ class ContrastMaximizationMixin(object):
     def _optimise_patch_grid(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
                              mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         H, W = self.orig_image_shape
+        if self.time_aware is not None and self.time_aware.get("native", False):
+            return self._optimise_time_aware_native(plan, theta, patch_size, sliding_window, n_iter, mask)
         theta = theta.requires_grad_(True)
 
         def evaluate():  # (mask: the gradient of a patch that is not estimated is zero, so it keeps its masked start)
@@ -344,6 +382,23 @@ class ContrastMaximizationMixin(object):
                 losses[it] = iteration(opt)
         self.history += losses[:n_iter].cpu().tolist()
         return theta.detach()
+
+    def _optimise_time_aware_native(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
+                                    mask: Optional[torch.Tensor]) -> torch.Tensor:
+        """One pyramid scale of a ``time_aware.native`` solve: the Adam loop as one C call, or a scipy method on the loop's
+        ``value_and_grad``."""
+        adam = self.opt_method == "Adam"
+        loop = time_aware_loop.TimeAwarePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.time_aware,
+                                                  self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                                                  self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo,
+                                                  self.lr, capacity=n_iter if adam else 1, theta_mask=mask)
+        self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
+        self.loop_modes.append(loop.last_run_mode)
+        if not adam:
+            return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=loop.value_and_grad)
+        loop.run(n_iter)
+        self.history += loop.losses[:n_iter].cpu().tolist()
+        return loop.theta
 
     def _run_scipy(self, evaluate, theta: torch.Tensor, n_iter: int, value_and_grad=None) -> torch.Tensor:
         """Gradient-based scipy optimisers on the GPU objective, the role of the reference's

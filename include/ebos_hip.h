@@ -1513,6 +1513,75 @@ int ebos_iwe_voxel_bwd_f32(const float* x, const float* y, const float* dt, cons
                            int64_t n, const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w,
                            const float* g_image, const float* affine, int g_lo, int sorted, float* d_voxel, float* d_weight,
                            ebos_stream_t stream);
+/* ebos_iwe_voxel_owner_bwd_f32: the addends of ebos_iwe_voxel_bwd_f32 for a BINNED plan (xs / ys / dts / bins in key order and
+ *   key_offsets of ebos_bin_events_f32 with (tile_h, tile_w)), summed by the owner of each source pixel: the lane that walks the
+ *   pixel's run key_offsets[key] .. key_offsets[key + 1] is the only writer of its 2 T cells.  No atomics; d_voxel [T, 2, H, W] is
+ *   OVERWRITTEN, every cell of it (zeros where no event lands, pixels of empty tiles included), so the caller neither clears nor
+ *   zero-allocates it; the order of the additions is the plan's, so two calls give the same bits.  Runs of more than 64 events
+ *   (a hot pixel) are walked by the whole wave with a fixed reduction tree per bin.  weight nullable; no d_weight. */
+int ebos_iwe_voxel_owner_bwd_f32(const float* xs, const float* ys, const float* dts, const float* weight, const uint8_t* bins,
+                                 const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                                 int tile_w, int pad_h, int pad_w, const float* g_image, const float* affine, int g_lo,
+                                 float* d_voxel, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Adam loop of the TIME-AWARE patch-flow contrast maximisation natively (the solver's `time_aware` block):
+ *     loss(theta) = -w_variance * var(IWE(events warped by voxel(dense(theta))))
+ *                   + w_flow_norm * flow_norm(dense) + w_image_gradient * image_gradient(dense)
+ * n_iter iterations enqueued back to back on `stream` by one C call: no host synchronisation, no allocation.  One iteration:
+ *     ebos_upsample_patch_flow_f32 -> ebos_flow_voxel_advect_f32 (unclamped; + ebos_flow_voxel_clamp_f32 with has_clamp)
+ *     -> memset + ebos_iwe_voxel_tiled_f32 (ebos_iwe_voxel_f32 when (tile, halo) is no ebos_tiled_config)
+ *     -> ebos_image_variance_f32 + ebos_image_variance_affine_f32 (upstream = -w_variance) [-> ebos_flow_regularisers_f32]
+ *     -> ebos_iwe_voxel_owner_bwd_f32 (owner_bwd = 1) or memset + ebos_iwe_voxel_bwd_f32 sorted (owner_bwd = 0)
+ *     -> ebos_flow_voxel_advect_adjoint_f32 [-> d_dense += d_reg] -> ebos_upsample_patch_flow_bwd_adam_f32
+ * All buffers are the caller's:
+ *   plan:     xs / ys / dts / bins in key order, key_offsets, n, H, W, tile, halo (a built halo; <= 0: the general forward kernel),
+ *             pad, omit_boundary, splits (>= 1, as ebos_iwe_voxel_tiled_f32)
+ *   voxel:    T in [1, 255], scheme EBOS_FLOW_UPWIND / _BURGERS, t0_index, wrap_last, route, has_clamp / clamp as
+ *             ebos_flow_voxel_advect_f32; voxel [T, 2, H, W] receives the UNCLAMPED voxel, voxel_clamped (nullable unless
+ *             has_clamp) the copy the events read; d_voxel [T, 2, H, W]; adjoint_workspace of
+ *             ebos_flow_voxel_advect_adjoint_workspace(scheme, 1, T, H, W, t0_index, wrap_last, route) floats (nullable when 0)
+ *   grid:     theta / d_theta / exp_avg / exp_avg_sq [2, gh, gw], step [1] int32, patch and sliding window, steps_done, theta_mask
+ *             as in ebos_cmax_patch_problem
+ *   images:   dense / d_dense [2, H, W], d_reg [2, H, W] (nullable iff both regulariser weights are 0), iwe [H + 2 pad_h,
+ *             W + 2 pad_w], variance [1] f32, moments [2] f64, upstream [1] f32 = -w_variance, affine [2] f32
+ *   scratch:  cost_scratch (ebos_cost_scratch_bytes(1)), reg_partials [ebos_flow_regularisers_partials()] f64,
+ *             upsample_scratch (ebos_upsample_bwd_scratch_bytes)
+ *   losses:   [losses_cap] f32, entry `step` written per iteration with the loss BEFORE the update (nullable)
+ * ebos_cmax_voxel_gradient_f32: one forward and backward at theta without the Adam step -- d_theta, variance and reg_partials are
+ *   left for the caller (loss = -w_variance * variance[0] + sum(reg_partials)); for optimisers that live on the host.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ebos_cmax_voxel_problem {
+  const float *xs, *ys, *dts;
+  const uint8_t* bins;
+  const int32_t* key_offsets;
+  int64_t n;
+  int H, W, tile_h, tile_w, halo, pad_h, pad_w, omit_boundary, splits;
+  int T, scheme, t0_index, wrap_last, route, has_clamp;
+  double clamp;
+  int owner_bwd;               /* 1: ebos_iwe_voxel_owner_bwd_f32; 0: memset + ebos_iwe_voxel_bwd_f32 (global float atomics) */
+  int gh, gw, patch_h, patch_w, slide_h, slide_w;
+  float w_variance, w_flow_norm, w_image_gradient;
+  double lr, beta1, beta2, eps;
+  float *theta, *d_theta, *exp_avg, *exp_avg_sq;
+  int* step;
+  int steps_done;
+  float *dense, *d_dense, *d_reg, *voxel, *voxel_clamped, *d_voxel, *iwe, *variance;
+  double* moments;
+  const float* upstream;
+  float* affine;
+  void* cost_scratch;
+  size_t cost_scratch_bytes;
+  double* reg_partials;
+  float* upsample_scratch;
+  float* adjoint_workspace;
+  int64_t adjoint_workspace_elems;
+  float* losses;
+  int losses_cap;
+  const float* theta_mask;
+} ebos_cmax_voxel_problem;
+int ebos_cmax_voxel_solve_f32(const ebos_cmax_voxel_problem* problem, int n_iter, ebos_stream_t stream);
+int ebos_cmax_voxel_gradient_f32(const ebos_cmax_voxel_problem* problem, ebos_stream_t stream);
 
 #ifdef __cplusplus
 }
