@@ -293,6 +293,14 @@ SIGNATURES = {
     "ebos_iwe_voxel_owner_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     "ebos_cmax_voxel_solve_f32": (_I, [_P, _I, _P]),
     "ebos_cmax_voxel_gradient_f32": (_I, [_P, _P]),
+    "ebos_upsample_patch_flow_batch_f32": (_I, [_P] + [_I] * 9 + [_P, _P]),
+    "ebos_iwe_voxel_tiled_batch_f32": (_I, [_P] * 6 + [_I, _P] + [_I] * 9 + [_P, _P]),
+    "ebos_iwe_voxel_owner_bwd_batch_f32": (_I, [_P] * 6 + [_I, _P] + [_I] * 7 + [_P, _P, _I, _P, _P]),
+    "ebos_flow_regularisers_batch_f32": (_I, [_P, _I, _I, _I, _F, _F, _P, _P, _P]),
+    "ebos_upsample_patch_flow_bwd_batch_f32": (_I, [_P] + [_I] * 9 + [_P, _P, _P]),
+    "ebos_upsample_patch_flow_bwd_adam_batch_f32": (_I, [_P] + [_I] * 9 + [_P] * 5 + [_D] * 4 + [_I, _P, _P, _F, _P, _I, _P, _I, _P, _P]),
+    "ebos_cmax_voxel_solve_batch_f32": (_I, [_P, _I, _P]),
+    "ebos_cmax_voxel_gradient_batch_f32": (_I, [_P, _P]),
 }
 
 
@@ -353,6 +361,16 @@ class CmaxVoxelProblem(C.Structure):
                                    "affine", "cost_scratch")] +
                 [("cost_scratch_bytes", _Z), ("reg_partials", _P), ("upsample_scratch", _P), ("adjoint_workspace", _P),
                  ("adjoint_workspace_elems", _L), ("losses", _P), ("losses_cap", _I), ("theta_mask", _P)])
+
+
+CMAX_VOXEL_MAX_BATCH = 64   # EBOS_CMAX_VOXEL_MAX_BATCH
+
+
+class CmaxVoxelBatchProblem(C.Structure):
+    """``ebos_cmax_voxel_batch_problem`` of include/ebos_hip.h (same field order): ``CmaxVoxelProblem`` with ``B`` in front and the
+    event counts of the windows, ``n``, as an array."""
+    _fields_ = ([("B", _I)] + [(k, _P) for k in ("xs", "ys", "dts", "bins", "key_offsets")] + [("n", _L * CMAX_VOXEL_MAX_BATCH)] +
+                CmaxVoxelProblem._fields_[6:])
 
 
 class Cmax2dofProblem(C.Structure):

@@ -9,6 +9,8 @@
 //     padded index i -> grid index clamp(i - pad, 0, g - 1)                      (replicate pad)
 // with R = r + (n_full / 2 - H / 2) the row in the un-cropped resize output.
 // The 2 x 30 x 40 grid of BASELINE config 4 lives in L1/L2; the kernel is a pure 7.4 MB store.
+// The *_batch_* entry points run B grids at once ([B, 2, gh, gw] is [2 B, gh, gw]: the kernels' channel dimension), the adjoint with
+// the Adam step and loss record of every window (upsample_bwd_cols_batch_kernel).
 #include <math.h>
 
 #include "common.h"
@@ -211,12 +213,13 @@ patch_grad_combine_kernel(const float* __restrict__ partials, const int32_t* __r
   adam_apply(job, idx, st, acc, d_grid);
 }
 
-// pass 2: one wavefront per grid cell, lanes stride over the cell's column support
-__global__ void __launch_bounds__(256)
-upsample_bwd_cols_kernel(const float* __restrict__ S, Axis ay, Axis ax, int W, float* __restrict__ d_grid, AdamJob job) {
+// pass 2: one wavefront per grid cell, lanes stride over the cell's column support.  `ch` counts the channels of every grid the
+// buffers hold ([2, gh, gw], or [B, 2, gh, gw] as 2 B channels); `record`: this workgroup's first wavefront records the job's loss.
+__device__ __forceinline__ void upsample_bwd_cols_body(const float* __restrict__ S, const Axis& ay, const Axis& ax, int W,
+                                                       float* __restrict__ d_grid, const AdamJob& job, int ch, bool record) {
   const int lane = threadIdx.x & 63;
-  const int gj = blockIdx.x * 4 + (threadIdx.x >> 6), gi = blockIdx.y, ch = blockIdx.z;
-  if (job.theta != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) adam_record_loss(job, lane);
+  const int gj = blockIdx.x * 4 + (threadIdx.x >> 6), gi = blockIdx.y;
+  if (job.theta != nullptr && record && threadIdx.x < 64) adam_record_loss(job, lane);
   if (gj >= ax.g) return;
   int c_lo, c_hi;
   support(ax, gj, W, &c_lo, &c_hi);
@@ -230,13 +233,32 @@ upsample_bwd_cols_kernel(const float* __restrict__ S, Axis ay, Axis ax, int W, f
   }
 }
 
+__global__ void __launch_bounds__(256)
+upsample_bwd_cols_kernel(const float* __restrict__ S, Axis ay, Axis ax, int W, float* __restrict__ d_grid, AdamJob job) {
+  upsample_bwd_cols_body(S, ay, ax, W, d_grid, job, blockIdx.z, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0);
+}
+
+// B grids at once: blockIdx.z = 2 b + component.  The grids, their Adam state and S are contiguous over the windows, so the element
+// index runs on; what is PER WINDOW -- the contrast, the regulariser partials, the mask, the row of losses -- is offset here.  The
+// step counter is one for all (every window's recorder stores the same t).
+__global__ void __launch_bounds__(256)
+upsample_bwd_cols_batch_kernel(const float* __restrict__ S, Axis ay, Axis ax, int W, float* __restrict__ d_grid, AdamJob job) {
+  const int b = blockIdx.z >> 1;
+  if (job.contrast != nullptr) job.contrast += b;
+  if (job.reg_partials != nullptr) job.reg_partials += (int64_t)b * job.n_reg;
+  if (job.losses != nullptr) job.losses += (int64_t)b * job.losses_cap;
+  if (job.grad_mask != nullptr) job.grad_mask += (int64_t)b * ay.g * ax.g;
+  upsample_bwd_cols_body(S, ay, ax, W, d_grid, job, blockIdx.z, blockIdx.x == 0 && blockIdx.y == 0 && (blockIdx.z & 1) == 0);
+}
+
 }  // namespace
 }  // namespace ebos
 
 extern "C" {
 
-int ebos_upsample_patch_flow_f32(const float* grid, int gh, int gw, int patch_h, int patch_w, int slide_h,
-                                 int slide_w, int H, int W, float* dense, ebos_stream_t stream) {
+// n_grids grids [2, gh, gw] -> n_grids flows [2, H, W]: the kernel's channel dimension counts 2 n_grids channels
+static int upsample_impl(const float* grid, int n_grids, int gh, int gw, int patch_h, int patch_w, int slide_h, int slide_w, int H, int W,
+                         float* dense, ebos_stream_t stream) {
   using namespace ebos;
   EBOS_REQUIRE(grid && dense, "ebos_upsample_patch_flow: NULL grid/dense");
   EBOS_REQUIRE(gh > 0 && gw > 0 && patch_h > 0 && patch_w > 0 && slide_h > 0 && slide_w > 0 && H > 0 && W > 0,
@@ -245,11 +267,24 @@ int ebos_upsample_patch_flow_f32(const float* grid, int gh, int gw, int patch_h,
   EBOS_REQUIRE(ay.off >= 0 && ax.off >= 0 && ay.off + H <= ay.n_in * slide_h && ax.off + W <= ax.n_in * slide_w,
                "ebos_upsample_patch_flow: image %dx%d larger than the resized grid %dx%d", H, W, ay.n_in * slide_h,
                ax.n_in * slide_w);
-  dim3 g((W + 1023) / 1024, (H + kUpRows - 1) / kUpRows, 2);
+  dim3 g((W + 1023) / 1024, (H + kUpRows - 1) / kUpRows, 2 * n_grids);
   if (W % 4 == 0) upsample_kernel<true><<<g, dim3(256), 0, as_stream(stream)>>>(grid, ay, ax, H, W, dense);
   else upsample_kernel<false><<<g, dim3(256), 0, as_stream(stream)>>>(grid, ay, ax, H, W, dense);
   EBOS_CHECK_LAUNCH("ebos_upsample_patch_flow");
   return EBOS_OK;
+}
+
+int ebos_upsample_patch_flow_f32(const float* grid, int gh, int gw, int patch_h, int patch_w, int slide_h,
+                                 int slide_w, int H, int W, float* dense, ebos_stream_t stream) {
+  return upsample_impl(grid, 1, gh, gw, patch_h, patch_w, slide_h, slide_w, H, W, dense, stream);
+}
+
+int ebos_upsample_patch_flow_batch_f32(const float* grid, int B, int gh, int gw, int patch_h, int patch_w, int slide_h, int slide_w,
+                                       int H, int W, float* dense, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= EBOS_CMAX_VOXEL_MAX_BATCH, "ebos_upsample_patch_flow_batch: B = %d is outside [1, %d]", B,
+               EBOS_CMAX_VOXEL_MAX_BATCH);
+  return upsample_impl(grid, B, gh, gw, patch_h, patch_w, slide_h, slide_w, H, W, dense, stream);
 }
 
 size_t ebos_upsample_bwd_scratch_bytes(int gh, int W) {
@@ -257,7 +292,7 @@ size_t ebos_upsample_bwd_scratch_bytes(int gh, int W) {
 }
 
 static int upsample_bwd_impl(const float* d_dense, int gh, int gw, int patch_h, int patch_w, int slide_h, int slide_w, int H,
-                            int W, float* scratch, float* d_grid, const ebos::AdamJob& job, ebos_stream_t stream) {
+                            int W, float* scratch, float* d_grid, const ebos::AdamJob& job, ebos_stream_t stream, int n_grids = 0) {
   using namespace ebos;
   EBOS_REQUIRE(d_dense && d_grid && scratch, "ebos_upsample_patch_flow_bwd: NULL d_dense/d_grid/scratch");
   EBOS_REQUIRE(gh > 0 && gw > 0 && patch_h > 0 && patch_w > 0 && slide_h > 0 && slide_w > 0 && H > 0 && W > 0,
@@ -265,6 +300,12 @@ static int upsample_bwd_impl(const float* d_dense, int gh, int gw, int patch_h, 
   const Axis ay = make_axis(gh, patch_h, slide_h, H), ax = make_axis(gw, patch_w, slide_w, W);
   EBOS_REQUIRE(ay.off >= 0 && ax.off >= 0, "ebos_upsample_patch_flow_bwd: image larger than the resized grid");
   hipStream_t s = as_stream(stream);
+  if (n_grids > 0) {  // the batch form: 2 n_grids channels, what is per window offset in the kernel
+    upsample_bwd_rows_kernel<<<dim3((W + 63) / 64, gh, 2 * n_grids), dim3(256), 0, s>>>(d_dense, ay, H, W, scratch);
+    upsample_bwd_cols_batch_kernel<<<dim3((gw + 3) / 4, gh, 2 * n_grids), dim3(256), 0, s>>>(scratch, ay, ax, W, d_grid, job);
+    EBOS_CHECK_LAUNCH("ebos_upsample_patch_flow_bwd_batch");
+    return EBOS_OK;
+  }
   upsample_bwd_rows_kernel<<<dim3((W + 63) / 64, gh, 2), dim3(256), 0, s>>>(d_dense, ay, H, W, scratch);
   upsample_bwd_cols_kernel<<<dim3((gw + 3) / 4, gh, 2), dim3(256), 0, s>>>(scratch, ay, ax, W, d_grid, job);
   EBOS_CHECK_LAUNCH("ebos_upsample_patch_flow_bwd");
@@ -318,6 +359,29 @@ int ebos_upsample_patch_flow_bwd_adam_f32(const float* d_dense, int gh, int gw, 
                              n_reg, losses, losses_cap, grad_mask, "ebos_upsample_patch_flow_bwd_adam"))
     return rc;
   return upsample_bwd_impl(d_dense, gh, gw, patch_h, patch_w, slide_h, slide_w, H, W, scratch, d_grid, job, stream);
+}
+
+int ebos_upsample_patch_flow_bwd_batch_f32(const float* d_dense, int B, int gh, int gw, int patch_h, int patch_w, int slide_h,
+                                           int slide_w, int H, int W, float* scratch, float* d_grid, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= EBOS_CMAX_VOXEL_MAX_BATCH, "ebos_upsample_patch_flow_bwd_batch: B = %d is outside [1, %d]", B,
+               EBOS_CMAX_VOXEL_MAX_BATCH);
+  return upsample_bwd_impl(d_dense, gh, gw, patch_h, patch_w, slide_h, slide_w, H, W, scratch, d_grid, ebos::AdamJob{}, stream, B);
+}
+
+int ebos_upsample_patch_flow_bwd_adam_batch_f32(const float* d_dense, int B, int gh, int gw, int patch_h, int patch_w, int slide_h,
+                                                int slide_w, int H, int W, float* scratch, float* d_grid, float* theta, float* exp_avg,
+                                                float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int t, int* step,
+                                                const float* contrast, float contrast_scale, const double* reg_partials, int n_reg,
+                                                float* losses, int losses_cap, const float* grad_mask, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= EBOS_CMAX_VOXEL_MAX_BATCH, "ebos_upsample_patch_flow_bwd_adam_batch: B = %d is outside [1, %d]", B,
+               EBOS_CMAX_VOXEL_MAX_BATCH);
+  ebos::AdamJob job{};
+  if (int rc = make_adam_job(&job, theta, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, t, step, contrast, contrast_scale, reg_partials,
+                             n_reg, losses, losses_cap, grad_mask, "ebos_upsample_patch_flow_bwd_adam_batch"))
+    return rc;
+  return upsample_bwd_impl(d_dense, gh, gw, patch_h, patch_w, slide_h, slide_w, H, W, scratch, d_grid, job, stream, B);
 }
 
 int ebos_patch_grad_combine_adam_f32(const float* grad_partials, const int32_t* part_table, int tile_h, int tile_w, int gh, int gw,

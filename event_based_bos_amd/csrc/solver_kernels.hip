@@ -1,5 +1,6 @@
 // solver_kernels.hip -- the pieces of one contrast-maximisation iteration that are not the event kernels:
-// the flow regularisers (value + gradient in one pass over the dense flow) and the Adam update of the patch grid.
+// the flow regularisers (value + gradient in one pass over the dense flow; ebos_flow_regularisers_batch_f32: of B flows) and the Adam
+// update of the patch grid.
 //
 // Why these exist: a solver iteration on a 2 M-event window is ~70 us of event-kernel time, but expressed through
 // autograd it is ~35 kernel launches (a dozen for a capturable Adam, ten for `norm(flow, dim=0).mean()` and its
@@ -63,9 +64,8 @@ __device__ __forceinline__ RegGrad reg_at(const float* __restrict__ flow, int r,
 // thread = 4 consecutive pixels of one row (16-byte loads / stores when W % 4 == 0); workgroups stride over the
 // (row, column-block) work items; one f64 partial per workgroup.
 template <bool VEC4>
-__global__ void __launch_bounds__(256)
-flow_regularisers_kernel(const float* __restrict__ flow, int H, int W, float w_norm, float w_tv, float* __restrict__ d_flow,
-                         double* __restrict__ partials, MomentsJob mj) {
+__device__ __forceinline__ void flow_regularisers_body(const float* __restrict__ flow, int H, int W, float w_norm, float w_tv,
+                                                       float* __restrict__ d_flow, double* __restrict__ partials, const MomentsJob& mj) {
   const int64_t hw = (int64_t)H * W;
   const float s_norm = w_norm / (float)hw, s_tv = w_tv / (float)(2 * hw);
   const int col_blocks = (W + 1023) / 1024;
@@ -130,6 +130,23 @@ flow_regularisers_kernel(const float* __restrict__ flow, int H, int W, float w_n
   }
 }
 
+template <bool VEC4>
+__global__ void __launch_bounds__(256)
+flow_regularisers_kernel(const float* __restrict__ flow, int H, int W, float w_norm, float w_tv, float* __restrict__ d_flow,
+                         double* __restrict__ partials, MomentsJob mj) {
+  flow_regularisers_body<VEC4>(flow, H, W, w_norm, w_tv, d_flow, partials, mj);
+}
+
+// B flows [B, 2, H, W] at once: blockIdx.y is the flow, with its own gradient image and its own row of partials [B, gridDim.x]
+template <bool VEC4>
+__global__ void __launch_bounds__(256)
+flow_regularisers_batch_kernel(const float* __restrict__ flow, int H, int W, float w_norm, float w_tv, float* __restrict__ d_flow,
+                               double* __restrict__ partials) {
+  const int64_t b = blockIdx.y, img = 2 * (int64_t)H * W;
+  flow_regularisers_body<VEC4>(flow + b * img, H, W, w_norm, w_tv, d_flow + b * img, partials + b * gridDim.x,
+                               MomentsJob{nullptr, 0, 0, nullptr, nullptr});
+}
+
 // One workgroup.  loss[t] = contrast_scale * contrast + sum(reg_partials) is recorded for the parameters BEFORE the
 // update (what the torch loop records), then Adam advances theta and the step counter.
 __global__ void __launch_bounds__(1024)
@@ -184,6 +201,26 @@ int ebos_flow_regularisers_f32(const float* flow, int H, int W, float w_flow_nor
     flow_regularisers_kernel<false><<<dim3(kRegGrid), dim3(256), 0, as_stream(stream)>>>(flow, H, W, w_flow_norm,
                                                                                         w_image_gradient, d_flow, partials, mj);
   EBOS_CHECK_LAUNCH("ebos_flow_regularisers");
+  return EBOS_OK;
+}
+
+int ebos_flow_regularisers_batch_f32(const float* flow, int B, int H, int W, float w_flow_norm, float w_image_gradient, float* d_flow,
+                                     double* partials, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= EBOS_CMAX_VOXEL_MAX_BATCH, "ebos_flow_regularisers_batch: B = %d is outside [1, %d]", B,
+               EBOS_CMAX_VOXEL_MAX_BATCH);
+  EBOS_REQUIRE(flow && d_flow && partials && flow != d_flow, "ebos_flow_regularisers_batch: NULL or aliased buffers");
+  EBOS_REQUIRE(H >= 1 && W >= 1, "ebos_flow_regularisers_batch: bad sizes");
+  EBOS_REQUIRE(w_image_gradient == 0.0f || (H >= 2 && W >= 2),
+               "ebos_flow_regularisers_batch: image_gradient needs at least 2 samples per axis (torch.gradient)");
+  const dim3 grid(kRegGrid, (unsigned)B);
+  if (W % 4 == 0)
+    flow_regularisers_batch_kernel<true><<<grid, dim3(256), 0, as_stream(stream)>>>(flow, H, W, w_flow_norm, w_image_gradient, d_flow,
+                                                                                   partials);
+  else
+    flow_regularisers_batch_kernel<false><<<grid, dim3(256), 0, as_stream(stream)>>>(flow, H, W, w_flow_norm, w_image_gradient, d_flow,
+                                                                                    partials);
+  EBOS_CHECK_LAUNCH("ebos_flow_regularisers_batch");
   return EBOS_OK;
 }
 

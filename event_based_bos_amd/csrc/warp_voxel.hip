@@ -9,6 +9,8 @@
 //            V[(k * 2 + c) * H * W + lin] and the bins as one more SoA stream (1 B/event)
 //   owner    iwe_voxel_owner_bwd_kernel: the backward for a binned plan, summed by the owner of each source pixel's run -- no
 //            atomics, every cell of d_voxel written, the same bits on every call
+//   batch    iwe_voxel_tiled_batch_kernel / iwe_voxel_owner_bwd_batch_kernel: the tiled forward and the owner backward for several
+//            windows of one geometry, the window an outer grid dimension (blockIdx.y) over a stacked plan; the single kernels' bodies
 //
 // Every kernel reads a bin as min(bins[i], T - 1): a bins array that was made for another T cannot index outside the voxel.
 // Dead and padding slots never gather.
@@ -195,16 +197,14 @@ iwe_voxel_kernel(const float* __restrict__ x, const float* __restrict__ y, const
 // accumulator rule -- f64 wherever tile + halo fits the LDS in doubles -- and the spill path beyond the halo are the same)
 constexpr int kTiledBlock = 1024;
 
+// the work item blockIdx.x = (tile, split) of ONE window: its offsets row, its voxel, its image
 template <int TH, int TW, int HALO, typename ACC>
-__global__ void __launch_bounds__(kTiledBlock)
-iwe_voxel_tiled_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ dts,
-                       const float* __restrict__ weight, const uint8_t* __restrict__ bins,
-                       const int32_t* __restrict__ key_offsets, const float* __restrict__ voxel, int nbins, int H, int W,
-                       int tiles_x, int splits, int pad_h, int pad_w, float* iwe) {
+__device__ __forceinline__ void iwe_voxel_tiled_body(ACC* s_img, const float* __restrict__ xs, const float* __restrict__ ys,
+                                                     const float* __restrict__ dts, const float* __restrict__ weight,
+                                                     const uint8_t* __restrict__ bins, const int32_t* __restrict__ key_offsets,
+                                                     const float* __restrict__ voxel, int nbins, int H, int W, int tiles_x, int splits,
+                                                     int pad_h, int pad_w, float* iwe) {
   constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
-  extern __shared__ double s_raw[];  // [LH][LW] of ACC
-  ACC* s_img = reinterpret_cast<ACC*>(s_raw);
-
   const int tile = blockIdx.x / splits, part = blockIdx.x - tile * splits;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
   const int32_t beg = key_offsets[tile * (TH * TW)], end = key_offsets[(tile + 1) * (TH * TW)];
@@ -290,6 +290,33 @@ iwe_voxel_tiled_kernel(const float* __restrict__ xs, const float* __restrict__ y
   }
 }
 
+template <int TH, int TW, int HALO, typename ACC>
+__global__ void __launch_bounds__(kTiledBlock)
+iwe_voxel_tiled_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ dts,
+                       const float* __restrict__ weight, const uint8_t* __restrict__ bins,
+                       const int32_t* __restrict__ key_offsets, const float* __restrict__ voxel, int nbins, int H, int W,
+                       int tiles_x, int splits, int pad_h, int pad_w, float* iwe) {
+  extern __shared__ double s_raw[];  // [LH][LW] of ACC
+  iwe_voxel_tiled_body<TH, TW, HALO, ACC>(reinterpret_cast<ACC*>(s_raw), xs, ys, dts, weight, bins, key_offsets, voxel, nbins, H, W,
+                                          tiles_x, splits, pad_h, pad_w, iwe);
+}
+
+// several windows of one geometry: blockIdx.y is the window.  The event streams are the windows' streams one after the other and
+// row b of key_offsets [B, n_keys + 1] holds window b's offsets INTO THE CONCATENATION, so a window is found without a pointer table.
+template <int TH, int TW, int HALO, typename ACC>
+__global__ void __launch_bounds__(kTiledBlock)
+iwe_voxel_tiled_batch_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ dts,
+                             const uint8_t* __restrict__ bins, const int32_t* __restrict__ key_offsets,
+                             const float* __restrict__ voxel, int nbins, int H, int W, int tiles_x, int tiles_y, int splits, int pad_h,
+                             int pad_w, float* iwe) {
+  extern __shared__ double s_raw[];  // [LH][LW] of ACC
+  const int64_t b = blockIdx.y;
+  const int64_t n_keys = (int64_t)tiles_y * tiles_x * (TH * TW);
+  iwe_voxel_tiled_body<TH, TW, HALO, ACC>(reinterpret_cast<ACC*>(s_raw), xs, ys, dts, nullptr, bins, key_offsets + b * (n_keys + 1),
+                                          voxel + b * nbins * 2 * (int64_t)H * W, nbins, H, W, tiles_x, splits, pad_h, pad_w,
+                                          iwe + b * (int64_t)(H + 2 * pad_h) * (W + 2 * pad_w));
+}
+
 template <int TH, int TW, int HALO>
 struct TileAcc {  // f64 when it fits the LDS, else f32
   static constexpr bool kF64 = (size_t)(TH + 2 * HALO) * (TW + 2 * HALO) * sizeof(double) <= 160 * 1024;
@@ -315,6 +342,27 @@ int launch_voxel_tiled(const float* xs, const float* ys, const float* dts, const
   }
   kern<<<dim3((unsigned)(tiles_y * tiles_x * splits)), dim3(kTiledBlock), lds, s>>>(
       xs, ys, dts, weight, bins, key_offsets, voxel, nbins, H, W, tiles_x, splits, pad_h, pad_w, iwe);
+  return EBOS_OK;
+}
+
+template <int TH, int TW, int HALO>
+int launch_voxel_tiled_batch(const float* xs, const float* ys, const float* dts, const uint8_t* bins, const int32_t* key_offsets,
+                             int B, const float* voxel, int nbins, int H, int W, int splits, int pad_h, int pad_w, float* iwe,
+                             hipStream_t s) {
+  constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
+  using ACC = typename TileAcc<TH, TW, HALO>::type;
+  constexpr size_t lds = (size_t)LH * LW * sizeof(ACC);
+  const int tiles_y = (H + TH - 1) / TH, tiles_x = (W + TW - 1) / TW;
+  auto kern = iwe_voxel_tiled_batch_kernel<TH, TW, HALO, ACC>;
+  if (lds > 64 * 1024) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      set_error("ebos_iwe_voxel_tiled_batch: cannot reserve %zu B of LDS", lds);
+      return EBOS_ERR_LAUNCH;
+    }
+  }
+  kern<<<dim3((unsigned)(tiles_y * tiles_x * splits), (unsigned)B), dim3(kTiledBlock), lds, s>>>(
+      xs, ys, dts, bins, key_offsets, voxel, nbins, H, W, tiles_x, tiles_y, splits, pad_h, pad_w, iwe);
   return EBOS_OK;
 }
 
@@ -481,12 +529,14 @@ __device__ __forceinline__ void owner_chunk(const GradImage& G, const float* __r
   }
 }
 
-__global__ void __launch_bounds__(256)
-iwe_voxel_owner_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
-                           const float* __restrict__ weight, const uint8_t* __restrict__ bins,
-                           const int32_t* __restrict__ key_offsets, int32_t n, const float* __restrict__ voxel, int nbins, int H,
-                           int W, int tile_h, int tile_w, int tiles_x, int64_t n_keys, int pad_h, int pad_w,
-                           const float* __restrict__ g_image, const float* __restrict__ affine, int g_lo, float* d_voxel) {
+// one window: its runs lie in [ev_lo, ev_hi) of the event arrays, and no run is followed outside that slice
+__device__ __forceinline__ void iwe_voxel_owner_bwd_body(const float* __restrict__ x, const float* __restrict__ y,
+                                                         const float* __restrict__ dt, const float* __restrict__ weight,
+                                                         const uint8_t* __restrict__ bins, const int32_t* __restrict__ key_offsets,
+                                                         int32_t ev_lo, int32_t ev_hi, const float* __restrict__ voxel, int nbins, int H,
+                                                         int W, int tile_h, int tile_w, int tiles_x, int64_t n_keys, int pad_h,
+                                                         int pad_w, const float* __restrict__ g_image,
+                                                         const float* __restrict__ affine, int g_lo, float* d_voxel) {
   const int64_t hw = (int64_t)H * W;
   GradImage G;
   G.g = g_image;
@@ -507,8 +557,8 @@ iwe_voxel_owner_bwd_kernel(const float* __restrict__ x, const float* __restrict_
     const int r = ty * tile_h + pit / tile_w, c = tx * tile_w + pit % tile_w;
     if (r < H && c < W) {
       lin = (int64_t)r * W + c;
-      beg = min(max(key_offsets[key], 0), n);  // a run never leaves the event arrays, whatever the table holds
-      end = min(max(key_offsets[key + 1], beg), n);
+      beg = min(max(key_offsets[key], ev_lo), ev_hi);  // a run never leaves the window's events, whatever the table holds
+      end = min(max(key_offsets[key + 1], beg), ev_hi);
     }
   }
   const int len = end - beg;
@@ -592,6 +642,38 @@ iwe_voxel_owner_bwd_kernel(const float* __restrict__ x, const float* __restrict_
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256)
+iwe_voxel_owner_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
+                           const float* __restrict__ weight, const uint8_t* __restrict__ bins,
+                           const int32_t* __restrict__ key_offsets, int32_t n, const float* __restrict__ voxel, int nbins, int H,
+                           int W, int tile_h, int tile_w, int tiles_x, int64_t n_keys, int pad_h, int pad_w,
+                           const float* __restrict__ g_image, const float* __restrict__ affine, int g_lo, float* d_voxel) {
+  iwe_voxel_owner_bwd_body(x, y, dt, weight, bins, key_offsets, 0, n, voxel, nbins, H, W, tile_h, tile_w, tiles_x, n_keys, pad_h, pad_w,
+                           g_image, affine, g_lo, d_voxel);
+}
+
+// first event of each window in the concatenated streams, and the end of the last (a kernel argument: no table in memory)
+constexpr int kMaxWindows = EBOS_CMAX_VOXEL_MAX_BATCH;
+struct WindowBases {
+  int32_t at[kMaxWindows + 1];
+};
+
+// several windows: the key is (pixel key, window = blockIdx.y); window b owns row b of the offsets, voxel[b], g_image[b], affine[b]
+// and d_voxel[b]
+__global__ void __launch_bounds__(256)
+iwe_voxel_owner_bwd_batch_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,
+                                 const uint8_t* __restrict__ bins, const int32_t* __restrict__ key_offsets, WindowBases bases,
+                                 const float* __restrict__ voxel, int nbins, int H, int W, int tile_h, int tile_w, int tiles_x,
+                                 int64_t n_keys, int pad_h, int pad_w, const float* __restrict__ g_image,
+                                 const float* __restrict__ affine, int g_lo, float* d_voxel) {
+  const int b = blockIdx.y;
+  const int64_t cells = (int64_t)nbins * 2 * H * W;
+  iwe_voxel_owner_bwd_body(x, y, dt, nullptr, bins, key_offsets + (int64_t)b * (n_keys + 1), bases.at[b], bases.at[b + 1],
+                           voxel + b * cells, nbins, H, W, tile_h, tile_w, tiles_x, n_keys, pad_h, pad_w,
+                           g_image + (int64_t)b * (H + 2 * pad_h) * (W + 2 * pad_w), affine ? affine + 2 * b : nullptr, g_lo,
+                           d_voxel + b * cells);
 }
 
 bool ref_mode_ok(int m) { return m >= EBOS_REF_FIRST && m <= EBOS_REF_TIMEBASE; }
@@ -733,6 +815,56 @@ int ebos_iwe_voxel_tiled_f32(const float* xs, const float* ys, const float* dts,
   return EBOS_OK;
 }
 
+int ebos_iwe_voxel_tiled_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                   const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H, int W,
+                                   int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w, float* iwe,
+                                   ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= kMaxWindows, "ebos_iwe_voxel_tiled_batch: B = %d is outside [1, %d]", B, kMaxWindows);
+  EBOS_REQUIRE(voxel && iwe && key_offsets && ns, "ebos_iwe_voxel_tiled_batch: NULL voxel/iwe/key_offsets/ns");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel_tiled_batch: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && pad_h >= 0 && pad_w >= 0 && splits >= 1 && splits <= 64,
+               "ebos_iwe_voxel_tiled_batch: bad sizes (splits=%d)", splits);
+  int64_t total = 0;
+  for (int b = 0; b < B; ++b) {
+    EBOS_REQUIRE(ns[b] >= 0, "ebos_iwe_voxel_tiled_batch: window %d has n = %lld", b, (long long)ns[b]);
+    total += ns[b];
+    EBOS_REQUIRE(total <= INT32_MAX, "ebos_iwe_voxel_tiled_batch: more than INT32_MAX events in the batch");
+  }
+  EBOS_REQUIRE((xs && ys && dts && bins) || total == 0, "ebos_iwe_voxel_tiled_batch: NULL event buffer");
+  if (total == 0) return EBOS_OK;
+  hipStream_t s = as_stream(stream);
+  int rc = EBOS_ERR_UNSUPPORTED;
+#define EBOS_VOXEL_TILED_CASE(TH, TW, HL)                         \
+  if (tile_h == TH && tile_w == TW && halo == HL)                 \
+    rc = launch_voxel_tiled_batch<TH, TW, HL>(xs, ys, dts, bins, key_offsets, B, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
+  EBOS_VOXEL_TILED_CASE(64, 64, 32)
+  EBOS_VOXEL_TILED_CASE(32, 64, 32)
+  EBOS_VOXEL_TILED_CASE(32, 32, 32)
+  EBOS_VOXEL_TILED_CASE(16, 64, 32)
+  EBOS_VOXEL_TILED_CASE(64, 64, 16)
+  EBOS_VOXEL_TILED_CASE(32, 32, 16)
+  EBOS_VOXEL_TILED_CASE(32, 32, 8)
+  EBOS_VOXEL_TILED_CASE(64, 64, 64)
+  EBOS_VOXEL_TILED_CASE(32, 64, 48)
+#undef EBOS_VOXEL_TILED_CASE
+  if (rc == EBOS_ERR_UNSUPPORTED) {
+    // (tile, halo) is no built configuration: the general kernel, window by window (any event order, global float atomics)
+    const int64_t cells = (int64_t)T * 2 * H * W, img = (int64_t)(H + 2 * pad_h) * (W + 2 * pad_w);
+    int64_t at = 0;
+    for (int b = 0; b < B; ++b) {
+      if (int r = ebos_iwe_voxel_f32(xs + at, ys + at, dts + at, nullptr, bins + at, ns[b], voxel + b * cells, T, H, W, W, pad_h, pad_w,
+                                     iwe + b * img, stream))
+        return r;
+      at += ns[b];
+    }
+    return EBOS_OK;
+  }
+  if (rc != EBOS_OK) return rc;
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel_tiled_batch");
+  return EBOS_OK;
+}
+
 int ebos_iwe_voxel_bwd_f32(const float* x, const float* y, const float* dt, const float* weight, const uint8_t* bins,
                            int64_t n, const float* voxel, int T, int H, int W, int row_stride, int pad_h, int pad_w,
                            const float* g_image, const float* affine, int g_lo, int sorted, float* d_voxel, float* d_weight,
@@ -775,6 +907,38 @@ int ebos_iwe_voxel_owner_bwd_f32(const float* xs, const float* ys, const float* 
       xs, ys, dts, weight, bins, key_offsets, (int32_t)n, voxel, T, H, W, tile_h, tile_w, tiles_x, n_keys, pad_h, pad_w, g_image,
       affine, g_lo, d_voxel);
   EBOS_CHECK_LAUNCH("ebos_iwe_voxel_owner_bwd");
+  return EBOS_OK;
+}
+
+int ebos_iwe_voxel_owner_bwd_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                       const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H, int W,
+                                       int tile_h, int tile_w, int pad_h, int pad_w, const float* g_image, const float* affine,
+                                       int g_lo, float* d_voxel, ebos_stream_t stream) {
+  using namespace ebos;
+  EBOS_REQUIRE(B >= 1 && B <= kMaxWindows, "ebos_iwe_voxel_owner_bwd_batch: B = %d is outside [1, %d]", B, kMaxWindows);
+  EBOS_REQUIRE(voxel && g_image && d_voxel, "ebos_iwe_voxel_owner_bwd_batch: NULL voxel/g_image/d_voxel");
+  EBOS_REQUIRE(key_offsets && ns, "ebos_iwe_voxel_owner_bwd_batch: key_offsets / ns is NULL (the kernel needs a stacked binned plan)");
+  EBOS_REQUIRE(bins_ok(T), "ebos_iwe_voxel_owner_bwd_batch: T = %d is outside [1, 255]", T);
+  EBOS_REQUIRE(H > 0 && W > 0 && tile_h > 0 && tile_w > 0 && pad_h >= 0 && pad_w >= 0 && g_lo >= 0,
+               "ebos_iwe_voxel_owner_bwd_batch: bad sizes");
+  WindowBases bases{};
+  int64_t total = 0;
+  for (int b = 0; b < B; ++b) {
+    EBOS_REQUIRE(ns[b] >= 0, "ebos_iwe_voxel_owner_bwd_batch: window %d has n = %lld", b, (long long)ns[b]);
+    bases.at[b] = (int32_t)total;
+    total += ns[b];
+    EBOS_REQUIRE(total <= INT32_MAX, "ebos_iwe_voxel_owner_bwd_batch: more than INT32_MAX events in the batch");
+  }
+  for (int b = B; b <= kMaxWindows; ++b) bases.at[b] = (int32_t)total;
+  EBOS_REQUIRE((xs && ys && dts && bins) || total == 0, "ebos_iwe_voxel_owner_bwd_batch: NULL event buffer");
+  const int tiles_y = (H + tile_h - 1) / tile_h, tiles_x = (W + tile_w - 1) / tile_w;
+  const int64_t n_keys = (int64_t)tiles_y * tiles_x * tile_h * tile_w;
+  EBOS_REQUIRE(n_keys < INT32_MAX, "ebos_iwe_voxel_owner_bwd_batch: %lld keys are more than a plan can hold", (long long)n_keys);
+  // (an empty window still runs: every cell of its d_voxel is written, with zeros)
+  iwe_voxel_owner_bwd_batch_kernel<<<dim3((unsigned)((n_keys + 255) / 256), (unsigned)B), dim3(256), 0, as_stream(stream)>>>(
+      xs, ys, dts, bins, key_offsets, bases, voxel, T, H, W, tile_h, tile_w, tiles_x, n_keys, pad_h, pad_w, g_image, affine, g_lo,
+      d_voxel);
+  EBOS_CHECK_LAUNCH("ebos_iwe_voxel_owner_bwd_batch");
   return EBOS_OK;
 }
 

@@ -490,6 +490,12 @@ class EventPlan:
             plans.append(plan)
         return plans
 
+    @staticmethod
+    def stack_time_aware(plans: Sequence["EventPlan"]) -> "TimeAwarePlanStack":
+        """Several binned time-aware plans of one geometry as ONE set of streams for the batched time-aware kernels
+        (``TimeAwarePlanStack``)."""
+        return TimeAwarePlanStack(plans)
+
     def bin(self, tile: Tuple[int, int] = DEFAULT_TILE, deferred: bool = False) -> "EventPlan":
         """Counting-sort the plan by source pixel, tile-major (ebos_bin_events_f32).
 
@@ -831,6 +837,67 @@ class EventPlan:
 
 
 # ----------------------------------------------------------------------------------------------
+INT32_MAX = 2 ** 31 - 1
+
+
+class TimeAwarePlanStack(object):
+    """B binned time-aware plans (``EventPlan.build(..., emit="full", time_bin=T, tile=...)``) of one geometry, stacked for the kernels
+    that take the window from an outer grid dimension (``ebos_iwe_voxel_tiled_batch_f32``, ``ebos_iwe_voxel_owner_bwd_batch_f32``,
+    ``ebos_cmax_voxel_solve_batch_f32``):
+
+        x / y / dt / bins   the windows' SoA streams, in key order, one after the other
+        key_offsets         int32 [B, n_keys + 1]: row b = window b's offsets + the window's base, so window b is the slice
+                            key_offsets[b][0] .. key_offsets[b][n_keys] of the streams and a kernel needs no pointer table
+        ns                  the windows' event counts (host)
+
+    ValueError for a plan that is un-binned, deferred or without bins, for plans that differ in image size, tile, ``time_bin`` or
+    warp direction (a plan keeps its direction as ``dt_bound``), and for more than INT32_MAX events in total.  An ``EventPlan`` holds no
+    per-event weights (they are an argument of the operators), and the stacked kernels take none."""
+
+    def __init__(self, plans: Sequence[EventPlan]):
+        plans = list(plans)
+        if not plans:
+            raise ValueError("stack_time_aware: no plans")
+        if len(plans) > _hip.CMAX_VOXEL_MAX_BATCH:
+            raise ValueError(f"stack_time_aware: {len(plans)} plans, the batched kernels take at most {_hip.CMAX_VOXEL_MAX_BATCH}")
+        first = plans[0]
+        for b, plan in enumerate(plans):
+            if not plan.binned or plan.x is None:
+                raise ValueError(f"stack_time_aware: plan {b} is un-binned or lean; build it with emit='full', tile=..., time_bin=T")
+            if plan.bins is None or plan.time_bin is None:
+                raise ValueError(f"stack_time_aware: plan {b} holds no time bins (EventPlan.build(..., time_bin=T))")
+            if plan.__dict__.get("_deferred"):
+                raise ValueError(f"stack_time_aware: plan {b} is deferred (its build was not read back)")
+            for what in ("image_size", "tile", "time_bin", "dt_bound"):
+                a, v = getattr(first, what), getattr(plan, what)
+                if (tuple(a) if isinstance(a, (tuple, list)) else a) != (tuple(v) if isinstance(v, (tuple, list)) else v):
+                    name = "warp direction (dt_bound)" if what == "dt_bound" else what
+                    raise ValueError(f"stack_time_aware: plan {b} differs from plan 0 in {name}: {v!r} against {a!r}")
+            if plan.device != first.device:
+                raise ValueError(f"stack_time_aware: plan {b} is on {plan.device}, plan 0 on {first.device}")
+        self.ns = [int(p.n) for p in plans]
+        if sum(self.ns) > INT32_MAX:
+            raise ValueError(f"stack_time_aware: {sum(self.ns)} events in total are more than INT32_MAX")
+        self.plans = plans
+        self.image_size, self.tile, self.time_bin, self.dt_bound = first.image_size, tuple(first.tile), first.time_bin, first.dt_bound
+        self.n = sum(self.ns)
+        self.x, self.y, self.dt = (torch.cat([getattr(p, k)[:p.n] for p in plans]).contiguous() for k in ("x", "y", "dt"))
+        self.bins = torch.cat([p.bins[:p.n] for p in plans]).contiguous()
+        bases = torch.tensor([sum(self.ns[:b]) for b in range(len(plans))], dtype=torch.int32, device=first.device)
+        self.key_offsets = (torch.stack([p.key_offsets for p in plans]) + bases[:, None]).to(torch.int32).contiguous()
+
+    def __len__(self) -> int:
+        return len(self.plans)
+
+    @property
+    def device(self) -> torch.device:
+        return self.key_offsets.device
+
+    def ns_array(self):
+        """The event counts as the ``int64_t`` host array of the C entry points."""
+        return (C.c_int64 * len(self.ns))(*self.ns)
+
+
 def _build_lean(source: int, events, raw, image_size, direction, normalize_t, tile, ticks_per_second, deferred):
     """``ebos_plan_lean``: compact plan straight from the window.  Returns None when the window cannot take it (fractional
     source coordinates, a geometry outside the LDS sort) -- the caller then runs the full build."""

@@ -37,7 +37,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .. import costs, ops
+from .. import _hip, costs, ops
 from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
@@ -251,6 +251,79 @@ class ContrastMaximizationMixin(object):
             else:
                 raise NotImplementedError(f"motion_model {self.motion_model!r}")
         return flow.detach().cpu().numpy().astype(np.float64)
+
+    def _native_batch(self) -> bool:
+        """Does ``estimate_batch`` solve several windows per launch?  The ``time_aware: {native: true}`` family with Adam."""
+        return (self.time_aware is not None and bool(self.time_aware.get("native", False)) and self.opt_method == "Adam"
+                and self.motion_model == "dense-flow")
+
+    def estimate_batch(self, windows, max_batch: int = 8) -> np.ndarray:
+        """``estimate`` for several windows of a recording: float64 [len(windows), 2, H, W].  A ``time_aware: {native: true}``
+        configuration with ``optimizer.method: Adam`` solves the windows in chunks of ``max_batch`` through
+        ``time_aware_loop.TimeAwarePatchLoopBatch`` (one Adam iteration of a chunk in the launches of one window), at every pyramid
+        scale; the coarse-to-fine initialisation and ``patch_mask`` are each window's own and ``_warm_start()`` is the common start.
+        Every other configuration is the loop of ``estimate``.  Per window: ``histories[b]`` and ``patch_flows[b]``; ``loop_modes`` per
+        pyramid scale; ``history`` and ``patch_flow`` hold the last window's.  A window ``estimate`` refuses is refused the same way."""
+        windows = list(windows)
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be at least 1, got {max_batch}")
+        H, W = self.orig_image_shape
+        self.histories, self.patch_flows = [], []
+        if not windows:
+            return np.zeros((0, 2, H, W), dtype=np.float64)
+        if not self._native_batch():
+            flows = []
+            for ev in windows:
+                flows.append(self.estimate(ev))
+                self.histories.append(list(self.history))
+                self.patch_flows.append(getattr(self, "patch_flow", None))
+            return np.stack(flows).astype(np.float64)
+        max_batch = min(max_batch, _hip.CMAX_VOXEL_MAX_BATCH)
+        flows = []
+        for c0 in range(0, len(windows), max_batch):
+            plans = [EventPlan.build(to_gpu(ev), self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
+                                     time_bin=self.time_aware["time_bin"]) for ev in windows[c0:c0 + max_batch]]
+            flows.append(self._estimate_patch_flow_batch(plans))
+        self.history, self.patch_flow = self.histories[-1], self.patch_flows[-1]
+        return torch.cat(flows).detach().cpu().numpy().astype(np.float64)
+
+    def _estimate_patch_flow_batch(self, plans) -> torch.Tensor:
+        """``_estimate_patch_flow`` for one chunk of windows through the batch loop: [B, 2, H, W] (device)."""
+        H, W = self.orig_image_shape
+        B, dev = len(plans), plans[0].device
+        stack = EventPlan.stack_time_aware(plans)
+        histories = [[] for _ in plans]
+        self.loop_modes, per_scale = [], []
+        theta = None
+        for patch_size, sliding_window, n_iter in self.pyramid_scales():
+            gh, gw = patch_grid_shape((H, W), patch_size, sliding_window)
+            if theta is not None:   # every window from its own coarser scale
+                init = torch.nn.functional.interpolate(theta, size=(gh, gw), mode="bilinear", align_corners=False)
+            elif self._warm_start() is not None:
+                init = to_gpu(self._warm_start(), device=dev, dtype=torch.float32).reshape(1, 2, gh, gw).repeat(B, 1, 1, 1)
+            else:
+                init = torch.zeros((B, 2, gh, gw), dtype=torch.float32, device=dev)
+            masks = [self.patch_mask(plan, patch_size, sliding_window) for plan in plans]
+            mask = None if masks[0] is None else torch.stack(masks)
+            if mask is not None:
+                init = init * mask[:, None]
+            loop = time_aware_loop.TimeAwarePatchLoopBatch(stack, patch_size, sliding_window, init, self.time_aware,
+                                                           self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                                                           self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
+                                                           self.halo, self.lr, capacity=n_iter, theta_mask=mask)
+            loop.run(n_iter)
+            self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
+            self.loop_modes.append(loop.last_run_mode)
+            for b, row in enumerate(loop.losses[:, :n_iter].cpu().tolist()):   # (one read-back per scale)
+                histories[b] += row
+            theta = loop.theta
+            per_scale.append(theta)
+        self.histories += histories
+        self.patch_flows += [theta[b] for b in range(B)]
+        self.patch_flow_per_scale = [t[B - 1] for t in per_scale]
+        self.patch_size_used, self.sliding_window_used = patch_size, sliding_window
+        return torch.stack([ops.upsample_patch_flow(theta[b], patch_size, sliding_window, (H, W)) for b in range(B)])
 
     def _warm_start(self):
         """Warm start handed over by ``set_previous_frame_best_estimation`` -- the build's base stores it as

@@ -18,6 +18,10 @@ One iteration, on buffers allocated once per loop:
 one loop; ``owner_bwd=None`` takes whichever was measured faster for the window's size and bins (``default_owner_bwd``).  The
 family: the variance contrast alone, optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``; anything else belongs to the
 autograd loop of ``ContrastMaximization``.
+
+``TimeAwarePatchLoopBatch`` runs the same loop for B windows of one geometry in the launches of one window
+(``ebos_cmax_voxel_solve_batch_f32``): every stage takes the window from an outer grid dimension, each window has its own events, grid
+and Adam state.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ import torch
 
 from .. import _hip
 from .._hip import check, ptr, stream_ptr
-from ..event_plan import EventPlan, _voxel_halo
+from ..event_plan import EventPlan, TimeAwarePlanStack, _voxel_halo
 from ..flow_voxel import _ADVECT, _t0_index
 
 DEFAULT_TILE = (64, 64)    # the plan tile of a native time-aware solve: a built ebos_tiled_config (the tiled forward kernel)
@@ -154,3 +158,121 @@ class TimeAwarePatchLoop(object):
             if self.n_reg:
                 loss = loss + self.reg_partials.sum().to(torch.float32)
         return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask)
+
+
+class TimeAwarePatchLoopBatch(object):
+    """``TimeAwarePatchLoop`` for B windows at once: ``plans`` is a sequence of binned time-aware plans of one geometry (or a
+    ``TimeAwarePlanStack``), ``theta0`` [B, 2, gh, gw], ``theta_mask`` [B, gh, gw]; the other arguments are the single loop's and hold
+    for every window.  ``owner_bwd=None`` resolves through ``default_owner_bwd(T, the largest window)``."""
+    graphed = False
+    last_run_mode = "native-batch"
+
+    def __init__(self, plans, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
+                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
+                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None, owner_bwd: Optional[bool] = None):
+        self.lib = lib = _hip.require_gpu()
+        ta = dict(time_aware)
+        self.stack = stack = plans if isinstance(plans, TimeAwarePlanStack) else EventPlan.stack_time_aware(plans)
+        self.B = B = len(stack)
+        if int(ta["time_bin"]) != stack.time_bin:
+            raise ValueError(f"the plans' bins were made for time_bin={stack.time_bin}, time_aware asks for {ta['time_bin']}")
+        if ta.get("scheme", "upwind") not in ("upwind", "burgers"):
+            raise NotImplementedError(f"time_aware.scheme {ta.get('scheme')!r}: the native loop runs 'upwind' and 'burgers'")
+        if float(w_variance) == 0.0:
+            raise ValueError("w_variance must be non-zero")
+        self.patch, self.slide = tuple(int(v) for v in patch_size), tuple(int(v) for v in sliding_window)
+        self.T, self.scheme = int(ta["time_bin"]), _ADVECT[ta.get("scheme", "upwind")]
+        self.t0 = _t0_index(ta.get("t0_location", "middle"), self.T)
+        self.clamp = None if ta.get("clamp") is None else float(ta["clamp"])
+        self.w_var, self.w_norm, self.w_tv = float(w_variance), float(w_flow_norm), float(w_image_gradient)
+        self.omit, self.pad = bool(omit_boundary), (int(pad), int(pad))
+        built = _voxel_halo(stack.plans[0], halo)       # None: (tile, halo) is no built configuration -> the general forward kernel
+        self.halo = 0 if built is None else int(built)
+        self.splits = max(1, max(p.resolve_splits(None) for p in stack.plans))
+        self.owner_bwd = default_owner_bwd(self.T, max(stack.ns)) if owner_bwd is None else bool(owner_bwd)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        from .. import flow_voxel as _fv
+
+        self.route = _hip.FLOW_ROUTE_AUTO if _fv._FORCE_ROUTE is None else _fv._FORCE_ROUTE
+        dev = stack.device
+        H, W = stack.image_size
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.theta = theta0.detach().to(**f32).contiguous().clone()
+        if self.theta.dim() != 4 or self.theta.shape[0] != B or self.theta.shape[1] != 2:
+            raise ValueError(f"theta0 must be [{B}, 2, gh, gw], got {tuple(theta0.shape)}")
+        _, _, self.gh, self.gw = self.theta.shape
+        self.theta_mask = None if theta_mask is None else theta_mask.detach().to(**f32).reshape(B, self.gh, self.gw).contiguous()
+        self.d_theta = torch.empty_like(self.theta)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.t = 0
+        self.has_reg = self.w_norm != 0.0 or self.w_tv != 0.0
+        self.dense, self.d_dense = torch.empty((B, 2, H, W), **f32), torch.empty((B, 2, H, W), **f32)
+        self.d_reg = torch.empty((B, 2, H, W), **f32) if self.has_reg else None
+        self.voxel, self.d_voxel = torch.empty((B, self.T, 2, H, W), **f32), torch.empty((B, self.T, 2, H, W), **f32)
+        self.voxel_clamped = torch.empty_like(self.voxel) if self.clamp is not None else None
+        self.iwe = torch.empty((B, H + 2 * self.pad[0], W + 2 * self.pad[1]), **f32)
+        self.variance = torch.empty(B, **f32)
+        self.moments = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        self.upstream = torch.full((B,), -self.w_var, **f32)   # loss = -w * contrast, per window
+        self.affine = torch.empty((B, 2), **f32)
+        self.cost_scratch = torch.empty(int(lib.ebos_cost_scratch_bytes(B)), dtype=torch.uint8, device=dev)
+        self.n_reg = int(lib.ebos_flow_regularisers_partials()) if self.has_reg else 0
+        self.reg_partials = torch.zeros((B, max(self.n_reg, 1)), dtype=torch.float64, device=dev)
+        self.scratch_up = torch.empty(B * (int(lib.ebos_upsample_bwd_scratch_bytes(self.gh, W)) // 4), **f32)
+        n_ws = int(lib.ebos_flow_voxel_advect_adjoint_workspace(self.scheme, B, self.T, H, W, self.t0, 0, self.route))
+        if n_ws < 0:
+            raise RuntimeError("ebos_flow_voxel_advect_adjoint_workspace: " + lib.ebos_last_error().decode("utf-8", "replace"))
+        self.adjoint_ws = torch.empty(n_ws, **f32) if n_ws else None
+        self.losses = torch.zeros((B, max(int(capacity), 1)), **f32)   # [B, capacity]: row b, entry it = window b's loss before update it
+
+    def problem(self) -> "_hip.CmaxVoxelBatchProblem":
+        """The loop's buffers as the ``ebos_cmax_voxel_batch_problem`` struct of the C ABI."""
+        st = self.stack
+        q = _hip.CmaxVoxelBatchProblem()
+        q.B = self.B
+        q.xs, q.ys, q.dts, q.bins, q.key_offsets = ptr(st.x), ptr(st.y), ptr(st.dt), ptr(st.bins), ptr(st.key_offsets)
+        for b, n in enumerate(st.ns):
+            q.n[b] = n
+        q.H, q.W = st.image_size
+        q.tile_h, q.tile_w, q.halo = st.tile[0], st.tile[1], self.halo
+        q.pad_h, q.pad_w, q.omit_boundary, q.splits = self.pad[0], self.pad[1], int(self.omit), self.splits
+        q.T, q.scheme, q.t0_index, q.wrap_last, q.route = self.T, self.scheme, self.t0, 0, self.route
+        q.has_clamp, q.clamp = int(self.clamp is not None), float(self.clamp or 0.0)
+        q.owner_bwd = int(self.owner_bwd)
+        q.gh, q.gw, (q.patch_h, q.patch_w), (q.slide_h, q.slide_w) = self.gh, self.gw, self.patch, self.slide
+        q.w_variance, q.w_flow_norm, q.w_image_gradient = self.w_var, self.w_norm, self.w_tv
+        q.lr, q.beta1, q.beta2, q.eps = self.lr, self.betas[0], self.betas[1], self.eps
+        q.theta, q.d_theta, q.exp_avg, q.exp_avg_sq = ptr(self.theta), ptr(self.d_theta), ptr(self.exp_avg), ptr(self.exp_avg_sq)
+        q.step, q.steps_done = ptr(self.step), self.t
+        q.dense, q.d_dense, q.d_reg = ptr(self.dense), ptr(self.d_dense), ptr(self.d_reg)
+        q.voxel, q.voxel_clamped, q.d_voxel = ptr(self.voxel), ptr(self.voxel_clamped), ptr(self.d_voxel)
+        q.iwe, q.variance, q.moments, q.upstream, q.affine = ptr(self.iwe), ptr(self.variance), ptr(self.moments), ptr(self.upstream), ptr(self.affine)
+        q.cost_scratch, q.cost_scratch_bytes = ptr(self.cost_scratch), self.cost_scratch.numel()
+        q.reg_partials, q.upsample_scratch = ptr(self.reg_partials), ptr(self.scratch_up)
+        q.adjoint_workspace = ptr(self.adjoint_ws)
+        q.adjoint_workspace_elems = self.adjoint_ws.numel() if self.adjoint_ws is not None else 0
+        q.losses, q.losses_cap, q.theta_mask = ptr(self.losses), self.losses.shape[1], ptr(self.theta_mask)
+        return q
+
+    def run(self, n_iter: int) -> torch.Tensor:
+        """``n_iter`` more iterations of every window, enqueued by one C call; returns their losses [B, n_iter] (device)."""
+        n_iter = int(n_iter)
+        if self.t + n_iter > self.losses.shape[1]:
+            raise ValueError(f"capacity {self.losses.shape[1]} < {self.t} steps done + {n_iter}")
+        t0 = self.t
+        with _hip.on_device(self.stack.device):
+            check(self.lib.ebos_cmax_voxel_solve_batch_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_voxel_solve_batch")
+        self.t += n_iter
+        return self.losses[:, t0:t0 + n_iter]
+
+    def value_and_grad(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(losses [B], d loss / d theta [B, 2, gh, gw]) at ``theta`` through the same kernels, without the Adam step."""
+        with _hip.on_device(self.stack.device):
+            self.theta.copy_(theta.detach().to(self.theta))
+            check(self.lib.ebos_cmax_voxel_gradient_batch_f32(ctypes.byref(self.problem()), stream_ptr()), "ebos_cmax_voxel_gradient_batch")
+            loss = -self.w_var * self.variance
+            if self.n_reg:
+                loss = loss + self.reg_partials.sum(dim=1).to(torch.float32)
+        return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask[:, None])

@@ -1583,6 +1583,98 @@ typedef struct ebos_cmax_voxel_problem {
 int ebos_cmax_voxel_solve_f32(const ebos_cmax_voxel_problem* problem, int n_iter, ebos_stream_t stream);
 int ebos_cmax_voxel_gradient_f32(const ebos_cmax_voxel_problem* problem, ebos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The time-aware loop for SEVERAL windows of one geometry per call: one Adam iteration of B windows runs in the launches of one
+ * window, the window being an outer grid dimension of every stage.  Each window has its own events, patch grid and Adam state.
+ *
+ * The stacked plan: xs / ys / dts / bins are the windows' streams (key order) one after the other; key_offsets [B, n_keys + 1] int32
+ * holds in row b window b's offsets shifted by the window's base, i.e. offsets INTO THE CONCATENATION, so the kernels need no pointer
+ * table; ns [B] (HOST memory) the windows' event counts, whose sum is at most INT32_MAX.  A window with ns[b] = 0 is valid.
+ *
+ * The stages (each is the single entry point of the same name with the window dimension; per window the same arithmetic in the
+ * same order, so on identical inputs the deterministic ones give the single call's bits):
+ *   ebos_upsample_patch_flow_batch_f32       grid [B, 2, gh, gw] -> dense [B, 2, H, W]; grid.z = 2 B channels
+ *   ebos_iwe_voxel_tiled_batch_f32           work item (tile, split, window): grid (tiles * splits, B); window b reads row b of
+ *       the offsets and voxel[b] ([B, T, 2, H, W]) and ACCUMULATES into iwe[b] ([B, h, w]).  Every ebos_tiled_config is served;
+ *       where (tile_h, tile_w, halo) is none, the general kernel ebos_iwe_voxel_f32 runs window by window.  No weights.
+ *   ebos_iwe_voxel_owner_bwd_batch_f32       key (pixel key, window): grid (n_keys / 256, B); g_image [B, h, w], affine [B, 2]
+ *       (nullable), d_voxel [B, T, 2, H, W] OVERWRITTEN.  A run is clamped to its own window's slice of the streams whatever the
+ *       table holds.  Per window the properties of ebos_iwe_voxel_owner_bwd_f32: no atomics, every cell written, a fixed order of
+ *       additions, hot pixels walked by the whole wave.
+ *   ebos_flow_regularisers_batch_f32         flow / d_flow [B, 2, H, W], partials [B, ebos_flow_regularisers_partials()]
+ *   ebos_upsample_patch_flow_bwd_batch_f32   d_dense [B, 2, H, W] -> d_grid [B, 2, gh, gw]; scratch of
+ *       B * ebos_upsample_bwd_scratch_bytes(gh, W) bytes
+ *   ebos_upsample_patch_flow_bwd_adam_batch_f32  ... + the Adam step of every window's grid (theta / exp_avg / exp_avg_sq
+ *       [B, 2, gh, gw]) and the loss record: contrast [B], reg_partials [B, n_reg], grad_mask [B, gh, gw] (nullable),
+ *       losses [B, losses_cap]; ONE step counter `step` [1] and one t for all windows.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_CMAX_VOXEL_MAX_BATCH 64
+int ebos_upsample_patch_flow_batch_f32(const float* grid, int B, int gh, int gw, int patch_h, int patch_w, int slide_h, int slide_w,
+                                       int H, int W, float* dense, ebos_stream_t stream);
+int ebos_iwe_voxel_tiled_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                   const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H, int W,
+                                   int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w, float* iwe,
+                                   ebos_stream_t stream);
+int ebos_iwe_voxel_owner_bwd_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                       const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H, int W,
+                                       int tile_h, int tile_w, int pad_h, int pad_w, const float* g_image, const float* affine,
+                                       int g_lo, float* d_voxel, ebos_stream_t stream);
+int ebos_flow_regularisers_batch_f32(const float* flow, int B, int H, int W, float w_flow_norm, float w_image_gradient, float* d_flow,
+                                     double* partials, ebos_stream_t stream);
+int ebos_upsample_patch_flow_bwd_batch_f32(const float* d_dense, int B, int gh, int gw, int patch_h, int patch_w, int slide_h,
+                                           int slide_w, int H, int W, float* scratch, float* d_grid, ebos_stream_t stream);
+int ebos_upsample_patch_flow_bwd_adam_batch_f32(const float* d_dense, int B, int gh, int gw, int patch_h, int patch_w, int slide_h,
+                                                int slide_w, int H, int W, float* scratch, float* d_grid, float* theta, float* exp_avg,
+                                                float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int t, int* step,
+                                                const float* contrast, float contrast_scale, const double* reg_partials, int n_reg,
+                                                float* losses, int losses_cap, const float* grad_mask, ebos_stream_t stream);
+
+/* ebos_cmax_voxel_solve_batch_f32: n_iter iterations of ebos_cmax_voxel_solve_f32's sequence with every stage called ONCE for all B
+ * windows (one memset clears every IWE, one pass adds the regularisers' gradients); no host synchronisation, no allocation.  With
+ * owner_bwd = 0 the atomic backward ebos_iwe_voxel_bwd_f32 runs window by window behind one memset of d_voxel.
+ * The fields are those of ebos_cmax_voxel_problem with the window dimension in front:
+ *   plan:     B in [1, 64]; the stacked plan above, n[b] for b < B the windows' event counts
+ *   grid:     theta / d_theta / exp_avg / exp_avg_sq [B, 2, gh, gw], theta_mask [B, gh, gw] (nullable), step [1], steps_done
+ *   images:   dense / d_dense / d_reg [B, 2, H, W], voxel / voxel_clamped / d_voxel [B, T, 2, H, W], iwe [B, h, w],
+ *             variance [B], moments [B, 2] f64, upstream [B] (each -w_variance), affine [B, 2]
+ *   scratch:  cost_scratch of ebos_cost_scratch_bytes(B), reg_partials [B, ebos_flow_regularisers_partials()], upsample_scratch of
+ *             B * ebos_upsample_bwd_scratch_bytes(gh, W), adjoint_workspace of
+ *             ebos_flow_voxel_advect_adjoint_workspace(scheme, B, T, H, W, t0_index, wrap_last, route) floats
+ *   losses:   [B, losses_cap]
+ * Everything is validated before the first launch.  ebos_cmax_voxel_gradient_batch_f32: one forward and backward without the step. */
+typedef struct ebos_cmax_voxel_batch_problem {
+  int B;
+  const float *xs, *ys, *dts;
+  const uint8_t* bins;
+  const int32_t* key_offsets;
+  int64_t n[EBOS_CMAX_VOXEL_MAX_BATCH];
+  int H, W, tile_h, tile_w, halo, pad_h, pad_w, omit_boundary, splits;
+  int T, scheme, t0_index, wrap_last, route, has_clamp;
+  double clamp;
+  int owner_bwd;
+  int gh, gw, patch_h, patch_w, slide_h, slide_w;
+  float w_variance, w_flow_norm, w_image_gradient;
+  double lr, beta1, beta2, eps;
+  float *theta, *d_theta, *exp_avg, *exp_avg_sq;
+  int* step;
+  int steps_done;
+  float *dense, *d_dense, *d_reg, *voxel, *voxel_clamped, *d_voxel, *iwe, *variance;
+  double* moments;
+  const float* upstream;
+  float* affine;
+  void* cost_scratch;
+  size_t cost_scratch_bytes;
+  double* reg_partials;
+  float* upsample_scratch;
+  float* adjoint_workspace;
+  int64_t adjoint_workspace_elems;
+  float* losses;
+  int losses_cap;
+  const float* theta_mask;
+} ebos_cmax_voxel_batch_problem;
+int ebos_cmax_voxel_solve_batch_f32(const ebos_cmax_voxel_batch_problem* problem, int n_iter, ebos_stream_t stream);
+int ebos_cmax_voxel_gradient_batch_f32(const ebos_cmax_voxel_batch_problem* problem, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

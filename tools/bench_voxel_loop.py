@@ -16,6 +16,11 @@ Per shape (2 M events at 1280 x 720, 100 k events at 346 x 260) and ``time_bin``
   backward alone  ``ebos_iwe_voxel_owner_bwd_f32`` into a caller-owned buffer against a zero-fill of that buffer +
                   ``ebos_iwe_voxel_bwd_f32`` (sorted: the segmented wave reduction)
 
+With ``--batch B`` the tool measures the batch loop instead (``TimeAwarePatchLoopBatch``: ``ebos_cmax_voxel_solve_batch_f32``): per case
+one row "per window, one batch solve of B windows" against "the loop of B single native solves" (B windows of the case's size drawn
+with B seeds, each with its own start grid; the backward ``default_owner_bwd`` picks), both per window and per iteration, through the
+same ``compare``; the raw output goes to profiles/voxel_loop_batch_bench.json.
+
 Times are device events around a loop of calls, taken in alternating rounds; ``min`` is the best round, [min, max] the spread.  A
 difference counts only where the two [min, max] intervals do not overlap (``overlap`` lists the pairs that do).  The rules of
 tools/bench_warp_voxel.py.  The losses of the variants are compared before anything is timed (printed per row, not judged here:
@@ -35,7 +40,7 @@ import event_based_bos_amd as ebos  # noqa: E402
 from event_based_bos_amd import _hip  # noqa: E402
 from event_based_bos_amd._hip import check, ptr, stream_ptr  # noqa: E402
 from event_based_bos_amd.solver.contrast_maximization import patch_grid_shape  # noqa: E402
-from event_based_bos_amd.solver.time_aware_loop import TimeAwarePatchLoop  # noqa: E402
+from event_based_bos_amd.solver.time_aware_loop import TimeAwarePatchLoop, TimeAwarePatchLoopBatch  # noqa: E402
 
 CASES = [((720, 1280), 2_000_000), ((260, 346), 100_000)]
 BINS = (5, 15)
@@ -150,17 +155,70 @@ def rows(rounds, reps, iters):
     return out
 
 
+def batch_rows(B, rounds, reps, iters):
+    """Per case: one batch solve of B windows against the loop of B single native solves, microseconds per window and iteration."""
+    out = []
+    for (H, W), n in CASES:
+        gh, gw = patch_grid_shape((H, W), PATCH, PATCH)
+        evs = [torch.from_numpy(O.synth_events(n, H, W, seed=7 + b, tmin=0.0, tmax=1.0)).cuda() for b in range(B)]
+        theta0 = torch.from_numpy(np.random.RandomState(3).uniform(0.5, 3.0, (B, 2, gh, gw)).astype(np.float32)).cuda()
+        for T in BINS:
+            plans = [ebos.EventPlan.build(ev, (H, W), "first", True, tile=TILE, emit="full", time_bin=T) for ev in evs]
+            ta = {"time_bin": T, "scheme": "upwind", "t0_location": "middle", "clamp": None}
+            batch = TimeAwarePatchLoopBatch(plans, PATCH, PATCH, theta0, ta, 1.0, lr=0.05, capacity=iters)
+            singles = [TimeAwarePatchLoop(plan, PATCH, PATCH, theta0[b], ta, 1.0, lr=0.05, capacity=iters, owner_bwd=batch.owner_bwd)
+                       for b, plan in enumerate(plans)]
+
+            def reset(loop, start):
+                loop.theta.copy_(start)
+                loop.exp_avg.zero_()
+                loop.exp_avg_sq.zero_()
+                loop.t = 0
+
+            def run_batch():
+                reset(batch, theta0)
+                batch.run(iters)
+
+            def run_singles():
+                for b, loop in enumerate(singles):
+                    reset(loop, theta0[b])
+                    loop.run(iters)
+
+            run_batch()
+            run_singles()
+            got = batch.losses[:, :iters].cpu().numpy().astype(np.float64)
+            want = np.stack([loop.losses[:iters].cpu().numpy().astype(np.float64) for loop in singles])
+            row = dict(shape=[H, W], events_per_window=n, windows=B, time_bin=T, tile=list(TILE), patch=list(PATCH), iterations_per_call=iters,
+                       owner_bwd=bool(batch.owner_bwd), what="per window, one batch solve of B windows against the loop of B single native solves",
+                       unit="us per window and iteration",
+                       first_loss_rel_to_single=float(np.max(np.abs(got[:, 0] - want[:, 0]) / np.abs(want[:, 0]))),
+                       last_loss_rel_to_single=float(np.max(np.abs(got[:, -1] - want[:, -1]) / np.abs(want[:, -1]))))
+            row.update(compare({"batch_per_window": run_batch, "single_loop_per_window": run_singles}, rounds, reps, per=iters * B))
+            print(json.dumps(row), flush=True)
+            out.append(row)
+            del batch, singles, plans
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "voxel_loop_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/voxel_loop_bench.json, with --batch profiles/voxel_loop_batch_bench.json")
+    ap.add_argument("--batch", type=int, nargs="+", default=None, metavar="B",
+                    help="measure the batch loop of B windows (several values: one set of rows each) instead of the single loop's rows")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--iters", type=int, default=50)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_voxel_loop needs a GPU"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "voxel_loop_batch_bench.json" if args.batch else "voxel_loop_bench.json")
+    if args.batch:
+        measured = [r for B in args.batch for r in batch_rows(B, args.rounds, args.reps, args.iters)]
+    else:
+        measured = rows(args.rounds, args.reps, args.iters)
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "reps": args.reps, "iters": args.iters,
            "method": "device events around a loop of calls; alternating rounds; best round (min) and [min, max] over the rounds",
-           "rows": rows(args.rounds, args.reps, args.iters)}
+           "rows": measured}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     json.dump(res, open(args.out, "w"), indent=1)
 
