@@ -10,6 +10,8 @@ tub-rip/event_based_bos:
     costs                drop-in for src/costs (+ image_variance, gradient_magnitude)
     EventPlan            device-resident SoA event window + the fused warp/IWE kernels
     SlabBatch            several independent windows per launch (ebos_iwe_slab_batch_f32)
+    TimeAwarePlanStack   the binned time-aware plans of several windows as one set of streams; from_raw builds them from the raw
+                         sensor columns in one set of launches (ebos_plan_time_aware_raw_batch)
     solver               contrast-maximisation solver behind the reference's solver registry
     event_filters        the reference's BAF / HOT event filters and EventFilter, on the GPU
     flow_error           the reference's flow-error metrics (EPE, NPE, AE), batched, on the GPU
@@ -33,7 +35,7 @@ operators raise ``HipUnavailableError``.
 from ._hip import HipUnavailableError, load_library  # noqa: F401
 from .warp import MotionModelKeyError, Warp  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
-from .event_plan import EventPlan, SlabBatch  # noqa: F401
+from .event_plan import EventPlan, SlabBatch, TimeAwarePlanStack  # noqa: F401
 from .data_loader import FrameStore, RawEventStore  # noqa: F401
 from .frame_warp import validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
 from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingEvaluator, plan_evaluation,  # noqa: F401

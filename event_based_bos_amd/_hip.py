@@ -301,6 +301,9 @@ SIGNATURES = {
     "ebos_upsample_patch_flow_bwd_adam_batch_f32": (_I, [_P] + [_I] * 9 + [_P] * 5 + [_D] * 4 + [_I, _P, _P, _F, _P, _I, _P, _I, _P, _P]),
     "ebos_cmax_voxel_solve_batch_f32": (_I, [_P, _I, _P]),
     "ebos_cmax_voxel_gradient_batch_f32": (_I, [_P, _P]),
+    "ebos_plan_time_aware_batch_scratch_bytes": (_Z, [_P, _I, _I, _I, _I, _I]),
+    "ebos_plan_time_aware_raw_batch": (_I, [_P, _P, _P, _I, _D, _L, _P, _I] + [_I] * 10 + [_I, _D] + [_I] * 6 + [_P] * 5 + [_L, _P, _P, _L] +
+                                       [_P, _P, _P, _Z, _P]),
 }
 
 

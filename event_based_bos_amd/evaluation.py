@@ -13,8 +13,11 @@ writes the reference's ``flow_error_per_frame_with_mask.txt``, ``flow_error_per_
 ``plan_evaluation`` restates the driver's index arithmetic on the host (no GPU): which frame pairs are evaluated and which slices
 of the event columns each pair reads.  ``window_ingest_raw_batch`` (csrc/window_ingest.hip) turns the estimation slices of a batch
 of steps into the solver's polarity images, the event masks of the masked error and the windows' time periods in one launch,
-straight from the raw sensor columns; the generative solvers take them through ``estimate_batch_prepared``.  Any other registered
-solver is driven window by window through ``preprocess`` + ``estimate``.
+straight from the raw sensor columns; the generative solvers and ``ContrastMaximization`` take them through
+``estimate_batch_prepared``.  A ``time_aware: {native: true}`` contrast maximisation with Adam builds the stacked time-aware plan of
+a batch from the same columns (``TimeAwarePlanStack.from_raw``) and solves the batch in one loop; its other configurations run
+``estimate`` on the windows' device events one after the other.  Any other registered solver is driven window by window through
+``preprocess`` + ``estimate``.
 
 ``run(pictures=True)`` also draws the driver's ten pictures per step (bos_event.py:202-207) on the device, batched
 (``visualizer.render_step_batch``), and writes them under ``save_dir`` in the driver's order and under its file names.

@@ -496,6 +496,15 @@ class EventPlan:
         (``TimeAwarePlanStack``)."""
         return TimeAwarePlanStack(plans)
 
+    @staticmethod
+    def build_raw_batch_time_aware(cols: Sequence[torch.Tensor], ranges: Sequence[Tuple[int, int]], image_size: Tuple[int, int],
+                                   direction: Union[str, float], tile: Tuple[int, int], time_bin: int, roi=None, remove=None,
+                                   ticks_per_second: float = 1e6, normalize_t: bool = True) -> "TimeAwarePlanStack":
+        """The binned time-aware plans of several windows of one recording, stacked, from the raw sensor columns in one set of
+        launches: ``TimeAwarePlanStack.from_raw``."""
+        return TimeAwarePlanStack.from_raw(cols, ranges, image_size, direction, tile, time_bin, roi=roi, remove=remove,
+                                           ticks_per_second=ticks_per_second, normalize_t=normalize_t)
+
     def bin(self, tile: Tuple[int, int] = DEFAULT_TILE, deferred: bool = False) -> "EventPlan":
         """Counting-sort the plan by source pixel, tile-major (ebos_bin_events_f32).
 
@@ -885,6 +894,110 @@ class TimeAwarePlanStack(object):
         self.bins = torch.cat([p.bins[:p.n] for p in plans]).contiguous()
         bases = torch.tensor([sum(self.ns[:b]) for b in range(len(plans))], dtype=torch.int32, device=first.device)
         self.key_offsets = (torch.stack([p.key_offsets for p in plans]) + bases[:, None]).to(torch.int32).contiguous()
+
+    @classmethod
+    def from_raw(cls, cols: Sequence[torch.Tensor], ranges: Sequence[Tuple[int, int]], image_size: Tuple[int, int],
+                 direction: Union[str, float], tile: Tuple[int, int], time_bin: int, roi=None, remove=None,
+                 ticks_per_second: float = 1e6, normalize_t: bool = True) -> "TimeAwarePlanStack":
+        """The stack of the windows ``ranges`` (half-open index ranges into the raw columns; they may overlap, come in any order and be
+        empty) straight from the raw sensor columns ``cols`` = (col int16, row int16, t int32 | int64 ticks, pol) on the GPU, in one
+        set of launches (``ebos_plan_time_aware_raw_batch``) and with ONE host read-back, the windows' event counts.  ``roi`` /
+        ``remove``: the CROP and removal rectangles of ``evaluation.window_ingest_raw_batch`` (rows xmin, xmax, columns ymin, ymax).
+        Window b holds what ``EventPlan.build(PreparedWindows.events(b), image_size, direction, normalize_t, tile=tile, emit="full",
+        time_bin=time_bin)`` holds, up to the order of the events of one source pixel; ``plans[b]`` are views into the stack's
+        buffers (their ``perm`` is the event's index inside its range, they carry no polarity stream, no compact layout and no work
+        items).  Argument errors are raised before the GPU is asked for."""
+        if isinstance(tile, str):
+            if tile != "auto":
+                raise ValueError("tile must be a (tile_h, tile_w) pair or 'auto'")
+            tile = choose_tile(image_size)
+        if tile is None:
+            raise ValueError("TimeAwarePlanStack.from_raw builds binned plans: tile must be a (tile_h, tile_w) pair or 'auto'")
+        time_bin = ops.check_time_bins(time_bin)
+        cols = tuple(cols)
+        if len(cols) not in (3, 4):
+            raise ValueError("cols must be (col, row, t) or (col, row, t, pol)")
+        col, row, t = cols[:3]
+        for name, v, dts in (("col", col, (torch.int16,)), ("row", row, (torch.int16,)), ("t", t, (torch.int32, torch.int64))):
+            if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.dtype not in dts:
+                raise ValueError(f"TimeAwarePlanStack.from_raw: {name} must be a 1-D tensor, dtype in {dts}; "
+                                 f"got {tuple(getattr(v, 'shape', ()))} {getattr(v, 'dtype', type(v).__name__)}")
+        n_total = int(t.shape[0])
+        if int(col.shape[0]) != n_total or int(row.shape[0]) != n_total:
+            raise ValueError("TimeAwarePlanStack.from_raw: the raw columns must be of equal length")
+        ranges = [(int(b), int(e)) for b, e in ranges]
+        if not ranges:
+            raise ValueError("TimeAwarePlanStack.from_raw: no windows")
+        if len(ranges) > _hip.CMAX_VOXEL_MAX_BATCH:
+            raise ValueError(f"TimeAwarePlanStack.from_raw: {len(ranges)} windows, the batched kernels take at most {_hip.CMAX_VOXEL_MAX_BATCH}")
+        for b, e in ranges:
+            if not 0 <= b <= e <= n_total:
+                raise IndexError(f"TimeAwarePlanStack.from_raw: range [{b}, {e}) outside the {n_total} events")
+        total = sum(e - b for b, e in ranges)
+        if total > INT32_MAX:
+            raise ValueError(f"TimeAwarePlanStack.from_raw: {total} events in total are more than INT32_MAX")
+        rects = []
+        for name, r in (("roi", roi), ("remove", remove)):
+            if r is not None:
+                r = tuple(r[k] for k in ("xmin", "xmax", "ymin", "ymax")) if isinstance(r, dict) else tuple(r)
+                if len(r) != 4 or any(int(v) != v for v in r):
+                    raise ValueError(f"{name} must be four integers (xmin, xmax, ymin, ymax), got {r!r}")
+                r = tuple(int(v) for v in r)
+                if r[0] > r[1] or r[2] > r[3]:
+                    raise ValueError(f"{name} must have xmin <= xmax and ymin <= ymax, got {r!r}")
+            rects.append(r)
+        roi, remove = rects
+        H, W = int(image_size[0]), int(image_size[1])
+        th, tw = int(tile[0]), int(tile[1])
+        if not (0 < H <= 32767 and 0 < W <= 32767 and th > 0 and tw > 0):
+            raise ValueError(f"TimeAwarePlanStack.from_raw: bad image size {H} x {W} or tile {th} x {tw}")
+        ref_mode, frac = parse_direction(direction)
+        lib = _hip.require_gpu()
+        for name, v in (("col", col), ("row", row), ("t", t)):
+            if not v.is_cuda:
+                raise _hip.HipUnavailableError(f"TimeAwarePlanStack.from_raw: {name} must be on the GPU")
+        col, row, t = col.contiguous(), row.contiguous(), t.contiguous()
+        dev, B = t.device, len(ranges)
+        n_keys = ((H + th - 1) // th) * ((W + tw - 1) // tw) * th * tw
+        c_ranges = (C.c_int64 * (2 * B))(*[v for r in ranges for v in r])
+        nbytes = int(lib.ebos_plan_time_aware_batch_scratch_bytes(c_ranges, B, H, W, th, tw))
+        if nbytes == 0:
+            raise ValueError(f"TimeAwarePlanStack.from_raw: bad geometry: {B} windows of {H} x {W}, tile {th} x {tw}")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        # (zeroed: what lies behind the kept events, the eight spare elements of EventPlan.bin included, is read as padding)
+        x, y, dt = (torch.zeros(total + 8, dtype=torch.float32, device=dev) for _ in range(3))
+        bins = torch.zeros(total + 8, dtype=torch.uint8, device=dev)
+        perm = torch.zeros(total + 8, dtype=torch.int32, device=dev)
+        key_local = torch.empty((B, n_keys + 1), dtype=torch.int32, device=dev)
+        key_stacked = torch.empty((B, n_keys + 1), dtype=torch.int32, device=dev)
+        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        tminmax = torch.empty((B, 2), dtype=torch.float64, device=dev)
+        r4, m4 = roi or (0, 0, 0, 0), remove or (0, 0, 0, 0)
+        with _hip.on_device(dev):
+            check(lib.ebos_plan_time_aware_raw_batch(ptr(col), ptr(row), ptr(t), int(t.dtype == torch.int64), float(ticks_per_second),
+                                                     n_total, c_ranges, B, int(roi is not None), *r4, int(remove is not None), *m4,
+                                                     ref_mode, frac, int(bool(normalize_t)), time_bin, H, W, th, tw, ptr(x), ptr(y),
+                                                     ptr(dt), ptr(bins), ptr(perm), total, ptr(key_local), ptr(key_stacked), n_keys + 1,
+                                                     ptr(counts), ptr(tminmax), ptr(scratch), nbytes, stream_ptr()),
+                  "ebos_plan_time_aware_raw_batch")
+        host = counts.tolist()   # the ONE host read-back of the build: (kept, outside the image) x B
+        self = object.__new__(cls)
+        self.ns = [int(c[0]) for c in host]
+        self.n = sum(self.ns)
+        self.image_size, self.tile, self.time_bin = (H, W), (th, tw), time_bin
+        self.dt_bound = dt_bound_for(direction, normalize_t)
+        self.x, self.y, self.dt, self.bins, self.perm = x[:self.n], y[:self.n], dt[:self.n], bins[:self.n], perm[:self.n]
+        self.key_offsets, self.tminmax = key_stacked, tminmax
+        self.plans, base = [], 0
+        for b, (n, dropped) in enumerate(host):
+            plan = EventPlan(x[base:base + n], y[base:base + n], dt[base:base + n], None, (H, W), n, n + dropped, (th, tw), key_local[b],
+                             perm[base:base + n], dropped, dt_bound=self.dt_bound, bins=bins[base:base + n], time_bin=time_bin)
+            plan.__dict__["_frac"], plan.__dict__["_frac_pending"] = None, False
+            plan.__dict__["_counts"], plan.__dict__["_deferred"] = None, False
+            plan.__dict__["_parts_used"], plan.__dict__["_fullest_tile"] = None, None
+            self.plans.append(plan)
+            base += n
+        return self
 
     def __len__(self) -> int:
         return len(self.plans)

@@ -41,7 +41,7 @@ from .. import _hip, costs, ops
 from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
-from ..event_plan import EventPlan
+from ..event_plan import EventPlan, TimeAwarePlanStack
 from . import fused_loop, time_aware_loop
 from .base import SolverBase
 
@@ -288,11 +288,50 @@ class ContrastMaximizationMixin(object):
         self.history, self.patch_flow = self.histories[-1], self.patch_flows[-1]
         return torch.cat(flows).detach().cpu().numpy().astype(np.float64)
 
-    def _estimate_patch_flow_batch(self, plans) -> torch.Tensor:
-        """``_estimate_patch_flow`` for one chunk of windows through the batch loop: [B, 2, H, W] (device)."""
+    def estimate_batch_prepared(self, prepared, frames=None, background=None, max_batch: int = 8, device_out: bool = False):
+        """``estimate_batch`` on ``evaluation.PreparedWindows`` that carry their raw columns (the signature of the generative
+        solvers' method; ``frames`` and ``background`` are not read): float64 [B, 2, H, W], numpy or -- ``device_out`` -- a device
+        tensor.  A ``time_aware: {native: true}`` configuration with Adam turns chunks of ``max_batch`` windows into a stacked plan
+        straight from the columns (``TimeAwarePlanStack.from_raw``: no float64 event array, one read-back per chunk) and solves them
+        through the batch loop; every other configuration is ``estimate`` on ``prepared.events(b)``, window by window.  Sets
+        ``histories``, ``patch_flows``, ``loop_modes``, ``history`` and ``patch_flow`` as ``estimate_batch`` does."""
+        if getattr(prepared, "cols", None) is None or getattr(prepared, "ranges", None) is None:
+            raise ValueError("estimate_batch_prepared needs windows that carry their raw columns (evaluation.window_ingest_raw_batch)")
+        max_batch = int(max_batch)
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be at least 1, got {max_batch}")
         H, W = self.orig_image_shape
-        B, dev = len(plans), plans[0].device
-        stack = EventPlan.stack_time_aware(plans)
+        ranges = list(prepared.ranges)
+        self.histories, self.patch_flows = [], []
+        if not ranges:
+            out = torch.zeros((0, 2, H, W), dtype=torch.float64, device=prepared.cols[2].device)
+            return out if device_out else out.cpu().numpy()
+        if not self._native_batch():
+            dev, flows = prepared.cols[2].device, []
+            for b in range(len(ranges)):
+                flows.append(self.estimate(prepared.events(b)))
+                self.histories.append(list(self.history))
+                self.patch_flows.append(getattr(self, "patch_flow", None))
+            out = np.stack(flows).astype(np.float64)
+            return torch.from_numpy(out).to(dev) if device_out else out
+        max_batch = min(max_batch, _hip.CMAX_VOXEL_MAX_BATCH)
+        flows = []
+        for c0 in range(0, len(ranges), max_batch):
+            stack = TimeAwarePlanStack.from_raw(prepared.cols, ranges[c0:c0 + max_batch], self.orig_image_shape, self.warp_direction,
+                                                self.plan_tile(), self.time_aware["time_bin"], roi=prepared.roi, remove=prepared.remove,
+                                                ticks_per_second=prepared.ticks_per_second)
+            flows.append(self._estimate_patch_flow_batch(stack))
+        self.history, self.patch_flow = self.histories[-1], self.patch_flows[-1]
+        out = torch.cat(flows).detach().to(torch.float64)
+        return out if device_out else out.cpu().numpy()
+
+    def _estimate_patch_flow_batch(self, plans) -> torch.Tensor:
+        """``_estimate_patch_flow`` for one chunk of windows through the batch loop: [B, 2, H, W] (device).  ``plans``: binned
+        time-aware plans of one geometry, or their ready ``TimeAwarePlanStack``."""
+        H, W = self.orig_image_shape
+        stack = plans if isinstance(plans, TimeAwarePlanStack) else EventPlan.stack_time_aware(plans)
+        plans = stack.plans
+        B, dev = len(plans), stack.device
         histories = [[] for _ in plans]
         self.loop_modes, per_scale = [], []
         theta = None

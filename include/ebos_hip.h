@@ -1675,6 +1675,35 @@ typedef struct ebos_cmax_voxel_batch_problem {
 int ebos_cmax_voxel_solve_batch_f32(const ebos_cmax_voxel_batch_problem* problem, int n_iter, ebos_stream_t stream);
 int ebos_cmax_voxel_gradient_batch_f32(const ebos_cmax_voxel_batch_problem* problem, ebos_stream_t stream);
 
+/* ---- the stacked plan above for B windows, built from the raw sensor columns in one set of launches (csrc/plan_time_aware.hip) ----
+ * col / row int16, t int32 (t_is_64 = 0) or int64 ticks: device columns of n_total events.  ranges: HOST int64 [B, 2], window b =
+ * events [begin, end) of the columns; the ranges may overlap, come in any order and be empty.  An event is kept when it lies inside
+ * the CROP rectangle (has_roi: rows [xmin, xmax), columns [ymin, ymax)), outside the removal rectangle (has_remove: rows
+ * [rm_x0, rm_x1), columns [rm_y0, rm_y1)) -- the rectangles of ebos_window_ingest_raw_batch -- and its pixel lies inside the image.
+ * Per window, what ebos_raw_time_range + ebos_raw_events_to_soa + ebos_event_time_bins_f64 + ebos_bin_events_f32 leave for the
+ * events that pass the rectangles: tminmax[b] = the tick range of those events / ticks_per_second (float64; 0, 0 for none), dt by
+ * the expression of ebos_raw_events_to_soa (float64, one rounding), bin by the rule of ebos_event_time_bins on
+ * (double)ticks / ticks_per_second, x = (float)row, y = (float)col, sorted by the tile-major source key.  Outputs:
+ *   xs, ys, dts float, bins uint8, perm int32 [capacity]  window b's kept events are the slice [base_b, base_b + n_b), base_b = the
+ *       kept events of the earlier windows; perm = the event's index inside its range (col[begin + perm[i]] is its source).
+ *       Only [0, sum n_b) is written.  capacity >= the sum of the range lengths.
+ *   key_offsets_local, key_offsets_stacked int32 [B, key_stride], key_stride >= n_keys + 1: the window's own offsets, and
+ *       local + base_b (the table of the batched kernels above when key_stride = n_keys + 1); an empty window's rows are constant.
+ *   counts int32 [B, 2]: kept events, events that pass the rectangles but lie outside the image.
+ * The order of the events of one source pixel is unspecified (as ebos_bin_events_f32).  Nine launches whatever B is, no host
+ * synchronisation.  Validated before the first launch: 1 <= B <= EBOS_CMAX_VOXEL_MAX_BATCH, 1 <= T <= 255, H, W <= 32767, the
+ * pointers, ranges inside n_total, at most INT32_MAX events in total, rectangle order (EBOS_ERR_INVALID_ARG), the scratch size
+ * (EBOS_ERR_SCRATCH).  scratch: ebos_plan_time_aware_batch_scratch_bytes(ranges, B, H, W, tile_h, tile_w) bytes (0: bad arguments).
+ * ---------------------------------------------------------------------------------------- */
+size_t ebos_plan_time_aware_batch_scratch_bytes(const int64_t* ranges, int B, int H, int W, int tile_h, int tile_w);
+int ebos_plan_time_aware_raw_batch(const int16_t* col, const int16_t* row, const void* t, int t_is_64, double ticks_per_second,
+                                   int64_t n_total, const int64_t* ranges, int B, int has_roi, int xmin, int xmax, int ymin, int ymax,
+                                   int has_remove, int rm_x0, int rm_x1, int rm_y0, int rm_y1, int ref_mode, double ref_fraction,
+                                   int normalize_t, int T, int H, int W, int tile_h, int tile_w, float* xs, float* ys, float* dts,
+                                   uint8_t* bins, int32_t* perm, int64_t capacity, int32_t* key_offsets_local,
+                                   int32_t* key_offsets_stacked, int64_t key_stride, int32_t* counts, double* tminmax, void* scratch,
+                                   size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,11 @@ sides do the same work (both write the three text files) and alternate, after on
 (``ebos_profile_start``) is never started and no torch profiler is used; the best and the spread (max - min) of each side are reported per step, and the raw
 times are written as JSON.  ``--ingest-only`` runs only the window ingest and the path it replaces (upload + polarity splat +
 event mask + period) a few times: the run to put under ``rocprofv3 --kernel-trace --stats -- python tools/bench_eval.py --ingest-only``.
+
+``--solvers cmax_time_aware``: the time-aware contrast maximisation as a native loop (configs/cmax_time_aware_eval.yaml's solver
+section, patch sized to the geometry).  Its two sides are the evaluator with the solver's ``estimate_batch_prepared`` (stacked plans
+from the raw columns, the batch loop) and the same evaluator with that method hidden, i.e. the window-by-window ``preprocess`` +
+``estimate`` route; both are timed with device events, best and [min, max] of alternating rounds.
 """
 import argparse
 import copy
@@ -97,6 +102,70 @@ def bench_case(ebos, size, kind, max_batches, n_iter, repeats, n_frames):
     return rows
 
 
+class HiddenPreparedPath(object):
+    """A solver without its ``estimate_batch_prepared``: the evaluator then drives it window by window."""
+
+    def __init__(self, solver):
+        object.__setattr__(self, "_solver", solver)
+
+    def __getattr__(self, name):
+        if name == "estimate_batch_prepared":
+            raise AttributeError(name)
+        return getattr(object.__getattribute__(self, "_solver"), name)
+
+    def __setattr__(self, name, value):
+        setattr(object.__getattribute__(self, "_solver"), name, value)
+
+
+def cmax_time_aware_solver(shape, n_iter):
+    here = os.path.dirname(os.path.abspath(__file__))
+    solver = run_eval.load_config(os.path.join(os.path.dirname(here), "configs", "cmax_time_aware_eval.yaml"))["solver"]
+    solver["optimizer"]["n_iter"] = n_iter
+    size = [max(8, shape[0] // 8), max(8, shape[1] // 8)]
+    solver["patch"] = {"size": size, "sliding_window": size}
+    return solver
+
+
+def bench_cmax_time_aware(ebos, size, max_batches, n_iter, repeats, n_frames):
+    """The evaluator with the batched prepared path against the same evaluator driving the solver window by window."""
+    import torch
+    from event_based_bos_amd.evaluation import RecordingEvaluator, synthetic_recording
+
+    shape, roi, per = GEOMETRY[size]
+    tmp = tempfile.mkdtemp(prefix="ebos_bench_eval_")
+    ev_path, fr_path, tr_path, stamps = synthetic_recording(tmp, shape, n_frames, per)
+    cfg = run_eval.synthetic_config(shape, roi, stamps, n_iter)
+    cfg["solver"] = cmax_time_aware_solver(shape, n_iter)
+    cfg = ebos.utils.propagate_config(cfg)
+    events, frames = ebos.RawEventStore(ev_path), ebos.FrameStore(fr_path, tr_path)
+    os.chdir(tmp)
+    rows = []
+    for mb in max_batches:
+        times = {"sequential": [], "prepared": []}
+        n_steps = None
+        for rep in range(repeats + 1):   # (rep 0 warms both sides up)
+            for side in ("sequential", "prepared"):
+                solv = run_eval.build_solver(ebos, copy.deepcopy(cfg))
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                start.record()
+                driven = HiddenPreparedPath(solv) if side == "sequential" else solv
+                n_steps = len(RecordingEvaluator(cfg, events, frames, driven, save_dir=tmp).run(max_batch=mb).steps)
+                stop.record()
+                stop.synchronize()
+                if rep:
+                    times[side].append(start.elapsed_time(stop) / n_steps)
+        row = {"size": size, "solver": "cmax_time_aware", "max_batch": mb, "n_iter": n_iter, "steps": n_steps, "events_per_window": per,
+               "unit": "ms per step (device events around the whole run)"}
+        for side, v in times.items():
+            row[side] = {"best": round(min(v), 3), "min_max": [round(min(v), 3), round(max(v), 3)], "rounds": [round(x, 3) for x in v]}
+        (lo_s, hi_s), (lo_p, hi_p) = row["sequential"]["min_max"], row["prepared"]["min_max"]
+        row["verdict"] = "faster" if hi_p < lo_s else ("SLOWER" if lo_p > hi_s else "intervals overlap: no difference counted")
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
 def ingest_only(ebos, size, repeats):
     import torch
     from event_based_bos_amd.evaluation import window_ingest_raw_batch
@@ -161,10 +230,16 @@ def main(argv=None) -> int:
 
     out_path = os.path.abspath(args.out) if args.out else None
     sizes = [int(v) for v in args.shapes.split(",")]
-    result = {"ingest": [ingest_only(ebos, s, args.repeats) for s in sizes], "evaluation": []}
+    kinds = args.solvers.split(",")
+    only_cmax = kinds == ["cmax_time_aware"]
+    result = {"ingest": [] if only_cmax else [ingest_only(ebos, s, args.repeats) for s in sizes], "evaluation": []}
     if not args.ingest_only:
         for s in sizes:
-            for kind in args.solvers.split(","):
+            for kind in kinds:
+                if kind == "cmax_time_aware":
+                    result["evaluation"] += bench_cmax_time_aware(ebos, s, [int(v) for v in args.max_batch.split(",")], args.n_iter,
+                                                                  args.repeats, args.frames)
+                    continue
                 result["evaluation"] += bench_case(ebos, s, kind, [int(v) for v in args.max_batch.split(",")], args.n_iter,
                                                    args.repeats, args.frames)
     if out_path:

@@ -7,6 +7,10 @@
 ``--batch K``: K consecutive windows of ``--events`` events of one recording (raw columns on the device), deferred lean builds:
 the per-window wall time of K single builds in a loop against ONE ``EventPlan.build_raw_batch`` of the same windows -- same process,
 alternating, after warm-up; best, median and spread (max - min) over ``--reps`` rounds of each.
+
+``--time-aware --batch K [--time-bin T]``: the stacked time-aware plan of the K windows -- ``TimeAwarePlanStack.from_raw`` against the
+route it replaces (``PreparedWindows.events`` -> ``EventPlan.build(time_bin=T)`` -> ``EventPlan.stack_time_aware``), same process,
+alternating rounds after warm-up, timed with device events; best and [min, max] per window over ``--reps`` rounds (5 by default).
 """
 import argparse
 import json
@@ -82,6 +86,57 @@ def bench_batch(a):
         json.dump(rows, open(a.out, "w"), indent=1)
 
 
+def bench_time_aware(a):
+    """One batched time-aware build from the raw columns against the window-by-window route, alternating in one process."""
+    from event_based_bos_amd.evaluation import PreparedWindows
+
+    H, W, n, K, T = a.height, a.width, a.events, a.batch, a.time_bin
+    reps = a.reps if a.reps != 20 else 5
+    rs = np.random.RandomState(0)
+    tile = (64, 64)
+    raw = (torch.from_numpy(rs.randint(0, W, n * K).astype(np.int16)).cuda(), torch.from_numpy(rs.randint(0, H, n * K).astype(np.int16)).cuda(),
+           torch.from_numpy((np.sort(rs.randint(0, 8333 * K, n * K)) + 10_000_000).astype(np.int32)).cuda(),
+           torch.from_numpy(rs.randint(0, 2, n * K).astype(np.uint8)).cuda())
+    ranges = [(k * n, (k + 1) * n) for k in range(K)]
+    prepared = PreparedWindows(None, None, None, torch.zeros(K), torch.zeros(K), raw, ranges, None, None, 1e6)
+
+    def parent():
+        return ebos.EventPlan.stack_time_aware([ebos.EventPlan.build(prepared.events(b), (H, W), "first", True, tile=tile, emit="full", time_bin=T)
+                                                for b in range(K)])
+
+    def new():
+        return ebos.TimeAwarePlanStack.from_raw(raw, ranges, (H, W), "first", tile, T)
+
+    old, got = parent(), new()   # the same stack, at the sizes timed (up to the order inside a pixel's run: the offsets and the counts)
+    if old.ns != got.ns or not torch.equal(old.key_offsets, got.key_offsets):
+        raise SystemExit("bench_plan_build: the stack from the raw columns differs from the window-by-window build")
+    for _ in range(2):
+        parent(), new()
+    torch.cuda.synchronize()
+    times = {"parent": [], "from_raw": []}
+    for _ in range(reps):
+        for name, fn in (("parent", parent), ("from_raw", new)):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            fn()
+            stop.record()
+            stop.synchronize()
+            times[name].append(start.elapsed_time(stop) / K)
+    res = {"time_aware": True, "windows": K, "events_per_window": n, "image": [H, W], "tile": list(tile), "time_bin": T, "reps": reps,
+           "unit": "ms per window (device events around the whole build, host gaps included)"}
+    for name, v in times.items():
+        res[name] = {"best": round(min(v), 4), "min_max": [round(min(v), 4), round(max(v), 4)], "rounds": [round(x, 4) for x in v]}
+    lo_p, hi_p = res["parent"]["min_max"]
+    lo_n, hi_n = res["from_raw"]["min_max"]
+    res["verdict"] = "faster" if hi_n < lo_p else ("SLOWER" if lo_n > hi_p else "intervals overlap: no difference counted")
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        rows = json.load(open(a.out)) if os.path.exists(a.out) else []
+        rows.append(res)
+        json.dump(rows, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--events", type=int, default=10_000_000)
@@ -90,7 +145,13 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="K > 0: K windows of --events events, loop of single builds against one batched build")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="--batch: append the result to this JSON list")
+    ap.add_argument("--time-aware", action="store_true", help="with --batch: the stacked time-aware plan, from_raw against the window-by-window route")
+    ap.add_argument("--time-bin", type=int, default=5, help="--time-aware: the number of time bins T")
     a = ap.parse_args()
+    if a.time_aware:
+        if a.batch <= 0:
+            ap.error("--time-aware needs --batch K")
+        return bench_time_aware(a)
     if a.batch > 0:
         return bench_batch(a)
     H, W, n = a.height, a.width, a.events

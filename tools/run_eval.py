@@ -4,10 +4,13 @@
     python tools/run_eval.py --config_file tests/golden/config_hot_plate1.json --events recording.npz --frames frames/ \
         --triggers trigger_events.txt [--homography homography.txt] [--max-batch 8] [--height H --width W] [--out out/]
     python tools/run_eval.py --synthetic [--n-iter 60] [--pictures]
+    python tools/run_eval.py --synthetic --config_file configs/cmax_time_aware_eval.yaml [--n-iter 60]
 
 ``--config_file`` is a JSON (or, where PyYAML is installed, YAML) file with the reference's keys; a file with an "input" section
 (tests/golden/config_hot_plate1.json) is read from there and propagated.  ``--synthetic`` builds a small recording in a temporary
-directory and evaluates it, so the tool runs anywhere a GPU is.
+directory and evaluates it, so the tool runs anywhere a GPU is; with ``--config_file`` too, the synthetic recording is evaluated
+with the ``solver`` section of that file (configs/cmax_time_aware_eval.yaml: the time-aware contrast maximisation as a native loop,
+solved in batches through ``estimate_batch_prepared``).
 """
 import argparse
 import copy
@@ -32,9 +35,13 @@ def load_config(path: str) -> dict:
     return copy.deepcopy(cfg["input"]) if "input" in cfg else cfg
 
 
-def synthetic_config(shape, roi, stamps, n_iter: int) -> dict:
+def synthetic_config(shape, roi, stamps, n_iter: int, solver_from: str = None) -> dict:
+    """The configuration of the synthetic recording; ``solver_from``: a config file whose ``solver`` section replaces the default's."""
     here = os.path.dirname(os.path.abspath(__file__))
     cfg = load_config(os.path.join(os.path.dirname(here), "tests", "golden", "config_hot_plate1.json"))
+    if solver_from is not None:
+        cfg["solver"] = copy.deepcopy(load_config(solver_from)["solver"])
+        cfg["solver"].setdefault("optimizer", {})
     cfg["common_params"].update({"xmin": roi[0], "xmax": roi[1], "ymin": roi[2], "ymax": roi[3]})
     cfg["data"].update({"height": shape[0], "width": shape[1]})
     cfg["evaluation"]["time_list"] = [[float(stamps[0]) + 0.004, float(stamps[-1]) + 0.004]]
@@ -74,7 +81,7 @@ def main(argv=None) -> int:
     if args.synthetic:
         shape, roi = (128, 160), (0, 128, 16, 144)
         ev_path, fr_path, tr_path, stamps = synthetic_recording(os.path.join(out, "recording"), shape, 8, 8000)
-        cfg = synthetic_config(shape, roi, stamps, args.n_iter)
+        cfg = synthetic_config(shape, roi, stamps, args.n_iter, args.config_file)
         events, frames = ebos.RawEventStore(ev_path), ebos.FrameStore(fr_path, tr_path)
     else:
         if not (args.config_file and args.events and args.frames):
