@@ -304,6 +304,9 @@ SIGNATURES = {
     "ebos_plan_time_aware_batch_scratch_bytes": (_Z, [_P, _I, _I, _I, _I, _I]),
     "ebos_plan_time_aware_raw_batch": (_I, [_P, _P, _P, _I, _D, _L, _P, _I] + [_I] * 10 + [_I, _D] + [_I] * 6 + [_P] * 5 + [_L, _P, _P, _L] +
                                        [_P, _P, _P, _Z, _P]),
+    "ebos_iwe_multiref_fits": (_I, [_I, _I, _I, _I]),
+    "ebos_iwe_dense_multiref_tiled_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 8 + [C.POINTER(_F), _I, _P, _P]),
+    "ebos_iwe_dense_multiref_owner_bwd_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 6 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
 }
 
 
@@ -367,6 +370,7 @@ class CmaxVoxelProblem(C.Structure):
 
 
 CMAX_VOXEL_MAX_BATCH = 64   # EBOS_CMAX_VOXEL_MAX_BATCH
+MULTIREF_MAX = 4            # EBOS_MULTIREF_MAX
 
 
 class CmaxVoxelBatchProblem(C.Structure):

@@ -76,6 +76,14 @@ def dt_bound_for(direction: Union[str, float], normalize_t: bool) -> Optional[fl
     return max(abs(frac), abs(1.0 - frac))
 
 
+def ref_fraction_for(direction: Union[str, float]) -> Optional[float]:
+    """The fraction f of the window at which a plan's reference time lies (``parse_direction``), kept on the plan as
+    ``ref_fraction``; None for ``'random'``, whose draw is not kept."""
+    if type(direction) is str and direction == "random":
+        return None
+    return float(parse_direction(direction)[1])
+
+
 def resolve_halo(plan: "EventPlan", halo) -> int:
     """The ``halo`` argument of the tile-private operators -> the integer the C ABI takes.  An int is a built halo;
     ``"auto"`` asks for run-time windows per tile (``EBOS_HALO_AUTO``: each work item sizes its LDS window from a bound on ITS
@@ -186,6 +194,8 @@ class EventPlan:
     dt_bound: Optional[float] = None             # max |dt| over the events as known on the host (dt_bound_for), else None
     bins: Optional[torch.Tensor] = None          # time-aware plan: uint8 [n] time bin of each planned event (ops.time_bins)
     time_bin: Optional[int] = None               # time-aware plan: the number of bins T the bins were made for
+    ref_fraction: Optional[float] = None         # the reference time of dt as a fraction of the window (None: 'random', or unknown)
+    normalized_t: Optional[bool] = None          # was dt divided by the window's length?
 
     @property
     def binned(self) -> bool:
@@ -209,7 +219,7 @@ class EventPlan:
     def clear_cache(self) -> None:
         """Free what the operators cached on the plan: workspaces, dense jobs and the sweep lanes of ``variance_2dof`` /
         ``variance_dense_many`` (streams, one workspace per hypothesis of a chunk, image buffers -- up to 1.7 GB at 1280x720)."""
-        for k in ("_workspaces", "_jobs", "_sweep_lanes"):
+        for k in ("_workspaces", "_jobs", "_sweep_lanes", "_multiref_dts"):
             self.__dict__.pop(k, None)
 
     def resolve_splits(self, splits: Optional[int]) -> int:
@@ -342,7 +352,8 @@ class EventPlan:
             fn = getattr(lib, "ebos_events_to_soa_" + _hip.suffix(events.dtype))
             check(fn(ptr(events), ptr(tmm), ref_mode, frac, int(normalize_t), n, ptr(x), ptr(y), ptr(dt), ptr(p),
                      stream_ptr()), "ebos_events_to_soa")
-        plan = EventPlan(x, y, dt, p, (H, W), n, n, dt_bound=dt_bound_for(direction, normalize_t))
+        plan = EventPlan(x, y, dt, p, (H, W), n, n, dt_bound=dt_bound_for(direction, normalize_t),
+                         ref_fraction=ref_fraction_for(direction), normalized_t=bool(normalize_t))
         if time_bin is not None:
             plan.bins, plan.time_bin = ops.time_bins(events[None], time_bin, tmm)[0], time_bin
         if tile is not None:
@@ -397,7 +408,8 @@ class EventPlan:
             check(lib.ebos_raw_events_to_soa(ptr(col), ptr(row), ptr(t), t.element_size(), ptr(pol), float(ticks_per_second),
                                              ptr(tmm), ref_mode, frac, int(normalize_t), n, ptr(x), ptr(y), ptr(dt), ptr(p),
                                              stream_ptr()), "ebos_raw_events_to_soa")
-        plan = EventPlan(x, y, dt, p, (H, W), n, n, dt_bound=dt_bound_for(direction, normalize_t))
+        plan = EventPlan(x, y, dt, p, (H, W), n, n, dt_bound=dt_bound_for(direction, normalize_t),
+                         ref_fraction=ref_fraction_for(direction), normalized_t=bool(normalize_t))
         if tile is not None:
             plan = plan.bin(tile, deferred=deferred)  # int16 columns: integer coordinates by construction
         return plan
@@ -484,7 +496,8 @@ class EventPlan:
             dropped, used, fullest = (0, None, None) if facts is None else (facts[w][0], facts[w][2], facts[w][3])
             o, cap = lay.slot_offsets[w], lay.capacities[w]
             plan = EventPlan(None, None, None, None, (H, W), n - dropped, n, (th, tw), key_all[w, :n_keys + 1], None, dropped,
-                             grp_all[w, :n_tiles + 1], cpix_all[o:o + cap], cdt_all[o:o + cap], part_all[w, :5 * n_tiles + 1], bound)
+                             grp_all[w, :n_tiles + 1], cpix_all[o:o + cap], cdt_all[o:o + cap], part_all[w, :5 * n_tiles + 1], bound,
+                             ref_fraction=ref_fraction_for(direction), normalized_t=bool(normalize_t))
             plan.__dict__["_counts"], plan.__dict__["_deferred"], plan.__dict__["_parts_used"] = counts_all[w], bool(deferred), used
             plan.__dict__["_fullest_tile"] = fullest
             plans.append(plan)
@@ -560,7 +573,8 @@ class EventPlan:
         # never do and no longer pay the rank loop, the hot-pixel pass and 14 B/event: ADVICE r05)
         frac_pending = bool(fractional > 0 and th <= 256 and tw <= 256)
         out = EventPlan(xs[:kept], ys[:kept], dts[:kept], ps[:kept], self.image_size, kept, self.n_input,
-                        (th, tw), key_offsets, src_perm, self.n_dropped + dropped, grp_offsets, cpix, cdt, part_table, self.dt_bound)
+                        (th, tw), key_offsets, src_perm, self.n_dropped + dropped, grp_offsets, cpix, cdt, part_table, self.dt_bound,
+                        ref_fraction=self.ref_fraction, normalized_t=self.normalized_t)
         if self.bins is not None:
             if deferred:
                 raise NotImplementedError('a time-aware plan (time_bin) needs the host read-back of the build: deferred=False, emit="full"')
@@ -781,6 +795,37 @@ class EventPlan:
         v = ops.gradient_magnitude(self.iwe_dense(flow, pad=pad, halo=halo, splits=splits), omit_boundary)
         return v if sign == 1.0 else v * sign
 
+    # ------------------------------------------------------------------------------------------ multi-reference contrast
+    def iwe_dense_multi(self, flow: torch.Tensor, directions, pad: Tuple[int, int] = (0, 0), halo=DEFAULT_HALO,
+                        splits: Optional[int] = None, fused: Optional[bool] = None) -> torch.Tensor:
+        """The IWEs of ``flow`` [2, H, W] at several reference times: ``directions`` holds 1 to 4 entries of ``'first' | 'middle' |
+        'last' | 'before' | 'after' | float`` (``parse_direction``) -> iwes [K, H + 2 pad_h, W + 2 pad_w], entry k what a plan built
+        with direction k gives from ``iwe_dense``.  Differentiable with respect to ``flow`` for any upstream [K, h, w].
+
+        The plan's dt was made with reference fraction f (``ref_fraction``) and normalised time, so reference k is the scalar shift
+        f - r_k of every dt.  ``fused=True``: ONE pass over the events makes all K images (``ebos_iwe_dense_multiref_tiled_f32``: K
+        LDS windows per tile) and the backward is the owner kernel (``ebos_iwe_dense_multiref_owner_bwd_f32``: no atomics, the same
+        bits on every call); ``halo`` is used where K windows of it fit the LDS, else the largest built halo of the plan's tile that
+        does (``ebos_iwe_multiref_fits``).  ``fused=False``: the loop route, K calls of ``ebos_iwe_dense_tiled_f32`` and of
+        ``ebos_iwe_dense_bwd_f32`` on ``dt + shift_k``.  ``fused=None``: the loop route where nothing fits, else
+        ``MULTIREF_DEFAULT_FUSED``.  ValueError for ``'random'``, an empty list, more than 4 directions, and a plan without
+        normalised time or without a reference fraction; NotImplementedError for an un-binned, lean or deferred plan."""
+        job = _multiref_job(self, directions, pad, halo, splits, fused, "iwe_dense_multi")
+        return _MultiRefIwe.apply(flow, self, job)
+
+    def contrast_dense_multi(self, flow: torch.Tensor, directions, cost: str = "image_variance", omit_boundary: bool = False,
+                             pad: Tuple[int, int] = (0, 0), halo=DEFAULT_HALO, splits: Optional[int] = None,
+                             fused: Optional[bool] = None) -> torch.Tensor:
+        """The multi-reference focus objective: the MEAN over the references of the raw contrast of ``iwe_dense_multi`` (0-d tensor),
+        differentiable with respect to ``flow``.  For ``image_variance`` the K variances come from one ``ebos_image_variance_f32`` call
+        and their gradients are folded into the event backward as an affine map per reference (no d_iwe images)."""
+        if cost not in ("image_variance", "gradient_magnitude"):
+            raise KeyError(f"unknown contrast cost {cost!r}")
+        job = _multiref_job(self, directions, pad, halo, splits, fused, "contrast_dense_multi")
+        if cost == "image_variance":
+            return _MultiRefVariance.apply(flow, self, job, bool(omit_boundary))
+        return ops.gradient_magnitude(_MultiRefIwe.apply(flow, self, job), omit_boundary).mean()
+
     # ------------------------------------------------------------------------------------------ time-aware warp
     def iwe_voxel(self, voxel: torch.Tensor, pad: Tuple[int, int] = (0, 0), weight: Optional[torch.Tensor] = None,
                   halo: Optional[int] = DEFAULT_HALO, splits: Optional[int] = None) -> torch.Tensor:
@@ -889,6 +934,7 @@ class TimeAwarePlanStack(object):
             raise ValueError(f"stack_time_aware: {sum(self.ns)} events in total are more than INT32_MAX")
         self.plans = plans
         self.image_size, self.tile, self.time_bin, self.dt_bound = first.image_size, tuple(first.tile), first.time_bin, first.dt_bound
+        self.ref_fraction, self.normalized_t = first.ref_fraction, first.normalized_t
         self.n = sum(self.ns)
         self.x, self.y, self.dt = (torch.cat([getattr(p, k)[:p.n] for p in plans]).contiguous() for k in ("x", "y", "dt"))
         self.bins = torch.cat([p.bins[:p.n] for p in plans]).contiguous()
@@ -986,12 +1032,14 @@ class TimeAwarePlanStack(object):
         self.n = sum(self.ns)
         self.image_size, self.tile, self.time_bin = (H, W), (th, tw), time_bin
         self.dt_bound = dt_bound_for(direction, normalize_t)
+        self.ref_fraction, self.normalized_t = ref_fraction_for(direction), bool(normalize_t)
         self.x, self.y, self.dt, self.bins, self.perm = x[:self.n], y[:self.n], dt[:self.n], bins[:self.n], perm[:self.n]
         self.key_offsets, self.tminmax = key_stacked, tminmax
         self.plans, base = [], 0
         for b, (n, dropped) in enumerate(host):
             plan = EventPlan(x[base:base + n], y[base:base + n], dt[base:base + n], None, (H, W), n, n + dropped, (th, tw), key_local[b],
-                             perm[base:base + n], dropped, dt_bound=self.dt_bound, bins=bins[base:base + n], time_bin=time_bin)
+                             perm[base:base + n], dropped, dt_bound=self.dt_bound, bins=bins[base:base + n], time_bin=time_bin,
+                             ref_fraction=self.ref_fraction, normalized_t=self.normalized_t)
             plan.__dict__["_frac"], plan.__dict__["_frac_pending"] = None, False
             plan.__dict__["_counts"], plan.__dict__["_deferred"] = None, False
             plan.__dict__["_parts_used"], plan.__dict__["_fullest_tile"] = None, None
@@ -1052,7 +1100,8 @@ def _build_lean(source: int, events, raw, image_size, direction, normalize_t, ti
         if fractional:
             return None  # fractional (undistorted) source coordinates: the (x, y, dt) format of the full build
     plan = EventPlan(None, None, None, None, (H, W), n - dropped, n, (th, tw), key_offsets, None, dropped, grp_offsets, cpix, cdt,
-                     part_table, dt_bound_for(direction, normalize_t))
+                     part_table, dt_bound_for(direction, normalize_t), ref_fraction=ref_fraction_for(direction),
+                     normalized_t=bool(normalize_t))
     plan.__dict__["_counts"], plan.__dict__["_deferred"], plan.__dict__["_parts_used"] = counts, bool(deferred), used
     plan.__dict__["_fullest_tile"] = fullest
     return plan
@@ -1373,6 +1422,204 @@ class _FusedIweDense(torch.autograd.Function):
                                         splits=splits)
         d_weight = _unpermute(plan, d_w).to(wdt) if need_w else None
         return (d_flow.to(fdt) if ctx.needs_input_grad[0] else None), d_weight, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# multi-reference contrast: the IWEs of one flow at several reference times
+# ----------------------------------------------------------------------------------------------
+MULTIREF_MAX = _hip.MULTIREF_MAX
+# fused=None where K windows fit the LDS: what tools/bench_multiref.py measured
+MULTIREF_DEFAULT_FUSED = False
+
+
+def multi_reference_fractions(directions) -> List[float]:
+    """``directions`` (1 to 4 of 'first' | 'middle' | 'last' | 'before' | 'after' | float) -> their fractions of the window."""
+    if isinstance(directions, (str, float, int)) or directions is None:
+        raise ValueError(f"directions must be a list of 1 to {MULTIREF_MAX} reference times, got {directions!r}")
+    directions = list(directions)
+    if not 1 <= len(directions) <= MULTIREF_MAX:
+        raise ValueError(f"directions must hold 1 to {MULTIREF_MAX} reference times, got {len(directions)}")
+    out = []
+    for d in directions:
+        if isinstance(d, str) and d == "random":
+            raise ValueError("directions: 'random' is no reference time of a multi-reference objective (its draw differs per call)")
+        if isinstance(d, (int, float)) and not isinstance(d, bool):
+            d = float(d)
+        frac = float(parse_direction(d)[1])
+        if frac != frac or frac in (float("inf"), float("-inf")):
+            raise ValueError(f"directions: {d!r} is not a finite fraction of the window")
+        out.append(frac)
+    return out
+
+
+def multi_reference_shifts(plan: "EventPlan", directions) -> List[float]:
+    """The float32 shifts f - r_k that turn the plan's dt (reference fraction f) into the dt of every direction."""
+    import numpy as np
+
+    fracs = multi_reference_fractions(directions)
+    if not plan.normalized_t:
+        raise ValueError("a multi-reference objective needs a plan built with normalised time (normalize_t=True): only then is another "
+                         "reference time a shift of dt that the host knows")
+    if plan.ref_fraction is None:
+        raise ValueError("the plan does not know the reference fraction of its dt (a 'random' direction): build it with 'first', "
+                         "'middle', 'last', 'before', 'after' or a float")
+    return [float(np.float32(plan.ref_fraction - r)) for r in fracs]
+
+
+class _MultiRefJob(NamedTuple):
+    shifts: Tuple[float, ...]   # float32 values
+    pad: Tuple[int, int]
+    fused: bool
+    halo: Optional[int]         # the built halo of the route's forward kernel (None: the loop route on the general kernel)
+    splits: int
+
+
+def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what: str) -> _MultiRefJob:
+    shifts = tuple(multi_reference_shifts(plan, directions))
+    if not plan.binned:
+        raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
+    _refuse_deferred(plan, what)
+    if fused not in (None, True, False):
+        raise ValueError(f"fused must be None, True or False, got {fused!r}")
+    lib = _hip.load_library()
+    K = len(shifts)
+    th, tw = int(plan.tile[0]), int(plan.tile[1])
+    built = sorted(hl for a, b, hl in _hip.tiled_configs() if (a, b) == (th, tw))
+    want = None if halo is None or halo == "auto" else _max_halo(int(halo))
+    fit = [hl for hl in built if lib.ebos_iwe_multiref_fits(th, tw, hl, K) != 0]
+    if want is not None and want in fit:
+        fused_halo = want
+    elif fit and (want is None or fused is True):
+        fused_halo = max(fit)
+    else:
+        fused_halo = None
+    if fused is True and fused_halo is None:
+        raise NotImplementedError(f"{what}: no built halo of tile {(th, tw)} keeps {K} windows in the LDS (ebos_iwe_multiref_fits); "
+                                  "fused=False runs the loop route")
+    use_fused = fused_halo is not None and (MULTIREF_DEFAULT_FUSED if fused is None else fused)
+    if use_fused:
+        route_halo = fused_halo
+    elif want is not None and want in built:
+        route_halo = want
+    elif built:
+        route_halo = DEFAULT_HALO if DEFAULT_HALO in built and want is None else max(built)
+    else:
+        route_halo = None   # a tile without a tiled kernel: the general forward kernel, reference by reference
+    return _MultiRefJob(shifts, (int(pad[0]), int(pad[1])), bool(use_fused), route_halo, max(1, plan.resolve_splits(splits)))
+
+
+def _multiref_dt(plan: "EventPlan", shift: float) -> torch.Tensor:
+    """``plan.dt + shift`` in float32 (the loop route's event times of one reference), kept on the plan."""
+    cache = plan.__dict__.setdefault("_multiref_dts", {})
+    t = cache.get(shift)
+    if t is None:
+        t = cache[shift] = plan.dt if shift == 0.0 else (plan.dt + shift).contiguous()
+    return t
+
+
+def _c_shifts(shifts):
+    return (C.c_float * len(shifts))(*shifts)
+
+
+def _launch_multiref_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob) -> torch.Tensor:
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    K, pad = len(job.shifts), job.pad
+    iwes = torch.zeros((K, H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
+    with _hip.on_device(plan.device):
+        if job.fused:
+            check(lib.ebos_iwe_dense_multiref_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                        H, W, plan.tile[0], plan.tile[1], job.halo, job.splits, pad[0], pad[1],
+                                                        _c_shifts(job.shifts), K, ptr(iwes), stream_ptr()),
+                  "ebos_iwe_dense_multiref_tiled")
+            return iwes
+        for k, shift in enumerate(job.shifts):
+            dt_k = _multiref_dt(plan, shift)
+            if job.halo is not None:
+                check(lib.ebos_iwe_dense_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(dt_k), None, ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                   H, W, plan.tile[0], plan.tile[1], job.halo, job.splits, pad[0], pad[1], ptr(iwes[k]),
+                                                   stream_ptr()), "ebos_iwe_dense_tiled")
+            else:
+                check(lib.ebos_iwe_dense_f32(ptr(plan.x), ptr(plan.y), ptr(dt_k), None, plan.n, ptr(flow32), H, W, W, pad[0], pad[1],
+                                             ptr(iwes[k]), stream_ptr()), "ebos_iwe_dense")
+    return iwes
+
+
+def _launch_multiref_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, g_images: torch.Tensor,
+                         affine: Optional[torch.Tensor], g_lo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_flow [2, H, W] = sum over the references of the event backward with upstream G_k = a_k g_images[k] + c_k."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    K, pad = len(job.shifts), job.pad
+    with _hip.on_device(plan.device):
+        if job.fused:
+            d_flow = torch.empty((2, H, W), dtype=torch.float32, device=plan.device) if out is None else out   # every cell is written
+            check(lib.ebos_iwe_dense_multiref_owner_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n,
+                                                            ptr(flow32), H, W, plan.tile[0], plan.tile[1], pad[0], pad[1],
+                                                            _c_shifts(job.shifts), K, ptr(g_images), ptr(affine), int(g_lo), ptr(d_flow),
+                                                            stream_ptr()), "ebos_iwe_dense_multiref_owner_bwd")
+            return d_flow
+        d_flow = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
+        for k, shift in enumerate(job.shifts):
+            dt_k = _multiref_dt(plan, shift)
+            check(lib.ebos_iwe_dense_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(dt_k), None, plan.n, ptr(flow32), H, W, W, pad[0], pad[1],
+                                             ptr(g_images[k]), None if affine is None else ptr(affine[k]), int(g_lo), 1, ptr(d_flow),
+                                             None, stream_ptr()), "ebos_iwe_dense_bwd")
+    return d_flow
+
+
+class _MultiRefIwe(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, plan, job):
+        flow32 = _check_flow(plan, flow)
+        iwes = _launch_multiref_fwd(plan, flow32, job)
+        ctx.save_for_backward(flow32)
+        ctx.meta = (plan, job, flow.dtype)
+        return iwes if flow.dtype == torch.float32 else iwes.to(flow.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (flow32,) = ctx.saved_tensors
+        plan, job, fdt = ctx.meta
+        d_flow = _launch_multiref_bwd(plan, flow32, job, g.to(torch.float32).contiguous(), None, 0)
+        return d_flow.to(fdt), None, None
+
+
+class _MultiRefVariance(torch.autograd.Function):
+    """mean_k var(IWE_k(flow)): the K variances and their moments by one cost-kernel call; the event backward reads the IWEs
+    through the variances' affine maps, so no d_iwe image is made."""
+
+    @staticmethod
+    def forward(ctx, flow, plan, job, omit):
+        lib = _hip.require_gpu()
+        flow32 = _check_flow(plan, flow)
+        iwes = _launch_multiref_fwd(plan, flow32, job)
+        K, h, w = iwes.shape
+        out = torch.empty(K, dtype=torch.float32, device=plan.device)
+        moments = torch.empty((K, 2), dtype=torch.float64, device=plan.device)
+        nbytes = int(lib.ebos_cost_scratch_bytes(K))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
+        with _hip.on_device(plan.device):
+            check(lib.ebos_image_variance_f32(ptr(iwes), K, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes,
+                                              stream_ptr()), "ebos_image_variance")
+        ctx.save_for_backward(flow32, iwes, moments)
+        ctx.meta = (plan, job, int(omit), flow.dtype)
+        return out.mean().to(flow.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _hip.require_gpu()
+        flow32, iwes, moments = ctx.saved_tensors
+        plan, job, omit, fdt = ctx.meta
+        K = iwes.shape[0]
+        up = (g.to(torch.float32).reshape(1) / K).repeat(K).contiguous()
+        affine = torch.empty((K, 2), dtype=torch.float32, device=plan.device)
+        with _hip.on_device(plan.device):
+            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
+        d_flow = _launch_multiref_bwd(plan, flow32, job, iwes, affine, omit)
+        return d_flow.to(fdt), None, None, None
 
 
 # ----------------------------------------------------------------------------------------------

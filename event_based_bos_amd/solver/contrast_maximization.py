@@ -28,6 +28,17 @@ every pyramid scale): ``loop_mode`` reports "native", ``fused`` is True, ``histo
 explicit ``tile`` the plan takes a built tile of the time-aware forward kernel, (64, 64).  Its family is the variance contrast alone
 with optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``, Adam or a scipy method; the constructor raises
 ``NotImplementedError`` naming the key that leaves it.
+
+``multi_reference: {directions: [...], normalize: false, fused: null}`` (optional, this build's; dense-flow only): the multi-reference
+focus objective against event collapse.  The same flow is scored at 1 to 4 reference times (``'first' | 'middle' | 'last' | 'before' |
+'after' | float``) and the contrasts are averaged:
+
+    loss(theta) = -(1/K) sum_k sum_c w_c C_c(blur(IWE_k)) / N_c + regularisers
+
+``normalize: true`` sets N_c to cost c of the window's zero-flow IWE (once per window, without gradient; 1 where that is 0), else
+N_c = 1.  ``fused`` is ``EventPlan.iwe_dense_multi``'s.  Such a solver runs the autograd loop (Adam or the scipy methods; ``fused``,
+``resident`` and graph capture are off, ``loop_mode`` reports "autograd"), builds its plan with ``emit="full"`` and, without an
+explicit ``tile``, on (64, 64).  Together with ``time_aware`` or a 2-DoF motion model the constructor raises ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -41,7 +52,7 @@ from .. import _hip, costs, ops
 from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
-from ..event_plan import EventPlan, TimeAwarePlanStack
+from ..event_plan import EventPlan, TimeAwarePlanStack, multi_reference_fractions
 from . import fused_loop, time_aware_loop
 from .base import SolverBase
 
@@ -73,6 +84,31 @@ def parse_time_aware(block) -> Optional[dict]:
     if out["t0_location"] not in ("first", "middle"):
         raise ValueError(f"time_aware.t0_location must be 'first' or 'middle', got {out['t0_location']!r}")
     return out
+
+
+MULTI_REFERENCE_TILE = (64, 64)   # halo 16 keeps up to four windows of it in the LDS (ebos_iwe_multiref_fits)
+
+
+def parse_multi_reference(block) -> Optional[dict]:
+    """The ``multi_reference`` block of the solver's configuration -> {directions, normalize, fused}, or None without one."""
+    if block is None:
+        return None
+    block = dict(block)
+    unknown = sorted(set(block) - {"directions", "normalize", "fused"})
+    if unknown:
+        raise ValueError(f"multi_reference: unknown key(s) {unknown}; it takes directions, normalize, fused")
+    if "directions" not in block:
+        raise ValueError("multi_reference needs directions, the reference times the flow is scored at")
+    directions = block["directions"]
+    if isinstance(directions, (list, tuple)):
+        directions = [float(d) if isinstance(d, (int, float)) and not isinstance(d, bool) else d for d in directions]
+    multi_reference_fractions(directions)   # (ValueError for 'random', an empty list, more than four, an unknown name)
+    normalize, fused = block.get("normalize", False), block.get("fused", None)
+    if not isinstance(normalize, bool):
+        raise ValueError(f"multi_reference.normalize must be true or false, got {normalize!r}")
+    if fused is not None and not isinstance(fused, bool):
+        raise ValueError(f"multi_reference.fused must be true, false or null, got {fused!r}")
+    return {"directions": list(directions), "normalize": normalize, "fused": fused}
 
 
 def patch_grid_shape(image_size, patch_size, sliding_window):
@@ -172,6 +208,16 @@ class ContrastMaximizationMixin(object):
             self.resident = False
             if self.time_aware.get("native", False):
                 self._check_native_time_aware()
+        # multi_reference (module docstring): the contrast is the mean over several reference times; the autograd loop only
+        self.multi_reference = parse_multi_reference(cfg.get("multi_reference"))
+        if self.multi_reference is not None:
+            if self.time_aware is not None:
+                raise NotImplementedError("multi_reference together with time_aware: the multi-reference objective is defined on the "
+                                          "plain dense-flow warp; drop one of the two blocks")
+            if self.motion_model != "dense-flow":
+                raise NotImplementedError(f"multi_reference is defined for motion_model 'dense-flow', not {self.motion_model!r}")
+            self.use_graph = self.fused_loop = False
+            self.resident = False
 
     def _check_native_time_aware(self) -> None:
         """``time_aware.native``: the family of ``time_aware_loop.TimeAwarePatchLoop``, or NotImplementedError naming the key outside it."""
@@ -188,8 +234,43 @@ class ContrastMaximizationMixin(object):
             raise NotImplementedError("time_aware.native does not cover " + what + "; drop native to run the autograd loop")
 
     # ------------------------------------------------------------------ objective pieces
+    def _multi_reference_norms(self, plan: EventPlan) -> Dict[str, float]:
+        """N_c of the ``multi_reference`` loss: cost c of the window's zero-flow IWE (the same image at every reference time), blurred
+        like the objective's; once per plan, without gradient, 1 where the value is 0 -- or all 1 without ``normalize``."""
+        if not self.multi_reference["normalize"]:
+            return {name: 1.0 for name in self.contrast_terms}
+        key = (self.pad, self.blur_sigma, self.omit_boundary, tuple(self.contrast_terms))
+        cached = plan.__dict__.get("_multiref_norms")
+        if cached is None or cached[0] != key:
+            with torch.no_grad():
+                H, W = plan.image_size
+                zero = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
+                iwe = plan.iwe_dense_multi(zero, [0.0 if plan.ref_fraction is None else float(plan.ref_fraction)],
+                                           pad=(self.pad, self.pad), halo=self.halo, fused=False)[0]
+                if self.blur_sigma > 0:
+                    iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
+                vals = {name: float((ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(iwe, self.omit_boundary))
+                        for name in self.contrast_terms}
+            cached = plan.__dict__["_multiref_norms"] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
+        return cached[1]
+
     def _contrast(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
         total = 0.0
+        if self.multi_reference is not None:
+            mr = self.multi_reference
+            norms = self._multi_reference_norms(plan)
+            if self.blur_sigma > 0:
+                iwes = plan.iwe_dense_multi(flow, mr["directions"], pad=(self.pad, self.pad), halo=self.halo, fused=mr["fused"])
+                iwes = EventImageConverter._gaussian_blur3(iwes, self.blur_sigma)
+                for name, wgt in self.contrast_terms.items():
+                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
+                    total = total + (wgt / norms[name]) * fn(iwes, self.omit_boundary).mean()
+                return total
+            for name, wgt in self.contrast_terms.items():
+                total = total + (wgt / norms[name]) * plan.contrast_dense_multi(flow, mr["directions"], name, self.omit_boundary,
+                                                                                pad=(self.pad, self.pad), halo=self.halo,
+                                                                                fused=mr["fused"])
+            return total
         if self.time_aware is not None:
             ta = self.time_aware
             voxel = flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0]
@@ -230,7 +311,9 @@ class ContrastMaximizationMixin(object):
         # (a stream of sub-pixel rectified events is fractional window after window: once a window fell back, the lean
         # attempt -- its kernels and its read-back, ~0.3 ms of a 100 k-event window's build -- is skipped until a full build finds
         # integer coordinates again; either build is valid for either kind of window)
-        if self.time_aware is not None:   # the bins travel with the SoA events of the full build
+        if self.multi_reference is not None:   # the shifted reference times read the SoA events of the full build
+            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full")
+        elif self.time_aware is not None:   # the bins travel with the SoA events of the full build
             plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
                                    time_bin=self.time_aware["time_bin"])
         else:
@@ -377,6 +460,8 @@ class ContrastMaximizationMixin(object):
 
         if self.tile is not None:
             return self.tile
+        if self.multi_reference is not None:
+            return MULTI_REFERENCE_TILE
         if self.time_aware is not None and self.time_aware.get("native", False):
             # the native loop's forward is the tiled time-aware kernel: a tile it is built for with this halo, (64, 64) first
             from .. import _hip
@@ -460,7 +545,7 @@ class ContrastMaximizationMixin(object):
             self.history += loop.losses[:n_iter].cpu().tolist()   # (one conversion: 600 float() calls cost 0.1 ms of a 12 ms window)
             return loop.theta
         self.fused = False
-        if self.time_aware is not None:
+        if self.time_aware is not None or self.multi_reference is not None:
             self.loop_mode = "autograd"
             self.loop_modes.append("autograd")
         if self.opt_method in SCIPY_METHODS:

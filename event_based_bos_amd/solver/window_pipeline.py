@@ -83,6 +83,9 @@ class WindowPipeline(object):
         if getattr(solver, "time_aware", None) is not None:
             raise NotImplementedError("WindowPipeline runs the native solver loops; a time_aware solver runs the autograd loop: "
                                       "call its estimate() window by window")
+        if getattr(solver, "multi_reference", None) is not None:
+            raise NotImplementedError("WindowPipeline runs the native solver loops; a multi_reference solver runs the autograd loop: "
+                                      "call its estimate() window by window")
         self.two_dof = solver.motion_model in ("2d-translation", "rigid-optical-flow")
         if solver.motion_model != "dense-flow" and not (self.two_dof and solver.opt_method == "Adam"):
             raise NotImplementedError("WindowPipeline drives the patch-flow (dense-flow) solver and the 2-DoF Adam loop")

@@ -1525,6 +1525,37 @@ int ebos_iwe_voxel_owner_bwd_f32(const float* xs, const float* ys, const float* 
                                  float* d_voxel, ebos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-reference contrast: the IWEs of ONE dense flow at K <= EBOS_MULTIREF_MAX reference times from one pass over a binned plan.
+ * A plan built with normalised time and reference fraction f holds dt = (t - tmin) / (tmax - tmin) - f; the dt of reference
+ * fraction r is dt + (f - r), so reference k is the scalar shifts[k] = f - r_k (HOST memory, float [K], finite; it travels to the
+ * kernels by value):   dt_k = dt + shifts[k] (float32);  x'_k = x - dt_k * flow[0][pix];  y'_k = y - dt_k * flow[1][pix].
+ * An event is decoded once and its flow cell gathered once for all K references.  No per-event weights.
+ *   xs, ys, dts: SoA f32 [n] in key order with key_offsets of ebos_bin_events_f32 (tile_h, tile_w);  flow [2, H, W].
+ * ebos_iwe_multiref_fits (host only): how K LDS windows of tile + halo are kept -- 2: f64, 1: f32 (ebos_iwe_dense_tiled_f32's
+ *   accumulator rule applied to K windows), 0: they do not fit the 160 KiB LDS, K is outside [1, EBOS_MULTIREF_MAX], or
+ *   (tile_h, tile_w, halo) is no ebos_tiled_config.
+ * ebos_iwe_dense_multiref_tiled_f32: ebos_iwe_dense_tiled_f32's organisation with K windows per (tile, split) workgroup; the votes,
+ *   their eps and the spill path beyond the halo (global float atomics) are that kernel's.  iwes [K, h, w], h = H + 2 pad_h ...;
+ *   ACCUMULATES into iwes.  EBOS_ERR_UNSUPPORTED, and no launch, where ebos_iwe_multiref_fits is 0.
+ * ebos_iwe_dense_multiref_owner_bwd_f32: d_flow[c][i] = sum over the events of source pixel i and the references k of
+ *   -dt_k * dL/d(x'_k, y'_k), the four taps read from G_k = a_k * g_images[k] + c_k (g_images [K, h, w]; affine [K, 2] on the device,
+ *   nullable: a = 1, c = 0), G_k = 0 outside [g_lo, h - g_lo) x [g_lo, w - g_lo).  The pattern of ebos_iwe_voxel_owner_bwd_f32: the
+ *   lane that walks a pixel's run gathers the flow cell once and is the only writer of the pixel's two cells.  No atomics;
+ *   d_flow [2, H, W] is OVERWRITTEN, every cell of it (zeros where no event lies, pixels of empty tiles included); the order of the
+ *   additions is the plan's, so two calls give the same bits.  Runs of more than 64 events (a hot pixel) are walked by the whole
+ *   wave with a fixed reduction tree.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_MULTIREF_MAX 4
+int ebos_iwe_multiref_fits(int tile_h, int tile_w, int halo, int K);
+int ebos_iwe_dense_multiref_tiled_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                      const float* flow, int H, int W, int tile_h, int tile_w, int halo, int splits, int pad_h,
+                                      int pad_w, const float* shifts, int K, float* iwes, ebos_stream_t stream);
+int ebos_iwe_dense_multiref_owner_bwd_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                          const float* flow, int H, int W, int tile_h, int tile_w, int pad_h, int pad_w,
+                                          const float* shifts, int K, const float* g_images, const float* affine, int g_lo,
+                                          float* d_flow, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The Adam loop of the TIME-AWARE patch-flow contrast maximisation natively (the solver's `time_aware` block):
  *     loss(theta) = -w_variance * var(IWE(events warped by voxel(dense(theta))))
  *                   + w_flow_norm * flow_norm(dense) + w_image_gradient * image_gradient(dense)
