@@ -27,6 +27,9 @@ tub-rip/event_based_bos:
                          (Warp.warp_event(.., "dense-flow-voxel"), EventPlan.build(.., time_bin=T).iwe_voxel / contrast_voxel)
                          and its contrast maximisation as a native loop: EventPlan.variance_voxel_value_and_grad (pixel-owner
                          backward into the voxel), solver.time_aware_loop.TimeAwarePatchLoop, solver block time_aware.native
+    multi-reference      one flow scored at 1 to 4 reference times from one plan: EventPlan.iwe_dense_multi / contrast_dense_multi
+                         (fused="slab": the K-image slab pipeline), EventPlan.variance_multi_value_and_grad,
+                         solver.multi_reference_loop.MultiReferencePatchLoop, solver block multi_reference (native: true)
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the

@@ -307,6 +307,13 @@ SIGNATURES = {
     "ebos_iwe_multiref_fits": (_I, [_I, _I, _I, _I]),
     "ebos_iwe_dense_multiref_tiled_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 8 + [C.POINTER(_F), _I, _P, _P]),
     "ebos_iwe_dense_multiref_owner_bwd_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 6 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
+    "ebos_slab_multiref_config": (_I, [C.POINTER(_I), _I]),
+    "ebos_iwe_slab_multiref_workspace_bytes": (_Z, [_I] * 9),
+    "ebos_iwe_dense_slab_multiref_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 8 + [C.POINTER(_F), _I, _P, _Z, _P, _I, _I, _P, _P, _P]),
+    "ebos_iwe_dense_tiled_multiref_bwd_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 7 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P, C.POINTER(_F),
+                                                   _P, _P, _P]),
+    "ebos_cmax_multiref_solve_f32": (_I, [_P, _I, _P]),
+    "ebos_cmax_multiref_gradient_f32": (_I, [_P, _P]),
 }
 
 
@@ -371,6 +378,20 @@ class CmaxVoxelProblem(C.Structure):
 
 CMAX_VOXEL_MAX_BATCH = 64   # EBOS_CMAX_VOXEL_MAX_BATCH
 MULTIREF_MAX = 4            # EBOS_MULTIREF_MAX
+
+
+class CmaxMultirefProblem(C.Structure):
+    """``ebos_cmax_multiref_problem`` of include/ebos_hip.h (same field order)."""
+    _fields_ = ([(k, _P) for k in ("xs", "ys", "dts", "key_offsets")] + [("n", _L)] +
+                [(k, _I) for k in ("H", "W", "tile_h", "tile_w", "halo", "pad_h", "pad_w", "omit_boundary", "splits", "K")] +
+                [("shifts", _F * MULTIREF_MAX)] +
+                [(k, _I) for k in ("gh", "gw", "patch_h", "patch_w", "slide_h", "slide_w")] +
+                [(k, _F) for k in ("w_variance", "w_flow_norm", "w_image_gradient")] +
+                [(k, _D) for k in ("norm", "lr", "beta1", "beta2", "eps")] +
+                [(k, _P) for k in ("theta", "d_theta", "exp_avg", "exp_avg_sq", "step")] + [("steps_done", _I)] +
+                [(k, _P) for k in ("dense", "d_dense", "d_reg", "iwes", "variances", "contrast", "moments", "upstream", "workspace")] +
+                [("workspace_bytes", _Z), ("reg_partials", _P), ("upsample_scratch", _P), ("upsample_scratch_bytes", _Z), ("losses", _P),
+                 ("losses_cap", _I), ("theta_mask", _P)])
 
 
 class CmaxVoxelBatchProblem(C.Structure):
@@ -515,6 +536,15 @@ def slab_configs():
     n = lib.ebos_slab_config(None, 0)
     buf = (C.c_int * (3 * n))()
     lib.ebos_slab_config(buf, n)
+    return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
+
+
+def slab_multiref_configs():
+    """The (tile_h, tile_w, halo) triples the multi-reference slab kernels are built for (``ebos_slab_multiref_config``)."""
+    lib = load_library()
+    n = lib.ebos_slab_multiref_config(None, 0)
+    buf = (C.c_int * (3 * n))()
+    lib.ebos_slab_multiref_config(buf, n)
     return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
 
 

@@ -30,7 +30,7 @@ SOURCES = ["errors.cpp", "warp_kernels.hip", "splat_kernels.hip", "event_plan.hi
            "cmax_resident_45x80_2dof.hip", "cmax_resident_32x32_2dof.hip", "cmax_resident_32x64_2dof.hip",
            "event_filters.hip", "flow_error.hip", "poisson.hip", "gml.hip", "farneback.hip", "frame_warp.hip", "window_ingest.hip", "visualize.hip",
            "event_voxel.hip", "flow_voxel.hip", "flow_voxel_grad.hip", "warp_voxel.hip", "cmax_voxel.hip",
-           "plan_time_aware.hip", "iwe_multiref.hip"]
+           "plan_time_aware.hip", "iwe_multiref.hip", "iwe_multiref_slab.hip", "cmax_multiref.hip"]
 
 # -munsafe-fp-atomics: hardware global_atomic_add_f32/f64 and ds_add_f32 instead of CAS loops.
 HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-fPIC",
@@ -91,7 +91,7 @@ def build_library(force: bool = False, keep_temps: bool = False, verbose: bool =
     extra += os.environ.get("EBOS_EXTRA_FLAGS", "").split()  # e.g. -DEBOS_STAMPS for the diagnostic build
     with cf.ThreadPoolExecutor(max_workers=min(int(os.environ.get("EBOS_BUILD_JOBS", "7")), len(SOURCES))) as ex:
         # (the slow units first: a tile configuration's kernels take 20 - 30 s, most other units a few)
-        order = sorted(SOURCES, key=lambda s: 0 if s.startswith("iwe_tiled_") else (1 if s.startswith("cmax_resident_") else 2))
+        order = sorted(SOURCES, key=lambda s: 0 if s.startswith(("iwe_tiled_", "iwe_multiref_slab")) else (1 if s.startswith("cmax_resident_") else 2))
         built = dict(zip(order, ex.map(lambda s: _compile(s, extra), order)))
         objs = [built[s] for s in SOURCES]
     if force or _needs_rebuild(LIB_PATH, objs):

@@ -184,9 +184,12 @@ __device__ __forceinline__ float4 load_weights4(const float* __restrict__ w, int
 // Branch-free: group indices past the slice are clamped (the loops never PROCESS such a group, they only prefetch
 // it).  Predicated loads would become exec-masked branches and hipcc then waits vmcnt(0) for them, draining the
 // prefetch that is supposed to stay in flight.
-template <int FMT, bool HAS_W, int TH, int TW>
+// SHIFT (multi-reference kernels, iwe_multiref_slab.hip): the (x, y, dt) format's event time is dt + dt_shift, ONE rounded float32 add
+// before anything else uses it; every other instantiation ignores the argument
+template <int FMT, bool HAS_W, int TH, int TW, bool SHIFT = false>
 __device__ __forceinline__ void load_group(Group& g, int32_t grp, const TileRange& tr, const EvPtrs& p, int tile_r0,
-                                           int tile_c0) {
+                                           int tile_c0, float dt_shift = 0.0f) {
+  static_assert(!SHIFT || FMT == FMT_XY, "a shifted reference time: the (x, y, dt) format only");
   const int32_t j = max(min(grp, tr.g_last), tr.g_first);
   if (FMT == FMT_COMPACT) {
     const float4 D = reinterpret_cast<const float4*>(p.cdt)[j];
@@ -221,7 +224,7 @@ __device__ __forceinline__ void load_group(Group& g, int32_t grp, const TileRang
     for (int e = 0; e < 4; ++e) {
       const int32_t i = 4 * j + e;
       const bool live = i >= tr.beg && i < tr.end;
-      g.dt[e] = dd[e];
+      g.dt[e] = SHIFT ? __fadd_rn(dd[e], dt_shift) : dd[e];
       g.w[e] = live ? ww[e] : 0.0f;
       const float x = live ? xx[e] : (float)tile_r0, y = live ? yy[e] : (float)tile_c0;
       g.rs[e] = (int)x;
@@ -781,12 +784,12 @@ enum Pass { PASS_MAIN = 0, PASS_SPILL = 1 };
 // FRAC: the compact plan carries fractional source coordinates (EvPtrs::cfx / cfy): every pass takes the general loop below, whose
 // groups hold the fractions (load_group); the lean loop assumes integer pixels.
 template <int TH, int TW, int HALO, bool HAS_W, int MODE, int PASS, int FMT, bool UNIFORM, bool GRID = false, bool DYN = false,
-          bool PAIRS = false, bool FRAC = false>
+          bool PAIRS = false, bool FRAC = false, bool SHIFT = false>
 __device__ __forceinline__ unsigned long long accumulate_slice(const TileRange& tr, double* s_acc, const EvPtrs& ev,
                                                      const float* __restrict__ flow, int H, int W, int pad_h, int pad_w,
                                                      float* spill, bool* any_spill, const ChunkQueue& queue,
                                                      const Win<TH, TW, HALO, DYN>& win, const CRaw* pre = nullptr,
-                                                     float wscale = kFxScale) {
+                                                     float wscale = kFxScale, float dt_shift = 0.0f) {
   const int LH = win.LH(), LW = win.LW(), PT = win.P();
   unsigned long long* s_fx = reinterpret_cast<unsigned long long*>(s_acc);
   const int h = H + 2 * pad_h, w = W + 2 * pad_w;
@@ -808,8 +811,8 @@ __device__ __forceinline__ unsigned long long accumulate_slice(const TileRange& 
   const int32_t g_last = tr.g_last;
   int32_t grp = tr.g_first + threadIdx.x;
   Group cur, nxt;
-  load_group<FMT, HAS_W, TH, TW>(cur, grp, tr, ev, tr0, tc0);
-  load_group<FMT, HAS_W, TH, TW>(nxt, grp + kBlock, tr, ev, tr0, tc0);
+  load_group<FMT, HAS_W, TH, TW, SHIFT>(cur, grp, tr, ev, tr0, tc0, dt_shift);
+  load_group<FMT, HAS_W, TH, TW, SHIFT>(nxt, grp + kBlock, tr, ev, tr0, tc0, dt_shift);
   float fu[4], fv[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -826,7 +829,7 @@ __device__ __forceinline__ unsigned long long accumulate_slice(const TileRange& 
       gv[e] = UNIFORM ? uni_v : flow1[lin];
     }
     Group nn;  // loads two groups ahead
-    load_group<FMT, HAS_W, TH, TW>(nn, grp + 2 * kBlock, tr, ev, tr0, tc0);
+    load_group<FMT, HAS_W, TH, TW, SHIFT>(nn, grp + 2 * kBlock, tr, ev, tr0, tc0, dt_shift);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float wv = cur.w[e];  // 0 for dead slots
@@ -1058,12 +1061,14 @@ struct OwnSumBlur {
 //               window's first chunks there, so that they arrive while this window's image is decoded and stored
 //   own         sees every quad the decode pass stores (NoOwn / OwnSum)
 //   FRAC        the compact plan carries fractional source coordinates (EvPtrs::cfx): the general loop instead of the lean one
+//   SHIFT       the event times are dt + dt_shift (load_group): the multi-reference kernels
 template <int TH, int TW, int HALO, bool HAS_W, int MODE, int FMT, bool UNIFORM, bool GRID, bool DYN, bool ZERO, bool FRAC = false,
-          typename Hook, typename Own>
+          bool SHIFT = false, typename Hook, typename Own>
 __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW, HALO, DYN>& win, const float* flow, double* s_acc,
                                           TileShared& sh, const EvPtrs& ev, int H, int W, int tiles_x, int pad_h, int pad_w,
                                           float* __restrict__ slabs, float* spill, unsigned* __restrict__ spill_epoch, unsigned epoch,
-                                          unsigned* __restrict__ halo_tab, const CRaw* pre, Hook&& after_loop, Own& own) {
+                                          unsigned* __restrict__ halo_tab, const CRaw* pre, Hook&& after_loop, Own& own,
+                                          float dt_shift = 0.0f) {
   constexpr int kLHmax = TH + 2 * HALO, kLWmax = TW + 2 * HALO;
   constexpr int kCells = acc_cells<TH, TW, HALO, DYN>();
   const ChunkQueue queue{&sh.next};
@@ -1084,8 +1089,8 @@ __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW,
     added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, kCanPair>(
         tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, nullptr);
   else
-    added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC>(
-        tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, pre, HAS_W ? sh.wscale : kFxScale);
+    added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC, SHIFT>(
+        tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, pre, HAS_W ? sh.wscale : kFxScale, dt_shift);
   after_loop();
   constexpr bool kLeanLoop = FMT == FMT_COMPACT && !HAS_W && !FRAC;  // accumulate_compact_fx: counts nothing per event
   if (kLeanLoop && threadIdx.x == 0 && tr.g_first <= tr.g_last)  // 2^20 units per event of the slice (padding slots excluded)
@@ -1099,8 +1104,8 @@ __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW,
   if (sh.flag[1] && spill_epoch != nullptr && threadIdx.x == 0) *spill_epoch = epoch;  // benign race: every writer stores the same value
   if (sh.flag[1] && spill != nullptr)  // rare: taps beyond the halo go to the spill image with global atomics (lean path: minus their units;
                                        // no spill image: the resident kernel ends its launch on a spill instead)
-    added -= accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_SPILL, FMT, UNIFORM, GRID, DYN, false, FRAC>(tr, s_acc, ev, flow, H, W, pad_h,
-                                                                                                           pad_w, spill, nullptr, queue, win);
+    added -= accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_SPILL, FMT, UNIFORM, GRID, DYN, false, FRAC, SHIFT>(
+        tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, nullptr, queue, win, nullptr, kFxScale, dt_shift);
 
   // (the slab stride is the LARGEST window's: a run-time window fills the first LH * LW floats of its slab)
   float4* out = reinterpret_cast<float4*>(slabs + (int64_t)tr.slab * (kLHmax * kLWmax));
@@ -1178,8 +1183,8 @@ __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW,
       for (int i = threadIdx.x; i < kCells; i += kBlock) s_acc[i] = 0.0;
       if (threadIdx.x == 0) sh.next = 2 * (kBlock / kWave);  // the redo draws its chunks afresh
       __syncthreads();
-      accumulate_slice<TH, TW, HALO, HAS_W, ACC_F64, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC>(tr, s_acc, ev, flow, H, W, pad_h, pad_w,
-                                                                                                      spill, nullptr, queue, win);
+      accumulate_slice<TH, TW, HALO, HAS_W, ACC_F64, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC, SHIFT>(
+          tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, nullptr, queue, win, nullptr, kFxScale, dt_shift);
       __syncthreads();
       f64_flush = true;
     }
@@ -1208,12 +1213,12 @@ __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW,
 // from a bound on the tile's displacements.  Returns false for an unused work item of an adaptive plan (nothing to do).
 // FRAC: a compact plan that carries the fractions of undistorted events (EvPtrs::cfx / cfy): the general loop on the compact slots
 template <int TH, int TW, int HALO, bool HAS_W, int MODE, int FMT, bool UNIFORM, bool GRID = false, bool DYN = false, bool ZERO = false,
-          bool FRAC = false>
+          bool FRAC = false, bool SHIFT = false>
 __device__ __forceinline__ void accumulate_tile(const EvPtrs& ev, const int32_t* __restrict__ key_offsets,
                                                 const float* __restrict__ flow_arg, int H, int W, int tiles_x, int splits, int pad_h,
                                                 int pad_w, float* __restrict__ slabs, float* spill, const GridSrc& gs,
                                                 unsigned* __restrict__ spill_epoch, unsigned epoch, float dt_bound = 0.0f,
-                                                unsigned* __restrict__ halo_tab = nullptr) {
+                                                unsigned* __restrict__ halo_tab = nullptr, float dt_shift = 0.0f) {
   constexpr int kLWmax = TW + 2 * HALO;
   constexpr int kCells = acc_cells<TH, TW, HALO, DYN>();
   static_assert(kLWmax % 4 == 0, "slab rows are written 4 cells at a time");
@@ -1336,9 +1341,9 @@ __device__ __forceinline__ void accumulate_tile(const EvPtrs& ev, const int32_t*
       return;
     }
   }
-  tile_body<TH, TW, HALO, HAS_W, MODE, FMT, UNIFORM, GRID, DYN, ZERO, FRAC>(tr, win, flow, s_acc, sh, ev, H, W, tiles_x, pad_h, pad_w, slabs,
-                                                                           spill, spill_epoch, epoch, halo_tab, kLeanPre ? pre : nullptr,
-                                                                           NoHook{}, no_own);
+  tile_body<TH, TW, HALO, HAS_W, MODE, FMT, UNIFORM, GRID, DYN, ZERO, FRAC, SHIFT>(tr, win, flow, s_acc, sh, ev, H, W, tiles_x, pad_h, pad_w,
+                                                                                  slabs, spill, spill_epoch, epoch, halo_tab,
+                                                                                  kLeanPre ? pre : nullptr, NoHook{}, no_own, dt_shift);
 }
 
 template <int TH, int TW, int HALO, bool HAS_W, int MODE, int FMT, bool UNIFORM, bool GRID = false, bool DYN = false, bool FRAC = false>

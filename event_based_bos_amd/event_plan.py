@@ -808,9 +808,15 @@ class EventPlan:
         bits on every call); ``halo`` is used where K windows of it fit the LDS, else the largest built halo of the plan's tile that
         does (``ebos_iwe_multiref_fits``).  ``fused=False``: the loop route, K calls of ``ebos_iwe_dense_tiled_f32`` and of
         ``ebos_iwe_dense_bwd_f32`` on ``dt + shift_k``.  ``fused=None``: the loop route where nothing fits, else
-        ``MULTIREF_DEFAULT_FUSED``.  ValueError for ``'random'``, an empty list, more than 4 directions, and a plan without
-        normalised time or without a reference fraction; NotImplementedError for an un-binned, lean or deferred plan."""
+        ``MULTIREF_DEFAULT_FUSED``.  ``fused="slab"``: the K-image form of the tile-private pipeline
+        (``ebos_iwe_dense_slab_multiref_f32``: the reference is an outer grid dimension, one LDS window per workgroup, two launches)
+        with the tile-private backward ``ebos_iwe_dense_tiled_multiref_bwd_f32`` (one launch, no atomics, the same bits on every
+        call); ``halo`` must be a built halo of the plan's tile (``_hip.slab_multiref_configs()``).  ValueError for ``'random'``, an
+        empty list, more than 4 directions, and a plan without normalised time or without a reference fraction; NotImplementedError
+        for an un-binned, lean or deferred plan."""
         job = _multiref_job(self, directions, pad, halo, splits, fused, "iwe_dense_multi")
+        if job.fused == "slab":
+            return _MultiRefSlabIwe.apply(flow, self, job)
         return _MultiRefIwe.apply(flow, self, job)
 
     def contrast_dense_multi(self, flow: torch.Tensor, directions, cost: str = "image_variance", omit_boundary: bool = False,
@@ -822,9 +828,25 @@ class EventPlan:
         if cost not in ("image_variance", "gradient_magnitude"):
             raise KeyError(f"unknown contrast cost {cost!r}")
         job = _multiref_job(self, directions, pad, halo, splits, fused, "contrast_dense_multi")
+        if job.fused == "slab":   # the variances come out of the combine pass; their gradients are folded into the backward kernel
+            if cost == "image_variance":
+                return _MultiRefSlabVariance.apply(flow, self, job, bool(omit_boundary))
+            return ops.gradient_magnitude(_MultiRefSlabIwe.apply(flow, self, job), omit_boundary).mean()
         if cost == "image_variance":
             return _MultiRefVariance.apply(flow, self, job, bool(omit_boundary))
         return ops.gradient_magnitude(_MultiRefIwe.apply(flow, self, job), omit_boundary).mean()
+
+    def variance_multi_value_and_grad(self, flow: torch.Tensor, directions, omit_boundary: bool = False, pad: Tuple[int, int] = (0, 0),
+                                      halo=DEFAULT_HALO, splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mean_k var(IWE_k(flow)) [0-d], its gradient d_flow [2, H, W]) on the ``fused="slab"`` route, without autograd: three
+        launches (accumulate, combine with the K variances, the K-reference backward with the variance gradients folded in)."""
+        job = _multiref_job(self, directions, pad, halo, splits, "slab", "variance_multi_value_and_grad")
+        flow32 = _check_flow(self, flow)
+        K = len(job.shifts)
+        iwes, variances, moments = _launch_multiref_slab_fwd(self, flow32, job, 1, bool(omit_boundary))
+        upstream = torch.full((1,), 1.0 / K, dtype=torch.float32, device=self.device)
+        d_flow = _launch_multiref_slab_bwd(self, flow32, job, iwes, None, int(bool(omit_boundary)), moments, upstream)
+        return variances.mean(), d_flow
 
     # ------------------------------------------------------------------------------------------ time-aware warp
     def iwe_voxel(self, voxel: torch.Tensor, pad: Tuple[int, int] = (0, 0), weight: Optional[torch.Tensor] = None,
@@ -1469,7 +1491,7 @@ def multi_reference_shifts(plan: "EventPlan", directions) -> List[float]:
 class _MultiRefJob(NamedTuple):
     shifts: Tuple[float, ...]   # float32 values
     pad: Tuple[int, int]
-    fused: bool
+    fused: Union[bool, str]     # True: K LDS windows per workgroup; False: the loop route; "slab": the K-image slab pipeline
     halo: Optional[int]         # the built halo of the route's forward kernel (None: the loop route on the general kernel)
     splits: int
 
@@ -1479,8 +1501,10 @@ def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what:
     if not plan.binned:
         raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
     _refuse_deferred(plan, what)
+    if isinstance(fused, str) and fused == "slab":
+        return _multiref_slab_job(plan, shifts, pad, halo, splits, what)
     if fused not in (None, True, False):
-        raise ValueError(f"fused must be None, True or False, got {fused!r}")
+        raise ValueError(f"fused must be None, True, False or 'slab', got {fused!r}")
     lib = _hip.load_library()
     K = len(shifts)
     th, tw = int(plan.tile[0]), int(plan.tile[1])
@@ -1506,6 +1530,118 @@ def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what:
     else:
         route_halo = None   # a tile without a tiled kernel: the general forward kernel, reference by reference
     return _MultiRefJob(shifts, (int(pad[0]), int(pad[1])), bool(use_fused), route_halo, max(1, plan.resolve_splits(splits)))
+
+
+def multiref_slab_halo(tile, halo) -> int:
+    """The built halo the ``fused="slab"`` route runs ``tile`` with: ``halo`` itself where (tile, halo) is a built triple, the
+    default (or else the largest) built halo of the tile for ``None`` / ``"auto"``; NotImplementedError names the built triples."""
+    built_all = _hip.slab_multiref_configs()
+    th, tw = int(tile[0]), int(tile[1])
+    built = sorted(hl for a, b, hl in built_all if (a, b) == (th, tw))
+    if halo is None or halo == "auto":
+        if built:
+            return DEFAULT_HALO if DEFAULT_HALO in built else max(built)
+    elif _max_halo(int(halo)) in built:
+        return _max_halo(int(halo))
+    raise NotImplementedError(f"fused='slab': no multi-reference kernel is built for tile {(th, tw)} with halo {halo!r}; the built "
+                              f"(tile_h, tile_w, halo) are {built_all}")
+
+
+def _multiref_slab_job(plan: "EventPlan", shifts, pad, halo, splits, what: str) -> _MultiRefJob:
+    try:
+        route_halo = multiref_slab_halo(plan.tile, halo)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{what}: {e}") from None
+    return _MultiRefJob(shifts, (int(pad[0]), int(pad[1])), "slab", route_halo, max(1, plan.resolve_splits(splits)))
+
+
+def _multiref_workspace(plan: "EventPlan", K: int, pad, halo: int, splits: int) -> torch.Tensor:
+    """K workspaces of the single form back to back, zero-filled once; the kernels keep the spill sections zero between calls."""
+    lib = _hip.require_gpu()
+    key = ("multiref", int(K), int(halo), int(splits), int(pad[0]), int(pad[1]))
+    cache = plan.__dict__.setdefault("_workspaces", {})
+    if key not in cache:
+        H, W = plan.image_size
+        nbytes = int(lib.ebos_iwe_slab_multiref_workspace_bytes(K, H, W, plan.tile[0], plan.tile[1], halo, splits, pad[0], pad[1]))
+        if nbytes <= 0:
+            raise RuntimeError(f"ebos_iwe_slab_multiref_workspace_bytes refused K={K} tile={plan.tile} halo={halo} splits={splits}")
+        cache[key] = torch.zeros(nbytes, dtype=torch.uint8, device=plan.device)
+    return cache[key]
+
+
+def _launch_multiref_slab_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, want_variance: int, omit: bool):
+    """-> (iwes [K, h, w], variances [K] | None, moments [K, 2] f64 | None); every output is overwritten by the kernels."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    K, pad = len(job.shifts), job.pad
+    ws = _multiref_workspace(plan, K, pad, job.halo, job.splits)
+    iwes = torch.empty((K, H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
+    variances = torch.empty(K, dtype=torch.float32, device=plan.device) if want_variance else None
+    moments = torch.empty((K, 2), dtype=torch.float64, device=plan.device) if want_variance else None
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_dense_slab_multiref_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32), H, W,
+                                                   plan.tile[0], plan.tile[1], job.halo, job.splits, pad[0], pad[1], _c_shifts(job.shifts), K,
+                                                   ptr(ws), ws.numel(), ptr(iwes), int(want_variance), int(omit), ptr(variances),
+                                                   ptr(moments), stream_ptr()), "ebos_iwe_dense_slab_multiref")
+    return iwes, variances, moments
+
+
+def _launch_multiref_slab_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, g_images: torch.Tensor,
+                              affine: Optional[torch.Tensor], g_lo: int, var_moments: Optional[torch.Tensor] = None,
+                              upstream: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_flow [2, H, W] (every cell written) from a generic upstream (``g_images``, ``affine``) or the folded variance gradient
+    (``g_images`` = the IWEs, ``var_moments`` [K, 2], ``upstream`` [1])."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    K, pad = len(job.shifts), job.pad
+    d_flow = torch.empty((2, H, W), dtype=torch.float32, device=plan.device) if out is None else out
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_dense_tiled_multiref_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                        H, W, plan.tile[0], plan.tile[1], job.halo, pad[0], pad[1], _c_shifts(job.shifts),
+                                                        K, ptr(g_images), ptr(affine), int(g_lo), ptr(var_moments), ptr(upstream), None,
+                                                        ptr(addend), ptr(d_flow), stream_ptr()), "ebos_iwe_dense_tiled_multiref_bwd")
+    return d_flow
+
+
+class _MultiRefSlabIwe(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, plan, job):
+        flow32 = _check_flow(plan, flow)
+        iwes, _, _ = _launch_multiref_slab_fwd(plan, flow32, job, 0, False)
+        ctx.save_for_backward(flow32)
+        ctx.meta = (plan, job, flow.dtype)
+        return iwes if flow.dtype == torch.float32 else iwes.to(flow.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (flow32,) = ctx.saved_tensors
+        plan, job, fdt = ctx.meta
+        d_flow = _launch_multiref_slab_bwd(plan, flow32, job, g.to(torch.float32).contiguous(), None, 0)
+        return d_flow.to(fdt), None, None
+
+
+class _MultiRefSlabVariance(torch.autograd.Function):
+    """mean_k var(IWE_k(flow)) on the slab route: the K variances and their moments come out of the combine pass, and the backward
+    kernel folds 2 (IWE_k - mean_k) / (M - 1) in per reference -- no d_iwe images, no cost or affine launch."""
+
+    @staticmethod
+    def forward(ctx, flow, plan, job, omit):
+        flow32 = _check_flow(plan, flow)
+        iwes, variances, moments = _launch_multiref_slab_fwd(plan, flow32, job, 1, omit)
+        ctx.save_for_backward(flow32, iwes, moments)
+        ctx.meta = (plan, job, int(omit), flow.dtype)
+        return variances.mean().to(flow.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        flow32, iwes, moments = ctx.saved_tensors
+        plan, job, omit, fdt = ctx.meta
+        upstream = (g.to(torch.float32).reshape(1) / iwes.shape[0]).contiguous()
+        d_flow = _launch_multiref_slab_bwd(plan, flow32, job, iwes, None, omit, moments, upstream)
+        return d_flow.to(fdt), None, None, None
 
 
 def _multiref_dt(plan: "EventPlan", shift: float) -> torch.Tensor:

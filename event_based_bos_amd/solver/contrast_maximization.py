@@ -39,6 +39,14 @@ focus objective against event collapse.  The same flow is scored at 1 to 4 refer
 N_c = 1.  ``fused`` is ``EventPlan.iwe_dense_multi``'s.  Such a solver runs the autograd loop (Adam or the scipy methods; ``fused``,
 ``resident`` and graph capture are off, ``loop_mode`` reports "autograd"), builds its plan with ``emit="full"`` and, without an
 explicit ``tile``, on (64, 64).  Together with ``time_aware`` or a 2-DoF motion model the constructor raises ``NotImplementedError``.
+
+``multi_reference.native: true`` (default false) runs the same objective as a fixed pipeline of HIP kernels instead
+(``solver/multi_reference_loop.py``: the K-image slab forward, the K-reference tile-private backward, one C call for the whole Adam
+loop; the scipy methods evaluate value and gradient through it, at every pyramid scale): ``loop_mode`` reports "native", ``fused`` is
+True and ``history`` comes from the loop's losses.  Its family is the variance contrast alone with optional ``flow_norm`` /
+``image_gradient``, no ``iwe.blur_sigma``, ``outer_padding`` 0, Adam or a scipy method, and a ``tile`` / ``halo`` that
+``_hip.slab_multiref_configs()`` lists (``halo: auto`` takes the tile's default built halo); the constructor raises
+``NotImplementedError`` naming the key that leaves it.
 """
 from __future__ import annotations
 
@@ -53,7 +61,7 @@ from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
 from ..event_plan import EventPlan, TimeAwarePlanStack, multi_reference_fractions
-from . import fused_loop, time_aware_loop
+from . import fused_loop, multi_reference_loop, time_aware_loop
 from .base import SolverBase
 
 logger = logging.getLogger(__name__)
@@ -90,13 +98,14 @@ MULTI_REFERENCE_TILE = (64, 64)   # halo 16 keeps up to four windows of it in th
 
 
 def parse_multi_reference(block) -> Optional[dict]:
-    """The ``multi_reference`` block of the solver's configuration -> {directions, normalize, fused}, or None without one."""
+    """The ``multi_reference`` block of the solver's configuration -> {directions, normalize, fused}, plus ``native`` where the block
+    gives it (absent means false), or None without one."""
     if block is None:
         return None
     block = dict(block)
-    unknown = sorted(set(block) - {"directions", "normalize", "fused"})
+    unknown = sorted(set(block) - {"directions", "normalize", "fused", "native"})
     if unknown:
-        raise ValueError(f"multi_reference: unknown key(s) {unknown}; it takes directions, normalize, fused")
+        raise ValueError(f"multi_reference: unknown key(s) {unknown}; it takes directions, normalize, fused, native")
     if "directions" not in block:
         raise ValueError("multi_reference needs directions, the reference times the flow is scored at")
     directions = block["directions"]
@@ -108,7 +117,12 @@ def parse_multi_reference(block) -> Optional[dict]:
         raise ValueError(f"multi_reference.normalize must be true or false, got {normalize!r}")
     if fused is not None and not isinstance(fused, bool):
         raise ValueError(f"multi_reference.fused must be true, false or null, got {fused!r}")
-    return {"directions": list(directions), "normalize": normalize, "fused": fused}
+    out = {"directions": list(directions), "normalize": normalize, "fused": fused}
+    if "native" in block:   # (returned as given; a block without the key parses to what it always did, and means false)
+        if not isinstance(block["native"], bool):
+            raise ValueError(f"multi_reference.native must be true or false, got {block['native']!r}")
+        out["native"] = block["native"]
+    return out
 
 
 def patch_grid_shape(image_size, patch_size, sliding_window):
@@ -218,6 +232,32 @@ class ContrastMaximizationMixin(object):
                 raise NotImplementedError(f"multi_reference is defined for motion_model 'dense-flow', not {self.motion_model!r}")
             self.use_graph = self.fused_loop = False
             self.resident = False
+            if self.multi_reference.get("native", False):
+                self._check_native_multi_reference()
+
+    def _check_native_multi_reference(self) -> None:
+        """``multi_reference.native``: the family of ``multi_reference_loop.MultiReferencePatchLoop``, or NotImplementedError naming the
+        key outside it."""
+        from ..event_plan import multiref_slab_halo
+
+        what = None
+        if set(self.contrast_terms) != {"image_variance"}:
+            what = f"cost / cost_with_weight: the contrast {sorted(self.contrast_terms)} (the variance contrast alone, no gradient_magnitude)"
+        elif not set(self.flow_terms) <= set(fused_loop.FLOW_TERMS):
+            what = f"cost_with_weight: {sorted(set(self.flow_terms) - set(fused_loop.FLOW_TERMS))} (flow_norm and image_gradient only)"
+        elif self.blur_sigma > 0:
+            what = f"iwe.blur_sigma: {self.blur_sigma} (the un-blurred IWE only)"
+        elif self.pad != 0:
+            what = f"outer_padding: {self.pad} (0 only)"
+        elif self.opt_method != "Adam" and self.opt_method not in SCIPY_METHODS:
+            what = f"optimizer.method: {self.opt_method!r} (Adam or one of {SCIPY_METHODS})"
+        else:
+            try:
+                multiref_slab_halo(self.plan_tile(), self.halo)
+            except NotImplementedError as e:
+                what = f"tile / halo: {e}"
+        if what is not None:
+            raise NotImplementedError("multi_reference.native does not cover " + what + "; drop native to run the autograd loop")
 
     def _check_native_time_aware(self) -> None:
         """``time_aware.native``: the family of ``time_aware_loop.TimeAwarePatchLoop``, or NotImplementedError naming the key outside it."""
@@ -522,6 +562,8 @@ class ContrastMaximizationMixin(object):
         H, W = self.orig_image_shape
         if self.time_aware is not None and self.time_aware.get("native", False):
             return self._optimise_time_aware_native(plan, theta, patch_size, sliding_window, n_iter, mask)
+        if self.multi_reference is not None and self.multi_reference.get("native", False):
+            return self._optimise_multi_reference_native(plan, theta, patch_size, sliding_window, n_iter, mask)
         theta = theta.requires_grad_(True)
 
         def evaluate():  # (mask: the gradient of a patch that is not estimated is zero, so it keeps its masked start)
@@ -594,6 +636,24 @@ class ContrastMaximizationMixin(object):
         if not adam:
             return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=loop.value_and_grad)
         loop.run(n_iter)
+        self.history += loop.losses[:n_iter].cpu().tolist()
+        return loop.theta
+
+    def _optimise_multi_reference_native(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
+                                         mask: Optional[torch.Tensor]) -> torch.Tensor:
+        """One pyramid scale of a ``multi_reference.native`` solve: the Adam loop as one C call, or a scipy method on the loop's
+        ``value_and_grad``."""
+        adam = self.opt_method == "Adam"
+        norm = self._multi_reference_norms(plan)["image_variance"]
+        loop = multi_reference_loop.MultiReferencePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.multi_reference["directions"],
+                                                            self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                                                            self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
+                                                            self.halo, self.lr, capacity=n_iter if adam else 1, theta_mask=mask, norm=norm)
+        self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
+        self.loop_modes.append(loop.last_run_mode)
+        if not adam:
+            return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=loop.value_and_grad)
+        loop.solve(n_iter)
         self.history += loop.losses[:n_iter].cpu().tolist()
         return loop.theta
 

@@ -1556,6 +1556,101 @@ int ebos_iwe_dense_multiref_owner_bwd_f32(const float* xs, const float* ys, cons
                                           float* d_flow, ebos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-reference contrast on the tile-private pipeline: the K-image form of ebos_iwe_dense_slab_f32 / ebos_iwe_dense_tiled_bwd_f32.
+ * Events, shifts and K as above: dt_k = dt + shifts[k] is ONE rounded float32 add per event, before anything else uses it.
+ * ebos_slab_multiref_config (host only): the built (tile_h, tile_w, halo) triples, as ebos_slab_config lists the single form's.
+ * ebos_iwe_slab_multiref_workspace_bytes (host only): K workspaces of the single form back to back (0: bad arguments, K outside
+ *   [1, EBOS_MULTIREF_MAX], splits < 1 or an unbuilt triple).  ZERO-FILLED ONCE by the caller; the spill / SpillEpoch / counter
+ *   contract of every one of the K sections is ebos_iwe_dense_slab_f32's.  One workspace serves one stream at a time.
+ * ebos_iwe_dense_slab_multiref_f32: the accumulate pass over a grid of (work item, k) -- workgroup (tile, split, k) keeps ONE LDS
+ *   window of tile + halo, fixed point with the exact f64 redo as in the single form, and writes its slab -- and the combine pass
+ *   over (pixel block, k), which OVERWRITES iwes [K, H + 2 pad_h, W + 2 pad_w].  Two launches whatever K is.  Image k has the bits
+ *   ebos_iwe_dense_slab_f32 gives on the same arrays with dts replaced by dt + shifts[k].  want_variance = 1: variances [K] (f32,
+ *   nullable) and moments [K, 2] = (mean_k, M) (f64, nullable), omit_boundary as in the costs; 2: only the (sum, sum of squares)
+ *   partials are left in each section (ebos_iwe_slab_partials gives their place inside a section); 0: neither.
+ * ebos_iwe_dense_tiled_multiref_bwd_f32: d_flow[c][i] = sum over the events of source pixel i and the references k of
+ *   -dt_k * dL/d(x'_k, y'_k) in ONE launch: one workgroup per tile keeps the two f64 planes of its tile's d_flow in LDS and sweeps
+ *   the references -- stage G_k of tile + halo in LDS, walk the tile's events with dt_k, add -- then OVERWRITES d_flow [2, H, W]
+ *   (+ addend [2, H, W], nullable) with plain stores: every cell, zeros where no event lies.  A source pixel's run is walked by
+ *   one owner thread in plan order (runs of more than 64 events by its wavefront with a fixed reduction tree): no atomics, the
+ *   same bits on every call.  Events whose taps leave the staged halo read G_k from global memory.  Upstream forms:
+ *     g_images [K, h, w] with affine [K, 2] on the device (nullable: a = 1, c = 0):  G_k = a_k g_images[k] + c_k;
+ *     var_moments [K, 2] (f64, the forward's moments) + upstream [1] (f32, device), both or neither, no affine: g_images are the
+ *       IWEs themselves and G_k = scales[k] * upstream[0] * 2 (IWE_k - mean_k) / (M - 1); scales: HOST float [K], nullable (1);
+ *     G_k = 0 outside [g_lo, h - g_lo) x [g_lo, w - g_lo).
+ *   LDS: 2 tile_h tile_w 8 B + (tile_h + 2 halo)(tile_w + 2 halo) 4 B, the single backward's budget.
+ * Both: the (x, y, dt) format of an emit = "full" binned plan (key_offsets of ebos_bin_events_f32, SoA arrays padded to 16-byte
+ *   loads), unit weights, a dense flow [2, H, W], splits >= 1.  EBOS_ERR_UNSUPPORTED before any launch: splits = 0 (adaptive work
+ *   items), halo < 0 (run-time windows), a triple that is not built.  The compact / fractional formats, per-event weights and the
+ *   patch-grid-sampling route have no form here.
+ * ---------------------------------------------------------------------------------------- */
+int ebos_slab_multiref_config(int* out, int cap);
+size_t ebos_iwe_slab_multiref_workspace_bytes(int K, int H, int W, int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w);
+int ebos_iwe_dense_slab_multiref_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                     const float* flow, int H, int W, int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w,
+                                     const float* shifts, int K, void* workspace, size_t workspace_bytes, float* iwes, int want_variance,
+                                     int omit_boundary, float* variances, double* moments, ebos_stream_t stream);
+int ebos_iwe_dense_tiled_multiref_bwd_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                          const float* flow, int H, int W, int tile_h, int tile_w, int halo, int pad_h, int pad_w,
+                                          const float* shifts, int K, const float* g_images, const float* affine, int g_lo,
+                                          const double* var_moments, const float* upstream, const float* scales, const float* addend,
+                                          float* d_flow, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The Adam loop of the MULTI-REFERENCE patch-flow contrast maximisation natively (the solver's `multi_reference` block with
+ * `native: true`):
+ *     loss(theta) = -(w_variance / (K norm)) sum_k var(IWE_k(dense(theta))) + w_flow_norm * flow_norm(dense)
+ *                   + w_image_gradient * image_gradient(dense)
+ * n_iter iterations enqueued back to back on `stream` by one C call: no host synchronisation, no allocation.  One iteration:
+ *     ebos_upsample_patch_flow_f32 -> ebos_iwe_dense_slab_multiref_f32 (want_variance = 1) [-> ebos_flow_regularisers_f32]
+ *     -> ebos_iwe_dense_tiled_multiref_bwd_f32 (var_moments, upstream, addend = regulariser gradient) -> a one-thread fold of the K
+ *     variances into contrast[0] -> ebos_upsample_patch_flow_bwd_adam_f32 (contrast_scale = -w_variance / (K norm))
+ * 7 launches per iteration, 8 with a regulariser weight, whatever K is.  All buffers are the caller's:
+ *   plan:     xs / ys / dts in key order, key_offsets, n, H, W, tile, halo, splits (>= 1), pad, omit_boundary as
+ *             ebos_iwe_dense_slab_multiref_f32; K and shifts[k] = f - r_k
+ *   grid:     theta / d_theta / exp_avg / exp_avg_sq [2, gh, gw], step [1] int32, patch and sliding window, steps_done, theta_mask
+ *             as in ebos_cmax_patch_problem
+ *   images:   dense / d_dense [2, H, W], d_reg [2, H, W] (nullable iff both regulariser weights are 0), iwes [K, H + 2 pad_h,
+ *             W + 2 pad_w], variances [K] f32, moments [K, 2] f64, contrast [1] f32, upstream [1] f32 = -w_variance / (K norm)
+ *   norm:     N of the block's `normalize` (the contrast of the zero-flow IWE), 1 without it; finite and non-zero
+ *   scratch:  workspace (ebos_iwe_slab_multiref_workspace_bytes, zero-filled once), reg_partials
+ *             [ebos_flow_regularisers_partials()] f64, upsample_scratch (ebos_upsample_bwd_scratch_bytes)
+ *   losses:   [losses_cap] f32, entry `step` written per iteration with the loss BEFORE the update (nullable)
+ * Checked before any launch, reported through ebos_last_error: NULL pointers, K, sizes (EBOS_ERR_INVALID_ARG), an unbuilt
+ * triple / splits = 0 / halo < 0 (EBOS_ERR_UNSUPPORTED), workspace_bytes and upsample_scratch_bytes (EBOS_ERR_SCRATCH).
+ * ebos_cmax_multiref_gradient_f32: one forward and backward at theta without the Adam step -- d_theta, variances and reg_partials are
+ *   left for the caller (loss = -(w_variance / (K norm)) sum(variances) + sum(reg_partials)); for optimisers that live on the host.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ebos_cmax_multiref_problem {
+  const float *xs, *ys, *dts;
+  const int32_t* key_offsets;
+  int64_t n;
+  int H, W, tile_h, tile_w, halo, pad_h, pad_w, omit_boundary, splits;
+  int K;
+  float shifts[EBOS_MULTIREF_MAX];
+  int gh, gw, patch_h, patch_w, slide_h, slide_w;
+  float w_variance, w_flow_norm, w_image_gradient;
+  double norm;
+  double lr, beta1, beta2, eps;
+  float *theta, *d_theta, *exp_avg, *exp_avg_sq;
+  int* step;
+  int steps_done;
+  float *dense, *d_dense, *d_reg, *iwes, *variances, *contrast;
+  double* moments;
+  const float* upstream;
+  void* workspace;
+  size_t workspace_bytes;
+  double* reg_partials;
+  float* upsample_scratch;
+  size_t upsample_scratch_bytes;
+  float* losses;
+  int losses_cap;
+  const float* theta_mask;
+} ebos_cmax_multiref_problem;
+int ebos_cmax_multiref_solve_f32(const ebos_cmax_multiref_problem* problem, int n_iter, ebos_stream_t stream);
+int ebos_cmax_multiref_gradient_f32(const ebos_cmax_multiref_problem* problem, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The Adam loop of the TIME-AWARE patch-flow contrast maximisation natively (the solver's `time_aware` block):
  *     loss(theta) = -w_variance * var(IWE(events warped by voxel(dense(theta))))
  *                   + w_flow_norm * flow_norm(dense) + w_image_gradient * image_gradient(dense)
