@@ -551,13 +551,25 @@ __device__ __forceinline__ int32_t chunk_group(int32_t g_first, int c, int lane)
 // then U = rint(w * wscale) <= 2^20 (wscale = 2^20 / max |w| of the slice, TileShared) instead of the constant 2^20, split between
 // the four taps by the same exact scheme; the units put inside the window are summed per lane (the return value) -- three
 // multiply-adds and a 64-bit add per event on top of the unit-weight loop.
+// TWO (dense field in memory, built window, unit weights, fixed point; single-window kernel): the plain mapping with TWO groups per
+// loop trip and the roles of the pipeline's registers written out, as in the PAIRS loop.  The one-group loop renames its buffers at
+// the bottom of every trip (cur = nxt, nxt = nn, fu = gu, fv = gv: 18 register moves per group that the compiler does not remove, the
+// flow ones each behind a wait for a gather the same trip issued), draws its next chunk with an LDS round trip at the top of every
+// trip (ds_add_rtn_u32, lgkmcnt(0), v_readfirstlane: it also drains the previous group's eight adds), adds the LDS address of s_acc to
+// every event's word offset and rebuilds the dummy word's address per event.  Here nothing is renamed, the queue is drawn one
+// step ahead (the index consumed now was requested a deposit ago), the base sits in the offset field of the adds (kAccBase) and the
+// dummy offset lives in one register.  Same depth as before -- event loads two groups ahead, gathers one --, same chunks, same
+// per-event arithmetic: the LDS image is a sum of integers and does not depend on the order of the trips.
+typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+constexpr unsigned kAccBase = 160u;  // LDS address of the dynamic LDS (s_acc) in a kernel whose only static LDS is its TileShared
 template <int TH, int TW, int HALO, bool UNIFORM, int MODE = ACC_FX, bool GRID = false, bool DYN = false, bool PAIRS = false,
-          bool HAS_W = false>
+          bool HAS_W = false, bool TWO = false>
 __device__ __forceinline__ unsigned long long accumulate_compact_fx(const TileRange& tr, double* s_acc, const EvPtrs& ev,
                                                           const float* __restrict__ flow, int H, int W, bool* any_spill,
                                                           const ChunkQueue& queue, const Win<TH, TW, HALO, DYN>& win,
                                                           const CRaw* pre = nullptr, float wscale = kFxScale) {
   static_assert(!HAS_W || (MODE == ACC_FX && !PAIRS && !DYN), "per-event weights: the plain fixed-point loop on the largest window");
+  static_assert(!TWO || (!UNIFORM && !GRID && !DYN && !PAIRS && !HAS_W && MODE == ACC_FX), "two groups per trip: the plain dense fixed-point loop");
   constexpr bool kMerge = PAIRS && MODE == ACC_FX;   // same-cell events of a lane merged before the add (see `deposit`)
   const int LH = win.LH(), LW = win.LW(), HR = win.HR(), HC = win.HC(), PT = win.P();  // (compile-time constants unless DYN)
   const unsigned kPlane = LH * PT / 2;  // words per plane
@@ -602,13 +614,16 @@ __device__ __forceinline__ unsigned long long accumulate_compact_fx(const TileRa
   constexpr int kWaves = kBlock / kWave;
   char* const s_bytes = reinterpret_cast<char*>(s_acc);
   unsigned long long added = 0ull;  // HAS_W: the units this lane put inside the window
+  unsigned dummy_off = 8u * kDummy;  // TWO: the dummy word's offset in ONE register for the whole loop (opaque: not rebuilt per event)
+  if constexpr (TWO) asm("" : "+v"(dummy_off));
   // the four events of one group into the LDS image (fu / fv: their flow, gathered one step earlier; wq: their weights)
   auto deposit = [&](const CGroupQ& cur, const float* fu, const float* fv, bool lane_live, const float4& wq4 = float4{}) {
     const float wq[4] = {wq4.x, wq4.y, wq4.z, wq4.w};
     unsigned m_byte = 0u, m00 = 0u, m01 = 0u, m10 = 0u, m11 = 0u;  // kMerge: the run of events that share a cell
 #pragma unroll
     for (int e = 0; e < 4; ++e) EBOS_KLOOP {
-      const float lx = -cur.dt[e] * EBOS_KOFF(fu[e], 0.37f), ly = -cur.dt[e] * EBOS_KOFF(fv[e], -0.21f);  // source coordinates are integers: x' = rs + lx
+      constexpr int kF = TWO ? 2 : 1;  // (TWO: fu = &uv[0].x, fv = &uv[0].y of an array of (u, v) pairs -- the two products are one packed multiply, and its operand is the register pair the gathers wrote)
+      const float lx = -cur.dt[e] * EBOS_KOFF(fu[kF * e], 0.37f), ly = -cur.dt[e] * EBOS_KOFF(fv[kF * e], -0.21f);  // source coordinates are integers: x' = rs + lx
       const float r0 = floorf(lx + kEps), c0 = floorf(ly + kEps);
       const float fr = fmaxf(lx - r0, 0.0f), fc = fmaxf(ly - c0, 0.0f);
       // row of the LDS window, and 4 x its column (= byte offset of the column's f32 / half the offset of its pair word)
@@ -618,7 +633,10 @@ __device__ __forceinline__ unsigned long long accumulate_compact_fx(const TileRa
       // (int)c0 << 2 WRAPS for |c0| >= 2^29 (INT_MAX << 2 = -4, INT_MIN << 2 = 0): such an event would pass the window test and be
       // deposited at column pc - 1 or pc with full weight -- the reference masks it out
       const bool ok = lane_live && (fabsf(lx) + fabsf(ly) < 5.0e8f);
-      const bool inside = ok && (unsigned)rl < (unsigned)(LH - 1) && (unsigned)cl4 < (unsigned)(4 * (LW - 1));
+      // (TWO: the same three tests joined without branches -- with `&&` the compiler turns the select of the word's address below into
+      // an exec-masked block per event, with a copy of the dummy address in front and a quarter-rate 32-bit multiply inside)
+      const bool inside = TWO ? bool(int(ok) & int((unsigned)rl < (unsigned)(LH - 1)) & int((unsigned)cl4 < (unsigned)(4 * (LW - 1))))
+                              : ok && (unsigned)rl < (unsigned)(LH - 1) && (unsigned)cl4 < (unsigned)(4 * (LW - 1));
       spilled |= ok && !inside;
       if (MODE == ACC_F64) {  // one double per cell; out-of-window / padding lanes add +0.0 to cell (0, 0) (select, not
         const float a = 1.0f - fr, b = 1.0f - fc;  // multiply: their weights may be NaN)
@@ -677,6 +695,15 @@ __device__ __forceinline__ unsigned long long accumulate_compact_fx(const TileRa
           atomicAdd(wp, ((unsigned long long)m01 << 32) | m00);
           atomicAdd(wp + PT / 2, ((unsigned long long)m11 << 32) | m10);
         }
+      } else if constexpr (TWO) {
+        // (the word's offset inside s_acc as an LDS address, s_acc's own address as the instruction's constant offset)
+        // (... and the word's offset through an opaque register: the select below stays a select -- left to itself the compiler
+        // moves the offset's arithmetic into an exec-masked block per event, behind a copy of the dummy offset)
+        unsigned byte_v = byte;
+        asm("" : "+v"(byte_v));
+        lds_u64* w = reinterpret_cast<lds_u64*>(inside ? byte_v : dummy_off) + kAccBase / 8;
+        __hip_atomic_fetch_add(w, ((unsigned long long)q01 << 32) | q00, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(w + PT / 2, ((unsigned long long)q11 << 32) | q10, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       } else {
         unsigned long long* w = reinterpret_cast<unsigned long long*>(s_bytes + (inside ? byte : 8u * kDummy));
         atomicAdd(w, ((unsigned long long)q01 << 32) | q00);
@@ -684,7 +711,70 @@ __device__ __forceinline__ unsigned long long accumulate_compact_fx(const TileRa
       }
     }
   };
-  if (PAIRS) {
+  if constexpr (TWO) {
+    // One trip = two chunks of this wave:  gather B | draw, load A' | deposit A  ||  gather A' | draw, load B' | deposit B.
+    // Register set A holds the wave's chunks number 0, 2, 4 ... and B its chunks 1, 3, 5 ...; a wave with an odd number of chunks leaves
+    // between the halves (wave-uniform).  Chunk indices grow along a wave's draws, so a chunk past the slice ends the wave.
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);  // (scalar: the loop's two exits are scalar branches)
+    int c_a = wave_s, c_b = wave_s + kWaves;
+    CRaw ra, rb;
+    CGroupQ ga, gb;
+    if (pre != nullptr) {
+      ra = pre[0], rb = pre[1];
+    } else {
+      ra = load_craw(chunk_group(tr.g_first, c_a, lane), tr, ev);
+      rb = load_craw(chunk_group(tr.g_first, c_b, lane), tr, ev);
+    }
+    // The queue one step ahead: a half-trip takes the index `c_new` that the half before it requested, requests the next one, and
+    // reads it back behind its deposit (lgkmcnt(8): the deposit's adds stay in flight, and the LDS queue is never drained in front of
+    // the event loads).  The counter's address goes through an opaque register: on an address it can prove uniform the compiler
+    // rewrites the add into its wave-reduced form, whose read-back waits for the LDS at once.
+    unsigned next_addr = (unsigned)reinterpret_cast<uintptr_t>(queue.next);
+    asm("" : "+v"(next_addr));
+    typedef __attribute__((address_space(3))) unsigned lds_u32;
+    auto request = [&]() {  // (not awaited; only lane 0's value is ever read: the other lanes' is left as it is, not set)
+      unsigned c;
+      asm("" : "=v"(c));
+      if (lane == 0) c = __hip_atomic_fetch_add(reinterpret_cast<lds_u32*>(next_addr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      return c;
+    };
+    auto take = [&](unsigned c) { return (int)__builtin_amdgcn_readfirstlane(c); };
+    int c_new = take(request());
+    decode_craw(ga, ra, hc4);
+    decode_craw(gb, rb, hc4);
+    v2f uva[4], uvb[4];  // gathered flow of the A / B group, (u, v) per event
+    auto fetch_uv = [&](const CGroupQ& g, int e, v2f& uv) {
+      float u, v;
+      fetch(g.pr[e], g.pcq[e], u, v);
+      uv = v2f{u, v};
+    };
+#pragma unroll
+    for (int e = 0; e < 4; ++e) fetch_uv(ga, e, uva[e]);
+    while (chunk_group(tr.g_first, c_a, 0) <= g_last) {  // wave-uniform
+#pragma unroll
+      for (int e = 0; e < 4; ++e) fetch_uv(gb, e, uvb[e]);
+      const int c_an = c_new;
+      unsigned drawn = request();
+      ra = load_craw(chunk_group(tr.g_first, c_an, lane), tr, ev);
+      deposit(ga, reinterpret_cast<const float*>(uva), reinterpret_cast<const float*>(uva) + 1, chunk_group(tr.g_first, c_a, lane) <= g_last);
+      c_new = take(drawn);
+      c_a = c_an;
+      if (chunk_group(tr.g_first, c_b, 0) > g_last) break;  // wave-uniform: this wave's last chunk was an A chunk
+      decode_craw(ga, ra, hc4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) fetch_uv(ga, e, uva[e]);
+      const int c_bn = c_new;
+      drawn = request();
+      rb = load_craw(chunk_group(tr.g_first, c_bn, lane), tr, ev);
+      deposit(gb, reinterpret_cast<const float*>(uvb), reinterpret_cast<const float*>(uvb) + 1, chunk_group(tr.g_first, c_b, lane) <= g_last);
+      c_new = take(drawn);
+      c_b = c_bn;
+      decode_craw(gb, rb, hc4);
+    }
+    // (a use of A' on the way out: with none the compiler moves its two loads from in front of deposit A to behind the exit test
+    // between the halves, i.e. directly in front of their decode -- a memory round trip per trip, in the open)
+    asm volatile("" ::"v"(ra.P.x), "v"(ra.D.x));
+  } else if (PAIRS) {
     // One loop iteration = the two groups of a lane's pair of macro chunk m, written out (no parity branch; the pipeline buffers
     // rotate once per TWO groups, which also halves the register moves per event): the pair of the next macro chunk was requested an
     // iteration ago; its first group is decoded after the first deposit, its second after the second group's gathers are on their way,
@@ -784,7 +874,7 @@ enum Pass { PASS_MAIN = 0, PASS_SPILL = 1 };
 // FRAC: the compact plan carries fractional source coordinates (EvPtrs::cfx / cfy): every pass takes the general loop below, whose
 // groups hold the fractions (load_group); the lean loop assumes integer pixels.
 template <int TH, int TW, int HALO, bool HAS_W, int MODE, int PASS, int FMT, bool UNIFORM, bool GRID = false, bool DYN = false,
-          bool PAIRS = false, bool FRAC = false, bool SHIFT = false>
+          bool PAIRS = false, bool FRAC = false, bool SHIFT = false, bool TWO = false>
 __device__ __forceinline__ unsigned long long accumulate_slice(const TileRange& tr, double* s_acc, const EvPtrs& ev,
                                                      const float* __restrict__ flow, int H, int W, int pad_h, int pad_w,
                                                      float* spill, bool* any_spill, const ChunkQueue& queue,
@@ -802,7 +892,7 @@ __device__ __forceinline__ unsigned long long accumulate_slice(const TileRange& 
   bool spilled = false;
   if (tr.g_first > tr.g_last) return 0;
   if (FMT == FMT_COMPACT && PASS == PASS_MAIN && !HAS_W && !FRAC)  // the lean hot loop (fixed point, or its exact f64 redo)
-    return accumulate_compact_fx<TH, TW, HALO, UNIFORM, MODE, GRID, DYN, PAIRS>(tr, s_acc, ev, flow, H, W, any_spill, queue, win, pre);
+    return accumulate_compact_fx<TH, TW, HALO, UNIFORM, MODE, GRID, DYN, PAIRS, false, TWO>(tr, s_acc, ev, flow, H, W, any_spill, queue, win, pre);
   if constexpr (FMT == FMT_COMPACT && PASS == PASS_MAIN && HAS_W && !FRAC && MODE == ACC_FX && !DYN && !PAIRS)  // ... with per-event weights
     return accumulate_compact_fx<TH, TW, HALO, UNIFORM, ACC_FX, GRID, false, false, true>(tr, s_acc, ev, flow, H, W, any_spill, queue, win,
                                                                                        nullptr, wscale);
@@ -982,6 +1072,7 @@ struct TileShared {
   // 4 ds_add_f64.  A slice with a negative (or non-finite) weight runs in f64 from the start (accumulate_tile).
   float wscale, wdec;
 };
+static_assert(kAccBase == ((sizeof(TileShared) + 15u) & ~15u), "kAccBase: the dynamic LDS starts right behind TileShared");
 struct NoHook {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -1085,9 +1176,16 @@ __device__ __forceinline__ void tile_body(const TileRange& tr, const Win<TH, TW,
   // (... or where the pixels are so full -- >= 24 events each: the 50 M-event window of the 2-DoF sweep holds 54 -- that even a 30 px
   // displacement leaves several events of a pixel on one word: 33.9 -> 33.1 ms per 512-hypothesis sweep)
   const int32_t n_ev = tr.end - tr.beg;
+  // the single-window kernel's dense-field, built-window, unit-weight loop: two groups per trip (accumulate_compact_fx, TWO).  Its adds
+  // carry s_acc's LDS address as a compile-time offset: the dynamic LDS of these kernels starts right behind `sh` (kAccBase), and a
+  // kernel laid out otherwise takes the one-group loop.
+  constexpr bool kTwoGroups = !ZERO && !UNIFORM && !GRID && !DYN && !HAS_W && MODE == ACC_FX && FMT == FMT_COMPACT && !FRAC && !SHIFT;
   if (kCanPair && n_ev >= 4 * TH * TW && ((win.HR() <= 16 && win.HC() <= 16) || n_ev >= 24 * TH * TW))
     added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, kCanPair>(
         tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, nullptr);
+  else if (kTwoGroups && (unsigned)reinterpret_cast<uintptr_t>(s_acc) == kAccBase)  // (the low half of an LDS pointer is its LDS address)
+    added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC, SHIFT, kTwoGroups>(
+        tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, pre);
   else
     added = accumulate_slice<TH, TW, HALO, HAS_W, MODE, PASS_MAIN, FMT, UNIFORM, GRID, DYN, false, FRAC, SHIFT>(
         tr, s_acc, ev, flow, H, W, pad_h, pad_w, spill, &spilled, queue, win, pre, HAS_W ? sh.wscale : kFxScale, dt_shift);
