@@ -926,6 +926,7 @@ class TimeAwarePlanStack(object):
                             key_offsets[b][0] .. key_offsets[b][n_keys] of the streams and a kernel needs no pointer table
         ns                  the windows' event counts (host)
 
+    A stack of ONE plan copies nothing: its streams are views of the plan's and its offsets the plan's own, ``key_offsets[None]``.
     ValueError for a plan that is un-binned, deferred or without bins, for plans that differ in image size, tile, ``time_bin`` or
     warp direction (a plan keeps its direction as ``dt_bound``), and for more than INT32_MAX events in total.  An ``EventPlan`` holds no
     per-event weights (they are an argument of the operators), and the stacked kernels take none."""
@@ -958,10 +959,14 @@ class TimeAwarePlanStack(object):
         self.image_size, self.tile, self.time_bin, self.dt_bound = first.image_size, tuple(first.tile), first.time_bin, first.dt_bound
         self.ref_fraction, self.normalized_t = first.ref_fraction, first.normalized_t
         self.n = sum(self.ns)
-        self.x, self.y, self.dt = (torch.cat([getattr(p, k)[:p.n] for p in plans]).contiguous() for k in ("x", "y", "dt"))
-        self.bins = torch.cat([p.bins[:p.n] for p in plans]).contiguous()
-        bases = torch.tensor([sum(self.ns[:b]) for b in range(len(plans))], dtype=torch.int32, device=first.device)
-        self.key_offsets = (torch.stack([p.key_offsets for p in plans]) + bases[:, None]).to(torch.int32).contiguous()
+        if len(plans) == 1:   # the plan's own storage, no copies: the base is 0, so its offsets already index its streams
+            self.x, self.y, self.dt, self.bins = (getattr(first, k)[:first.n] for k in ("x", "y", "dt", "bins"))
+            self.key_offsets = first.key_offsets.to(torch.int32).contiguous()[None]
+        else:
+            self.x, self.y, self.dt = (torch.cat([getattr(p, k)[:p.n] for p in plans]).contiguous() for k in ("x", "y", "dt"))
+            self.bins = torch.cat([p.bins[:p.n] for p in plans]).contiguous()
+            bases = torch.tensor([sum(self.ns[:b]) for b in range(len(plans))], dtype=torch.int32, device=first.device)
+            self.key_offsets = (torch.stack([p.key_offsets for p in plans]) + bases[:, None]).to(torch.int32).contiguous()
 
     @classmethod
     def from_raw(cls, cols: Sequence[torch.Tensor], ranges: Sequence[Tuple[int, int]], image_size: Tuple[int, int],

@@ -1,27 +1,28 @@
 """The Adam loop of the time-aware patch-flow contrast maximisation (the solver's ``time_aware`` block with ``native: true``) as
-one C call, without autograd (kernels: csrc/cmax_voxel.hip, csrc/warp_voxel.hip).
+one C call, without autograd (kernels: csrc/cmax_voxel.hip, csrc/warp_voxel.hip), for B windows of one geometry in the launches of
+one window (``TimeAwarePatchLoopBatch``: ``ebos_cmax_voxel_solve_batch_f32``).  Per window
 
     loss(theta) = -w var(IWE(events warped by voxel(dense(theta)))) + w_n flow_norm(dense) + w_g image_gradient(dense)
 
-One iteration, on buffers allocated once per loop:
+One iteration, on buffers allocated once per loop; every stage takes the window from an outer grid dimension, each window has its
+own events, grid and Adam state:
 
-    ebos_upsample_patch_flow_f32           theta [2, gh, gw] -> dense [2, H, W], the flow at t0
-    ebos_flow_voxel_advect_f32             dense -> voxel [T, 2, H, W] (upwind | burgers; with a clamp: + the clamped copy)
-    memset + ebos_iwe_voxel_tiled_f32      every event displaced by the flow of its own bin -> IWE
-    ebos_image_variance_f32 / _affine_f32  variance, its moments, and its gradient as an affine map of the IWE
-    ebos_flow_regularisers_f32             (with a regulariser weight) value partials + gradient image
-    ebos_iwe_voxel_owner_bwd_f32           -> d_voxel: the owner of a source pixel's run writes its 2 T cells; no atomics, no clearing
-    ebos_flow_voxel_advect_adjoint_f32     -> d_dense (+ the regularisers' gradient)
-    ebos_upsample_patch_flow_bwd_adam_f32  -> d_theta, the Adam step of every grid element, loss[it]
+    ebos_upsample_patch_flow_batch_f32           theta [B, 2, gh, gw] -> dense [B, 2, H, W], the flow at t0
+    ebos_flow_voxel_advect_f32                   dense -> voxel [B, T, 2, H, W] (upwind | burgers; with a clamp: + the clamped copy)
+    memset + ebos_iwe_voxel_tiled_batch_f32      every event displaced by the flow of its own bin -> IWE [B, h, w]
+    ebos_image_variance_f32 / _affine_f32        variance, its moments, and its gradient as an affine map of the IWE
+    ebos_flow_regularisers_batch_f32             (with a regulariser weight) value partials + gradient image
+    ebos_iwe_voxel_owner_bwd_batch_f32           -> d_voxel: the owner of a source pixel's run writes its 2 T cells; no atomics, no clearing
+    ebos_flow_voxel_advect_adjoint_f32           -> d_dense (+ the regularisers' gradient)
+    ebos_upsample_patch_flow_bwd_adam_batch_f32  -> d_theta, the Adam step of every grid element, loss[b, it]
 
-``owner_bwd=False`` swaps the backward for a memset and the global-atomic ``ebos_iwe_voxel_bwd_f32``: the two stay comparable inside
-one loop; ``owner_bwd=None`` takes whichever was measured faster for the window's size and bins (``default_owner_bwd``).  The
-family: the variance contrast alone, optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``; anything else belongs to the
-autograd loop of ``ContrastMaximization``.
+``owner_bwd=False`` swaps the backward for a memset and the global-atomic ``ebos_iwe_voxel_bwd_f32`` window by window: the two stay
+comparable inside one loop; ``owner_bwd=None`` takes whichever was measured faster for the window's size and bins
+(``default_owner_bwd``).  The family: the variance contrast alone, optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``;
+anything else belongs to the autograd loop of ``ContrastMaximization``.
 
-``TimeAwarePatchLoopBatch`` runs the same loop for B windows of one geometry in the launches of one window
-(``ebos_cmax_voxel_solve_batch_f32``): every stage takes the window from an outer grid dimension, each window has its own events, grid
-and Adam state.
+One window is a batch of one, on the same code path: ``TimeAwarePatchLoop`` is the face of a ``TimeAwarePatchLoopBatch`` of B = 1
+without the window dimension.
 """
 from __future__ import annotations
 
@@ -46,124 +47,11 @@ def default_owner_bwd(time_bin: int, n_events: int) -> bool:
     return int(time_bin) >= 10 and int(n_events) >= 1_000_000
 
 
-class TimeAwarePatchLoop(object):
-    """Constructor shape of ``fused_loop.FusedPatchLoop`` plus ``time_aware``, the parsed block (``parse_time_aware``)."""
-    graphed = False
-    last_run_mode = "native"
-
-    def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
-                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
-                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
-                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None, owner_bwd: Optional[bool] = None):
-        self.lib = lib = _hip.require_gpu()
-        ta = dict(time_aware)
-        if plan.bins is None or not plan.binned:
-            raise ValueError('TimeAwarePatchLoop needs a binned time-aware plan: EventPlan.build(..., emit="full", time_bin=T, tile=...)')
-        if plan.__dict__.get("_deferred"):
-            raise ValueError("TimeAwarePatchLoop needs a plan whose build was read back (not deferred)")
-        if int(ta["time_bin"]) != plan.time_bin:
-            raise ValueError(f"the plan's bins were made for time_bin={plan.time_bin}, time_aware asks for {ta['time_bin']}")
-        if ta.get("scheme", "upwind") not in ("upwind", "burgers"):
-            raise NotImplementedError(f"time_aware.scheme {ta.get('scheme')!r}: the native loop runs 'upwind' and 'burgers'")
-        if float(w_variance) == 0.0:
-            raise ValueError("w_variance must be non-zero")
-        self.plan, self.patch, self.slide = plan, tuple(int(v) for v in patch_size), tuple(int(v) for v in sliding_window)
-        self.T, self.scheme = int(ta["time_bin"]), _ADVECT[ta.get("scheme", "upwind")]
-        self.t0 = _t0_index(ta.get("t0_location", "middle"), self.T)
-        self.clamp = None if ta.get("clamp") is None else float(ta["clamp"])
-        self.w_var, self.w_norm, self.w_tv = float(w_variance), float(w_flow_norm), float(w_image_gradient)
-        self.omit, self.pad = bool(omit_boundary), (int(pad), int(pad))
-        built = _voxel_halo(plan, halo)                 # None: (tile, halo) is no built configuration -> the general forward kernel
-        self.halo = 0 if built is None else int(built)
-        self.splits = max(1, plan.resolve_splits(None))
-        self.owner_bwd = default_owner_bwd(self.T, plan.n) if owner_bwd is None else bool(owner_bwd)
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        from .. import flow_voxel as _fv
-
-        self.route = _hip.FLOW_ROUTE_AUTO if _fv._FORCE_ROUTE is None else _fv._FORCE_ROUTE
-        dev = plan.device
-        H, W = plan.image_size
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.theta = theta0.detach().to(**f32).contiguous().clone()
-        _, self.gh, self.gw = self.theta.shape
-        self.theta_mask = None if theta_mask is None else theta_mask.detach().to(**f32).reshape(self.gh, self.gw).contiguous()
-        self.d_theta = torch.empty_like(self.theta)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
-        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.t = 0
-        self.has_reg = self.w_norm != 0.0 or self.w_tv != 0.0
-        self.dense, self.d_dense = torch.empty((2, H, W), **f32), torch.empty((2, H, W), **f32)
-        self.d_reg = torch.empty((2, H, W), **f32) if self.has_reg else None
-        self.voxel, self.d_voxel = torch.empty((self.T, 2, H, W), **f32), torch.empty((self.T, 2, H, W), **f32)
-        self.voxel_clamped = torch.empty_like(self.voxel) if self.clamp is not None else None
-        self.iwe = torch.empty((H + 2 * self.pad[0], W + 2 * self.pad[1]), **f32)
-        self.variance = torch.empty(1, **f32)
-        self.moments = torch.empty((1, 2), dtype=torch.float64, device=dev)
-        self.upstream = torch.full((1,), -self.w_var, **f32)   # loss = -w * contrast
-        self.affine = torch.empty(2, **f32)
-        self.cost_scratch = torch.empty(int(lib.ebos_cost_scratch_bytes(1)), dtype=torch.uint8, device=dev)
-        self.n_reg = int(lib.ebos_flow_regularisers_partials()) if self.has_reg else 0
-        self.reg_partials = torch.zeros(max(self.n_reg, 1), dtype=torch.float64, device=dev)
-        self.scratch_up = torch.empty(int(lib.ebos_upsample_bwd_scratch_bytes(self.gh, W)) // 4, **f32)
-        n_ws = int(lib.ebos_flow_voxel_advect_adjoint_workspace(self.scheme, 1, self.T, H, W, self.t0, 0, self.route))
-        if n_ws < 0:
-            raise RuntimeError("ebos_flow_voxel_advect_adjoint_workspace: " + lib.ebos_last_error().decode("utf-8", "replace"))
-        self.adjoint_ws = torch.empty(n_ws, **f32) if n_ws else None
-        self.losses = torch.zeros(max(int(capacity), 1), **f32)
-
-    def problem(self) -> "_hip.CmaxVoxelProblem":
-        """The loop's buffers as the ``ebos_cmax_voxel_problem`` struct of the C ABI."""
-        plan = self.plan
-        q = _hip.CmaxVoxelProblem()
-        q.xs, q.ys, q.dts, q.bins, q.key_offsets, q.n = ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.bins), ptr(plan.key_offsets), plan.n
-        q.H, q.W = plan.image_size
-        q.tile_h, q.tile_w, q.halo = plan.tile[0], plan.tile[1], self.halo
-        q.pad_h, q.pad_w, q.omit_boundary, q.splits = self.pad[0], self.pad[1], int(self.omit), self.splits
-        q.T, q.scheme, q.t0_index, q.wrap_last, q.route = self.T, self.scheme, self.t0, 0, self.route
-        q.has_clamp, q.clamp = int(self.clamp is not None), float(self.clamp or 0.0)
-        q.owner_bwd = int(self.owner_bwd)
-        q.gh, q.gw, (q.patch_h, q.patch_w), (q.slide_h, q.slide_w) = self.gh, self.gw, self.patch, self.slide
-        q.w_variance, q.w_flow_norm, q.w_image_gradient = self.w_var, self.w_norm, self.w_tv
-        q.lr, q.beta1, q.beta2, q.eps = self.lr, self.betas[0], self.betas[1], self.eps
-        q.theta, q.d_theta, q.exp_avg, q.exp_avg_sq = ptr(self.theta), ptr(self.d_theta), ptr(self.exp_avg), ptr(self.exp_avg_sq)
-        q.step, q.steps_done = ptr(self.step), self.t
-        q.dense, q.d_dense, q.d_reg = ptr(self.dense), ptr(self.d_dense), ptr(self.d_reg)
-        q.voxel, q.voxel_clamped, q.d_voxel = ptr(self.voxel), ptr(self.voxel_clamped), ptr(self.d_voxel)
-        q.iwe, q.variance, q.moments, q.upstream, q.affine = ptr(self.iwe), ptr(self.variance), ptr(self.moments), ptr(self.upstream), ptr(self.affine)
-        q.cost_scratch, q.cost_scratch_bytes = ptr(self.cost_scratch), self.cost_scratch.numel()
-        q.reg_partials, q.upsample_scratch = ptr(self.reg_partials), ptr(self.scratch_up)
-        q.adjoint_workspace = ptr(self.adjoint_ws)
-        q.adjoint_workspace_elems = self.adjoint_ws.numel() if self.adjoint_ws is not None else 0
-        q.losses, q.losses_cap, q.theta_mask = ptr(self.losses), self.losses.numel(), ptr(self.theta_mask)
-        return q
-
-    def run(self, n_iter: int) -> torch.Tensor:
-        """``n_iter`` more iterations, enqueued by one C call; returns their losses [n_iter] (device)."""
-        n_iter = int(n_iter)
-        if self.t + n_iter > self.losses.numel():
-            raise ValueError(f"capacity {self.losses.numel()} < {self.t} steps done + {n_iter}")
-        t0 = self.t
-        with _hip.on_device(self.plan.device):
-            check(self.lib.ebos_cmax_voxel_solve_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_voxel_solve")
-        self.t += n_iter
-        return self.losses[t0:t0 + n_iter]
-
-    def value_and_grad(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(loss [0-d], d loss / d theta [2, gh, gw]) at ``theta`` through the same kernels, without the Adam step -- for optimisers
-        that live on the host (scipy)."""
-        with _hip.on_device(self.plan.device):
-            self.theta.copy_(theta.detach().to(self.theta))
-            check(self.lib.ebos_cmax_voxel_gradient_f32(ctypes.byref(self.problem()), stream_ptr()), "ebos_cmax_voxel_gradient")
-            loss = -self.w_var * self.variance[0]
-            if self.n_reg:
-                loss = loss + self.reg_partials.sum().to(torch.float32)
-        return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask)
-
-
 class TimeAwarePatchLoopBatch(object):
-    """``TimeAwarePatchLoop`` for B windows at once: ``plans`` is a sequence of binned time-aware plans of one geometry (or a
-    ``TimeAwarePlanStack``), ``theta0`` [B, 2, gh, gw], ``theta_mask`` [B, gh, gw]; the other arguments are the single loop's and hold
-    for every window.  ``owner_bwd=None`` resolves through ``default_owner_bwd(T, the largest window)``."""
+    """The loop for B windows at once.  Constructor shape of ``fused_loop.FusedPatchLoop`` plus ``time_aware``, the parsed block
+    (``parse_time_aware``): ``plans`` is a sequence of binned time-aware plans of one geometry (or a ``TimeAwarePlanStack``), ``theta0``
+    [B, 2, gh, gw], ``theta_mask`` [B, gh, gw]; the other arguments hold for every window.  ``owner_bwd=None`` resolves through
+    ``default_owner_bwd(T, the largest window)``."""
     graphed = False
     last_run_mode = "native-batch"
 
@@ -276,3 +164,37 @@ class TimeAwarePatchLoopBatch(object):
             if self.n_reg:
                 loss = loss + self.reg_partials.sum(dim=1).to(torch.float32)
         return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask[:, None])
+
+
+class TimeAwarePatchLoop(object):
+    """One window: the face of a ``TimeAwarePatchLoopBatch`` of B = 1 (``batch``) without the window dimension.  ``theta0`` and the
+    state ``theta`` / ``d_theta`` / ``exp_avg`` / ``exp_avg_sq`` are [2, gh, gw], ``theta_mask`` [gh, gw], ``losses`` [capacity]: views
+    of the batch's buffers, so writing into them writes what the kernels read.  Every other attribute is the batch's."""
+    graphed = False
+    last_run_mode = "native"
+
+    def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
+                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
+                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None, owner_bwd: Optional[bool] = None):
+        self.plan = plan
+        self.batch = b = TimeAwarePatchLoopBatch([plan], patch_size, sliding_window, theta0[None], time_aware, w_variance, w_flow_norm,
+                                                 w_image_gradient, omit_boundary, pad, halo, lr, betas, eps, capacity, theta_mask, owner_bwd)
+        self.theta, self.d_theta, self.exp_avg, self.exp_avg_sq, self.losses = b.theta[0], b.d_theta[0], b.exp_avg[0], b.exp_avg_sq[0], b.losses[0]
+
+    def __getattr__(self, name):                       # (only what the face does not hold itself: step, voxel, iwe, affine, ...)
+        if name == "batch":
+            raise AttributeError(name)
+        return getattr(self.batch, name)
+
+    t, owner_bwd = (property(lambda self, k=k: getattr(self.batch, k), lambda self, v, k=k: setattr(self.batch, k, v)) for k in ("t", "owner_bwd"))
+
+    def run(self, n_iter: int) -> torch.Tensor:
+        """``n_iter`` more iterations, enqueued by one C call; returns their losses [n_iter] (device)."""
+        return self.batch.run(n_iter)[0]
+
+    def value_and_grad(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(loss [0-d], d loss / d theta [2, gh, gw]) at ``theta`` through the same kernels, without the Adam step -- for optimisers
+        that live on the host (scipy)."""
+        loss, grad = self.batch.value_and_grad(theta[None])
+        return loss[0], grad[0]

@@ -1654,12 +1654,10 @@ int ebos_cmax_multiref_gradient_f32(const ebos_cmax_multiref_problem* problem, e
  * The Adam loop of the TIME-AWARE patch-flow contrast maximisation natively (the solver's `time_aware` block):
  *     loss(theta) = -w_variance * var(IWE(events warped by voxel(dense(theta))))
  *                   + w_flow_norm * flow_norm(dense) + w_image_gradient * image_gradient(dense)
- * n_iter iterations enqueued back to back on `stream` by one C call: no host synchronisation, no allocation.  One iteration:
- *     ebos_upsample_patch_flow_f32 -> ebos_flow_voxel_advect_f32 (unclamped; + ebos_flow_voxel_clamp_f32 with has_clamp)
- *     -> memset + ebos_iwe_voxel_tiled_f32 (ebos_iwe_voxel_f32 when (tile, halo) is no ebos_tiled_config)
- *     -> ebos_image_variance_f32 + ebos_image_variance_affine_f32 (upstream = -w_variance) [-> ebos_flow_regularisers_f32]
- *     -> ebos_iwe_voxel_owner_bwd_f32 (owner_bwd = 1) or memset + ebos_iwe_voxel_bwd_f32 sorted (owner_bwd = 0)
- *     -> ebos_flow_voxel_advect_adjoint_f32 [-> d_dense += d_reg] -> ebos_upsample_patch_flow_bwd_adam_f32
+ * n_iter iterations enqueued back to back on `stream` by one C call: no host synchronisation, no allocation.  ONE window is a batch
+ * of one: ebos_cmax_voxel_solve_f32 / _gradient_f32 copy the problem into an ebos_cmax_voxel_batch_problem (below) with B = 1,
+ * n[0] = n and every other field under its own name, and run ebos_cmax_voxel_solve_batch_f32's code: its checks (a refusal names
+ * ebos_cmax_voxel_solve / ebos_cmax_voxel_gradient), its sequence of stages, its results.  A NULL problem is refused first.
  * All buffers are the caller's:
  *   plan:     xs / ys / dts / bins in key order, key_offsets, n, H, W, tile, halo (a built halo; <= 0: the general forward kernel),
  *             pad, omit_boundary, splits (>= 1, as ebos_iwe_voxel_tiled_f32)
@@ -1685,7 +1683,7 @@ typedef struct ebos_cmax_voxel_problem {
   int H, W, tile_h, tile_w, halo, pad_h, pad_w, omit_boundary, splits;
   int T, scheme, t0_index, wrap_last, route, has_clamp;
   double clamp;
-  int owner_bwd;               /* 1: ebos_iwe_voxel_owner_bwd_f32; 0: memset + ebos_iwe_voxel_bwd_f32 (global float atomics) */
+  int owner_bwd;               /* 1: the pixel-owner backward; 0: memset + ebos_iwe_voxel_bwd_f32 (global float atomics) */
   int gh, gw, patch_h, patch_w, slide_h, slide_w;
   float w_variance, w_flow_norm, w_image_gradient;
   double lr, beta1, beta2, eps;
@@ -1755,9 +1753,14 @@ int ebos_upsample_patch_flow_bwd_adam_batch_f32(const float* d_dense, int B, int
                                                 const float* contrast, float contrast_scale, const double* reg_partials, int n_reg,
                                                 float* losses, int losses_cap, const float* grad_mask, ebos_stream_t stream);
 
-/* ebos_cmax_voxel_solve_batch_f32: n_iter iterations of ebos_cmax_voxel_solve_f32's sequence with every stage called ONCE for all B
- * windows (one memset clears every IWE, one pass adds the regularisers' gradients); no host synchronisation, no allocation.  With
- * owner_bwd = 0 the atomic backward ebos_iwe_voxel_bwd_f32 runs window by window behind one memset of d_voxel.
+/* ebos_cmax_voxel_solve_batch_f32: the loop's one implementation.  n_iter iterations, every stage called ONCE for all B windows
+ * (one memset clears every IWE, one pass adds the regularisers' gradients); no host synchronisation, no allocation.  One iteration:
+ *     ebos_upsample_patch_flow_batch_f32 -> ebos_flow_voxel_advect_f32 (unclamped; + ebos_flow_voxel_clamp_f32 with has_clamp)
+ *     -> memset + ebos_iwe_voxel_tiled_batch_f32 (ebos_iwe_voxel_f32 window by window when (tile, halo) is no ebos_tiled_config)
+ *     -> ebos_image_variance_f32 + ebos_image_variance_affine_f32 (upstream = -w_variance) [-> ebos_flow_regularisers_batch_f32]
+ *     -> ebos_iwe_voxel_owner_bwd_batch_f32 (owner_bwd = 1) or one memset of d_voxel + ebos_iwe_voxel_bwd_f32 sorted, window by
+ *        window (owner_bwd = 0)
+ *     -> ebos_flow_voxel_advect_adjoint_f32 [-> d_dense += d_reg] -> ebos_upsample_patch_flow_bwd_adam_batch_f32
  * The fields are those of ebos_cmax_voxel_problem with the window dimension in front:
  *   plan:     B in [1, 64]; the stacked plan above, n[b] for b < B the windows' event counts
  *   grid:     theta / d_theta / exp_avg / exp_avg_sq [B, 2, gh, gw], theta_mask [B, gh, gw] (nullable), step [1], steps_done

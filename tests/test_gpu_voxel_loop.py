@@ -1,6 +1,6 @@
 """GPU tests of the native time-aware loop: the pixel-owner backward into the flow voxel (``ebos_iwe_voxel_owner_bwd_f32`` through
-``EventPlan.variance_voxel_value_and_grad``), the loop of one C call (``TimeAwarePatchLoop``: ``ebos_cmax_voxel_solve_f32``) and the
-solver's ``time_aware.native`` switch.  Yardsticks and windows: tests/_voxel_loop_cases.py (CPU, float64, torch autograd).  Bars are the
+``EventPlan.variance_voxel_value_and_grad``), the loop of one C call (``TimeAwarePatchLoop``: the batch loop with one window; the C
+entry points of one window, ``ebos_cmax_voxel_solve_f32`` / ``_gradient_f32``, by hand) and the solver's ``time_aware.native`` switch.  Yardsticks and windows: tests/_voxel_loop_cases.py (CPU, float64, torch autograd).  Bars are the
 project's: values relative < 1e-5, gradients relative L2 < 1e-3."""
 import os
 import sys
@@ -222,6 +222,81 @@ def test_loop_five_iterations_follow_the_float64_adam_loop(ebos):
         print(f"native loop (owner_bwd={owner}), deviation per iteration:", dev.tolist())
         assert want[-1] < want[0] and got[-1] < got[0]                               # the loss falls
         assert (dev <= NATIVE_LOOP_FACTOR * max(AUTOGRAD_LOOP_DEVIATION)).all(), (dev, AUTOGRAD_LOOP_DEVIATION)
+
+
+def single_problem(loop, **over):
+    """``ebos_cmax_voxel_problem`` of a one-window loop's buffers: the batch problem's fields copied by name, ``n`` from ``n[0]``."""
+    from event_based_bos_amd import _hip
+
+    batch, q = loop.problem(), _hip.CmaxVoxelProblem()
+    assert batch.B == 1
+    for name, _ in q._fields_:
+        setattr(q, name, batch.n[0] if name == "n" else getattr(batch, name))
+    for name, value in over.items():
+        setattr(q, name, value)
+    return q
+
+
+# both regularisers and a clamp with the owner backward; neither with the atomic backward; halo 24, which is no built configuration:
+# the tiled batch entry point finds no kernel for it and runs the general forward kernel
+@pytest.mark.parametrize("reg,clamp,owner,halo", [(0.1, 2.0, 1, None), (0.0, None, 0, None), (0.0, None, 1, 24)])
+def test_single_c_entry_points_are_float64_autograd(ebos, reg, clamp, owner, halo):
+    """``ebos_cmax_voxel_gradient_f32`` and one iteration of ``ebos_cmax_voxel_solve_f32``, which Python no longer calls."""
+    import ctypes
+
+    from event_based_bos_amd import _hip
+
+    lib = _hip.require_gpu()
+    if halo is not None:
+        assert (C.TILE[0], C.TILE[1], halo) not in set(_hip.tiled_configs())
+    ev = C.loop_events("upwind", clamp)
+    loss_ref, grad_ref = C.ref_value_and_grad(ev, "upwind", clamp, reg, reg)
+    loop = make_loop(ebos, ev, "upwind", clamp, reg, reg, owner_bwd=bool(owner))
+    start = loop.theta.clone()
+    q = single_problem(loop, **({} if halo is None else {"halo": halo}))
+    assert q.n == len(ev) and q.owner_bwd == owner and q.has_clamp == int(clamp is not None)
+    loop.d_theta.fill_(float("nan"))
+    _hip.check(lib.ebos_cmax_voxel_gradient_f32(ctypes.byref(q), _hip.stream_ptr()), "ebos_cmax_voxel_gradient")
+    value = -loop.variance[0].item() + (loop.reg_partials.sum().item() if reg else 0.0)
+    print(f"gradient entry, reg={reg} clamp={clamp} owner_bwd={owner} halo={halo}: loss rel {abs(value - loss_ref) / abs(loss_ref):.3e}, "
+          f"d_theta rel L2 {rel(loop.d_theta, grad_ref):.3e}")
+    assert abs(value - loss_ref) < 1e-5 * abs(loss_ref) and rel(loop.d_theta, grad_ref) < 1e-3
+    assert torch.equal(loop.theta, start) and int(loop.step.item()) == 0               # no step
+    loop.d_theta.fill_(float("nan"))
+    _hip.check(lib.ebos_cmax_voxel_solve_f32(ctypes.byref(q), 1, _hip.stream_ptr()), "ebos_cmax_voxel_solve")
+    loss = loop.losses[0].item()
+    print(f"solve entry, reg={reg} clamp={clamp} owner_bwd={owner} halo={halo}: loss rel {abs(loss - loss_ref) / abs(loss_ref):.3e}, "
+          f"d_theta rel L2 {rel(loop.d_theta, grad_ref):.3e}")
+    assert abs(loss - loss_ref) < 1e-5 * abs(loss_ref) and rel(loop.d_theta, grad_ref) < 1e-3
+    assert int(loop.step.item()) == 1 and not torch.equal(loop.theta, start)          # Adam moved the grid
+
+
+def test_one_window_face_of_the_batch_loop(ebos):
+    """``TimeAwarePatchLoop`` is a batch loop of one window without the window dimension; its state tensors are views of the buffers
+    the kernels read, so the reset of tools/bench_voxel_loop.py starts the same solve again."""
+    ev = C.loop_events("upwind")
+    want = np.array(C.ref_adam_losses(ev, "upwind", 5))[:3]
+    bound = NATIVE_LOOP_FACTOR * max(AUTOGRAD_LOOP_DEVIATION)
+    loop = make_loop(ebos, ev, "upwind", owner_bwd=True)
+    gh, gw = C.theta_start().shape[1:]
+    assert loop.theta.shape == loop.d_theta.shape == loop.exp_avg.shape == loop.exp_avg_sq.shape == (2, gh, gw)
+    assert loop.losses.shape == (8,) and loop.batch.B == 1 and loop.theta.data_ptr() == loop.batch.theta.data_ptr()
+    assert loop.last_run_mode == "native" and loop.graphed is False and loop.owner_bwd is True and loop.t == 0
+    start = loop.theta.clone()
+    first = loop.run(3).clone()
+    assert first.shape == (3,) and loop.t == 3 and int(loop.step.item()) == 3 and not torch.equal(loop.theta, start)
+    loop.theta.copy_(start)
+    loop.exp_avg.zero_()
+    loop.exp_avg_sq.zero_()
+    loop.t = 0
+    second = loop.run(3)
+    assert second.shape == (3,) and loop.t == 3 and loop.batch.t == 3
+    print("two runs of three iterations from one start:", "bit-identical" if torch.equal(first, second) else
+          f"relative difference {((first - second).abs() / second.abs()).tolist()}")
+    for name, got in (("first", first), ("second", second)):
+        dev = np.abs(got.cpu().numpy().astype(np.float64) - want) / np.abs(want)
+        print(f"{name} run, deviation per iteration:", dev.tolist())
+        assert (dev <= bound).all(), (name, dev, bound)
 
 
 # ---------------------------------------------------------------------------------------------- the solver

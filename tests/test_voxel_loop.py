@@ -100,6 +100,45 @@ def test_solve_validates_before_any_launch(lib):
     assert lib.ebos_cmax_voxel_gradient_f32(None, None) == -1 and b"NULL problem" in lib.ebos_last_error()
 
 
+def test_single_entries_are_adapters_of_the_batch_loop(lib):
+    """``ebos_cmax_voxel_solve_f32`` / ``_gradient_f32`` run the batch loop's checks on a batch of one: a refusal names the entry
+    point the caller used, the scratch asked for is the one of ONE window, and ``n`` is checked as the window's count."""
+    def solve(q):
+        return lib.ebos_cmax_voxel_solve_f32(ctypes.byref(q), 1, None), lib.ebos_last_error()
+
+    def gradient(q):
+        return lib.ebos_cmax_voxel_gradient_f32(ctypes.byref(q), None), lib.ebos_last_error()
+
+    for call, who in ((solve, b"ebos_cmax_voxel_solve:"), (gradient, b"ebos_cmax_voxel_gradient:")):
+        q = _problem()
+        q.T = 0
+        rc, msg = call(q)
+        assert rc == -1 and msg.startswith(who) and b"_batch" not in msg and b"outside [1, 255]" in msg, (rc, msg)
+        q = _problem()
+        q.cost_scratch_bytes = lib.ebos_cost_scratch_bytes(1)              # exactly enough for one window: past this check
+        q.theta = None
+        rc, msg = call(q)
+        assert rc == -1 and msg.startswith(who) and b"NULL theta" in msg, (rc, msg)
+        q = _problem()
+        q.cost_scratch_bytes = lib.ebos_cost_scratch_bytes(1) - 1
+        rc, msg = call(q)
+        assert rc == -4 and msg.startswith(who) and b"_batch" not in msg and b"cost_scratch too small for 1 windows" in msg, (rc, msg)
+        q = _problem()
+        q.n = -1
+        rc, msg = call(q)
+        assert rc == -1 and msg.startswith(who) and b"n = -1" in msg, (rc, msg)
+        q = _problem()
+        q.n = 2 ** 31
+        rc, msg = call(q)
+        assert rc == -1 and msg.startswith(who) and b"INT32_MAX" in msg, (rc, msg)
+    assert lib.ebos_cmax_voxel_solve_f32(None, 1, None) == -1 and lib.ebos_last_error() == b"ebos_cmax_voxel_solve: NULL problem"
+    assert lib.ebos_cmax_voxel_gradient_f32(None, None) == -1 and lib.ebos_last_error() == b"ebos_cmax_voxel_gradient: NULL problem"
+    # exactly the scratch of one window passes every check: with no iterations asked for, nothing is launched
+    q = _problem()
+    q.cost_scratch_bytes = lib.ebos_cost_scratch_bytes(1)
+    assert lib.ebos_cmax_voxel_solve_f32(ctypes.byref(q), 0, None) == 0
+
+
 def test_owner_backward_validates_before_any_launch(lib):
     p = 0x1000
     args = dict(xs=p, ys=p, dts=p, weight=None, bins=p, key_offsets=p, n=10, voxel=p, T=5, H=37, W=70, tile_h=32, tile_w=32, pad_h=0,

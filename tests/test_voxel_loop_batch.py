@@ -205,6 +205,30 @@ def test_stack_time_aware_stacks_and_refuses():
         EventPlan.stack_time_aware([big, a])
 
 
+def test_stack_of_one_plan_shares_the_plans_storage():
+    """One window is a batch of one without a copy: the stack's streams are views of the plan's, its offsets the plan's own with a
+    leading dimension (the base is 0).  Two plans still concatenate."""
+    from event_based_bos_amd.event_plan import EventPlan
+
+    a = _cpu_plan(12)
+    st = EventPlan.stack_time_aware([a])
+    assert len(st) == 1 and st.ns == [a.n] == [12] and st.n == 12 and list(st.ns_array()) == [12]
+    for k in ("x", "y", "dt", "bins"):
+        assert getattr(st, k).data_ptr() == getattr(a, k).data_ptr() and getattr(st, k).shape == (12,), k
+    assert st.key_offsets.data_ptr() == a.key_offsets.data_ptr() and st.key_offsets.dtype == torch.int32
+    assert st.key_offsets.shape == (1, a.key_offsets.numel()) and st.key_offsets.is_contiguous() and torch.equal(st.key_offsets[0], a.key_offsets)
+    # a plan whose streams are longer than n (a build pads them): the view stops at n
+    padded = _cpu_plan(12)
+    padded.n = 9
+    st = EventPlan.stack_time_aware([padded])
+    assert st.x.shape == (9,) and st.bins.shape == (9,) and st.x.data_ptr() == padded.x.data_ptr() and st.ns == [9]
+    c = _cpu_plan(7)
+    two = EventPlan.stack_time_aware([a, c])
+    assert two.x.data_ptr() != a.x.data_ptr() and torch.equal(two.x, torch.cat([a.x, c.x])) and torch.equal(two.bins, torch.cat([a.bins, c.bins]))
+    assert two.key_offsets.shape == (2, a.key_offsets.numel()) and torch.equal(two.key_offsets[0], a.key_offsets)
+    assert torch.equal(two.key_offsets[1] - 12, c.key_offsets)
+
+
 def _config(**over):
     cfg = {"motion_model": "dense-flow", "warp_direction": "first", "cost": "image_variance", "outer_padding": 0,
            "patch": {"size": [12, 14], "sliding_window": [12, 14]}, "optimizer": {"method": "Adam", "n_iter": 5, "parameters": {"lr": 0.05}},
