@@ -203,6 +203,7 @@ SIGNATURES = {
     "ebos_iwe_slab_partials": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ebos_cmax_adam_step_f32": (_I, [_P, _P, _P, _P, _I, _D, _D, _D, _D, _P, _P, _F, _P, _I, _P, _I, _P]),
     "ebos_cmax_patch_solve_f32": (_I, [_P, _I, _P]),
+    "ebos_cmax_patch_gradient_f32": (_I, [_P, _P]),
     "ebos_cmax_patch_solve_many_f32": (_I, [_P, _P, _I, _I]),
     "ebos_cmax_resident_mailbox_bytes": (_Z, [_I, _I, _I, _I]),
     "ebos_cmax_resident_supported": (_I, [_P]),

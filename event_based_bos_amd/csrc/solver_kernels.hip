@@ -240,79 +240,81 @@ int ebos_cmax_adam_step_f32(float* theta, const float* grad, float* exp_avg, flo
   return EBOS_OK;
 }
 
-static int cmax_check_problem(const ebos_cmax_patch_problem* q) {
+static int cmax_check_problem(const char* who, const ebos_cmax_patch_problem* q) {
   using namespace ebos;
-  EBOS_REQUIRE(q != nullptr && q->steps_done >= 0, "ebos_cmax_patch_solve: NULL problem or negative steps_done");
-  EBOS_REQUIRE((q->cfx == nullptr) == (q->cfy == nullptr), "ebos_cmax_patch_solve: cfx / cfy come together");
+  EBOS_REQUIRE(q != nullptr && q->steps_done >= 0, "%s: NULL problem or negative steps_done", who);
+  EBOS_REQUIRE((q->cfx == nullptr) == (q->cfy == nullptr), "%s: cfx / cfy come together", who);
   EBOS_REQUIRE(q->theta && q->d_theta && q->exp_avg && q->exp_avg_sq && q->step && q->iwe && q->variance && q->moments &&
                    q->upstream && q->workspace && q->reg_partials,
-               "ebos_cmax_patch_solve: NULL buffer");
+               "%s: NULL buffer", who);
   const bool has_reg_ = q->w_flow_norm != 0.0f || q->w_image_gradient != 0.0f;
-  if (q->grad_partials != nullptr) {  // the event kernels sample the patch grid: dense only feeds the regulariser pass
-    EBOS_REQUIRE(q->grp_offsets && q->cpix && q->cdt, "ebos_cmax_patch_solve: grad_partials (grid-sampling kernels) needs the compact plan");
+  if (q->grad_partials != nullptr) {  // the event kernels sample the patch grid: dense is not used
+    EBOS_REQUIRE(q->grp_offsets && q->cpix && q->cdt, "%s: grad_partials (grid-sampling kernels) needs the compact plan", who);
     EBOS_REQUIRE(ebos_patch_fused_supported(q->tile_h, q->tile_w, q->halo, q->slide_h, q->slide_w),
-                 "ebos_cmax_patch_solve: grad_partials given but tile %dx%d halo %d / sliding window %dx%d is outside "
-                 "ebos_patch_fused_supported", q->tile_h, q->tile_w, q->halo, q->slide_h, q->slide_w);
+                 "%s: grad_partials given but tile %dx%d halo %d / sliding window %dx%d is outside "
+                 "ebos_patch_fused_supported", who, q->tile_h, q->tile_w, q->halo, q->slide_h, q->slide_w);
   } else {
-    EBOS_REQUIRE(q->dense && q->d_dense && q->upsample_scratch, "ebos_cmax_patch_solve: NULL dense / d_dense / upsample_scratch");
+    EBOS_REQUIRE(q->dense && q->d_dense && q->upsample_scratch, "%s: NULL dense / d_dense / upsample_scratch", who);
     EBOS_REQUIRE(q->cfx == nullptr || (q->xs && q->ys && q->dts),
-                 "ebos_cmax_patch_solve: a window of fractional source coordinates on the dense route needs xs / ys / dts");
+                 "%s: a window of fractional source coordinates on the dense route needs xs / ys / dts", who);
   }
   // (grid sampling: the backward kernel evaluates the regularisers from the tile's flow, no d_reg image)
-  EBOS_REQUIRE(!has_reg_ || q->d_reg || q->grad_partials != nullptr,
-               "ebos_cmax_patch_solve: regulariser weights given but d_reg is NULL");
+  EBOS_REQUIRE(!has_reg_ || q->d_reg || q->grad_partials != nullptr, "%s: regulariser weights given but d_reg is NULL", who);
   EBOS_REQUIRE((q->w_variance != 0.0f) != (q->w_gradient_magnitude != 0.0f),
-               "ebos_cmax_patch_solve: exactly one of w_variance / w_gradient_magnitude must be non-zero");
+               "%s: exactly one of w_variance / w_gradient_magnitude must be non-zero", who);
   EBOS_REQUIRE(q->w_gradient_magnitude == 0.0f || (q->d_iwe && q->cost_scratch),
-               "ebos_cmax_patch_solve: the gradient-magnitude contrast needs d_iwe and cost_scratch");
+               "%s: the gradient-magnitude contrast needs d_iwe and cost_scratch", who);
   if (q->blur_k0 != 0.0f) {  // the variance of the 3-tap blurred image (iwe.blur_sigma > 0)
     EBOS_REQUIRE(q->blur_k0 > 0.0f && q->blur_k1 > 0.0f && q->blur_image && q->cost_scratch,
-                 "ebos_cmax_patch_solve: the blurred contrast needs positive taps, blur_image and cost_scratch");
+                 "%s: the blurred contrast needs positive taps, blur_image and cost_scratch", who);
     if (q->w_gradient_magnitude != 0.0f) {
-      set_error("ebos_cmax_patch_solve: the blurred image goes with the variance contrast only");
+      set_error("%s: the blurred image goes with the variance contrast only", who);
       return EBOS_ERR_UNSUPPORTED;
     }
     const size_t need = (size_t)16 * (size_t)ebos_blur3_variance_partials(q->H + 2 * q->pad_h, q->W + 2 * q->pad_w);
     if (q->cost_scratch_bytes < need) {
-      set_error("ebos_cmax_patch_solve: cost_scratch too small for the blur's partials (%zu < %zu)", q->cost_scratch_bytes, need);
+      set_error("%s: cost_scratch too small for the blur's partials (%zu < %zu)", who, q->cost_scratch_bytes, need);
       return EBOS_ERR_SCRATCH;
     }
   }
   return EBOS_OK;
 }
 
-static int cmax_enqueue_iteration(const ebos_cmax_patch_problem* q, int t, ebos_stream_t stream) {
+static bool cmax_has_reg(const ebos_cmax_patch_problem* q) { return q->w_flow_norm != 0.0f || q->w_image_gradient != 0.0f; }
+
+// theta -> ... -> the backward event kernel: partial cell gradients per tile (grid) or d_dense; variance / moments and reg_partials hold
+// the value's parts.  grid: the event kernels evaluate the grid -> dense map per tile themselves, and the backward kernel the flow
+// regularisers too, from the tile's own flow (2 px apron in LDS); otherwise the regularisers are a launch on the dense field.
+static int cmax_forward_backward(const ebos_cmax_patch_problem* q, ebos_stream_t stream) {
   using namespace ebos;
-  const bool grid = q->grad_partials != nullptr;  // the event kernels evaluate the grid -> dense map per tile themselves
-  // with grid sampling the backward kernel evaluates the flow regularisers from the tile's own flow (2 px apron in LDS)
-  const bool fuse_norm = grid && (q->w_image_gradient != 0.0f || q->w_flow_norm != 0.0f);
-  const bool has_reg = (q->w_flow_norm != 0.0f || q->w_image_gradient != 0.0f) && !fuse_norm;  // regulariser LAUNCH needed
-  int rc = EBOS_OK;
-  if (!grid || has_reg) {  // (the regulariser pass reads the dense field)
-    rc = ebos_upsample_patch_flow_f32(q->theta, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->dense,
-                                      stream);
-    if (rc) return rc;
-  }
+  const bool grid = q->grad_partials != nullptr, reg = cmax_has_reg(q);
+  const bool has_reg = reg && !grid;  // regulariser LAUNCH needed
   const bool use_gm = q->w_gradient_magnitude != 0.0f;
   const bool blur = q->blur_k0 != 0.0f;  // (variance contrast: cmax_check_problem)
+  const int h = q->H + 2 * q->pad_h, w = q->W + 2 * q->pad_w, lo = q->omit_boundary ? 1 : 0;
+  const int32_t* part_table = q->splits == 0 ? q->part_table : nullptr;
   // dense route: compact arrays that carry fractions (cfx / cfy) are the grid-sampling and the resident kernels' -- the dense-flow
   // kernels read such a window from xs / ys / dts
   const bool frac = q->cfx != nullptr;
   const int32_t* d_grp = frac ? nullptr : q->grp_offsets;
   const uint16_t* d_cpix = frac ? nullptr : q->cpix;
   const float* d_cdt = frac ? nullptr : q->cdt;
-  const int h = q->H + 2 * q->pad_h, w = q->W + 2 * q->pad_w;
-  const float contrast_weight = use_gm ? q->w_gradient_magnitude : q->w_variance;
-  if (grid)  // (cfx / cfy: the compact slots carry the fractions of undistorted events; NULL: integer source pixels)
+  int rc = EBOS_OK;
+  // the slab pass's variance: none (the Sobel or the blur pass has the contrast), partials only (2: the regulariser or the backward
+  // kernel reduces them) or a finalize launch (1)
+  const int want_var = (use_gm || blur) ? 0 : ((grid || has_reg) ? 2 : 1);
+  if (grid) {  // (cfx / cfy: the compact slots carry the fractions of undistorted events; NULL: integer source pixels)
     rc = ebos_iwe_patch_slab_frac_f32(q->grp_offsets, q->cpix, q->cdt, q->cfx, q->cfy, q->key_offsets, q->n, q->theta, q->gh, q->gw, q->patch_h,
                                       q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->tile_h, q->tile_w, q->halo, q->splits, q->pad_h,
-                                      q->pad_w, q->workspace, q->workspace_bytes, q->iwe, (use_gm || blur) ? 0 : 2, q->omit_boundary,
-                                      q->variance, q->moments, q->part_table, stream);  // (variance: partials only; the regulariser or backward kernel reduces them)
-  else
+                                      q->pad_w, q->workspace, q->workspace_bytes, q->iwe, want_var, q->omit_boundary, q->variance,
+                                      q->moments, q->part_table, stream);
+  } else {
+    rc = ebos_upsample_patch_flow_f32(q->theta, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->dense, stream);
+    if (rc) return rc;
     rc = ebos_iwe_dense_slab_f32(q->xs, q->ys, q->dts, nullptr, d_grp, d_cpix, d_cdt, q->key_offsets, q->n, q->dense,
                                  q->H, q->W, q->tile_h, q->tile_w, q->halo, q->splits, q->pad_h, q->pad_w, q->workspace,
-                                 q->workspace_bytes, q->iwe, (use_gm || blur) ? 0 : (has_reg ? 2 : 1), q->omit_boundary, q->variance,
-                                 q->moments, q->part_table, stream);
+                                 q->workspace_bytes, q->iwe, want_var, q->omit_boundary, q->variance, q->moments, q->part_table, stream);
+  }
   if (rc) return rc;
   if (use_gm) {  // contrast = mean squared Sobel gradient of the IWE; its gradient image feeds the backward event kernel
     // (one Sobel pass: value partials + gradient image; cost_scratch holds the partials)
@@ -320,6 +322,7 @@ static int cmax_enqueue_iteration(const ebos_cmax_patch_problem* q, int t, ebos_
                                            reinterpret_cast<double*>(q->cost_scratch), (int64_t)(q->cost_scratch_bytes / sizeof(double)), stream);
     if (rc) return rc;
   }
+  // the (sum, sum of squares) partials a later kernel reduces to the variance: the slab pass's, or the blur pass's below
   size_t off = 0;
   int64_t n_parts = 0, n_px = 0;
   if (has_reg || (grid && !use_gm)) {
@@ -327,88 +330,71 @@ static int cmax_enqueue_iteration(const ebos_cmax_patch_problem* q, int t, ebos_
                                 &n_parts, &n_px);
     if (rc) return rc;
   }
-  const double* var_partials = reinterpret_cast<const double*>(static_cast<const char*>(q->workspace) + off);
+  const double* partials = (use_gm || blur) ? nullptr : reinterpret_cast<const double*>(static_cast<const char*>(q->workspace) + off);
   if (has_reg) {  // the regulariser pass also reduces the variance moments the combine pass left (no finalize launch)
-    rc = ebos_flow_regularisers_f32(q->dense, q->H, q->W, q->w_flow_norm, q->w_image_gradient, q->d_reg, q->reg_partials,
-                                    (use_gm || blur) ? nullptr : var_partials, n_parts, n_px, q->variance, q->moments, stream);
+    rc = ebos_flow_regularisers_f32(q->dense, q->H, q->W, q->w_flow_norm, q->w_image_gradient, q->d_reg, q->reg_partials, partials,
+                                    n_parts, n_px, q->variance, q->moments, stream);
     if (rc) return rc;
   }
-  if (grid && blur) {
+  const float* image = blur ? q->blur_image : (use_gm ? q->d_iwe : q->iwe);  // what the backward kernel gathers its upstream from
+  if (blur) {
     // the blurred contrast: one pass over the image -> (sum, sum of squares) partials of the blurred pixels + z = B^T (m . B x);
     // the backward kernel reduces the partials and forms its upstream a z + c wgt itself (blur3.h)
-    const int64_t n_blur = ebos_blur3_variance_partials(h, w);
-    const int lo = q->omit_boundary ? 1 : 0;
-    const int64_t n_valid = (int64_t)(h - 2 * lo > 0 ? h - 2 * lo : 0) * (w - 2 * lo > 0 ? w - 2 * lo : 0);
+    partials = reinterpret_cast<const double*>(q->cost_scratch);
+    n_parts = ebos_blur3_variance_partials(h, w);
+    n_px = (int64_t)(h - 2 * lo > 0 ? h - 2 * lo : 0) * (w - 2 * lo > 0 ? w - 2 * lo : 0);
     rc = ebos_blur3_variance_adjoint_f32(q->iwe, h, w, q->omit_boundary, q->blur_k0, q->blur_k1, q->blur_image,
-                                         reinterpret_cast<double*>(q->cost_scratch), n_blur, stream);
+                                         reinterpret_cast<double*>(q->cost_scratch), n_parts, stream);
     if (rc) return rc;
-    rc = ebos_iwe_patch_tiled_bwd_frac_f32(q->grp_offsets, q->cpix, q->cdt, q->cfx, q->cfy, q->key_offsets, q->n, q->theta, q->gh, q->gw,
-                                           q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->tile_h, q->tile_w, q->halo,
-                                           q->pad_h, q->pad_w, q->blur_image, lo, nullptr, q->upstream, nullptr, q->grad_partials,
-                                           q->grad_partials_bytes, q->splits == 0 ? q->part_table : nullptr,
-                                           fuse_norm ? q->w_flow_norm : 0.0f, fuse_norm ? q->w_image_gradient : 0.0f, q->reg_partials,
-                                           reinterpret_cast<const double*>(q->cost_scratch), n_blur, n_valid, q->variance, q->moments,
-                                           q->blur_k0, q->blur_k1, stream);
-    if (rc) return rc;
-    const int n_items = (int)(ebos_patch_grad_partials_bytes(q->H, q->W, q->tile_h, q->tile_w, q->splits == 0) / 2048);
-    return ebos_patch_grad_combine_adam_f32(q->grad_partials, q->splits == 0 ? q->part_table : nullptr, q->tile_h, q->tile_w, q->gh,
-                                            q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->d_theta, q->theta,
-                                            q->exp_avg, q->exp_avg_sq, q->lr, q->beta1, q->beta2, q->eps, t, q->step, q->variance,
-                                            -contrast_weight, q->reg_partials, fuse_norm ? n_items : 0, q->losses, q->losses_cap,
-                                            q->theta_mask, stream);
   }
-  if (grid) {
-    rc = ebos_iwe_patch_tiled_bwd_frac_f32(q->grp_offsets, q->cpix, q->cdt, q->cfx, q->cfy, q->key_offsets, q->n, q->theta, q->gh, q->gw,
-                                           q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->tile_h, q->tile_w, q->halo,
-                                           q->pad_h, q->pad_w, use_gm ? q->d_iwe : q->iwe, use_gm ? 0 : (q->omit_boundary ? 1 : 0),
-                                           (use_gm || !has_reg) ? nullptr : q->moments, use_gm ? nullptr : q->upstream,
-                                           has_reg ? q->d_reg : nullptr, q->grad_partials, q->grad_partials_bytes,
-                                           q->splits == 0 ? q->part_table : nullptr, fuse_norm ? q->w_flow_norm : 0.0f,
-                                           fuse_norm ? q->w_image_gradient : 0.0f, q->reg_partials,
-                                           (use_gm || has_reg) ? nullptr : var_partials, n_parts, n_px, q->variance, q->moments, 0.0f, 0.0f,
-                                           stream);
-    if (rc) return rc;
-    const int n_items = (int)(ebos_patch_grad_partials_bytes(q->H, q->W, q->tile_h, q->tile_w, q->splits == 0) / 2048);
-    // partial cell gradients -> d_theta, the Adam step of every grid element and the loss of the iteration
+  if (grid)  // -> partial cell gradients per tile; reduces the partials, evaluates the flow regularisers (one value partial per work item)
+    return ebos_iwe_patch_tiled_bwd_frac_f32(q->grp_offsets, q->cpix, q->cdt, q->cfx, q->cfy, q->key_offsets, q->n, q->theta, q->gh, q->gw,
+                                             q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->tile_h, q->tile_w, q->halo,
+                                             q->pad_h, q->pad_w, image, use_gm ? 0 : lo, nullptr, use_gm ? nullptr : q->upstream, nullptr,
+                                             q->grad_partials, q->grad_partials_bytes, part_table, reg ? q->w_flow_norm : 0.0f,
+                                             reg ? q->w_image_gradient : 0.0f, q->reg_partials, partials, n_parts, n_px, q->variance,
+                                             q->moments, blur ? q->blur_k0 : 0.0f, blur ? q->blur_k1 : 0.0f, stream);
+  if (blur)  // dense route: the backward kernel reduces the blur's partials, reports the variance and folds a z + c wgt
+    return ebos_iwe_dense_tiled_bwd_blur_f32(q->xs, q->ys, q->dts, d_grp, d_cpix, d_cdt, q->key_offsets, q->n, q->dense, q->H, q->W,
+                                             q->tile_h, q->tile_w, q->halo, q->pad_h, q->pad_w, image, lo, q->upstream,
+                                             has_reg ? q->d_reg : nullptr, q->d_dense, q->workspace, q->workspace_bytes, part_table,
+                                             partials, n_parts, n_px, q->variance, q->moments, q->blur_k0, q->blur_k1, stream);
+  return ebos_iwe_dense_tiled_bwd_f32(q->xs, q->ys, q->dts, nullptr, d_grp, d_cpix, d_cdt, q->key_offsets, q->n, q->dense, q->H, q->W,
+                                      q->tile_h, q->tile_w, q->halo, q->pad_h, q->pad_w, image, nullptr, use_gm ? 0 : lo, q->d_dense, nullptr,
+                                      use_gm ? nullptr : q->moments, use_gm ? nullptr : q->upstream, has_reg ? q->d_reg : nullptr,
+                                      q->workspace, q->workspace_bytes, part_table, stream);
+}
+
+// forward_backward, then the finishing call: partial cell gradients (grid) or d_dense -> d_theta.  t >= 1: with the Adam step t of every
+// grid element where its gradient appears and the loss of the iteration; t == 0: the plain adjoint -- no optimiser state, no loss, no mask.
+static int cmax_iteration(const ebos_cmax_patch_problem* q, int t, ebos_stream_t stream) {
+  if (int rc = cmax_forward_backward(q, stream)) return rc;
+  const bool grid = q->grad_partials != nullptr, step = t > 0;
+  const float scale = -(q->w_gradient_magnitude != 0.0f ? q->w_gradient_magnitude : q->w_variance);  // loss = -w * contrast
+  int n_reg = 0;  // value partials in reg_partials: one per work item of the backward kernel, or the regulariser launch's
+  if (cmax_has_reg(q))
+    n_reg = grid ? (int)(ebos_patch_grad_partials_bytes(q->H, q->W, q->tile_h, q->tile_w, q->splits == 0) / 2048) : ebos::kRegGrid;
+  if (grid)  // (theta == NULL: the plain-gradient form)
     return ebos_patch_grad_combine_adam_f32(q->grad_partials, q->splits == 0 ? q->part_table : nullptr, q->tile_h, q->tile_w, q->gh,
-                                            q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->d_theta, q->theta,
-                                            q->exp_avg, q->exp_avg_sq, q->lr, q->beta1, q->beta2, q->eps, t, q->step, q->variance,
-                                            -contrast_weight, q->reg_partials, fuse_norm ? n_items : (has_reg ? ebos::kRegGrid : 0),
-                                            q->losses, q->losses_cap, q->theta_mask, stream);
-  }
-  if (blur) {  // dense route: the same image pass; the backward kernel reduces its partials, reports the variance and folds a z + c wgt
-    const int64_t n_blur = ebos_blur3_variance_partials(h, w);
-    const int lo = q->omit_boundary ? 1 : 0;
-    const int64_t n_valid = (int64_t)(h - 2 * lo > 0 ? h - 2 * lo : 0) * (w - 2 * lo > 0 ? w - 2 * lo : 0);
-    rc = ebos_blur3_variance_adjoint_f32(q->iwe, h, w, q->omit_boundary, q->blur_k0, q->blur_k1, q->blur_image,
-                                         reinterpret_cast<double*>(q->cost_scratch), n_blur, stream);
-    if (rc) return rc;
-    rc = ebos_iwe_dense_tiled_bwd_blur_f32(q->xs, q->ys, q->dts, d_grp, d_cpix, d_cdt, q->key_offsets, q->n, q->dense, q->H, q->W,
-                                           q->tile_h, q->tile_w, q->halo, q->pad_h, q->pad_w, q->blur_image, lo, q->upstream,
-                                           has_reg ? q->d_reg : nullptr, q->d_dense, q->workspace, q->workspace_bytes,
-                                           q->splits == 0 ? q->part_table : nullptr, reinterpret_cast<const double*>(q->cost_scratch), n_blur,
-                                           n_valid, q->variance, q->moments, q->blur_k0, q->blur_k1, stream);
-  } else
-  rc = ebos_iwe_dense_tiled_bwd_f32(q->xs, q->ys, q->dts, nullptr, d_grp, d_cpix, d_cdt, q->key_offsets, q->n,
-                                    q->dense, q->H, q->W, q->tile_h, q->tile_w, q->halo, q->pad_h, q->pad_w,
-                                    use_gm ? q->d_iwe : q->iwe, nullptr, use_gm ? 0 : (q->omit_boundary ? 1 : 0), q->d_dense, nullptr,
-                                    use_gm ? nullptr : q->moments, use_gm ? nullptr : q->upstream,
-                                    has_reg ? q->d_reg : nullptr, q->workspace, q->workspace_bytes,
-                                    q->splits == 0 ? q->part_table : nullptr, stream);
-  if (rc) return rc;
-  // adjoint of the upsample + the Adam step of every grid element where its gradient appears + the loss of the iteration
+                                            q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->d_theta,
+                                            step ? q->theta : nullptr, q->exp_avg, q->exp_avg_sq, q->lr, q->beta1, q->beta2, q->eps, t,
+                                            q->step, q->variance, scale, q->reg_partials, n_reg, q->losses, q->losses_cap,
+                                            step ? q->theta_mask : nullptr, stream);
+  if (!step)
+    return ebos_upsample_patch_flow_bwd_f32(q->d_dense, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W,
+                                            q->upsample_scratch, q->d_theta, stream);
   return ebos_upsample_patch_flow_bwd_adam_f32(q->d_dense, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W,
                                                q->upsample_scratch, q->d_theta, q->theta, q->exp_avg, q->exp_avg_sq, q->lr, q->beta1,
-                                               q->beta2, q->eps, t, q->step, q->variance, -contrast_weight, q->reg_partials,
-                                               has_reg ? ebos::kRegGrid : 0, q->losses, q->losses_cap, q->theta_mask, stream);
+                                               q->beta2, q->eps, t, q->step, q->variance, scale, q->reg_partials, n_reg, q->losses,
+                                               q->losses_cap, q->theta_mask, stream);
 }
 
 int ebos_cmax_patch_solve_f32(const ebos_cmax_patch_problem* q, int n_iter, ebos_stream_t stream) {
   using namespace ebos;
   EBOS_REQUIRE(n_iter >= 0, "ebos_cmax_patch_solve: negative n_iter");
-  if (int rc = cmax_check_problem(q)) return rc;
+  if (int rc = cmax_check_problem("ebos_cmax_patch_solve", q)) return rc;
   for (int it = 0; it < n_iter; ++it)
-    if (int rc = cmax_enqueue_iteration(q, q->steps_done + it + 1, stream)) return rc;
+    if (int rc = cmax_iteration(q, q->steps_done + it + 1, stream)) return rc;
   return EBOS_OK;
 }
 
@@ -417,14 +403,24 @@ int ebos_cmax_patch_solve_many_f32(const ebos_cmax_patch_problem* problems, cons
   using namespace ebos;
   EBOS_REQUIRE(problems && streams && n_problems >= 1 && n_iter >= 0, "ebos_cmax_patch_solve_many: bad arguments");
   for (int w = 0; w < n_problems; ++w)
-    if (int rc = cmax_check_problem(problems + w)) return rc;
+    if (int rc = cmax_check_problem("ebos_cmax_patch_solve", problems + w)) return rc;
   // iteration-major: the windows' kernels alternate in the launch order, so that the small kernels of one window
   // (combine, finalize, regularisers, upsample, Adam) find free wave slots next to the one-workgroup-per-CU event
   // kernels of another
   for (int it = 0; it < n_iter; ++it)
     for (int w = 0; w < n_problems; ++w)
-      if (int rc = cmax_enqueue_iteration(problems + w, problems[w].steps_done + it + 1, streams[w])) return rc;
+      if (int rc = cmax_iteration(problems + w, problems[w].steps_done + it + 1, streams[w])) return rc;
   return EBOS_OK;
+}
+
+int ebos_cmax_patch_gradient_f32(const ebos_cmax_patch_problem* q, ebos_stream_t stream) {
+  using namespace ebos;
+  if (int rc = cmax_check_problem("ebos_cmax_patch_gradient", q)) return rc;
+  if (q->blur_k0 != 0.0f) {
+    set_error("ebos_cmax_patch_gradient: the blurred contrast (blur_k0 != 0) is part of the Adam loop only (ebos_cmax_patch_solve_f32)");
+    return EBOS_ERR_UNSUPPORTED;
+  }
+  return cmax_iteration(q, 0, stream);
 }
 
 }  // extern "C"

@@ -221,7 +221,7 @@ class ContrastMaximizationMixin(object):
             self.use_graph = self.fused_loop = False
             self.resident = False
             if self.time_aware.get("native", False):
-                self._check_native_time_aware()
+                self._check_native("time_aware", "the variance contrast alone")
         # multi_reference (module docstring): the contrast is the mean over several reference times; the autograd loop only
         self.multi_reference = parse_multi_reference(cfg.get("multi_reference"))
         if self.multi_reference is not None:
@@ -235,43 +235,39 @@ class ContrastMaximizationMixin(object):
             if self.multi_reference.get("native", False):
                 self._check_native_multi_reference()
 
-    def _check_native_multi_reference(self) -> None:
-        """``multi_reference.native``: the family of ``multi_reference_loop.MultiReferencePatchLoop``, or NotImplementedError naming the
-        key outside it."""
-        from ..event_plan import multiref_slab_halo
-
+    def _check_native(self, block: str, variance_alone: str, before_method=None, last=None) -> None:
+        """``<block>.native``: the family of the block's native loop (``time_aware_loop.TimeAwarePatchLoop`` /
+        ``multi_reference_loop.MultiReferencePatchLoop``), or NotImplementedError naming the key outside it.  ``variance_alone``: the
+        block's wording of the contrast clause; ``before_method`` / ``last``: the block's own clauses (-> what, or None), in their place
+        among the shared ones -- the first clause that fails is the one reported."""
         what = None
         if set(self.contrast_terms) != {"image_variance"}:
-            what = f"cost / cost_with_weight: the contrast {sorted(self.contrast_terms)} (the variance contrast alone, no gradient_magnitude)"
+            what = f"cost / cost_with_weight: the contrast {sorted(self.contrast_terms)} ({variance_alone})"
         elif not set(self.flow_terms) <= set(fused_loop.FLOW_TERMS):
             what = f"cost_with_weight: {sorted(set(self.flow_terms) - set(fused_loop.FLOW_TERMS))} (flow_norm and image_gradient only)"
         elif self.blur_sigma > 0:
             what = f"iwe.blur_sigma: {self.blur_sigma} (the un-blurred IWE only)"
-        elif self.pad != 0:
-            what = f"outer_padding: {self.pad} (0 only)"
-        elif self.opt_method != "Adam" and self.opt_method not in SCIPY_METHODS:
-            what = f"optimizer.method: {self.opt_method!r} (Adam or one of {SCIPY_METHODS})"
         else:
+            what = before_method() if before_method is not None else None
+            if what is None and self.opt_method != "Adam" and self.opt_method not in SCIPY_METHODS:
+                what = f"optimizer.method: {self.opt_method!r} (Adam or one of {SCIPY_METHODS})"
+            if what is None and last is not None:
+                what = last()
+        if what is not None:
+            raise NotImplementedError(f"{block}.native does not cover " + what + "; drop native to run the autograd loop")
+
+    def _check_native_multi_reference(self) -> None:
+        """``multi_reference.native``: the shared clauses, no ``outer_padding``, a (tile, halo) the K-image kernels are built for."""
+        from ..event_plan import multiref_slab_halo
+
+        def tile_halo():
             try:
                 multiref_slab_halo(self.plan_tile(), self.halo)
             except NotImplementedError as e:
-                what = f"tile / halo: {e}"
-        if what is not None:
-            raise NotImplementedError("multi_reference.native does not cover " + what + "; drop native to run the autograd loop")
+                return f"tile / halo: {e}"
 
-    def _check_native_time_aware(self) -> None:
-        """``time_aware.native``: the family of ``time_aware_loop.TimeAwarePatchLoop``, or NotImplementedError naming the key outside it."""
-        what = None
-        if set(self.contrast_terms) != {"image_variance"}:
-            what = f"cost / cost_with_weight: the contrast {sorted(self.contrast_terms)} (the variance contrast alone)"
-        elif not set(self.flow_terms) <= set(fused_loop.FLOW_TERMS):
-            what = f"cost_with_weight: {sorted(set(self.flow_terms) - set(fused_loop.FLOW_TERMS))} (flow_norm and image_gradient only)"
-        elif self.blur_sigma > 0:
-            what = f"iwe.blur_sigma: {self.blur_sigma} (the un-blurred IWE only)"
-        elif self.opt_method != "Adam" and self.opt_method not in SCIPY_METHODS:
-            what = f"optimizer.method: {self.opt_method!r} (Adam or one of {SCIPY_METHODS})"
-        if what is not None:
-            raise NotImplementedError("time_aware.native does not cover " + what + "; drop native to run the autograd loop")
+        self._check_native("multi_reference", "the variance contrast alone, no gradient_magnitude",
+                           lambda: f"outer_padding: {self.pad} (0 only)" if self.pad != 0 else None, tile_halo)
 
     # ------------------------------------------------------------------ objective pieces
     def _multi_reference_norms(self, plan: EventPlan) -> Dict[str, float]:
@@ -560,10 +556,20 @@ class ContrastMaximizationMixin(object):
     def _optimise_patch_grid(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
                              mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         H, W = self.orig_image_shape
+        capacity = n_iter if self.opt_method == "Adam" else 1   # (of a native block's loop: a scipy method records no losses there)
         if self.time_aware is not None and self.time_aware.get("native", False):
-            return self._optimise_time_aware_native(plan, theta, patch_size, sliding_window, n_iter, mask)
+            loop = time_aware_loop.TimeAwarePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.time_aware,
+                                                      self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                                                      self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo,
+                                                      self.lr, capacity=capacity, theta_mask=mask)
+            return self._optimise_native(loop, theta, n_iter)
         if self.multi_reference is not None and self.multi_reference.get("native", False):
-            return self._optimise_multi_reference_native(plan, theta, patch_size, sliding_window, n_iter, mask)
+            norm = self._multi_reference_norms(plan)["image_variance"]
+            loop = multi_reference_loop.MultiReferencePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.multi_reference["directions"],
+                                                                self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                                                                self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
+                                                                self.halo, self.lr, capacity=capacity, theta_mask=mask, norm=norm)
+            return self._optimise_native(loop, theta, n_iter)
         theta = theta.requires_grad_(True)
 
         def evaluate():  # (mask: the gradient of a patch that is not estimated is zero, so it keeps its masked start)
@@ -622,38 +628,14 @@ class ContrastMaximizationMixin(object):
         self.history += losses[:n_iter].cpu().tolist()
         return theta.detach()
 
-    def _optimise_time_aware_native(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
-                                    mask: Optional[torch.Tensor]) -> torch.Tensor:
-        """One pyramid scale of a ``time_aware.native`` solve: the Adam loop as one C call, or a scipy method on the loop's
-        ``value_and_grad``."""
-        adam = self.opt_method == "Adam"
-        loop = time_aware_loop.TimeAwarePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.time_aware,
-                                                  self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
-                                                  self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo,
-                                                  self.lr, capacity=n_iter if adam else 1, theta_mask=mask)
+    def _optimise_native(self, loop, theta: torch.Tensor, n_iter: int) -> torch.Tensor:
+        """One pyramid scale of a ``time_aware.native`` / ``multi_reference.native`` solve on the block's loop: the Adam loop as one C
+        call, or a scipy method on the loop's ``value_and_grad``."""
         self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
         self.loop_modes.append(loop.last_run_mode)
-        if not adam:
+        if self.opt_method != "Adam":
             return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=loop.value_and_grad)
         loop.run(n_iter)
-        self.history += loop.losses[:n_iter].cpu().tolist()
-        return loop.theta
-
-    def _optimise_multi_reference_native(self, plan: EventPlan, theta: torch.Tensor, patch_size, sliding_window, n_iter: int,
-                                         mask: Optional[torch.Tensor]) -> torch.Tensor:
-        """One pyramid scale of a ``multi_reference.native`` solve: the Adam loop as one C call, or a scipy method on the loop's
-        ``value_and_grad``."""
-        adam = self.opt_method == "Adam"
-        norm = self._multi_reference_norms(plan)["image_variance"]
-        loop = multi_reference_loop.MultiReferencePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.multi_reference["directions"],
-                                                            self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
-                                                            self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
-                                                            self.halo, self.lr, capacity=n_iter if adam else 1, theta_mask=mask, norm=norm)
-        self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
-        self.loop_modes.append(loop.last_run_mode)
-        if not adam:
-            return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=loop.value_and_grad)
-        loop.solve(n_iter)
         self.history += loop.losses[:n_iter].cpu().tolist()
         return loop.theta
 

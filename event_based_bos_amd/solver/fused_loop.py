@@ -3,25 +3,33 @@
 One iteration of the loop in src/solver/generative_max_likelihood.py:306-341 (zero_grad -> objective -> backward ->
 optimizer.step) for the objective  ``-w * contrast(IWE(dense(theta))) + w_n * flow_norm(dense) + w_g * image_gradient(dense)``
 (contrast = image variance, or the gradient magnitude with two more cost kernels)
-is, on the MATERIALISED route, five C-ABI calls / eight kernels on one stream, all on buffers allocated once per window:
+is a fixed sequence of launches on one stream, all on buffers allocated once per window.  The sequence is written once, in C
+(``cmax_forward_backward`` in csrc/solver_kernels.hip); this module holds the buffers, hands them over as one
+``ebos_cmax_patch_problem`` (``FusedPatchLoop.problem``) and calls two entry points: ``ebos_cmax_patch_solve_f32`` (n iterations,
+each ending in the Adam step) and ``ebos_cmax_patch_gradient_f32`` (one forward and backward ending in the plain adjoint:
+``value_and_grad``, for optimisers on the host).
+
+Dense route -- what C enqueues per iteration (5 entry points / 8 kernels):
 
     ebos_upsample_patch_flow_f32      theta [2, gh, gw] -> dense [2, H, W]
-    ebos_iwe_dense_slab_f32           dense -> IWE + variance partials           (2 kernels; 3 without regularisers)
-    ebos_flow_regularisers_f32        dense -> regulariser value partials + gradient image; variance, (mean, M)
+    ebos_iwe_dense_slab_f32           dense -> IWE + variance partials           (2 kernels; 3 without regularisers: a finalize)
+    ebos_flow_regularisers_f32        dense -> regulariser value partials + gradient image; reduces the variance partials
     ebos_iwe_dense_tiled_bwd_f32      -> d loss / d dense  (variance gradient folded in, regulariser gradient added)
     ebos_upsample_patch_flow_bwd_adam_f32  -> d loss / d theta (2 kernels); the second one applies the Adam step of every
                                       grid element where its gradient appears and records loss[it]
+                                      (gradient entry: ebos_upsample_patch_flow_bwd_f32, no step)
 
 Grid-sampling route (``sample_grid``, the default whenever ``ebos_patch_fused_supported``): the event kernels take theta
 itself and evaluate the grid -> dense map per source tile in LDS, so the iteration shrinks to
 
-    ebos_iwe_patch_slab_f32           theta -> IWE + variance partials                         (2 kernels)
-    ebos_iwe_patch_tiled_bwd_f32      reduces the variance partials, folds the variance gradient in, evaluates the flow regularisers from the
+    ebos_iwe_patch_slab_frac_f32      theta -> IWE + variance partials                         (2 kernels)
+    ebos_iwe_patch_tiled_bwd_frac_f32 reduces the variance partials, folds the variance gradient in, evaluates the flow regularisers from the
                                       tile's flow, and leaves partial CELL gradients per tile    (1 kernel)
-    ebos_patch_grad_combine_adam_f32  -> d loss / d theta, Adam step, loss[it]                  (1 kernel)
+    ebos_patch_grad_combine_adam_f32  -> d loss / d theta, Adam step, loss[it]                  (1 kernel; gradient entry: theta = NULL, no step)
 
 (4 launches, 48.5 us at 2 M events against 64.9 us; image_gradient too is evaluated there, on a 2 px apron of the tile's flow:
-55 us against 98 us.)
+55 us against 98 us.)  On either route the gradient-magnitude contrast adds ebos_gradient_magnitude_fused_f32 after the slab pass
+and iwe.blur_sigma > 0 adds ebos_blur3_variance_adjoint_f32 before the backward kernel (solve entry only).
 
 Expressed through autograd the same iteration is ~35 launches (capturable Adam alone is a dozen) and runs at ~235 us
 even as a replayed HIP graph; this pipeline is bounded by its event kernels.  Anything outside this objective family
@@ -272,7 +280,6 @@ class FusedPatchLoop(_ResidentLoop):
         if sample_grid is None and os.environ.get("EBOS_SAMPLE_GRID", "1") == "0":  # A/B switch for measurements
             can = False
         self.sample_grid = can if sample_grid is None else bool(sample_grid)
-        self.native_grid = self.sample_grid  # (kept for callers of the round's first form, where the two differed for fractional plans)
         # iwe.blur_sigma > 0: the contrast of the 3-tap blurred image (ebos_blur3_variance_adjoint_f32 between the combine and the
         # backward pass; the backward kernel folds the variance gradient in as a z + c wgt, csrc/blur3.h)
         self.blur_sigma = float(blur_sigma or 0.0)
@@ -308,109 +315,22 @@ class FusedPatchLoop(_ResidentLoop):
         self.reg_partials = torch.zeros(max(self.n_reg, 1), dtype=torch.float64, device=dev)
         self.ws = _workspace(plan, self.pad, self.halo, self.splits)
         self.graphed = False  # kept for callers that report it: this loop is never graph-replayed
-        off, n_parts, n_px = ctypes.c_size_t(), ctypes.c_int64(), ctypes.c_int64()
-        check(self.lib.ebos_iwe_slab_partials(H, W, plan.tile[0], plan.tile[1], self.halo, self.splits, self.pad[0], self.pad[1],
-                                              int(self.omit), ctypes.byref(off), ctypes.byref(n_parts), ctypes.byref(n_px)),
-              "ebos_iwe_slab_partials")
-        self._var_partials = (off.value, n_parts.value, n_px.value)
-
-    def _forward_backward(self, lib, plan, s) -> None:
-        """upsample -> IWE + contrast -> regularisers -> d loss / d dense (shared by iteration() and value_and_grad())."""
-        H, W = plan.image_size
-        gh, gw, (ph, pw), (sh, sw) = self.gh, self.gw, self.patch, self.slide
-        grid = self.sample_grid
-        if self.dense is not None:  # (with sample_grid only the regulariser pass reads the dense field)
-            check(lib.ebos_upsample_patch_flow_f32(ptr(self.theta), gh, gw, ph, pw, sh, sw, H, W, ptr(self.dense), s),
-                  "ebos_upsample_patch_flow")
-        use_gm = self.w_gm != 0.0
-        h, w = self.iwe.shape
-        # variance: with a regulariser launch that kernel reduces the combine pass's partials; with grid sampling the backward
-        # kernel does; otherwise a finalize launch
-        want_var = 0 if use_gm else (2 if (self.has_reg or grid) else 1)
-        off, n_parts, n_px = self._var_partials
-        if grid:
-            check(lib.ebos_iwe_patch_slab_frac_f32(*self._grid_ptrs(), ptr(plan.key_offsets), plan.n, ptr(self.theta), gh, gw, ph, pw,
-                                                   sh, sw, H, W, plan.tile[0], plan.tile[1], self.halo, self.splits, self.pad[0],
-                                                   self.pad[1], ptr(self.ws), self.ws.numel(), ptr(self.iwe), want_var, int(self.omit),
-                                                   ptr(self.variance), ptr(self.moments), ptr(plan.part_table), s), "ebos_iwe_patch_slab")
-        else:
-            check(lib.ebos_iwe_dense_slab_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), None, *plan._compact_ptrs(),
-                                              ptr(plan.key_offsets), plan.n, ptr(self.dense), H, W, plan.tile[0], plan.tile[1],
-                                              self.halo, self.splits, self.pad[0], self.pad[1], ptr(self.ws), self.ws.numel(),
-                                              ptr(self.iwe), want_var, int(self.omit),
-                                              ptr(self.variance), ptr(self.moments), ptr(plan.part_table), s), "ebos_iwe_dense_slab")
-        if use_gm:  # contrast = mean squared Sobel gradient; its gradient image is the upstream of the backward kernel
-            check(lib.ebos_gradient_magnitude_fused_f32(ptr(self.iwe), h, w, int(self.omit), ptr(self.upstream), ptr(self.variance),
-                                                        ptr(self.d_iwe), ptr(self.cost_scratch), self.cost_scratch.numel() // 8, s),
-                  "ebos_gradient_magnitude_fused")
-        if self.has_reg:  # ... which also reduces the variance partials of the combine pass (no finalize launch)
-            check(lib.ebos_flow_regularisers_f32(ptr(self.dense), H, W, self.w_norm, self.w_tv, ptr(self.d_reg),
-                                                 ptr(self.reg_partials), None if use_gm else self.ws.data_ptr() + off, n_parts, n_px,
-                                                 ptr(self.variance), ptr(self.moments), s), "ebos_flow_regularisers")
-        if grid:  # -> partial cell gradients per tile; _grid_gradient() sums them (and applies Adam)
-            check(lib.ebos_iwe_patch_tiled_bwd_frac_f32(*self._grid_ptrs(), ptr(plan.key_offsets), plan.n, ptr(self.theta), gh, gw, ph, pw,
-                                                        sh, sw, H, W, plan.tile[0], plan.tile[1], self.halo, self.pad[0], self.pad[1],
-                                                        ptr(self.d_iwe if use_gm else self.iwe), 0 if use_gm else int(self.omit),
-                                                        ptr(self.moments) if (self.has_reg and not use_gm) else None,
-                                                        None if use_gm else ptr(self.upstream),
-                                                        ptr(self.d_reg), ptr(self.grad_partials), self.grad_partials.numel() * 4,
-                                                        ptr(plan.part_table) if self.splits == 0 else None,
-                                                        self.w_norm if self.fuse_norm else 0.0, self.w_tv if self.fuse_norm else 0.0,
-                                                        ptr(self.reg_partials),
-                                                        None if (use_gm or self.has_reg) else self.ws.data_ptr() + off, n_parts, n_px,
-                                                        ptr(self.variance), ptr(self.moments), 0.0, 0.0, s), "ebos_iwe_patch_tiled_bwd")
-            return
-        check(lib.ebos_iwe_dense_tiled_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), None, *plan._compact_ptrs(),
-                                               ptr(plan.key_offsets), plan.n, ptr(self.dense), H, W, plan.tile[0], plan.tile[1],
-                                               self.halo, self.pad[0], self.pad[1], ptr(self.d_iwe if use_gm else self.iwe), None,
-                                               0 if use_gm else int(self.omit), ptr(self.d_dense), None,
-                                               None if use_gm else ptr(self.moments), None if use_gm else ptr(self.upstream),
-                                               ptr(self.d_reg), ptr(self.ws), self.ws.numel(),
-                                               ptr(plan.part_table) if self.splits == 0 else None, s),
-              "ebos_iwe_dense_tiled_bwd")
 
     def iteration(self) -> None:
+        """One more iteration as one host call: ``ebos_cmax_patch_solve_f32`` with ``n_iter = 1`` (``run(native=False)``)."""
         if self.blur_sigma > 0:
             raise NotImplementedError("blur_sigma > 0: run(native=True) -- the blurred contrast is part of the natively enqueued loop")
-        lib, plan, s = self.lib, self.plan, stream_ptr()
-        H, W = plan.image_size
-        gh, gw, (ph, pw), (sh, sw) = self.gh, self.gw, self.patch, self.slide
-        self._forward_backward(lib, plan, s)
-        self.t += 1
-        if self.sample_grid:
-            check(lib.ebos_patch_grad_combine_adam_f32(ptr(self.grad_partials), ptr(plan.part_table) if self.splits == 0 else None,
-                                                       plan.tile[0], plan.tile[1], gh, gw, ph, pw, sh, sw, H, W, ptr(self.d_theta),
-                                                       ptr(self.theta), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.lr, self.betas[0],
-                                                       self.betas[1], self.eps, self.t, ptr(self.step), ptr(self.variance),
-                                                       -(self.w_gm or self.w_var), ptr(self.reg_partials), self.n_reg, ptr(self.losses),
-                                                       self.losses.numel(), ptr(self.theta_mask), s), "ebos_patch_grad_combine_adam")
-            return
-        check(lib.ebos_upsample_patch_flow_bwd_adam_f32(ptr(self.d_dense), gh, gw, ph, pw, sh, sw, H, W, ptr(self.scratch_up),
-                                                        ptr(self.d_theta), ptr(self.theta), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                                                        self.lr, self.betas[0], self.betas[1], self.eps, self.t, ptr(self.step),
-                                                        ptr(self.variance), -(self.w_gm or self.w_var), ptr(self.reg_partials), self.n_reg,
-                                                        ptr(self.losses), self.losses.numel(), ptr(self.theta_mask), s),
-              "ebos_upsample_patch_flow_bwd_adam")
+        self._pipeline(1)
 
     def value_and_grad(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(loss [0-d], d loss / d theta [2, gh, gw]) at ``theta`` through the same kernels, without the Adam update --
-        for optimisers that live on the host (scipy)."""
-        lib, plan, s = self.lib, self.plan, stream_ptr()
-        H, W = plan.image_size
-        gh, gw, (ph, pw), (sh, sw) = self.gh, self.gw, self.patch, self.slide
+        """(loss [0-d], d loss / d theta [2, gh, gw]) at ``theta`` through the same kernels, without the Adam update
+        (``ebos_cmax_patch_gradient_f32``: the optimiser state, the step counter and the losses stay as they are) -- for optimisers
+        that live on the host (scipy)."""
         if self.blur_sigma > 0:
             raise NotImplementedError("blur_sigma > 0: value_and_grad is not part of the blurred pipeline (use the autograd objective)")
-        with _hip.on_device(plan.device):
+        with _hip.on_device(self.plan.device):
             self.theta.copy_(theta.detach().to(self.theta))
-            self._forward_backward(lib, plan, s)
-            if self.sample_grid:  # plain gradient: theta = NULL, no optimiser step
-                check(lib.ebos_patch_grad_combine_adam_f32(ptr(self.grad_partials), ptr(plan.part_table) if self.splits == 0 else None,
-                                                           plan.tile[0], plan.tile[1], gh, gw, ph, pw, sh, sw, H, W, ptr(self.d_theta),
-                                                           None, None, None, 0.0, 0.0, 0.0, 0.0, 0, None, None, 0.0, None, 0, None, 0,
-                                                           None, s), "ebos_patch_grad_combine_adam")
-            else:
-                check(lib.ebos_upsample_patch_flow_bwd_f32(ptr(self.d_dense), gh, gw, ph, pw, sh, sw, H, W, ptr(self.scratch_up),
-                                                           ptr(self.d_theta), s), "ebos_upsample_patch_flow_bwd")
+            check(self.lib.ebos_cmax_patch_gradient_f32(ctypes.byref(self.problem()), stream_ptr()), "ebos_cmax_patch_gradient")
             loss = -(self.w_gm or self.w_var) * self.variance[0]
             if self.n_reg:
                 loss = loss + self.reg_partials.sum().to(torch.float32)
@@ -448,14 +368,6 @@ class FusedPatchLoop(_ResidentLoop):
             q.grp_offsets, q.cpix, q.cdt, q.cfx, q.cfy = plan._frac_ptrs(query)
         return q
 
-    def _grid_ptrs(self):
-        """(grp_offsets, cpix, cdt, cfx, cfy) of the grid-sampling entries: the compact plan, or -- fractional source coordinates -- the
-        compact layout with the fractions per slot."""
-        plan = self.plan
-        if plan.compact:
-            return plan._compact_ptrs() + (None, None)
-        return plan._frac_ptrs()
-
     def _resident_gates(self) -> bool:
         """(``resident_supported``) the grid-sampling route, or fractional source coordinates -- the four launches run the dense
         route, the resident launch the compact layout with the fractions per slot (62 -> 31 us per iteration at 2 M events) --;
@@ -474,9 +386,10 @@ class FusedPatchLoop(_ResidentLoop):
         ``resident`` (default: whenever ``resident_supported()``; ``EBOS_RESIDENT=0`` turns the default off): the whole loop as
         ONE resident launch; a launch that ends early (status < 0: see ``run_resident``) leaves the state untouched and the
         four-launch pipeline below runs instead.  The resident call synchronises the stream once, to read its status.
-        ``native`` (default): one C call enqueues the whole loop (ebos_cmax_patch_solve_f32); otherwise one Python call
-        per kernel group.  (A HIP-graph replay of the iteration was measured slower than plain launches on ROCm 7.2 --
-        172 vs 111 us at 2 M events -- and cannot carry the step number, which is a kernel argument.)"""
+        ``native`` (default): one C call enqueues the whole loop (ebos_cmax_patch_solve_f32); otherwise one such call
+        per iteration (the same launches with the same arguments).  (A HIP-graph replay of the iteration was measured slower
+        than plain launches on ROCm 7.2 -- 172 vs 111 us at 2 M events -- and cannot carry the step number, which is a kernel
+        argument.)"""
         return self._run(n_iter, False if resident is None and not native else resident,
                          self._pipeline if native else self._iterations)
 

@@ -814,8 +814,8 @@ typedef struct ebos_cmax_patch_problem {
   int losses_cap;
   const float* theta_mask;     /* [gh, gw], nullable: grad_mask of ebos_upsample_patch_flow_bwd_adam_f32 */
   float* grad_partials;        /* non-NULL: the event kernels sample the patch grid themselves (ebos_iwe_patch_*; needs
-                                  ebos_patch_fused_supported and the compact plan); `dense` is then only written when a flow
-                                  regulariser is on, d_dense / upsample_scratch are not used */
+                                  ebos_patch_fused_supported and the compact plan); dense / d_dense / d_reg / upsample_scratch are
+                                  then not used (the backward kernel evaluates the flow regularisers from the tile's flow) */
   size_t grad_partials_bytes;  /* ebos_patch_grad_partials_bytes(H, W, tile_h, tile_w, splits == 0) */
   /* ABI 2: iwe.blur_sigma > 0 -- the variance is taken on the 3-tap blurred IWE (src/event_image_converter.py:399-404).
    * blur_k0 = 0: no blur.  Otherwise the taps (blur_k0, blur_k1, blur_k0), blur_image [H + 2 pad_h, W + 2 pad_w] and cost_scratch
@@ -829,6 +829,14 @@ typedef struct ebos_cmax_patch_problem {
   const float *cfx, *cfy;
 } ebos_cmax_patch_problem;
 int ebos_cmax_patch_solve_f32(const ebos_cmax_patch_problem* problem, int n_iter, ebos_stream_t stream);
+/* ebos_cmax_patch_gradient_f32: one forward and backward at theta without the Adam step -- d_theta, variance (the contrast value),
+ *   moments and reg_partials are left for the caller (loss = -(w_variance or w_gradient_magnitude) * variance[0] + sum of the first
+ *   n reg_partials, n = ebos_flow_regularisers_partials() on the dense route, grad_partials_bytes / 2048 with grad_partials, 0 without
+ *   a regulariser weight); for optimisers that live on the host.  The same checks and the same launches as one iteration of
+ *   ebos_cmax_patch_solve_f32 up to the finishing call, which is the plain adjoint (ebos_patch_grad_combine_adam_f32 with theta = NULL,
+ *   or ebos_upsample_patch_flow_bwd_f32): theta, exp_avg, exp_avg_sq, step and losses are not written, theta_mask is not applied.
+ *   blur_k0 != 0 is refused (EBOS_ERR_UNSUPPORTED): the blurred contrast is part of the Adam loop only. */
+int ebos_cmax_patch_gradient_f32(const ebos_cmax_patch_problem* problem, ebos_stream_t stream);
 /* Several independent windows at once (windows are the unit that shards): problem w runs on
  * streams[w]; launches are enqueued iteration-major so that the windows' kernels interleave on the GPU. */
 int ebos_cmax_patch_solve_many_f32(const ebos_cmax_patch_problem* problems, const ebos_stream_t* streams,

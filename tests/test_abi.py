@@ -64,6 +64,99 @@ def test_host_only_entry_points(lib):
     assert rc == -1
 
 
+def test_patch_gradient_entry_is_declared_and_mirrored():
+    """``ebos_cmax_patch_gradient_f32`` next to the solve entry: the problem and a stream, in the header and in the ctypes table."""
+    import ctypes
+
+    from event_based_bos_amd import _hip
+
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"\bint\s+ebos_cmax_patch_gradient_f32\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+    assert m and [" ".join(a.split()) for a in m.group(1).split(",")] == ["const ebos_cmax_patch_problem* problem", "ebos_stream_t stream"]
+    res, args = _hip.SIGNATURES["ebos_cmax_patch_gradient_f32"]
+    assert res is ctypes.c_int and len(args) == 2 and all(a is ctypes.c_void_p for a in args)
+    assert text.index("ebos_cmax_patch_solve_f32(") < text.index("ebos_cmax_patch_gradient_f32(") < text.index("ebos_cmax_patch_solve_many_f32(")
+
+
+def _patch_problem(**over):
+    """An ``ebos_cmax_patch_problem`` that passes every check (the dense route, the variance contrast; pointers that are never read:
+    only calls that are refused before any launch get it)."""
+    from event_based_bos_amd import _hip
+
+    q = _hip.CmaxPatchProblem()
+    for name in ("xs", "ys", "dts", "key_offsets", "theta", "d_theta", "exp_avg", "exp_avg_sq", "step", "dense", "d_dense", "iwe", "variance",
+                 "moments", "upstream", "reg_partials", "upsample_scratch", "workspace", "losses"):
+        setattr(q, name, 0x1000)
+    q.n, q.H, q.W, q.tile_h, q.tile_w, q.halo, q.splits = 10, 37, 70, 32, 32, 8, 1
+    q.gh, q.gw, q.patch_h, q.patch_w, q.slide_h, q.slide_w = 4, 5, 12, 14, 12, 14
+    q.w_variance, q.lr, q.beta1, q.beta2, q.eps, q.losses_cap = 1.0, 0.05, 0.9, 0.999, 1e-8, 8
+    for k, v in over.items():
+        setattr(q, k, v)
+    return q
+
+
+# (what is wrong with the problem, the return code, the message after the entry's prefix -- the texts of ebos_cmax_patch_solve_f32
+# as they were before the gradient entry shared its checks)
+_PATCH_DEFECTS = [
+    (dict(steps_done=-1), -1, "NULL problem or negative steps_done"),
+    (dict(cfx=0x1000), -1, "cfx / cfy come together"),
+    (dict(moments=None), -1, "NULL buffer"),
+    (dict(grad_partials=0x1000), -1, "grad_partials (grid-sampling kernels) needs the compact plan"),
+    (dict(grad_partials=0x1000, grp_offsets=0x1000, cpix=0x1000, cdt=0x1000, tile_h=33),
+     -1, "grad_partials given but tile 33x32 halo 8 / sliding window 12x14 is outside ebos_patch_fused_supported"),
+    (dict(dense=None), -1, "NULL dense / d_dense / upsample_scratch"),
+    (dict(cfx=0x1000, cfy=0x1000, xs=None), -1, "a window of fractional source coordinates on the dense route needs xs / ys / dts"),
+    (dict(w_flow_norm=0.1), -1, "regulariser weights given but d_reg is NULL"),
+    (dict(w_variance=0.0), -1, "exactly one of w_variance / w_gradient_magnitude must be non-zero"),
+    (dict(w_variance=1.0, w_gradient_magnitude=1.0), -1, "exactly one of w_variance / w_gradient_magnitude must be non-zero"),
+    (dict(w_variance=0.0, w_gradient_magnitude=1.0), -1, "the gradient-magnitude contrast needs d_iwe and cost_scratch"),
+    (dict(blur_k0=0.3, blur_k1=0.4), -1, "the blurred contrast needs positive taps, blur_image and cost_scratch"),
+    (dict(blur_k0=0.3, blur_k1=0.4, blur_image=0x1000, cost_scratch=0x1000, d_iwe=0x1000, w_variance=0.0, w_gradient_magnitude=1.0),
+     -3, "the blurred image goes with the variance contrast only"),
+    (dict(blur_k0=0.3, blur_k1=0.4, blur_image=0x1000, cost_scratch=0x1000, cost_scratch_bytes=15),
+     -4, "cost_scratch too small for the blur's partials (15 < {blur_need})"),
+]
+
+
+def test_patch_solve_refusals_keep_their_messages(lib):
+    """The checks the solve and the gradient entry share report under the caller's name: ``ebos_cmax_patch_solve_f32`` keeps every
+    message it had, byte for byte (``_solve_many_f32`` shares its prefix, as before)."""
+    import ctypes
+
+    blur_need = 16 * lib.ebos_blur3_variance_partials(37, 70)
+    assert lib.ebos_cmax_patch_solve_f32(None, 1, None) == -1
+    assert lib.ebos_last_error() == b"ebos_cmax_patch_solve: NULL problem or negative steps_done"
+    assert lib.ebos_cmax_patch_solve_f32(ctypes.byref(_patch_problem()), -1, None) == -1
+    assert lib.ebos_last_error() == b"ebos_cmax_patch_solve: negative n_iter"
+    assert lib.ebos_cmax_patch_solve_f32(ctypes.byref(_patch_problem()), 0, None) == 0   # (the problem passes: nothing to enqueue)
+    for over, rc, text in _PATCH_DEFECTS:
+        want = ("ebos_cmax_patch_solve: " + text.format(blur_need=blur_need)).encode()
+        assert lib.ebos_cmax_patch_solve_f32(ctypes.byref(_patch_problem(**over)), 1, None) == rc, over
+        assert lib.ebos_last_error() == want, over
+        problems = (type(_patch_problem()) * 2)(_patch_problem(), _patch_problem(**over))
+        streams = (ctypes.c_void_p * 2)()
+        assert lib.ebos_cmax_patch_solve_many_f32(problems, streams, 2, 1) == rc and lib.ebos_last_error() == want, over
+    assert lib.ebos_cmax_patch_solve_many_f32(None, None, 0, 1) == -1
+    assert lib.ebos_last_error() == b"ebos_cmax_patch_solve_many: bad arguments"
+
+
+def test_patch_gradient_refuses_before_any_launch(lib):
+    """``ebos_cmax_patch_gradient_f32``: the solve entry's checks under its own name, and no blurred contrast (-3 =
+    EBOS_ERR_UNSUPPORTED) -- all before any HIP call: usable without a GPU."""
+    import ctypes
+
+    blur_need = 16 * lib.ebos_blur3_variance_partials(37, 70)
+    assert lib.ebos_cmax_patch_gradient_f32(None, None) == -1
+    assert lib.ebos_last_error() == b"ebos_cmax_patch_gradient: NULL problem or negative steps_done"
+    for over, rc, text in _PATCH_DEFECTS:
+        assert lib.ebos_cmax_patch_gradient_f32(ctypes.byref(_patch_problem(**over)), None) == rc, over
+        assert lib.ebos_last_error() == ("ebos_cmax_patch_gradient: " + text.format(blur_need=blur_need)).encode(), over
+    blurred = _patch_problem(blur_k0=0.3, blur_k1=0.4, blur_image=0x1000, cost_scratch=0x1000, cost_scratch_bytes=blur_need)
+    assert lib.ebos_cmax_patch_solve_f32(ctypes.byref(blurred), 0, None) == 0             # a problem of the solve entry ...
+    assert lib.ebos_cmax_patch_gradient_f32(ctypes.byref(blurred), None) == -3            # ... that this one refuses
+    assert lib.ebos_last_error().startswith(b"ebos_cmax_patch_gradient: the blurred contrast (blur_k0 != 0)")
+
+
 def test_run_time_window_halo_code(lib):
     """EBOS_HALO_AUTO (include/ebos_hip.h): the `halo` arguments take -(max_halo + 256 q) with q = ceil(64 max |dt|), the bound
     ROUNDED UP; host-only entry points decode it to the built halo that sizes the workspace -- usable without a GPU."""

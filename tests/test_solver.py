@@ -130,9 +130,9 @@ def test_fused_loop_follows_the_autograd_loop(terms):
 
 @pytest.mark.gpu
 def test_fused_loop_run_modes_agree():
-    """FusedPatchLoop: the native loop (ebos_cmax_patch_solve_f32), the per-call Python loop and the resident launch
-    (ebos_cmax_patch_solve_resident_f32) run the same arithmetic in the same order: losses agree to 1e-5 relative over 30
-    iterations (resident vs native: exactly); a loop can be continued in another mode (10 + 20 steps)."""
+    """FusedPatchLoop: the native loop (ebos_cmax_patch_solve_f32 once), one such call per iteration (``native=False``: the same
+    launches with the same arguments) and the resident launch (ebos_cmax_patch_solve_resident_f32) run the same arithmetic in the
+    same order: the losses of 30 iterations are the same bit for bit; a loop can be continued in another mode (10 + 20 steps)."""
     import torch
 
     import event_based_bos_amd as ebos
@@ -147,7 +147,7 @@ def test_fused_loop_run_modes_agree():
         # fixed-point unit follows max |upstream| over the staged WINDOW -- against a built halo it agrees to ~1e-6, not bit for bit
         loop = FusedPatchLoop(plan, (24, 32), (24, 32), torch.zeros((2, 4, 4)), 1.0, 0.01, 0.02, halo="auto", lr=0.1, capacity=30)
         assert loop.resident_supported(), ebos.load_library().ebos_last_error()
-        if mode == "split":    # 10 iterations of the resident launch (the default mode), continued per call from Python
+        if mode == "split":    # 10 iterations of the resident launch (the default mode), continued with one host call per iteration
             first = loop.run(10).cpu().numpy()
             assert loop.last_run_mode == "resident"
             hist[mode] = np.concatenate([first, loop.run(20, native=False).cpu().numpy()])
@@ -158,8 +158,8 @@ def test_fused_loop_run_modes_agree():
             hist[mode] = loop.run(30, native=mode == "native", resident=False).cpu().numpy()
             assert loop.last_run_mode == "pipeline"
         assert loop.t == 30 and int(loop.step.item()) == 30
-    np.testing.assert_allclose(hist["python"], hist["native"], rtol=1e-5)
-    np.testing.assert_allclose(hist["split"], hist["native"], rtol=1e-5)
+    np.testing.assert_array_equal(hist["python"], hist["native"])
+    np.testing.assert_array_equal(hist["split"], hist["native"])
     np.testing.assert_array_equal(hist["resident"], hist["native"])   # the resident launch follows the pipeline bit for bit
     # EBOS_RESIDENT=0 turns the default off (resident=True still asks for it explicitly)
     os.environ["EBOS_RESIDENT"] = "0"
@@ -171,6 +171,97 @@ def test_fused_loop_run_modes_agree():
         del os.environ["EBOS_RESIDENT"]
     with pytest.raises(ValueError):
         loop.run(1)
+
+
+_VG_OBJECTIVES = {"variance": (1.0, 0.0, 0.0, 0.0), "variance+reg": (2.0, 0.01, 0.05, 0.0), "gm+reg": (0.0, 0.02, 0.03, 1.5)}  # (w_var, w_norm, w_tv, w_gm)
+_VG_SHAPE, _VG_PATCH = (96, 128), (24, 32)
+_vg_cache = {}
+
+
+def _vg_events(frac):
+    """~20 k events of moving points on the 96 x 128 image; ``frac``: with fractional source coordinates (1/64 px steps)."""
+    if frac not in _vg_cache:
+        h, w = _VG_SHAPE
+        ev = moving_points(h, w, 500, 40, np.array([4.0, -2.5]), seed=6)
+        if frac:
+            rs = np.random.RandomState(19)
+            ev[:, :2] = np.clip(ev[:, :2] + rs.randint(0, 64, (len(ev), 2)) / 64.0, 0, [h - 1, w - 1])
+        _vg_cache[frac] = ev
+    return _vg_cache[frac]
+
+
+def _vg_theta0():
+    return torch.from_numpy(np.random.RandomState(3).uniform(-2, 2, (2, 4, 4))).float()
+
+
+def _vg_oracle(objective):
+    """(loss, d loss / d theta) of the fp64 oracle's autograd at the start, on the integer-pixel events; once per objective."""
+    key = ("oracle", objective)
+    if key not in _vg_cache:
+        w_var, w_norm, w_tv, w_gm = _VG_OBJECTIVES[objective]
+        t64 = _vg_theta0().double().requires_grad_(True)
+        dense = O.upsample_patch_flow(t64, _VG_SHAPE, _VG_PATCH, _VG_PATCH)
+        iwe = O.iwe_dense(torch.from_numpy(_vg_events(False)), dense, _VG_SHAPE)
+        loss = (w_gm * O.gradient_magnitude(iwe) if w_gm else w_var * O.image_variance(iwe)) + w_norm * O.flow_norm(dense)
+        loss = loss + w_tv * O.image_gradient_tv(dense, torch.ones(_VG_SHAPE, dtype=torch.float64))
+        loss.backward()
+        _vg_cache[key] = (loss.item(), t64.grad.numpy().copy())
+    return _vg_cache[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route,objective,masked", [(r, o, False) for r in ("grid", "dense", "frac") for o in _VG_OBJECTIVES]
+                         + [("grid", "variance+reg", True)])
+def test_patch_gradient_entry_is_the_step_without_the_update(route, objective, masked):
+    """``FusedPatchLoop.value_and_grad`` is one ``ebos_cmax_patch_gradient_f32``: the launches of the first Adam step of
+    ``ebos_cmax_patch_solve_f32`` ending in the plain adjoint.  On each route (grid sampling on a compact plan, the dense flow field,
+    grid sampling on fractional source coordinates) and objective: the loss (1e-6 relative) and d_theta (1e-5 rel-L2) of the first step
+    of a twin loop; theta, the Adam state, the step counter and the losses bit for bit what they were -- on a fresh loop and on one that
+    has stepped --; on the compact grid route the fp64 oracle's autograd (loss 1e-5, gradient 1e-3 rel-L2); with a ``theta_mask``,
+    exactly zero on the masked patches."""
+    import event_based_bos_amd as ebos
+    from event_based_bos_amd.solver.fused_loop import FusedPatchLoop
+
+    h, w = _VG_SHAPE
+    w_var, w_norm, w_tv, w_gm = _VG_OBJECTIVES[objective]
+    plan = ebos.EventPlan.build(torch.from_numpy(_vg_events(route == "frac")).cuda(), (h, w), "first", True, tile="auto")
+    assert plan.compact != (route == "frac")
+    theta0 = _vg_theta0()
+    mask = None
+    if masked:
+        mask = torch.ones((4, 4))
+        mask[0, 1] = mask[2, 3] = 0.0
+
+    def make():
+        return FusedPatchLoop(plan, _VG_PATCH, _VG_PATCH, theta0, w_var, w_norm, w_tv, halo="auto", lr=0.1, capacity=4, w_gradient_magnitude=w_gm,
+                              theta_mask=mask, sample_grid=False if route == "dense" else None)
+
+    def state(loop):
+        return [t.clone() for t in (loop.theta, loop.exp_avg, loop.exp_avg_sq, loop.step, loop.losses)]
+
+    a, b = make(), make()
+    assert a.sample_grid == (route != "dense")
+    before = state(a)
+    loss, grad = a.value_and_grad(theta0.cuda())
+    assert all(torch.equal(x, y) for x, y in zip(before, state(a))) and a.t == 0
+    l1 = b.run(1, resident=False).cpu().numpy()
+    assert b.last_run_mode == "pipeline"
+    d_step = b.d_theta if mask is None else b.d_theta * mask.cuda()
+    e_loss, e_grad = abs(float(loss) / float(l1[0]) - 1), float((grad - d_step).norm() / d_step.norm())
+    print(f"{route} {objective}: against the first step: loss rel {e_loss:.2e}, d_theta rel-L2 {e_grad:.2e}")
+    assert e_loss < 1e-6 and e_grad < 1e-5
+    before = state(b)   # ... and on a loop whose Adam state, step counter and losses are not zero
+    b.value_and_grad(b.theta.clone())
+    assert all(torch.equal(x, y) for x, y in zip(before, state(b))) and b.t == 1
+    if route == "grid":
+        loss_ref, grad_ref = _vg_oracle(objective)
+        if mask is not None:
+            grad_ref = grad_ref * mask.numpy()
+        e_loss, e_grad = abs(float(loss) - loss_ref) / abs(loss_ref), O.rel_l2(grad.cpu().numpy(), grad_ref)
+        print(f"{route} {objective}: against the fp64 oracle: loss rel {e_loss:.2e}, d_theta rel-L2 {e_grad:.2e}")
+        assert e_loss <= 1e-5 and e_grad < 1e-3
+    if mask is not None:
+        assert torch.count_nonzero(grad[:, mask.cuda() == 0]) == 0 and torch.count_nonzero(grad) > 0
 
 
 @pytest.mark.gpu
@@ -936,9 +1027,9 @@ def test_resident_2dof_loop_matches_the_four_launch_loop(size, n_ev, omit, sigma
 def test_resident_patch_loop_on_fractional_source_coordinates(size, n_ev, patch, terms, gm, blur):
     """Events rectified with a sub-pixel map (or warped by an earlier stage) have fractional source coordinates.  The natively enqueued
     four-launch loop and the resident launch read the compact layout with the fractions per slot (EventPlan.frac_compact; FRAC
-    kernels: general forward loop, f64 backward sweep -- the grid-sampling route); the per-call Python forms, and
-    ``sample_grid=False``, run the (x, y, dt) arrays through a dense flow field (upsample, general event kernels, adjoint of the
-    upsample).  First iteration against the fp64 oracle's autograd (loss 1e-5, patch-flow gradient rel-L2 1e-3 where the oracle is
+    kernels: general forward loop, f64 backward sweep -- the grid-sampling route), and so does ``value_and_grad``
+    (ebos_cmax_patch_gradient_f32: the step's launches, ending in the plain adjoint); ``sample_grid=False`` runs the (x, y, dt)
+    arrays through a dense flow field (upsample, general event kernels, adjoint of the upsample).  First iteration against the fp64 oracle's autograd (loss 1e-5, patch-flow gradient rel-L2 1e-3 where the oracle is
     affordable), against the four launches (the same arithmetic: to the last bits of the f64 atomics) and against the dense route
     (which forms x' from the absolute f32 coordinate instead of the fraction: ~1e-4 px apart at x ~ 1000); 60 iterations to
     rounding; a resident run is continued by the four launches."""
@@ -968,7 +1059,7 @@ def test_resident_patch_loop_on_fractional_source_coordinates(size, n_ev, patch,
     dense = FusedPatchLoop(plan, patch, patch, theta0, *terms, halo="auto", lr=0.02, capacity=4, w_gradient_magnitude=gm, blur_sigma=blur,
                            sample_grid=False)
     assert not dense.sample_grid
-    if not blur:  # ... and the per-call Python form of the grid route (what the scipy optimisers drive): the natively enqueued step's numbers
+    if not blur:  # ... and the gradient entry on the grid route (what the scipy optimisers drive): the natively enqueued step's numbers
         l_v, g_v = make().value_and_grad(theta0.cuda())
         assert abs(float(l_v) / l1_ref[0] - 1) < 1e-6 and float((g_v - ref.d_theta).norm() / ref.d_theta.norm()) < 1e-5
     l1_dense = dense.run(1, resident=False).cpu().numpy()
