@@ -315,6 +315,12 @@ SIGNATURES = {
                                                    _P, _P, _P]),
     "ebos_cmax_multiref_solve_f32": (_I, [_P, _I, _P]),
     "ebos_cmax_multiref_gradient_f32": (_I, [_P, _P]),
+    "ebos_iwe_voxel_multiref_tiled_f32": (_I, [_P] * 5 + [_L, _P] + [_I] * 9 + [C.POINTER(_F), _I, _P, _P]),
+    "ebos_iwe_voxel_multiref_owner_bwd_f32": (_I, [_P] * 5 + [_L, _P] + [_I] * 7 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
+    "ebos_iwe_voxel_multiref_tiled_batch_f32": (_I, [_P] * 6 + [_I, _P] + [_I] * 9 + [C.POINTER(_F), _I, _P, _P]),
+    "ebos_iwe_voxel_multiref_owner_bwd_batch_f32": (_I, [_P] * 6 + [_I, _P] + [_I] * 7 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
+    "ebos_cmax_voxel_multiref_solve_batch_f32": (_I, [_P, _I, _P]),
+    "ebos_cmax_voxel_multiref_gradient_batch_f32": (_I, [_P, _P]),
 }
 
 
@@ -400,6 +406,23 @@ class CmaxVoxelBatchProblem(C.Structure):
     event counts of the windows, ``n``, as an array."""
     _fields_ = ([("B", _I)] + [(k, _P) for k in ("xs", "ys", "dts", "bins", "key_offsets")] + [("n", _L * CMAX_VOXEL_MAX_BATCH)] +
                 CmaxVoxelProblem._fields_[6:])
+
+
+class CmaxVoxelMultirefBatchProblem(C.Structure):
+    """``ebos_cmax_voxel_multiref_batch_problem`` of include/ebos_hip.h (same field order): ``CmaxVoxelBatchProblem`` with ``K`` and
+    ``shifts`` in the place of ``owner_bwd``, and ``inv_norm`` / ``value`` after ``affine``."""
+    _fields_ = ([("B", _I)] + [(k, _P) for k in ("xs", "ys", "dts", "bins", "key_offsets")] + [("n", _L * CMAX_VOXEL_MAX_BATCH)] +
+                [(k, _I) for k in ("H", "W", "tile_h", "tile_w", "halo", "pad_h", "pad_w", "omit_boundary", "splits")] +
+                [(k, _I) for k in ("T", "scheme", "t0_index", "wrap_last", "route", "has_clamp")] + [("clamp", _D), ("K", _I)] +
+                [("shifts", _F * MULTIREF_MAX)] +
+                [(k, _I) for k in ("gh", "gw", "patch_h", "patch_w", "slide_h", "slide_w")] +
+                [(k, _F) for k in ("w_variance", "w_flow_norm", "w_image_gradient")] +
+                [(k, _D) for k in ("lr", "beta1", "beta2", "eps")] +
+                [(k, _P) for k in ("theta", "d_theta", "exp_avg", "exp_avg_sq", "step")] + [("steps_done", _I)] +
+                [(k, _P) for k in ("dense", "d_dense", "d_reg", "voxel", "voxel_clamped", "d_voxel", "iwe", "variance", "moments", "upstream",
+                                   "affine", "inv_norm", "value", "cost_scratch")] +
+                [("cost_scratch_bytes", _Z), ("reg_partials", _P), ("upsample_scratch", _P), ("adjoint_workspace", _P),
+                 ("adjoint_workspace_elems", _L), ("losses", _P), ("losses_cap", _I), ("theta_mask", _P)])
 
 
 class Cmax2dofProblem(C.Structure):

@@ -5,6 +5,11 @@
 // kernel here adds the regularisers' gradient to d_dense.
 // One window is a batch of one: ebos_cmax_voxel_solve_f32 / _gradient_f32 copy their problem into a batch problem with B = 1 and run
 // this same code.
+// K reference times (ebos_cmax_voxel_multiref_solve_batch_f32): the same stages on B K images -- the forward and the owner backward of
+// warp_voxel_multiref.hip in the place of the single reference's, and one small kernel that folds a window's K variances into its
+// value; the problem is copied into a batch problem plus a `MultiRef` and runs this same code too.
+#include <cmath>
+
 #include "common.h"
 
 namespace ebos {
@@ -13,6 +18,24 @@ namespace {
 __global__ void __launch_bounds__(256) add_inplace_kernel(float* __restrict__ acc, const float* __restrict__ add, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc[i] += add[i];
 }
+
+// value[b] = inv_norm[b] * mean_k variance[b][k]: what the Adam kernel records as window b's contrast
+__global__ void __launch_bounds__(64) multiref_value_kernel(const float* __restrict__ variance, const float* __restrict__ inv_norm, int B,
+                                                            int K, float* __restrict__ value) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double sum = 0.0;
+  for (int k = 0; k < K; ++k) sum += (double)variance[b * K + k];
+  value[b] = (float)((double)inv_norm[b] * (sum / K));
+}
+
+// what K reference times add to a batch problem (nullptr: one reference time, the plan's own)
+struct MultiRef {
+  int K;
+  const float* shifts;    // [K], host
+  const float* inv_norm;  // [B], device
+  float* value;           // [B], device
+};
 
 bool has_reg(const ebos_cmax_voxel_batch_problem* q) { return q->w_flow_norm != 0.0f || q->w_image_gradient != 0.0f; }
 
@@ -26,7 +49,8 @@ bool tiled_forward(const ebos_cmax_voxel_batch_problem* q) {
 }
 
 // `who`: the entry point the caller used, in front of every refusal
-int check_problem(const char* who, const ebos_cmax_voxel_batch_problem* q) {
+// `n_ref`: images per window (the cost kernels' scratch holds B * n_ref of them)
+int check_problem(const char* who, const ebos_cmax_voxel_batch_problem* q, int n_ref = 1) {
   EBOS_REQUIRE(q != nullptr, "%s: NULL problem", who);
   EBOS_REQUIRE(q->B >= 1 && q->B <= EBOS_CMAX_VOXEL_MAX_BATCH, "%s: B = %d is outside [1, %d]", who, q->B,
                EBOS_CMAX_VOXEL_MAX_BATCH);
@@ -62,17 +86,24 @@ int check_problem(const char* who, const ebos_cmax_voxel_batch_problem* q) {
               (long long)(q->adjoint_workspace ? q->adjoint_workspace_elems : 0), q->B, (long long)need);
     return EBOS_ERR_SCRATCH;
   }
-  if (q->cost_scratch_bytes < ebos_cost_scratch_bytes(q->B)) {
-    set_error("%s: cost_scratch too small for %d windows (%zu < %zu)", who, q->B, q->cost_scratch_bytes,
-              ebos_cost_scratch_bytes(q->B));
+  if (q->cost_scratch_bytes < ebos_cost_scratch_bytes(q->B * n_ref)) {
+    if (n_ref == 1)
+      set_error("%s: cost_scratch too small for %d windows (%zu < %zu)", who, q->B, q->cost_scratch_bytes,
+                ebos_cost_scratch_bytes(q->B));
+    else
+      set_error("%s: cost_scratch too small for %d windows x %d reference times (%zu < %zu)", who, q->B, n_ref, q->cost_scratch_bytes,
+                ebos_cost_scratch_bytes(q->B * n_ref));
     return EBOS_ERR_SCRATCH;
   }
   return EBOS_OK;
 }
 
 // theta -> ... -> d_dense (steps 1 to 7 of an iteration), every stage called once for the B windows; variance and reg_partials hold
-// the value's two parts
-int forward_backward(const char* who, const ebos_cmax_voxel_batch_problem* q, bool tiled, ebos_stream_t stream) {
+// the value's two parts.  With `mr` the images are [B, K, h, w] (variance, moments, upstream and affine hold B K entries, window-major)
+// and mr->value receives the windows' values.
+int forward_backward(const char* who, const ebos_cmax_voxel_batch_problem* q, bool tiled, ebos_stream_t stream,
+                     const MultiRef* mr = nullptr) {
+  const int n_img = q->B * (mr ? mr->K : 1);
   const int B = q->B, H = q->H, W = q->W, T = q->T, h = H + 2 * q->pad_h, w = W + 2 * q->pad_w;
   const int64_t cells = (int64_t)T * 2 * H * W;
   int rc = ebos_upsample_patch_flow_batch_f32(q->theta, B, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, H, W, q->dense,
@@ -86,24 +117,38 @@ int forward_backward(const char* who, const ebos_cmax_voxel_batch_problem* q, bo
     if (rc) return rc;
     vox = q->voxel_clamped;
   }
-  if (hipMemsetAsync(q->iwe, 0, (size_t)B * h * w * sizeof(float), as_stream(stream)) != hipSuccess) {
+  if (hipMemsetAsync(q->iwe, 0, (size_t)n_img * h * w * sizeof(float), as_stream(stream)) != hipSuccess) {
     set_error("%s: clearing the IWEs failed", who);
     return EBOS_ERR_LAUNCH;
   }
   // (halo <= 0 names no built configuration: the entry point falls back to the general kernel window by window)
-  rc = ebos_iwe_voxel_tiled_batch_f32(q->xs, q->ys, q->dts, q->bins, q->key_offsets, q->n, B, vox, T, H, W, q->tile_h, q->tile_w,
-                                      tiled ? q->halo : 0, q->splits, q->pad_h, q->pad_w, q->iwe, stream);
+  if (mr)
+    rc = ebos_iwe_voxel_multiref_tiled_batch_f32(q->xs, q->ys, q->dts, q->bins, q->key_offsets, q->n, B, vox, T, H, W, q->tile_h, q->tile_w,
+                                                 tiled ? q->halo : 0, q->splits, q->pad_h, q->pad_w, mr->shifts, mr->K, q->iwe, stream);
+  else
+    rc = ebos_iwe_voxel_tiled_batch_f32(q->xs, q->ys, q->dts, q->bins, q->key_offsets, q->n, B, vox, T, H, W, q->tile_h, q->tile_w,
+                                        tiled ? q->halo : 0, q->splits, q->pad_h, q->pad_w, q->iwe, stream);
   if (rc) return rc;
-  rc = ebos_image_variance_f32(q->iwe, B, h, w, q->omit_boundary, q->variance, q->moments, q->cost_scratch, q->cost_scratch_bytes, stream);
+  rc = ebos_image_variance_f32(q->iwe, n_img, h, w, q->omit_boundary, q->variance, q->moments, q->cost_scratch, q->cost_scratch_bytes,
+                               stream);
   if (rc) return rc;
-  rc = ebos_image_variance_affine_f32(q->moments, q->upstream, B, q->affine, stream);
+  rc = ebos_image_variance_affine_f32(q->moments, q->upstream, n_img, q->affine, stream);
   if (rc) return rc;
+  if (mr) {
+    multiref_value_kernel<<<dim3((B + 63) / 64), dim3(64), 0, as_stream(stream)>>>(q->variance, mr->inv_norm, B, mr->K, mr->value);
+    EBOS_CHECK_LAUNCH(who);  // (the windows' values)
+  }
   if (has_reg(q)) {
     rc = ebos_flow_regularisers_batch_f32(q->dense, B, H, W, q->w_flow_norm, q->w_image_gradient, q->d_reg, q->reg_partials, stream);
     if (rc) return rc;
   }
   const int g_lo = q->omit_boundary ? 1 : 0;
-  if (q->owner_bwd) {
+  if (mr) {
+    rc = ebos_iwe_voxel_multiref_owner_bwd_batch_f32(q->xs, q->ys, q->dts, q->bins, q->key_offsets, q->n, B, vox, T, H, W, q->tile_h,
+                                                     q->tile_w, q->pad_h, q->pad_w, mr->shifts, mr->K, q->iwe, q->affine, g_lo, q->d_voxel,
+                                                     stream);
+    if (rc) return rc;
+  } else if (q->owner_bwd) {
     rc = ebos_iwe_voxel_owner_bwd_batch_f32(q->xs, q->ys, q->dts, q->bins, q->key_offsets, q->n, B, vox, T, H, W, q->tile_h, q->tile_w,
                                             q->pad_h, q->pad_w, q->iwe, q->affine, g_lo, q->d_voxel, stream);
     if (rc) return rc;
@@ -132,26 +177,35 @@ int forward_backward(const char* who, const ebos_cmax_voxel_batch_problem* q, bo
   return EBOS_OK;
 }
 
-int solve(const char* who, const ebos_cmax_voxel_batch_problem* q, int n_iter, ebos_stream_t stream) {
+// the refusals K reference times add, then check_problem's
+int check_multiref(const char* who, const ebos_cmax_voxel_batch_problem* q, const MultiRef* mr) {
+  if (mr == nullptr) return check_problem(who, q);
+  EBOS_REQUIRE(mr->K >= 1 && mr->K <= EBOS_MULTIREF_MAX, "%s: K = %d is outside [1, %d]", who, mr->K, EBOS_MULTIREF_MAX);
+  for (int k = 0; k < mr->K; ++k) EBOS_REQUIRE(std::isfinite(mr->shifts[k]), "%s: shifts[%d] is not finite", who, k);
+  EBOS_REQUIRE(mr->inv_norm && mr->value, "%s: NULL inv_norm / value", who);
+  return check_problem(who, q, mr->K);
+}
+
+int solve(const char* who, const ebos_cmax_voxel_batch_problem* q, int n_iter, ebos_stream_t stream, const MultiRef* mr = nullptr) {
   EBOS_REQUIRE(n_iter >= 0, "%s: negative n_iter", who);
-  if (int rc = check_problem(who, q)) return rc;
+  if (int rc = check_multiref(who, q, mr)) return rc;
   const bool tiled = tiled_forward(q);
   const int n_reg = has_reg(q) ? ebos_flow_regularisers_partials() : 0;
   for (int it = 0; it < n_iter; ++it) {
-    if (int rc = forward_backward(who, q, tiled, stream)) return rc;
+    if (int rc = forward_backward(who, q, tiled, stream, mr)) return rc;
     // adjoint of the upsample + the Adam step of every grid element where its gradient appears + the loss of the iteration
     if (int rc = ebos_upsample_patch_flow_bwd_adam_batch_f32(
             q->d_dense, q->B, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W, q->upsample_scratch, q->d_theta,
-            q->theta, q->exp_avg, q->exp_avg_sq, q->lr, q->beta1, q->beta2, q->eps, q->steps_done + it + 1, q->step, q->variance,
-            -q->w_variance, q->reg_partials, n_reg, q->losses, q->losses_cap, q->theta_mask, stream))
+            q->theta, q->exp_avg, q->exp_avg_sq, q->lr, q->beta1, q->beta2, q->eps, q->steps_done + it + 1, q->step,
+            mr ? mr->value : q->variance, -q->w_variance, q->reg_partials, n_reg, q->losses, q->losses_cap, q->theta_mask, stream))
       return rc;
   }
   return EBOS_OK;
 }
 
-int gradient(const char* who, const ebos_cmax_voxel_batch_problem* q, ebos_stream_t stream) {
-  if (int rc = check_problem(who, q)) return rc;
-  if (int rc = forward_backward(who, q, tiled_forward(q), stream)) return rc;
+int gradient(const char* who, const ebos_cmax_voxel_batch_problem* q, ebos_stream_t stream, const MultiRef* mr = nullptr) {
+  if (int rc = check_multiref(who, q, mr)) return rc;
+  if (int rc = forward_backward(who, q, tiled_forward(q), stream, mr)) return rc;
   return ebos_upsample_patch_flow_bwd_batch_f32(q->d_dense, q->B, q->gh, q->gw, q->patch_h, q->patch_w, q->slide_h, q->slide_w, q->H, q->W,
                                                 q->upsample_scratch, q->d_theta, stream);
 }
@@ -172,6 +226,27 @@ ebos_cmax_voxel_batch_problem batch_of_one(const ebos_cmax_voxel_problem* q) {
   EBOS_COPY(cost_scratch_bytes) EBOS_COPY(reg_partials) EBOS_COPY(upsample_scratch) EBOS_COPY(adjoint_workspace)
   EBOS_COPY(adjoint_workspace_elems) EBOS_COPY(losses) EBOS_COPY(losses_cap) EBOS_COPY(theta_mask)
 #undef EBOS_COPY
+  return b;
+}
+
+// K reference times: the batch problem under the same field names (the owner backward is the only one), and what K adds
+ebos_cmax_voxel_batch_problem batch_of_multiref(const ebos_cmax_voxel_multiref_batch_problem* q, MultiRef* mr) {
+  ebos_cmax_voxel_batch_problem b{};
+  b.B = q->B, b.owner_bwd = 1;
+  for (int i = 0; i < EBOS_CMAX_VOXEL_MAX_BATCH; ++i) b.n[i] = q->n[i];
+#define EBOS_COPY(f) b.f = q->f;
+  EBOS_COPY(xs) EBOS_COPY(ys) EBOS_COPY(dts) EBOS_COPY(bins) EBOS_COPY(key_offsets)
+  EBOS_COPY(H) EBOS_COPY(W) EBOS_COPY(tile_h) EBOS_COPY(tile_w) EBOS_COPY(halo) EBOS_COPY(pad_h) EBOS_COPY(pad_w)
+  EBOS_COPY(omit_boundary) EBOS_COPY(splits) EBOS_COPY(T) EBOS_COPY(scheme) EBOS_COPY(t0_index) EBOS_COPY(wrap_last) EBOS_COPY(route)
+  EBOS_COPY(has_clamp) EBOS_COPY(clamp) EBOS_COPY(gh) EBOS_COPY(gw) EBOS_COPY(patch_h) EBOS_COPY(patch_w)
+  EBOS_COPY(slide_h) EBOS_COPY(slide_w) EBOS_COPY(w_variance) EBOS_COPY(w_flow_norm) EBOS_COPY(w_image_gradient) EBOS_COPY(lr)
+  EBOS_COPY(beta1) EBOS_COPY(beta2) EBOS_COPY(eps) EBOS_COPY(theta) EBOS_COPY(d_theta) EBOS_COPY(exp_avg) EBOS_COPY(exp_avg_sq)
+  EBOS_COPY(step) EBOS_COPY(steps_done) EBOS_COPY(dense) EBOS_COPY(d_dense) EBOS_COPY(d_reg) EBOS_COPY(voxel) EBOS_COPY(voxel_clamped)
+  EBOS_COPY(d_voxel) EBOS_COPY(iwe) EBOS_COPY(variance) EBOS_COPY(moments) EBOS_COPY(upstream) EBOS_COPY(affine) EBOS_COPY(cost_scratch)
+  EBOS_COPY(cost_scratch_bytes) EBOS_COPY(reg_partials) EBOS_COPY(upsample_scratch) EBOS_COPY(adjoint_workspace)
+  EBOS_COPY(adjoint_workspace_elems) EBOS_COPY(losses) EBOS_COPY(losses_cap) EBOS_COPY(theta_mask)
+#undef EBOS_COPY
+  mr->K = q->K, mr->shifts = q->shifts, mr->inv_norm = q->inv_norm, mr->value = q->value;
   return b;
 }
 
@@ -198,6 +273,20 @@ int ebos_cmax_voxel_gradient_f32(const ebos_cmax_voxel_problem* q, ebos_stream_t
   EBOS_REQUIRE(q != nullptr, "ebos_cmax_voxel_gradient: NULL problem");
   const ebos_cmax_voxel_batch_problem one = ebos::batch_of_one(q);
   return ebos::gradient("ebos_cmax_voxel_gradient", &one, stream);
+}
+
+int ebos_cmax_voxel_multiref_solve_batch_f32(const ebos_cmax_voxel_multiref_batch_problem* q, int n_iter, ebos_stream_t stream) {
+  EBOS_REQUIRE(q != nullptr, "ebos_cmax_voxel_multiref_solve_batch: NULL problem");
+  ebos::MultiRef mr;
+  const ebos_cmax_voxel_batch_problem one = ebos::batch_of_multiref(q, &mr);
+  return ebos::solve("ebos_cmax_voxel_multiref_solve_batch", &one, n_iter, stream, &mr);
+}
+
+int ebos_cmax_voxel_multiref_gradient_batch_f32(const ebos_cmax_voxel_multiref_batch_problem* q, ebos_stream_t stream) {
+  EBOS_REQUIRE(q != nullptr, "ebos_cmax_voxel_multiref_gradient_batch: NULL problem");
+  ebos::MultiRef mr;
+  const ebos_cmax_voxel_batch_problem one = ebos::batch_of_multiref(q, &mr);
+  return ebos::gradient("ebos_cmax_voxel_multiref_gradient_batch", &one, stream, &mr);
 }
 
 }  // extern "C"

@@ -219,7 +219,7 @@ class EventPlan:
     def clear_cache(self) -> None:
         """Free what the operators cached on the plan: workspaces, dense jobs and the sweep lanes of ``variance_2dof`` /
         ``variance_dense_many`` (streams, one workspace per hypothesis of a chunk, image buffers -- up to 1.7 GB at 1280x720)."""
-        for k in ("_workspaces", "_jobs", "_sweep_lanes", "_multiref_dts"):
+        for k in ("_workspaces", "_jobs", "_sweep_lanes", "_multiref_dts", "_canonical_stack"):
             self.__dict__.pop(k, None)
 
     def resolve_splits(self, splits: Optional[int]) -> int:
@@ -911,6 +911,59 @@ class EventPlan:
                   "ebos_iwe_voxel_owner_bwd")
         return value, out
 
+    # ------------------------------------------------------------------------------------------ time-aware warp at K reference times
+    def iwe_voxel_multi(self, voxel: torch.Tensor, directions, pad: Tuple[int, int] = (0, 0), halo: Optional[int] = DEFAULT_HALO,
+                        splits: Optional[int] = None) -> torch.Tensor:
+        """The time-aware IWEs of ``voxel`` [T, 2, H, W] at several reference times: ``directions`` holds 1 to 4 entries of ``'first' |
+        'middle' | 'last' | 'before' | 'after' | float`` -> iwes [K, H + 2 pad_h, W + 2 pad_w], entry k what a plan built with
+        direction k gives from ``iwe_voxel``.  Differentiable with respect to ``voxel`` for any upstream [K, h, w].
+
+        Reference k is the scalar shift f - r_k of every dt (``multi_reference_shifts``); the bin of an event does not depend on it.
+        One launch makes the K images (``ebos_iwe_voxel_multiref_tiled_f32``: the reference is an outer grid dimension of the tiled
+        kernel of ``iwe_voxel``; where (tile, halo) is no built configuration, the general kernel reference by reference) and one
+        launch the backward (``ebos_iwe_voxel_multiref_owner_bwd_f32``: an event is loaded and its flow gathered once for all
+        references; no atomics, every cell of d_voxel written, the same bits on every call).  ValueError as ``multi_reference_shifts``
+        and ``iwe_voxel``; NotImplementedError for an un-binned or deferred plan."""
+        job = _voxel_multi_job(self, directions, pad, halo, splits, "iwe_voxel_multi")
+        return _MultiRefIweVoxel.apply(voxel, self, job)
+
+    def contrast_voxel_multi(self, voxel: torch.Tensor, directions, cost: str = "image_variance", omit_boundary: bool = False,
+                             pad: Tuple[int, int] = (0, 0), halo: Optional[int] = DEFAULT_HALO,
+                             splits: Optional[int] = None) -> torch.Tensor:
+        """The time-aware multi-reference focus objective: the MEAN over the references of the raw contrast of ``iwe_voxel_multi``
+        (0-d tensor), differentiable with respect to ``voxel``.  For ``image_variance`` the K variances come from one
+        ``ebos_image_variance_f32`` call and their gradients are folded into the event backward as an affine map per reference (no
+        d_iwe images)."""
+        if cost not in ("image_variance", "gradient_magnitude"):
+            raise KeyError(f"unknown contrast cost {cost!r}")
+        job = _voxel_multi_job(self, directions, pad, halo, splits, "contrast_voxel_multi")
+        if cost == "image_variance":
+            return _MultiRefVarianceVoxel.apply(voxel, self, job, bool(omit_boundary))
+        return ops.gradient_magnitude(_MultiRefIweVoxel.apply(voxel, self, job), omit_boundary).mean()
+
+    def variance_voxel_multi_value_and_grad(self, voxel: torch.Tensor, directions, omit_boundary: bool = False,
+                                            pad: Tuple[int, int] = (0, 0), halo="auto", upstream: float = 1.0,
+                                            out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mean_k var(IWE_k(voxel)) [0-d] f32, ``upstream`` * its gradient d_voxel [T, 2, H, W] f32) without an autograd node: the
+        K-image forward, one variance call, its K affine maps and the K-reference owner backward.  ``out``: a caller-owned contiguous
+        float32 [T, 2, H, W] on the plan's device that is overwritten (it needs no clearing)."""
+        job = _voxel_multi_job(self, directions, pad, halo, None, "variance_voxel_multi_value_and_grad")
+        vox32 = _check_voxel(self, voxel)
+        lib = _hip.require_gpu()
+        H, W = self.image_size
+        T, K, dev = int(vox32.shape[0]), len(job.shifts), self.device
+        if out is not None and (tuple(out.shape) != (T, 2, H, W) or out.dtype != torch.float32 or out.device != dev
+                                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(T, 2, H, W)} on {dev}")
+        iwes = _launch_iwe_voxel_multi(self, vox32, job)
+        variances, moments = _image_variances(iwes, bool(omit_boundary))
+        up = torch.full((K,), float(upstream) / K, dtype=torch.float32, device=dev)
+        affine = torch.empty((K, 2), dtype=torch.float32, device=dev)
+        with _hip.on_device(dev):
+            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
+        d_voxel = _launch_voxel_multi_bwd(self, vox32, job, iwes, affine, int(bool(omit_boundary)), out)
+        return variances.mean(), d_voxel
+
 
 # ----------------------------------------------------------------------------------------------
 INT32_MAX = 2 ** 31 - 1
@@ -1080,6 +1133,32 @@ class TimeAwarePlanStack(object):
     @property
     def device(self) -> torch.device:
         return self.key_offsets.device
+
+    def canonical(self) -> "TimeAwarePlanStack":
+        """The same stack with the events of every source pixel's run in a canonical order: by (dt, x, y, bin).  A plan build leaves
+        the order inside a run to its counting sort's atomic counter, and a kernel that adds in run order (the owner backwards)
+        inherits it; on the canonical stack two builds of the same window give such a kernel the same bits.  Events that tie in all
+        four are interchangeable.  The offsets are shared, the four streams are new tensors; ``perm`` is not carried.  Cached on the
+        stack, and for a stack of one plan on that plan (a solver stacks the same plan again at every pyramid scale)."""
+        cached = self.__dict__.get("_canonical")
+        if cached is None and len(self.plans) == 1:
+            cached = self.__dict__["_canonical"] = self.plans[0].__dict__.get("_canonical_stack")
+        if cached is None:
+            cached = self.__dict__["_canonical"] = object.__new__(type(self))
+            cached.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_canonical", "perm")})
+            if self.n > 0:
+                n = self.n
+                x, y, dt, bins = self.x[:n], self.y[:n], self.dt[:n], self.bins[:n]
+                # the run of an event: the stacked offsets are non-decreasing over (window, key)
+                run = torch.searchsorted(self.key_offsets.reshape(-1).to(torch.int64), torch.arange(n, device=x.device), right=True)
+                order = torch.arange(n, device=x.device)
+                for key in (bins, y, x, dt, run):            # least significant first, each sort stable
+                    order = order[torch.sort(key[order], stable=True)[1]]
+                cached.x, cached.y, cached.dt, cached.bins = (v[order].contiguous() for v in (x, y, dt, bins))
+            cached.__dict__["_canonical"] = cached
+            if len(self.plans) == 1:
+                self.plans[0].__dict__["_canonical_stack"] = cached
+        return cached
 
     def ns_array(self):
         """The event counts as the ``int64_t`` host array of the C entry points."""
@@ -1883,6 +1962,114 @@ class _FusedVarianceVoxel(torch.autograd.Function):
         up = g.to(torch.float32).reshape(1).contiguous()
         d_voxel, _ = _launch_voxel_bwd(plan, vox32, None, pad, iwe, None, omit, False, moments, up)
         return d_voxel.to(vdt), None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# time-aware warp at K reference times: the voxel kernels with the reference as one more dimension
+# ----------------------------------------------------------------------------------------------
+class _VoxelMultiJob(NamedTuple):
+    shifts: Tuple[float, ...]   # float32 values
+    pad: Tuple[int, int]
+    halo: Optional[int]         # the built halo of the tiled kernel (None: the general kernel, reference by reference)
+    splits: int
+
+
+def _voxel_multi_job(plan: "EventPlan", directions, pad, halo, splits, what: str) -> _VoxelMultiJob:
+    shifts = tuple(multi_reference_shifts(plan, directions))
+    if plan.bins is None:
+        raise ValueError('the plan holds no time bins: build it with EventPlan.build(..., emit="full", time_bin=T)')
+    if not plan.binned:
+        raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
+    _refuse_deferred(plan, what)
+    return _VoxelMultiJob(shifts, (int(pad[0]), int(pad[1])), _voxel_halo(plan, halo), max(1, plan.resolve_splits(splits)))
+
+
+def _image_variances(images: torch.Tensor, omit: bool):
+    """(variances [K] f32, moments [K, 2] f64) of images [K, h, w] by one cost-kernel call."""
+    lib = _hip.require_gpu()
+    K, h, w = images.shape
+    out = torch.empty(K, dtype=torch.float32, device=images.device)
+    moments = torch.empty((K, 2), dtype=torch.float64, device=images.device)
+    nbytes = int(lib.ebos_cost_scratch_bytes(K))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
+    with _hip.on_device(images.device):
+        check(lib.ebos_image_variance_f32(ptr(images), K, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes, stream_ptr()),
+              "ebos_image_variance")
+    return out, moments
+
+
+def _launch_iwe_voxel_multi(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelMultiJob) -> torch.Tensor:
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    T, K, pad = int(vox32.shape[0]), len(job.shifts), job.pad
+    iwes = torch.zeros((K, H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_voxel_multiref_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.bins), ptr(plan.key_offsets), plan.n,
+                                                    ptr(vox32), T, H, W, plan.tile[0], plan.tile[1], 0 if job.halo is None else job.halo,
+                                                    job.splits, pad[0], pad[1], _c_shifts(job.shifts), K, ptr(iwes), stream_ptr()),
+              "ebos_iwe_voxel_multiref_tiled")
+    return iwes
+
+
+def _launch_voxel_multi_bwd(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelMultiJob, g_images: torch.Tensor,
+                            affine: Optional[torch.Tensor], g_lo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d_voxel [T, 2, H, W] = sum over the references of the event backward with upstream G_k = a_k g_images[k] + c_k."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    T, K, pad = int(vox32.shape[0]), len(job.shifts), job.pad
+    d_voxel = torch.empty((T, 2, H, W), dtype=torch.float32, device=plan.device) if out is None else out   # every cell is written
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_voxel_multiref_owner_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.bins), ptr(plan.key_offsets),
+                                                        plan.n, ptr(vox32), T, H, W, plan.tile[0], plan.tile[1], pad[0], pad[1],
+                                                        _c_shifts(job.shifts), K, ptr(g_images), ptr(affine), int(g_lo), ptr(d_voxel),
+                                                        stream_ptr()), "ebos_iwe_voxel_multiref_owner_bwd")
+    return d_voxel
+
+
+class _MultiRefIweVoxel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, voxel, plan, job):
+        vox32 = _check_voxel(plan, voxel)
+        iwes = _launch_iwe_voxel_multi(plan, vox32, job)
+        ctx.save_for_backward(vox32)
+        ctx.meta = (plan, job, voxel.dtype)
+        return iwes if voxel.dtype == torch.float32 else iwes.to(voxel.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (vox32,) = ctx.saved_tensors
+        plan, job, vdt = ctx.meta
+        d_voxel = _launch_voxel_multi_bwd(plan, vox32, job, g.to(torch.float32).contiguous(), None, 0)
+        return d_voxel.to(vdt), None, None
+
+
+class _MultiRefVarianceVoxel(torch.autograd.Function):
+    """mean_k var(IWE_k(voxel)): the K variances and their moments by one cost-kernel call; the event backward reads the IWEs through
+    the variances' affine maps, so no d_iwe image is made."""
+
+    @staticmethod
+    def forward(ctx, voxel, plan, job, omit):
+        vox32 = _check_voxel(plan, voxel)
+        iwes = _launch_iwe_voxel_multi(plan, vox32, job)
+        out, moments = _image_variances(iwes, omit)
+        ctx.save_for_backward(vox32, iwes, moments)
+        ctx.meta = (plan, job, int(omit), voxel.dtype)
+        return out.mean().to(voxel.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _hip.require_gpu()
+        vox32, iwes, moments = ctx.saved_tensors
+        plan, job, omit, vdt = ctx.meta
+        K = iwes.shape[0]
+        up = (g.to(torch.float32).reshape(1) / K).repeat(K).contiguous()
+        affine = torch.empty((K, 2), dtype=torch.float32, device=plan.device)
+        with _hip.on_device(plan.device):
+            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
+        d_voxel = _launch_voxel_multi_bwd(plan, vox32, job, iwes, affine, omit)
+        return d_voxel.to(vdt), None, None, None
 
 
 def _eager_ok(plan: EventPlan, flow: torch.Tensor, halo) -> bool:

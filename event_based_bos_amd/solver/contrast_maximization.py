@@ -29,6 +29,17 @@ explicit ``tile`` the plan takes a built tile of the time-aware forward kernel, 
 with optional ``flow_norm`` / ``image_gradient``, no ``iwe.blur_sigma``, Adam or a scipy method; the constructor raises
 ``NotImplementedError`` naming the key that leaves it.
 
+``time_aware.directions: [...]`` (optional; 1 to 4 of ``'first' | 'middle' | 'last' | 'before' | 'after' | float``) scores the
+time-aware flow at several reference times and averages the contrasts, ``time_aware.normalize: true`` (default false, needs
+``directions``) divides each by cost c of the window's zero-flow IWE (1 where that is 0):
+
+    loss(theta) = -(1/K) sum_k sum_c w_c C_c(blur(IWE_k(voxel(dense(theta))))) / N_c + regularisers
+
+``t0_location`` says where the base flow lives in the voxel and does not depend on the reference times.  Without ``native`` this is
+the autograd loop through ``EventPlan.contrast_voxel_multi`` / ``iwe_voxel_multi``; with ``native: true`` the loop of
+``time_aware_loop.TimeAwareMultiReferencePatchLoopBatch`` (``ebos_cmax_voxel_multiref_solve_batch_f32``), in the same family and
+with the same batch methods as ``native`` alone.  Without ``directions`` nothing changes.
+
 ``multi_reference: {directions: [...], normalize: false, fused: null}`` (optional, this build's; dense-flow only): the multi-reference
 focus objective against event collapse.  The same flow is scored at 1 to 4 reference times (``'first' | 'middle' | 'last' | 'before' |
 'after' | float``) and the contrasts are averaged:
@@ -71,14 +82,16 @@ SCIPY_METHODS = ("CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")  # first-order method
 
 
 def parse_time_aware(block) -> Optional[dict]:
-    """The ``time_aware`` block of the solver's configuration -> {time_bin, scheme, t0_location, clamp}, plus ``native`` where the block
-    gives it (absent means false), or None without one."""
+    """The ``time_aware`` block of the solver's configuration -> {time_bin, scheme, t0_location, clamp}, plus ``native``,
+    ``directions`` and ``normalize`` where the block gives them (absent means false / one reference time, the plan's own), or None
+    without one."""
     if block is None:
         return None
     block = dict(block)
-    unknown = sorted(set(block) - {"time_bin", "scheme", "t0_location", "clamp", "native"})
+    unknown = sorted(set(block) - {"time_bin", "scheme", "t0_location", "clamp", "native", "directions", "normalize"})
     if unknown:
-        raise ValueError(f"time_aware: unknown key(s) {unknown}; it takes time_bin, scheme, t0_location, clamp, native")
+        raise ValueError(f"time_aware: unknown key(s) {unknown}; it takes time_bin, scheme, t0_location, clamp, native, directions, "
+                         "normalize")
     if "time_bin" not in block:
         raise ValueError("time_aware needs time_bin, the number of bins of the flow voxel")
     out = {"time_bin": ops.check_time_bins(block["time_bin"]), "scheme": block.get("scheme", "upwind"),
@@ -91,6 +104,18 @@ def parse_time_aware(block) -> Optional[dict]:
         raise ValueError(f"time_aware.scheme must be 'upwind' or 'burgers', got {out['scheme']!r}")
     if out["t0_location"] not in ("first", "middle"):
         raise ValueError(f"time_aware.t0_location must be 'first' or 'middle', got {out['t0_location']!r}")
+    if "directions" in block:   # (the reference times the voxel is scored at; returned only where given, like native)
+        directions = block["directions"]
+        if isinstance(directions, (list, tuple)):
+            directions = [float(d) if isinstance(d, (int, float)) and not isinstance(d, bool) else d for d in directions]
+        multi_reference_fractions(directions)   # (ValueError for 'random', an empty list, more than four, an unknown name)
+        out["directions"] = list(directions)
+    if "normalize" in block:
+        if not isinstance(block["normalize"], bool):
+            raise ValueError(f"time_aware.normalize must be true or false, got {block['normalize']!r}")
+        if "directions" not in block:
+            raise ValueError("time_aware.normalize belongs to the multi-reference objective: it needs time_aware.directions")
+        out["normalize"] = block["normalize"]
     return out
 
 
@@ -226,8 +251,9 @@ class ContrastMaximizationMixin(object):
         self.multi_reference = parse_multi_reference(cfg.get("multi_reference"))
         if self.multi_reference is not None:
             if self.time_aware is not None:
-                raise NotImplementedError("multi_reference together with time_aware: the multi-reference objective is defined on the "
-                                          "plain dense-flow warp; drop one of the two blocks")
+                raise NotImplementedError("multi_reference together with time_aware: the multi_reference block is defined on the "
+                                          "plain dense-flow warp; to score the time-aware flow at several reference times, put "
+                                          "`directions` (and `normalize`) into the time_aware block and drop multi_reference")
             if self.motion_model != "dense-flow":
                 raise NotImplementedError(f"multi_reference is defined for motion_model 'dense-flow', not {self.motion_model!r}")
             self.use_graph = self.fused_loop = False
@@ -290,6 +316,26 @@ class ContrastMaximizationMixin(object):
             cached = plan.__dict__["_multiref_norms"] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
         return cached[1]
 
+    def _time_aware_norms(self, plan: EventPlan) -> Dict[str, float]:
+        """N_c of the ``time_aware`` loss with ``directions``: cost c of the window's zero-flow IWE (the same image at every reference
+        time and for every voxel bin), blurred like the objective's; once per plan, without gradient, 1 where the value is 0 -- or all
+        1 without ``normalize``."""
+        if not self.time_aware.get("normalize", False):
+            return {name: 1.0 for name in self.contrast_terms}
+        key = (self.pad, self.blur_sigma, self.omit_boundary, tuple(self.contrast_terms))
+        cached = plan.__dict__.get("_time_aware_norms")
+        if cached is None or cached[0] != key:
+            with torch.no_grad():
+                H, W = plan.image_size
+                zero = torch.zeros((self.time_aware["time_bin"], 2, H, W), dtype=torch.float32, device=plan.device)
+                iwe = plan.iwe_voxel(zero, pad=(self.pad, self.pad), halo=self.halo)
+                if self.blur_sigma > 0:
+                    iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
+                vals = {name: float((ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(iwe, self.omit_boundary))
+                        for name in self.contrast_terms}
+            cached = plan.__dict__["_time_aware_norms"] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
+        return cached[1]
+
     def _contrast(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
         total = 0.0
         if self.multi_reference is not None:
@@ -306,6 +352,21 @@ class ContrastMaximizationMixin(object):
                 total = total + (wgt / norms[name]) * plan.contrast_dense_multi(flow, mr["directions"], name, self.omit_boundary,
                                                                                 pad=(self.pad, self.pad), halo=self.halo,
                                                                                 fused=mr["fused"])
+            return total
+        if self.time_aware is not None and self.time_aware.get("directions") is not None:
+            ta = self.time_aware
+            voxel = flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0]
+            norms = self._time_aware_norms(plan)
+            if self.blur_sigma > 0:
+                iwes = plan.iwe_voxel_multi(voxel, ta["directions"], pad=(self.pad, self.pad), halo=self.halo)
+                iwes = EventImageConverter._gaussian_blur3(iwes, self.blur_sigma)
+                for name, wgt in self.contrast_terms.items():
+                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
+                    total = total + (wgt / norms[name]) * fn(iwes, self.omit_boundary).mean()
+                return total
+            for name, wgt in self.contrast_terms.items():
+                total = total + (wgt / norms[name]) * plan.contrast_voxel_multi(voxel, ta["directions"], name, self.omit_boundary,
+                                                                                pad=(self.pad, self.pad), halo=self.halo)
             return total
         if self.time_aware is not None:
             ta = self.time_aware
@@ -466,10 +527,12 @@ class ContrastMaximizationMixin(object):
             mask = None if masks[0] is None else torch.stack(masks)
             if mask is not None:
                 init = init * mask[:, None]
-            loop = time_aware_loop.TimeAwarePatchLoopBatch(stack, patch_size, sliding_window, init, self.time_aware,
-                                                           self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
-                                                           self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
-                                                           self.halo, self.lr, capacity=n_iter, theta_mask=mask)
+            loop_cls = (time_aware_loop.TimeAwarePatchLoopBatch if self.time_aware.get("directions") is None
+                        else time_aware_loop.TimeAwareMultiReferencePatchLoopBatch)
+            loop = loop_cls(stack, patch_size, sliding_window, init, self.time_aware,
+                            self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
+                            self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo, self.lr, capacity=n_iter,
+                            theta_mask=mask)
             loop.run(n_iter)
             self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
             self.loop_modes.append(loop.last_run_mode)
@@ -558,10 +621,11 @@ class ContrastMaximizationMixin(object):
         H, W = self.orig_image_shape
         capacity = n_iter if self.opt_method == "Adam" else 1   # (of a native block's loop: a scipy method records no losses there)
         if self.time_aware is not None and self.time_aware.get("native", False):
-            loop = time_aware_loop.TimeAwarePatchLoop(plan, patch_size, sliding_window, theta.detach(), self.time_aware,
-                                                      self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
-                                                      self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo,
-                                                      self.lr, capacity=capacity, theta_mask=mask)
+            loop_cls = (time_aware_loop.TimeAwarePatchLoop if self.time_aware.get("directions") is None
+                        else time_aware_loop.TimeAwareMultiReferencePatchLoop)
+            loop = loop_cls(plan, patch_size, sliding_window, theta.detach(), self.time_aware, self.contrast_terms["image_variance"],
+                            self.flow_terms.get("flow_norm", 0.0), self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
+                            self.halo, self.lr, capacity=capacity, theta_mask=mask)
             return self._optimise_native(loop, theta, n_iter)
         if self.multi_reference is not None and self.multi_reference.get("native", False):
             norm = self._multi_reference_norms(plan)["image_variance"]

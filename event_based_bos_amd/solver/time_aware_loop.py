@@ -23,6 +23,15 @@ anything else belongs to the autograd loop of ``ContrastMaximization``.
 
 One window is a batch of one, on the same code path: ``TimeAwarePatchLoop`` is the face of a ``TimeAwarePatchLoopBatch`` of B = 1
 without the window dimension.
+
+``time_aware.directions`` (K reference times, ``TimeAwareMultiReferencePatchLoopBatch`` and its one-window face): the same loop on
+B K images, ``ebos_cmax_voxel_multiref_solve_batch_f32`` --
+
+    loss(theta) = -(w / (K N)) sum_k var(IWE_k(events warped by voxel(dense(theta)), reference time k)) + the regularisers
+
+with ``ebos_iwe_voxel_multiref_tiled_batch_f32`` and ``ebos_iwe_voxel_multiref_owner_bwd_batch_f32`` in the place of the forward and
+the backward (an event is loaded and its bin's flow gathered once for all K references; d_voxel is written once), and N the variance
+of the window's zero-flow IWE with ``time_aware.normalize`` (1 without it).
 """
 from __future__ import annotations
 
@@ -54,6 +63,8 @@ class TimeAwarePatchLoopBatch(object):
     ``default_owner_bwd(T, the largest window)``."""
     graphed = False
     last_run_mode = "native-batch"
+    K = None                   # reference times per window (None: one, the plan's own; the image buffers then have no such dimension)
+    _SOLVE, _GRADIENT = "ebos_cmax_voxel_solve_batch", "ebos_cmax_voxel_gradient_batch"   # the C entry points, without _f32
 
     def __init__(self, plans, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
                  time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
@@ -100,12 +111,13 @@ class TimeAwarePatchLoopBatch(object):
         self.d_reg = torch.empty((B, 2, H, W), **f32) if self.has_reg else None
         self.voxel, self.d_voxel = torch.empty((B, self.T, 2, H, W), **f32), torch.empty((B, self.T, 2, H, W), **f32)
         self.voxel_clamped = torch.empty_like(self.voxel) if self.clamp is not None else None
-        self.iwe = torch.empty((B, H + 2 * self.pad[0], W + 2 * self.pad[1]), **f32)
-        self.variance = torch.empty(B, **f32)
-        self.moments = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        self.upstream = torch.full((B,), -self.w_var, **f32)   # loss = -w * contrast, per window
-        self.affine = torch.empty((B, 2), **f32)
-        self.cost_scratch = torch.empty(int(lib.ebos_cost_scratch_bytes(B)), dtype=torch.uint8, device=dev)
+        lead = (B,) if self.K is None else (B, self.K)         # one image per window, or per (window, reference time)
+        self.iwe = torch.empty(lead + (H + 2 * self.pad[0], W + 2 * self.pad[1]), **f32)
+        self.variance = torch.empty(lead, **f32)
+        self.moments = torch.empty(lead + (2,), dtype=torch.float64, device=dev)
+        self.upstream = torch.full(lead, -self.w_var / (self.K or 1), **f32)   # loss = -w * (mean) contrast, per window
+        self.affine = torch.empty(lead + (2,), **f32)
+        self.cost_scratch = torch.empty(int(lib.ebos_cost_scratch_bytes(B * (self.K or 1))), dtype=torch.uint8, device=dev)
         self.n_reg = int(lib.ebos_flow_regularisers_partials()) if self.has_reg else 0
         self.reg_partials = torch.zeros((B, max(self.n_reg, 1)), dtype=torch.float64, device=dev)
         self.scratch_up = torch.empty(B * (int(lib.ebos_upsample_bwd_scratch_bytes(self.gh, W)) // 4), **f32)
@@ -151,35 +163,93 @@ class TimeAwarePatchLoopBatch(object):
             raise ValueError(f"capacity {self.losses.shape[1]} < {self.t} steps done + {n_iter}")
         t0 = self.t
         with _hip.on_device(self.stack.device):
-            check(self.lib.ebos_cmax_voxel_solve_batch_f32(ctypes.byref(self.problem()), n_iter, stream_ptr()), "ebos_cmax_voxel_solve_batch")
+            check(getattr(self.lib, self._SOLVE + "_f32")(ctypes.byref(self.problem()), n_iter, stream_ptr()), self._SOLVE)
         self.t += n_iter
         return self.losses[:, t0:t0 + n_iter]
+
+    def _contrast(self) -> torch.Tensor:
+        """[B]: what the last forward left as every window's contrast."""
+        return self.variance
 
     def value_and_grad(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(losses [B], d loss / d theta [B, 2, gh, gw]) at ``theta`` through the same kernels, without the Adam step."""
         with _hip.on_device(self.stack.device):
             self.theta.copy_(theta.detach().to(self.theta))
-            check(self.lib.ebos_cmax_voxel_gradient_batch_f32(ctypes.byref(self.problem()), stream_ptr()), "ebos_cmax_voxel_gradient_batch")
-            loss = -self.w_var * self.variance
+            check(getattr(self.lib, self._GRADIENT + "_f32")(ctypes.byref(self.problem()), stream_ptr()), self._GRADIENT)
+            loss = -self.w_var * self._contrast()
             if self.n_reg:
                 loss = loss + self.reg_partials.sum(dim=1).to(torch.float32)
         return loss, (self.d_theta.clone() if self.theta_mask is None else self.d_theta * self.theta_mask[:, None])
 
 
-class TimeAwarePatchLoop(object):
-    """One window: the face of a ``TimeAwarePatchLoopBatch`` of B = 1 (``batch``) without the window dimension.  ``theta0`` and the
-    state ``theta`` / ``d_theta`` / ``exp_avg`` / ``exp_avg_sq`` are [2, gh, gw], ``theta_mask`` [gh, gw], ``losses`` [capacity]: views
-    of the batch's buffers, so writing into them writes what the kernels read.  Every other attribute is the batch's."""
+class TimeAwareMultiReferencePatchLoopBatch(TimeAwarePatchLoopBatch):
+    """The loop at K reference times: ``time_aware`` carries ``directions`` (1 to 4 reference times, ``multi_reference_fractions``) and
+    optionally ``normalize``.  The interface and the buffers are ``TimeAwarePatchLoopBatch``'s with the images per (window, reference):
+    ``iwe`` [B, K, h, w], ``variance`` / ``upstream`` [B, K], ``moments`` / ``affine`` [B, K, 2]; ``value`` [B] holds
+    ``inv_norm[b] * mean_k variance[b, k]`` and ``inv_norm`` [B] the windows' 1 / N.  Only the owner backward exists for K references."""
+    _SOLVE, _GRADIENT = "ebos_cmax_voxel_multiref_solve_batch", "ebos_cmax_voxel_multiref_gradient_batch"
+
+    def __init__(self, plans, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
+                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
+                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None):
+        from ..event_plan import multi_reference_shifts
+
+        ta = dict(time_aware)
+        if ta.get("directions") is None:
+            raise ValueError("time_aware.directions is missing: the reference times the voxel is scored at")
+        stack = plans if isinstance(plans, TimeAwarePlanStack) else EventPlan.stack_time_aware(plans)
+        self.shifts = multi_reference_shifts(stack, ta["directions"])   # (ValueError before any buffer is made)
+        self.K = K = len(self.shifts)
+        # every stage that adds in run order is the owner backward: on the canonical order of a pixel's events two builds of a
+        # window's plan give the same d_voxel, bit for bit, and so the same solve
+        stack = stack.canonical()
+        super().__init__(stack, patch_size, sliding_window, theta0, ta, w_variance, w_flow_norm, w_image_gradient, omit_boundary, pad,
+                         halo, lr, betas, eps, capacity, theta_mask, owner_bwd=True)
+        lib, B, dev = self.lib, self.B, stack.device
+        H, W = stack.image_size
+        h, w = H + 2 * self.pad[0], W + 2 * self.pad[1]
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.inv_norm = torch.ones(B, **f32)
+        if ta.get("normalize", False):   # N: the variance of the window's zero-flow IWE (the same image at every reference time)
+            iwe0 = torch.zeros((B, h, w), **f32)
+            var0 = torch.empty(B, **f32)
+            with _hip.on_device(dev):
+                self.voxel.zero_()
+                check(lib.ebos_iwe_voxel_tiled_batch_f32(ptr(stack.x), ptr(stack.y), ptr(stack.dt), ptr(stack.bins), ptr(stack.key_offsets),
+                                                         stack.ns_array(), B, ptr(self.voxel), self.T, H, W, stack.tile[0], stack.tile[1],
+                                                         self.halo, self.splits, self.pad[0], self.pad[1], ptr(iwe0), stream_ptr()),
+                      "ebos_iwe_voxel_tiled_batch")
+                check(lib.ebos_image_variance_f32(ptr(iwe0), B, h, w, int(self.omit), ptr(var0), None, ptr(self.cost_scratch),
+                                                  self.cost_scratch.numel(), stream_ptr()), "ebos_image_variance")
+            self.inv_norm = torch.where(var0 == 0, torch.ones_like(var0), 1.0 / var0).contiguous()
+            self.upstream.mul_(self.inv_norm[:, None])         # loss = -(w / (K N)) sum_k var_k
+        self.value = torch.empty(B, **f32)
+
+    def problem(self) -> "_hip.CmaxVoxelMultirefBatchProblem":
+        """The loop's buffers as the ``ebos_cmax_voxel_multiref_batch_problem`` struct of the C ABI."""
+        base = super().problem()
+        q = _hip.CmaxVoxelMultirefBatchProblem()
+        for name, _ in _hip.CmaxVoxelMultirefBatchProblem._fields_:
+            if hasattr(base, name):
+                setattr(q, name, getattr(base, name))
+        q.K = self.K
+        for k, s in enumerate(self.shifts):
+            q.shifts[k] = s
+        q.inv_norm, q.value = ptr(self.inv_norm), ptr(self.value)
+        return q
+
+    def _contrast(self) -> torch.Tensor:
+        return self.value
+
+
+class _OneWindow(object):
+    """One window: the face of a batch loop of B = 1 (``batch``) without the window dimension (``TimeAwarePatchLoop``)."""
     graphed = False
     last_run_mode = "native"
 
-    def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
-                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
-                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
-                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None, owner_bwd: Optional[bool] = None):
-        self.plan = plan
-        self.batch = b = TimeAwarePatchLoopBatch([plan], patch_size, sliding_window, theta0[None], time_aware, w_variance, w_flow_norm,
-                                                 w_image_gradient, omit_boundary, pad, halo, lr, betas, eps, capacity, theta_mask, owner_bwd)
+    def _face(self, batch) -> None:
+        self.batch = b = batch
         self.theta, self.d_theta, self.exp_avg, self.exp_avg_sq, self.losses = b.theta[0], b.d_theta[0], b.exp_avg[0], b.exp_avg_sq[0], b.losses[0]
 
     def __getattr__(self, name):                       # (only what the face does not hold itself: step, voxel, iwe, affine, ...)
@@ -198,3 +268,30 @@ class TimeAwarePatchLoop(object):
         that live on the host (scipy)."""
         loss, grad = self.batch.value_and_grad(theta[None])
         return loss[0], grad[0]
+
+
+class TimeAwareMultiReferencePatchLoop(_OneWindow):
+    """One window at K reference times: the face of a ``TimeAwareMultiReferencePatchLoopBatch`` of B = 1."""
+
+    def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
+                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
+                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None):
+        self.plan = plan
+        self._face(TimeAwareMultiReferencePatchLoopBatch([plan], patch_size, sliding_window, theta0[None], time_aware, w_variance,
+                                                         w_flow_norm, w_image_gradient, omit_boundary, pad, halo, lr, betas, eps, capacity,
+                                                         theta_mask))
+
+
+class TimeAwarePatchLoop(_OneWindow):
+    """One window: the face of a ``TimeAwarePatchLoopBatch`` of B = 1 (``batch``) without the window dimension.  ``theta0`` and the
+    state ``theta`` / ``d_theta`` / ``exp_avg`` / ``exp_avg_sq`` are [2, gh, gw], ``theta_mask`` [gh, gw], ``losses`` [capacity]: views
+    of the batch's buffers, so writing into them writes what the kernels read.  Every other attribute is the batch's."""
+
+    def __init__(self, plan: EventPlan, patch_size: Tuple[int, int], sliding_window: Tuple[int, int], theta0: torch.Tensor,
+                 time_aware: dict, w_variance: float = 1.0, w_flow_norm: float = 0.0, w_image_gradient: float = 0.0,
+                 omit_boundary: bool = False, pad: int = 0, halo="auto", lr: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8,
+                 capacity: int = 1024, theta_mask: Optional[torch.Tensor] = None, owner_bwd: Optional[bool] = None):
+        self.plan = plan
+        self._face(TimeAwarePatchLoopBatch([plan], patch_size, sliding_window, theta0[None], time_aware, w_variance, w_flow_norm,
+                                           w_image_gradient, omit_boundary, pad, halo, lr, betas, eps, capacity, theta_mask, owner_bwd))

@@ -1812,6 +1812,104 @@ typedef struct ebos_cmax_voxel_batch_problem {
 int ebos_cmax_voxel_solve_batch_f32(const ebos_cmax_voxel_batch_problem* problem, int n_iter, ebos_stream_t stream);
 int ebos_cmax_voxel_gradient_batch_f32(const ebos_cmax_voxel_batch_problem* problem, ebos_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Time-aware warp at K <= EBOS_MULTIREF_MAX reference times (csrc/warp_voxel_multiref.hip): the flow voxel of the time-aware
+ * entries above, scored at K reference times as the multi-reference entries score a dense flow.  The plan is binned, time-aware
+ * and built with normalised time; reference k is the scalar shifts[k] = f - r_k (HOST memory, float [K], finite):
+ *     dt_k = dt + shifts[k] (float32; shifts[k] == 0: dt as it is)
+ *     x'_k = x - dt_k * voxel[bin][0][src],  y'_k = y - dt_k * voxel[bin][1][src];  the bin of an event does not depend on k.
+ * The stacked plan, ns, B and the voxels [B, T, 2, H, W] are those of ebos_iwe_voxel_tiled_batch_f32.  No per-event weights.
+ *   ebos_iwe_voxel_multiref_tiled_batch_f32      work item (tile, split, window, reference): grid (tiles * splits, B, K), ONE LDS
+ *       window per workgroup, the body, accumulator rule and spill path (exact for any displacement) of ebos_iwe_voxel_tiled_f32.
+ *       ACCUMULATES into iwes [B, K, h, w], which the caller zero-fills once.  Every ebos_tiled_config is served; where
+ *       (tile_h, tile_w, halo) is none, the general global-atomic kernel runs window by window and reference by reference.
+ *   ebos_iwe_voxel_multiref_owner_bwd_batch_f32  d_voxel[b][bin][c][i] = sum over the events e of window b with source pixel i and
+ *       that bin, and over the references k, of -dt_k * dL/d(x', y')_{e,k}; the four taps are read from G_k = a_k * g_images[b][k] +
+ *       c_k (g_images [B, K, h, w]; affine [B, K, 2] on the device, nullable: a = 1, c = 0), G_k = 0 outside
+ *       [g_lo, h - g_lo) x [g_lo, w - g_lo).  The organisation of ebos_iwe_voxel_owner_bwd_batch_f32 -- one lane per source-pixel key,
+ *       the three regimes of a run's length -- with the events loaded and their flow cells gathered ONCE and the references swept
+ *       per chunk of events; an event's addend is summed over k = 0 .. K - 1 before the per-bin sums.  No atomics;
+ *       d_voxel [B, T, 2, H, W] is OVERWRITTEN, every cell (zeros where nothing lands, empty windows included); the order of the
+ *       additions is the plan's, so two calls give the same bits, and a window's bits do not depend on its place in the batch.
+ *   ebos_iwe_voxel_multiref_tiled_f32 / ebos_iwe_voxel_multiref_owner_bwd_f32: one window -- the batch entries with B = 1
+ *       (iwes [K, h, w], g_images [K, h, w], affine [K, 2], d_voxel [T, 2, H, W]).
+ * Refused before any launch (EBOS_ERR_INVALID_ARG): K outside [1, EBOS_MULTIREF_MAX], NULL or non-finite shifts, and what the
+ * single-reference entries refuse.
+ * ---------------------------------------------------------------------------------------- */
+int ebos_iwe_voxel_multiref_tiled_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                      const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                                      int tile_w, int halo, int splits, int pad_h, int pad_w, const float* shifts, int K, float* iwes,
+                                      ebos_stream_t stream);
+int ebos_iwe_voxel_multiref_owner_bwd_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                          const int32_t* key_offsets, int64_t n, const float* voxel, int T, int H, int W, int tile_h,
+                                          int tile_w, int pad_h, int pad_w, const float* shifts, int K, const float* g_images,
+                                          const float* affine, int g_lo, float* d_voxel, ebos_stream_t stream);
+int ebos_iwe_voxel_multiref_tiled_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                            const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H,
+                                            int W, int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w,
+                                            const float* shifts, int K, float* iwes, ebos_stream_t stream);
+int ebos_iwe_voxel_multiref_owner_bwd_batch_f32(const float* xs, const float* ys, const float* dts, const uint8_t* bins,
+                                                const int32_t* key_offsets, const int64_t* ns, int B, const float* voxel, int T, int H,
+                                                int W, int tile_h, int tile_w, int pad_h, int pad_w, const float* shifts, int K,
+                                                const float* g_images, const float* affine, int g_lo, float* d_voxel,
+                                                ebos_stream_t stream);
+
+/* ebos_cmax_voxel_multiref_solve_batch_f32: the time-aware loop above scored at K reference times (the solver's `time_aware` block
+ * with `directions` and `native: true`).  Per window
+ *     loss(theta) = -(w_variance inv_norm / K) sum_k var(IWE_k(events warped by voxel(dense(theta)))) + the regularisers
+ * through the stages of ebos_cmax_voxel_solve_batch_f32 -- its code -- on B K images:
+ *     ebos_upsample_patch_flow_batch_f32 -> ebos_flow_voxel_advect_f32 [+ clamp] -> one memset of B K IWEs
+ *     -> ebos_iwe_voxel_multiref_tiled_batch_f32 -> ebos_image_variance_f32 + ebos_image_variance_affine_f32 over B K images
+ *     -> value[b] = inv_norm[b] * mean_k variance[b][k] (one small kernel) [-> ebos_flow_regularisers_batch_f32]
+ *     -> ebos_iwe_voxel_multiref_owner_bwd_batch_f32 -> ebos_flow_voxel_advect_adjoint_f32 [-> d_dense += d_reg]
+ *     -> ebos_upsample_patch_flow_bwd_adam_batch_f32 (contrast = value, contrast_scale = -w_variance)
+ * The fields are ebos_cmax_voxel_batch_problem's, without owner_bwd (only the owner backward exists for K references), plus
+ *   K, shifts:  1 <= K <= EBOS_MULTIREF_MAX reference times, shifts[k] = f - r_k (finite)
+ *   inv_norm:   [B] f32 on the device, 1 / N of the block's `normalize` (N: the variance of the window's zero-flow IWE), 1 without it
+ *   images:     iwe [B, K, h, w], variance [B, K] f32, moments [B, K, 2] f64, affine [B, K, 2] f32,
+ *               upstream [B, K] f32 = -w_variance inv_norm[b] / K, value [B] f32
+ *   scratch:    cost_scratch of ebos_cost_scratch_bytes(B K)
+ * t0_index says where the base flow lives in the voxel and is independent of the reference times.  Refused before the first launch,
+ * under the caller's entry-point name: a NULL problem, K outside [1, EBOS_MULTIREF_MAX], a non-finite shift, NULL inv_norm / value,
+ * a cost_scratch too small for B K images (EBOS_ERR_SCRATCH), and everything ebos_cmax_voxel_solve_batch_f32 refuses.
+ * ebos_cmax_voxel_multiref_gradient_batch_f32: one forward and backward at theta without the Adam step -- d_theta, value and
+ *   reg_partials are left for the caller (loss[b] = -w_variance * value[b] + sum(reg_partials[b])). */
+typedef struct ebos_cmax_voxel_multiref_batch_problem {
+  int B;
+  const float *xs, *ys, *dts;
+  const uint8_t* bins;
+  const int32_t* key_offsets;
+  int64_t n[EBOS_CMAX_VOXEL_MAX_BATCH];
+  int H, W, tile_h, tile_w, halo, pad_h, pad_w, omit_boundary, splits;
+  int T, scheme, t0_index, wrap_last, route, has_clamp;
+  double clamp;
+  int K;
+  float shifts[EBOS_MULTIREF_MAX];
+  int gh, gw, patch_h, patch_w, slide_h, slide_w;
+  float w_variance, w_flow_norm, w_image_gradient;
+  double lr, beta1, beta2, eps;
+  float *theta, *d_theta, *exp_avg, *exp_avg_sq;
+  int* step;
+  int steps_done;
+  float *dense, *d_dense, *d_reg, *voxel, *voxel_clamped, *d_voxel, *iwe, *variance;
+  double* moments;
+  const float* upstream;
+  float* affine;
+  const float* inv_norm;
+  float* value;
+  void* cost_scratch;
+  size_t cost_scratch_bytes;
+  double* reg_partials;
+  float* upsample_scratch;
+  float* adjoint_workspace;
+  int64_t adjoint_workspace_elems;
+  float* losses;
+  int losses_cap;
+  const float* theta_mask;
+} ebos_cmax_voxel_multiref_batch_problem;
+int ebos_cmax_voxel_multiref_solve_batch_f32(const ebos_cmax_voxel_multiref_batch_problem* problem, int n_iter, ebos_stream_t stream);
+int ebos_cmax_voxel_multiref_gradient_batch_f32(const ebos_cmax_voxel_multiref_batch_problem* problem, ebos_stream_t stream);
+
 /* ---- the stacked plan above for B windows, built from the raw sensor columns in one set of launches (csrc/plan_time_aware.hip) ----
  * col / row int16, t int32 (t_is_64 = 0) or int64 ticks: device columns of n_total events.  ranges: HOST int64 [B, 2], window b =
  * events [begin, end) of the columns; the ranges may overlap, come in any order and be empty.  An event is kept when it lies inside
