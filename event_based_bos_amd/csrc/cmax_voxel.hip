@@ -210,22 +210,25 @@ int gradient(const char* who, const ebos_cmax_voxel_batch_problem* q, ebos_strea
                                                 q->upsample_scratch, q->d_theta, stream);
 }
 
+// the fields the three problem structs of include/ebos_hip.h share under one name (all but B / n, owner_bwd and what K adds)
+#define EBOS_CMAX_VOXEL_SHARED_FIELDS(X)                                                                                          \
+  X(xs) X(ys) X(dts) X(bins) X(key_offsets)                                                                                        \
+  X(H) X(W) X(tile_h) X(tile_w) X(halo) X(pad_h) X(pad_w)                                                                          \
+  X(omit_boundary) X(splits) X(T) X(scheme) X(t0_index) X(wrap_last) X(route)                                                      \
+  X(has_clamp) X(clamp) X(gh) X(gw) X(patch_h) X(patch_w)                                                                          \
+  X(slide_h) X(slide_w) X(w_variance) X(w_flow_norm) X(w_image_gradient) X(lr)                                                     \
+  X(beta1) X(beta2) X(eps) X(theta) X(d_theta) X(exp_avg) X(exp_avg_sq)                                                            \
+  X(step) X(steps_done) X(dense) X(d_dense) X(d_reg) X(voxel) X(voxel_clamped)                                                     \
+  X(d_voxel) X(iwe) X(variance) X(moments) X(upstream) X(affine) X(cost_scratch)                                                   \
+  X(cost_scratch_bytes) X(reg_partials) X(upsample_scratch) X(adjoint_workspace)                                                   \
+  X(adjoint_workspace_elems) X(losses) X(losses_cap) X(theta_mask)
+#define EBOS_COPY(f) b.f = q->f;
+
 // one window as a batch of one: B = 1, n[0] = n, every other field under its own name
 ebos_cmax_voxel_batch_problem batch_of_one(const ebos_cmax_voxel_problem* q) {
   ebos_cmax_voxel_batch_problem b{};
-  b.B = 1, b.n[0] = q->n;
-#define EBOS_COPY(f) b.f = q->f;
-  EBOS_COPY(xs) EBOS_COPY(ys) EBOS_COPY(dts) EBOS_COPY(bins) EBOS_COPY(key_offsets)
-  EBOS_COPY(H) EBOS_COPY(W) EBOS_COPY(tile_h) EBOS_COPY(tile_w) EBOS_COPY(halo) EBOS_COPY(pad_h) EBOS_COPY(pad_w)
-  EBOS_COPY(omit_boundary) EBOS_COPY(splits) EBOS_COPY(T) EBOS_COPY(scheme) EBOS_COPY(t0_index) EBOS_COPY(wrap_last) EBOS_COPY(route)
-  EBOS_COPY(has_clamp) EBOS_COPY(clamp) EBOS_COPY(owner_bwd) EBOS_COPY(gh) EBOS_COPY(gw) EBOS_COPY(patch_h) EBOS_COPY(patch_w)
-  EBOS_COPY(slide_h) EBOS_COPY(slide_w) EBOS_COPY(w_variance) EBOS_COPY(w_flow_norm) EBOS_COPY(w_image_gradient) EBOS_COPY(lr)
-  EBOS_COPY(beta1) EBOS_COPY(beta2) EBOS_COPY(eps) EBOS_COPY(theta) EBOS_COPY(d_theta) EBOS_COPY(exp_avg) EBOS_COPY(exp_avg_sq)
-  EBOS_COPY(step) EBOS_COPY(steps_done) EBOS_COPY(dense) EBOS_COPY(d_dense) EBOS_COPY(d_reg) EBOS_COPY(voxel) EBOS_COPY(voxel_clamped)
-  EBOS_COPY(d_voxel) EBOS_COPY(iwe) EBOS_COPY(variance) EBOS_COPY(moments) EBOS_COPY(upstream) EBOS_COPY(affine) EBOS_COPY(cost_scratch)
-  EBOS_COPY(cost_scratch_bytes) EBOS_COPY(reg_partials) EBOS_COPY(upsample_scratch) EBOS_COPY(adjoint_workspace)
-  EBOS_COPY(adjoint_workspace_elems) EBOS_COPY(losses) EBOS_COPY(losses_cap) EBOS_COPY(theta_mask)
-#undef EBOS_COPY
+  b.B = 1, b.n[0] = q->n, b.owner_bwd = q->owner_bwd;
+  EBOS_CMAX_VOXEL_SHARED_FIELDS(EBOS_COPY)
   return b;
 }
 
@@ -234,21 +237,12 @@ ebos_cmax_voxel_batch_problem batch_of_multiref(const ebos_cmax_voxel_multiref_b
   ebos_cmax_voxel_batch_problem b{};
   b.B = q->B, b.owner_bwd = 1;
   for (int i = 0; i < EBOS_CMAX_VOXEL_MAX_BATCH; ++i) b.n[i] = q->n[i];
-#define EBOS_COPY(f) b.f = q->f;
-  EBOS_COPY(xs) EBOS_COPY(ys) EBOS_COPY(dts) EBOS_COPY(bins) EBOS_COPY(key_offsets)
-  EBOS_COPY(H) EBOS_COPY(W) EBOS_COPY(tile_h) EBOS_COPY(tile_w) EBOS_COPY(halo) EBOS_COPY(pad_h) EBOS_COPY(pad_w)
-  EBOS_COPY(omit_boundary) EBOS_COPY(splits) EBOS_COPY(T) EBOS_COPY(scheme) EBOS_COPY(t0_index) EBOS_COPY(wrap_last) EBOS_COPY(route)
-  EBOS_COPY(has_clamp) EBOS_COPY(clamp) EBOS_COPY(gh) EBOS_COPY(gw) EBOS_COPY(patch_h) EBOS_COPY(patch_w)
-  EBOS_COPY(slide_h) EBOS_COPY(slide_w) EBOS_COPY(w_variance) EBOS_COPY(w_flow_norm) EBOS_COPY(w_image_gradient) EBOS_COPY(lr)
-  EBOS_COPY(beta1) EBOS_COPY(beta2) EBOS_COPY(eps) EBOS_COPY(theta) EBOS_COPY(d_theta) EBOS_COPY(exp_avg) EBOS_COPY(exp_avg_sq)
-  EBOS_COPY(step) EBOS_COPY(steps_done) EBOS_COPY(dense) EBOS_COPY(d_dense) EBOS_COPY(d_reg) EBOS_COPY(voxel) EBOS_COPY(voxel_clamped)
-  EBOS_COPY(d_voxel) EBOS_COPY(iwe) EBOS_COPY(variance) EBOS_COPY(moments) EBOS_COPY(upstream) EBOS_COPY(affine) EBOS_COPY(cost_scratch)
-  EBOS_COPY(cost_scratch_bytes) EBOS_COPY(reg_partials) EBOS_COPY(upsample_scratch) EBOS_COPY(adjoint_workspace)
-  EBOS_COPY(adjoint_workspace_elems) EBOS_COPY(losses) EBOS_COPY(losses_cap) EBOS_COPY(theta_mask)
-#undef EBOS_COPY
+  EBOS_CMAX_VOXEL_SHARED_FIELDS(EBOS_COPY)
   mr->K = q->K, mr->shifts = q->shifts, mr->inv_norm = q->inv_norm, mr->value = q->value;
   return b;
 }
+#undef EBOS_COPY
+#undef EBOS_CMAX_VOXEL_SHARED_FIELDS
 
 }  // namespace
 }  // namespace ebos

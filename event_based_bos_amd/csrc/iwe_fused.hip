@@ -14,38 +14,11 @@
 //                             global atomics (256 B per wave instruction, the shape the memory-side
 //                             atomic unit wants).  Taps beyond the halo go straight to global atomics,
 //                             so any flow magnitude stays correct.
-// All kernels evaluate the warp in source-pixel-relative coordinates (warped_taps below).
-#include <type_traits>
-
-#include "common.h"
+// All kernels evaluate the warp in source-pixel-relative coordinates (warped_taps of warp_footprint.h).
+#include "warp_footprint.h"
 
 namespace ebos {
 namespace {
-
-constexpr float kEps = 1e-6f;  // src/event_image_converter.py:586
-
-// Warped footprint in SOURCE-PIXEL-RELATIVE coordinates.  x' = x + d with d = -dt * u.  Writing
-// x = rs + fx (rs = trunc(x), fx exact) gives floor(x' + eps) = rs + floor(fx + d + eps): the float
-// arithmetic only ever sees |fx + d| <~ 32, so its rounding error is ~2e-6 px instead of the ~1e-4 px
-// of absolute 1280-px coordinates.  That matters because the bilinear splat's derivative jumps at
-// integer coordinates: every event rounded across an integer flips its gradient contribution.
-struct Taps {
-  int R, C;      // top-left tap, padded image coordinates
-  float fr, fc;  // fractional offsets
-  bool ok;       // finite
-};
-__device__ __forceinline__ Taps warped_taps(float ex, float ey, float dx, float dy, int pad_h, int pad_w) {
-  const int rs = (int)ex, cs = (int)ey;
-  const float lx = (ex - (float)rs) + dx, ly = (ey - (float)cs) + dy;
-  const float r0 = floorf(lx + kEps), c0 = floorf(ly + kEps);
-  Taps t;
-  t.fr = lx - r0;
-  t.fc = ly - c0;
-  t.ok = (r0 > -1e9f) && (r0 < 1e9f) && (c0 > -1e9f) && (c0 < 1e9f);
-  t.R = t.ok ? rs + (int)r0 + pad_h : -4;
-  t.C = t.ok ? cs + (int)c0 + pad_w : -4;
-  return t;
-}
 
 // ---------------------------------------------------------------------------------------------
 // general forward: global atomics
@@ -184,12 +157,6 @@ constexpr TiledConfig kTiledConfigs[] = {{64, 64, 32}, {32, 64, 32}, {32, 32, 32
 constexpr int kNumTiledConfigs = sizeof(kTiledConfigs) / sizeof(kTiledConfigs[0]);
 
 template <int TH, int TW, int HALO>
-struct TileAcc {  // f64 when it fits the LDS, else f32
-  static constexpr bool kF64 = (size_t)(TH + 2 * HALO) * (TW + 2 * HALO) * sizeof(double) <= 160 * 1024;
-  using type = typename std::conditional<kF64, double, float>::type;
-};
-
-template <int TH, int TW, int HALO>
 int launch_tiled(const float* xs, const float* ys, const float* dts, const float* weight, const int32_t* key_offsets,
                  const float* flow, int H, int W, int splits, int pad_h, int pad_w, float* iwe, hipStream_t s) {
   constexpr int LH = TH + 2 * HALO, LW = TW + 2 * HALO;
@@ -213,16 +180,6 @@ int launch_tiled(const float* xs, const float* ys, const float* dts, const float
 // ---------------------------------------------------------------------------------------------
 // backward, dense flow
 // ---------------------------------------------------------------------------------------------
-struct GradImage {
-  const float* g;
-  float a, c;  // G = a * g + c inside the valid region
-  int h, w, lo;
-  __device__ __forceinline__ float at(int R, int C) const {
-    if (R < lo || R >= h - lo || C < lo || C >= w - lo) return 0.0f;
-    return a * g[(int64_t)R * w + C] + c;
-  }
-};
-
 template <bool SORTED>
 __global__ void __launch_bounds__(256)
 iwe_dense_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dt,

@@ -12,39 +12,18 @@
 //            walk of a run -- all events of a source pixel share ONE flow cell, so its owner writes d_flow once: no atomics, every
 //            cell written, the same bits on every call
 #include <cmath>
-#include <type_traits>
 
-#include "common.h"
+#include "warp_footprint.h"
 
 namespace ebos {
 namespace {
 
 constexpr int kMaxRef = EBOS_MULTIREF_MAX;
-constexpr float kEps = 1e-6f;  // src/event_image_converter.py:586
 constexpr size_t kLdsBytes = 160 * 1024;
 
 struct Shifts {
   float at[kMaxRef];
 };
-
-// Warped footprint in SOURCE-PIXEL-RELATIVE coordinates (iwe_fused.hip)
-struct Taps {
-  int R, C;      // top-left tap, padded image coordinates
-  float fr, fc;  // fractional offsets
-  bool ok;       // finite
-};
-__device__ __forceinline__ Taps warped_taps(float ex, float ey, float dx, float dy, int pad_h, int pad_w) {
-  const int rs = (int)ex, cs = (int)ey;
-  const float lx = (ex - (float)rs) + dx, ly = (ey - (float)cs) + dy;
-  const float r0 = floorf(lx + kEps), c0 = floorf(ly + kEps);
-  Taps t;
-  t.fr = lx - r0;
-  t.fc = ly - c0;
-  t.ok = (r0 > -1e9f) && (r0 < 1e9f) && (c0 > -1e9f) && (c0 < 1e9f);
-  t.R = t.ok ? rs + (int)r0 + pad_h : -4;
-  t.C = t.ok ? cs + (int)c0 + pad_w : -4;
-  return t;
-}
 
 // ---- tiled forward: K LDS-privatised windows per workgroup ---------------------------------------
 constexpr int kTiledBlock = 1024;

@@ -1,37 +1,13 @@
 // warp_voxel_core.h -- the device pieces the time-aware warp's translation units share: warp_voxel.hip (one reference time) and
-// warp_voxel_multiref.hip (K reference times on the same voxel).  The bilinear footprint, the LDS-tiled forward body, the upstream
-// image of the backwards and the constants of the pixel-owner backward.
+// warp_voxel_multiref.hip (K reference times on the same voxel).  The general and the LDS-tiled forward body and the constants and
+// run walk of the pixel-owner backward; the bilinear footprint and the upstream image of the backwards are warp_footprint.h's.
 #pragma once
-#include <type_traits>
-
-#include "common.h"
+#include "warp_footprint.h"
 
 namespace ebos {
 namespace {
 
 __device__ __forceinline__ int clamp_bin(uint8_t b, int T) { return min((int)b, T - 1); }
-
-constexpr float kEps = 1e-6f;  // src/event_image_converter.py:586
-
-// Warped footprint in SOURCE-PIXEL-RELATIVE coordinates (iwe_fused.hip: the float arithmetic only ever sees the fraction of
-// the source coordinate plus the displacement, so its rounding error does not grow with the image size).
-struct Taps {
-  int R, C;      // top-left tap, padded image coordinates
-  float fr, fc;  // fractional offsets
-  bool ok;       // finite
-};
-__device__ __forceinline__ Taps warped_taps(float ex, float ey, float dx, float dy, int pad_h, int pad_w) {
-  const int rs = (int)ex, cs = (int)ey;
-  const float lx = (ex - (float)rs) + dx, ly = (ey - (float)cs) + dy;
-  const float r0 = floorf(lx + kEps), c0 = floorf(ly + kEps);
-  Taps t;
-  t.fr = lx - r0;
-  t.fc = ly - c0;
-  t.ok = (r0 > -1e9f) && (r0 < 1e9f) && (c0 > -1e9f) && (c0 < 1e9f);
-  t.R = t.ok ? rs + (int)r0 + pad_h : -4;
-  t.C = t.ok ? cs + (int)c0 + pad_w : -4;
-  return t;
-}
 
 // general forward: any event order, four global float atomics per event (SHIFT as in the tiled body below)
 template <bool SHIFT = false>
@@ -159,22 +135,6 @@ __device__ __forceinline__ void iwe_voxel_tiled_body(ACC* s_img, const float* __
     if (R >= 0 && R < h && C >= 0 && C < w) atomic_add(&iwe[(int64_t)R * w + C], v);
   }
 }
-
-template <int TH, int TW, int HALO>
-struct TileAcc {  // f64 when it fits the LDS, else f32
-  static constexpr bool kF64 = (size_t)(TH + 2 * HALO) * (TW + 2 * HALO) * sizeof(double) <= 160 * 1024;
-  using type = typename std::conditional<kF64, double, float>::type;
-};
-
-struct GradImage {
-  const float* g;
-  float a, c;  // G = a * g + c inside the valid region
-  int h, w, lo;
-  __device__ __forceinline__ float at(int R, int C) const {
-    if (R < lo || R >= h - lo || C < lo || C >= w - lo) return 0.0f;
-    return a * g[(int64_t)R * w + C] + c;
-  }
-};
 
 constexpr int kOwnerChunk = 8;
 constexpr int kOwnerHot = 64;

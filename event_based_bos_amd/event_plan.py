@@ -814,10 +814,7 @@ class EventPlan:
         call); ``halo`` must be a built halo of the plan's tile (``_hip.slab_multiref_configs()``).  ValueError for ``'random'``, an
         empty list, more than 4 directions, and a plan without normalised time or without a reference fraction; NotImplementedError
         for an un-binned, lean or deferred plan."""
-        job = _multiref_job(self, directions, pad, halo, splits, fused, "iwe_dense_multi")
-        if job.fused == "slab":
-            return _MultiRefSlabIwe.apply(flow, self, job)
-        return _MultiRefIwe.apply(flow, self, job)
+        return _KImages.apply(flow, self, _multiref_job(self, directions, pad, halo, splits, fused, "iwe_dense_multi"))
 
     def contrast_dense_multi(self, flow: torch.Tensor, directions, cost: str = "image_variance", omit_boundary: bool = False,
                              pad: Tuple[int, int] = (0, 0), halo=DEFAULT_HALO, splits: Optional[int] = None,
@@ -828,13 +825,11 @@ class EventPlan:
         if cost not in ("image_variance", "gradient_magnitude"):
             raise KeyError(f"unknown contrast cost {cost!r}")
         job = _multiref_job(self, directions, pad, halo, splits, fused, "contrast_dense_multi")
-        if job.fused == "slab":   # the variances come out of the combine pass; their gradients are folded into the backward kernel
-            if cost == "image_variance":
-                return _MultiRefSlabVariance.apply(flow, self, job, bool(omit_boundary))
-            return ops.gradient_magnitude(_MultiRefSlabIwe.apply(flow, self, job), omit_boundary).mean()
-        if cost == "image_variance":
-            return _MultiRefVariance.apply(flow, self, job, bool(omit_boundary))
-        return ops.gradient_magnitude(_MultiRefIwe.apply(flow, self, job), omit_boundary).mean()
+        if cost != "image_variance":
+            return ops.gradient_magnitude(_KImages.apply(flow, self, job), omit_boundary).mean()
+        if job.route == "slab":   # the variances come out of the combine pass; their gradients are folded into the backward kernel
+            return _MultiRefSlabVariance.apply(flow, self, job, bool(omit_boundary))
+        return _KImagesVariance.apply(flow, self, job, bool(omit_boundary))
 
     def variance_multi_value_and_grad(self, flow: torch.Tensor, directions, omit_boundary: bool = False, pad: Tuple[int, int] = (0, 0),
                                       halo=DEFAULT_HALO, splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -889,22 +884,13 @@ class EventPlan:
         H, W = self.image_size
         T = int(vox32.shape[0])
         dev = self.device
+        _check_out(out, (T, 2, H, W), dev)
         if out is None:
             out = torch.empty((T, 2, H, W), dtype=torch.float32, device=dev)
-        elif tuple(out.shape) != (T, 2, H, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {(T, 2, H, W)} on {dev}")
         iwe = _launch_iwe_voxel(self, vox32, None, pad2, _voxel_halo(self, halo), self.resolve_splits(None))
-        h, w = iwe.shape
-        value = torch.empty(1, dtype=torch.float32, device=dev)
-        moments = torch.empty((1, 2), dtype=torch.float64, device=dev)
-        affine = torch.empty(2, dtype=torch.float32, device=dev)
-        up = torch.full((1,), float(upstream), dtype=torch.float32, device=dev)
-        nbytes = int(lib.ebos_cost_scratch_bytes(1))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        value, moments = _image_variances(iwe[None], bool(omit_boundary))
+        affine = _variance_affines(moments, torch.full((1,), float(upstream), dtype=torch.float32, device=dev))
         with _hip.on_device(dev):
-            check(lib.ebos_image_variance_f32(ptr(iwe), 1, h, w, int(bool(omit_boundary)), ptr(value), ptr(moments), ptr(scratch), nbytes,
-                                              stream_ptr()), "ebos_image_variance")
-            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), 1, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
             check(lib.ebos_iwe_voxel_owner_bwd_f32(ptr(self.x), ptr(self.y), ptr(self.dt), None, ptr(self.bins), ptr(self.key_offsets),
                                                    self.n, ptr(vox32), T, H, W, self.tile[0], self.tile[1], pad2[0], pad2[1], ptr(iwe),
                                                    ptr(affine), int(bool(omit_boundary)), ptr(out), stream_ptr()),
@@ -924,8 +910,7 @@ class EventPlan:
         launch the backward (``ebos_iwe_voxel_multiref_owner_bwd_f32``: an event is loaded and its flow gathered once for all
         references; no atomics, every cell of d_voxel written, the same bits on every call).  ValueError as ``multi_reference_shifts``
         and ``iwe_voxel``; NotImplementedError for an un-binned or deferred plan."""
-        job = _voxel_multi_job(self, directions, pad, halo, splits, "iwe_voxel_multi")
-        return _MultiRefIweVoxel.apply(voxel, self, job)
+        return _KImages.apply(voxel, self, _voxel_multi_job(self, directions, pad, halo, splits, "iwe_voxel_multi"))
 
     def contrast_voxel_multi(self, voxel: torch.Tensor, directions, cost: str = "image_variance", omit_boundary: bool = False,
                              pad: Tuple[int, int] = (0, 0), halo: Optional[int] = DEFAULT_HALO,
@@ -938,8 +923,8 @@ class EventPlan:
             raise KeyError(f"unknown contrast cost {cost!r}")
         job = _voxel_multi_job(self, directions, pad, halo, splits, "contrast_voxel_multi")
         if cost == "image_variance":
-            return _MultiRefVarianceVoxel.apply(voxel, self, job, bool(omit_boundary))
-        return ops.gradient_magnitude(_MultiRefIweVoxel.apply(voxel, self, job), omit_boundary).mean()
+            return _KImagesVariance.apply(voxel, self, job, bool(omit_boundary))
+        return ops.gradient_magnitude(_KImages.apply(voxel, self, job), omit_boundary).mean()
 
     def variance_voxel_multi_value_and_grad(self, voxel: torch.Tensor, directions, omit_boundary: bool = False,
                                             pad: Tuple[int, int] = (0, 0), halo="auto", upstream: float = 1.0,
@@ -949,19 +934,14 @@ class EventPlan:
         float32 [T, 2, H, W] on the plan's device that is overwritten (it needs no clearing)."""
         job = _voxel_multi_job(self, directions, pad, halo, None, "variance_voxel_multi_value_and_grad")
         vox32 = _check_voxel(self, voxel)
-        lib = _hip.require_gpu()
+        _hip.require_gpu()
         H, W = self.image_size
         T, K, dev = int(vox32.shape[0]), len(job.shifts), self.device
-        if out is not None and (tuple(out.shape) != (T, 2, H, W) or out.dtype != torch.float32 or out.device != dev
-                                or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {(T, 2, H, W)} on {dev}")
-        iwes = _launch_iwe_voxel_multi(self, vox32, job)
+        _check_out(out, (T, 2, H, W), dev)
+        iwes = job.forward(self, vox32)
         variances, moments = _image_variances(iwes, bool(omit_boundary))
-        up = torch.full((K,), float(upstream) / K, dtype=torch.float32, device=dev)
-        affine = torch.empty((K, 2), dtype=torch.float32, device=dev)
-        with _hip.on_device(dev):
-            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
-        d_voxel = _launch_voxel_multi_bwd(self, vox32, job, iwes, affine, int(bool(omit_boundary)), out)
+        affine = _variance_affines(moments, torch.full((K,), float(upstream) / K, dtype=torch.float32, device=dev))
+        d_voxel = job.backward(self, vox32, iwes, affine, int(bool(omit_boundary)), out=out)
         return variances.mean(), d_voxel
 
 
@@ -1230,6 +1210,37 @@ def _check_flow(plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
     return flow.to(torch.float32).contiguous()
 
 
+def _image_variances(images: torch.Tensor, omit: bool):
+    """(variances [K] f32, moments [K, 2] f64) of images [K, h, w] by one cost-kernel call."""
+    lib = _hip.require_gpu()
+    K, h, w = images.shape
+    out = torch.empty(K, dtype=torch.float32, device=images.device)
+    moments = torch.empty((K, 2), dtype=torch.float64, device=images.device)
+    nbytes = int(lib.ebos_cost_scratch_bytes(K))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
+    with _hip.on_device(images.device):
+        check(lib.ebos_image_variance_f32(ptr(images), K, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes, stream_ptr()),
+              "ebos_image_variance")
+    return out, moments
+
+
+def _variance_affines(moments: torch.Tensor, upstream: torch.Tensor) -> torch.Tensor:
+    """affine [K, 2] f32: the gradient of variance k times upstream[k] as the map a_k IWE_k + c_k of its image, from moments [K, 2]."""
+    lib = _hip.require_gpu()
+    K = moments.shape[0]
+    affine = torch.empty((K, 2), dtype=torch.float32, device=moments.device)
+    with _hip.on_device(moments.device):
+        check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(upstream), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
+    return affine
+
+
+def _check_out(out: Optional[torch.Tensor], shape, device: torch.device) -> None:
+    """A caller-owned gradient buffer of a ``..._value_and_grad`` method, where given."""
+    if out is not None and (tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != device
+                            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(shape)} on {device}")
+
+
 _SLAB_CONFIGS = None
 
 
@@ -1487,10 +1498,7 @@ def _launch_dense_bwd(plan, flow32, weight_p, pad, g_image, affine, g_lo, want_d
         return d_flow, d_w
     _refuse_deferred(plan, "iwe_dense backward")
     if var_moments is not None:  # general kernels take the affine form
-        affine = torch.empty(2, dtype=torch.float32, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_affine_f32(ptr(var_moments), ptr(upstream), 1, ptr(affine), stream_ptr()),
-                  "ebos_image_variance_affine")
+        affine = _variance_affines(var_moments, upstream)
     d_flow = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
     with _hip.on_device(plan.device):
         check(lib.ebos_iwe_dense_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(weight_p), plan.n, ptr(flow32), H, W,
@@ -1572,15 +1580,36 @@ def multi_reference_shifts(plan: "EventPlan", directions) -> List[float]:
     return [float(np.float32(plan.ref_fraction - r)) for r in fracs]
 
 
-class _MultiRefJob(NamedTuple):
+class _KImagesJob(NamedTuple):
+    """K images of a plan, one per reference time, and the route that makes them (``_ROUTES``: its operand check and its two
+    launchers).  The operand x is the dense flow [2, H, W] on the dense routes and the flow voxel [T, 2, H, W] on "voxel"."""
     shifts: Tuple[float, ...]   # float32 values
     pad: Tuple[int, int]
-    fused: Union[bool, str]     # True: K LDS windows per workgroup; False: the loop route; "slab": the K-image slab pipeline
-    halo: Optional[int]         # the built halo of the route's forward kernel (None: the loop route on the general kernel)
+    halo: Optional[int]         # the built halo of the route's forward kernel (None: the general kernel, reference by reference)
     splits: int
+    route: str                  # "loop": K calls of the single kernels; "fused": K LDS windows per workgroup; "slab": the K-image
+    #                             slab pipeline; "voxel": the time-aware kernels with the reference as an outer grid dimension
+
+    @property
+    def fused(self):
+        """What ``fused=`` of ``iwe_dense_multi`` resolved to: False, True or "slab" (None on the voxel route, which has no such option)."""
+        return {"loop": False, "fused": True, "slab": "slab"}.get(self.route)
+
+    def check(self, plan: "EventPlan", x: torch.Tensor) -> torch.Tensor:
+        """x as the contiguous float32 operand of the route, or the operand's refusal."""
+        return _ROUTES[self.route][0](plan, x)
+
+    def forward(self, plan: "EventPlan", x32: torch.Tensor) -> torch.Tensor:
+        """-> images [K, h, w]."""
+        return _ROUTES[self.route][1](plan, x32, self)
+
+    def backward(self, plan: "EventPlan", x32: torch.Tensor, g_images: torch.Tensor, affine: Optional[torch.Tensor], g_lo: int,
+                 **kw) -> torch.Tensor:
+        """-> d_x = sum over the references of the event backward with upstream G_k = a_k g_images[k] + c_k."""
+        return _ROUTES[self.route][2](plan, x32, self, g_images, affine, g_lo, **kw)
 
 
-def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what: str) -> _MultiRefJob:
+def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what: str) -> _KImagesJob:
     shifts = tuple(multi_reference_shifts(plan, directions))
     if not plan.binned:
         raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
@@ -1613,7 +1642,7 @@ def _multiref_job(plan: "EventPlan", directions, pad, halo, splits, fused, what:
         route_halo = DEFAULT_HALO if DEFAULT_HALO in built and want is None else max(built)
     else:
         route_halo = None   # a tile without a tiled kernel: the general forward kernel, reference by reference
-    return _MultiRefJob(shifts, (int(pad[0]), int(pad[1])), bool(use_fused), route_halo, max(1, plan.resolve_splits(splits)))
+    return _KImagesJob(shifts, (int(pad[0]), int(pad[1])), route_halo, max(1, plan.resolve_splits(splits)), "fused" if use_fused else "loop")
 
 
 def multiref_slab_halo(tile, halo) -> int:
@@ -1631,12 +1660,12 @@ def multiref_slab_halo(tile, halo) -> int:
                               f"(tile_h, tile_w, halo) are {built_all}")
 
 
-def _multiref_slab_job(plan: "EventPlan", shifts, pad, halo, splits, what: str) -> _MultiRefJob:
+def _multiref_slab_job(plan: "EventPlan", shifts, pad, halo, splits, what: str) -> _KImagesJob:
     try:
         route_halo = multiref_slab_halo(plan.tile, halo)
     except NotImplementedError as e:
         raise NotImplementedError(f"{what}: {e}") from None
-    return _MultiRefJob(shifts, (int(pad[0]), int(pad[1])), "slab", route_halo, max(1, plan.resolve_splits(splits)))
+    return _KImagesJob(shifts, (int(pad[0]), int(pad[1])), route_halo, max(1, plan.resolve_splits(splits)), "slab")
 
 
 def _multiref_workspace(plan: "EventPlan", K: int, pad, halo: int, splits: int) -> torch.Tensor:
@@ -1653,7 +1682,7 @@ def _multiref_workspace(plan: "EventPlan", K: int, pad, halo: int, splits: int) 
     return cache[key]
 
 
-def _launch_multiref_slab_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, want_variance: int, omit: bool):
+def _launch_multiref_slab_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _KImagesJob, want_variance: int, omit: bool):
     """-> (iwes [K, h, w], variances [K] | None, moments [K, 2] f64 | None); every output is overwritten by the kernels."""
     lib = _hip.require_gpu()
     H, W = plan.image_size
@@ -1670,7 +1699,7 @@ def _launch_multiref_slab_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _Mul
     return iwes, variances, moments
 
 
-def _launch_multiref_slab_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, g_images: torch.Tensor,
+def _launch_multiref_slab_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _KImagesJob, g_images: torch.Tensor,
                               affine: Optional[torch.Tensor], g_lo: int, var_moments: Optional[torch.Tensor] = None,
                               upstream: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None,
                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1686,24 +1715,6 @@ def _launch_multiref_slab_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _Mul
                                                         K, ptr(g_images), ptr(affine), int(g_lo), ptr(var_moments), ptr(upstream), None,
                                                         ptr(addend), ptr(d_flow), stream_ptr()), "ebos_iwe_dense_tiled_multiref_bwd")
     return d_flow
-
-
-class _MultiRefSlabIwe(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, flow, plan, job):
-        flow32 = _check_flow(plan, flow)
-        iwes, _, _ = _launch_multiref_slab_fwd(plan, flow32, job, 0, False)
-        ctx.save_for_backward(flow32)
-        ctx.meta = (plan, job, flow.dtype)
-        return iwes if flow.dtype == torch.float32 else iwes.to(flow.dtype)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        (flow32,) = ctx.saved_tensors
-        plan, job, fdt = ctx.meta
-        d_flow = _launch_multiref_slab_bwd(plan, flow32, job, g.to(torch.float32).contiguous(), None, 0)
-        return d_flow.to(fdt), None, None
 
 
 class _MultiRefSlabVariance(torch.autograd.Function):
@@ -1741,13 +1752,13 @@ def _c_shifts(shifts):
     return (C.c_float * len(shifts))(*shifts)
 
 
-def _launch_multiref_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob) -> torch.Tensor:
+def _launch_multiref_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _KImagesJob) -> torch.Tensor:
     lib = _hip.require_gpu()
     H, W = plan.image_size
     K, pad = len(job.shifts), job.pad
     iwes = torch.zeros((K, H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
     with _hip.on_device(plan.device):
-        if job.fused:
+        if job.route == "fused":
             check(lib.ebos_iwe_dense_multiref_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
                                                         H, W, plan.tile[0], plan.tile[1], job.halo, job.splits, pad[0], pad[1],
                                                         _c_shifts(job.shifts), K, ptr(iwes), stream_ptr()),
@@ -1765,14 +1776,14 @@ def _launch_multiref_fwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRef
     return iwes
 
 
-def _launch_multiref_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRefJob, g_images: torch.Tensor,
+def _launch_multiref_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _KImagesJob, g_images: torch.Tensor,
                          affine: Optional[torch.Tensor], g_lo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """d_flow [2, H, W] = sum over the references of the event backward with upstream G_k = a_k g_images[k] + c_k."""
     lib = _hip.require_gpu()
     H, W = plan.image_size
     K, pad = len(job.shifts), job.pad
     with _hip.on_device(plan.device):
-        if job.fused:
+        if job.route == "fused":
             d_flow = torch.empty((2, H, W), dtype=torch.float32, device=plan.device) if out is None else out   # every cell is written
             check(lib.ebos_iwe_dense_multiref_owner_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n,
                                                             ptr(flow32), H, W, plan.tile[0], plan.tile[1], pad[0], pad[1],
@@ -1786,60 +1797,6 @@ def _launch_multiref_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _MultiRef
                                              ptr(g_images[k]), None if affine is None else ptr(affine[k]), int(g_lo), 1, ptr(d_flow),
                                              None, stream_ptr()), "ebos_iwe_dense_bwd")
     return d_flow
-
-
-class _MultiRefIwe(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, flow, plan, job):
-        flow32 = _check_flow(plan, flow)
-        iwes = _launch_multiref_fwd(plan, flow32, job)
-        ctx.save_for_backward(flow32)
-        ctx.meta = (plan, job, flow.dtype)
-        return iwes if flow.dtype == torch.float32 else iwes.to(flow.dtype)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        (flow32,) = ctx.saved_tensors
-        plan, job, fdt = ctx.meta
-        d_flow = _launch_multiref_bwd(plan, flow32, job, g.to(torch.float32).contiguous(), None, 0)
-        return d_flow.to(fdt), None, None
-
-
-class _MultiRefVariance(torch.autograd.Function):
-    """mean_k var(IWE_k(flow)): the K variances and their moments by one cost-kernel call; the event backward reads the IWEs
-    through the variances' affine maps, so no d_iwe image is made."""
-
-    @staticmethod
-    def forward(ctx, flow, plan, job, omit):
-        lib = _hip.require_gpu()
-        flow32 = _check_flow(plan, flow)
-        iwes = _launch_multiref_fwd(plan, flow32, job)
-        K, h, w = iwes.shape
-        out = torch.empty(K, dtype=torch.float32, device=plan.device)
-        moments = torch.empty((K, 2), dtype=torch.float64, device=plan.device)
-        nbytes = int(lib.ebos_cost_scratch_bytes(K))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_f32(ptr(iwes), K, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes,
-                                              stream_ptr()), "ebos_image_variance")
-        ctx.save_for_backward(flow32, iwes, moments)
-        ctx.meta = (plan, job, int(omit), flow.dtype)
-        return out.mean().to(flow.dtype)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        lib = _hip.require_gpu()
-        flow32, iwes, moments = ctx.saved_tensors
-        plan, job, omit, fdt = ctx.meta
-        K = iwes.shape[0]
-        up = (g.to(torch.float32).reshape(1) / K).repeat(K).contiguous()
-        affine = torch.empty((K, 2), dtype=torch.float32, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
-        d_flow = _launch_multiref_bwd(plan, flow32, job, iwes, affine, omit)
-        return d_flow.to(fdt), None, None, None
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1899,10 +1856,7 @@ def _launch_voxel_bwd(plan: EventPlan, vox32, weight_p, pad, g_image, affine, g_
     T = int(vox32.shape[0])
     d_w = torch.empty(plan.n, dtype=torch.float32, device=plan.device) if want_dweight else None
     if var_moments is not None:
-        affine = torch.empty(2, dtype=torch.float32, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_affine_f32(ptr(var_moments), ptr(upstream), 1, ptr(affine), stream_ptr()),
-                  "ebos_image_variance_affine")
+        affine = _variance_affines(var_moments, upstream)
     d_voxel = torch.zeros((T, 2, H, W), dtype=torch.float32, device=plan.device)
     with _hip.on_device(plan.device):
         check(lib.ebos_iwe_voxel_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(weight_p), ptr(plan.bins), plan.n, ptr(vox32), T,
@@ -1939,17 +1893,10 @@ class _FusedVarianceVoxel(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, voxel, plan, pad, omit, halo, splits):
-        lib = _hip.require_gpu()
+        _hip.require_gpu()
         vox32 = _check_voxel(plan, voxel)
         iwe = _launch_iwe_voxel(plan, vox32, None, pad, halo, splits)
-        h, w = iwe.shape
-        out = torch.empty(1, dtype=torch.float32, device=plan.device)
-        moments = torch.empty((1, 2), dtype=torch.float64, device=plan.device)
-        nbytes = int(lib.ebos_cost_scratch_bytes(1))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_f32(ptr(iwe), 1, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes,
-                                              stream_ptr()), "ebos_image_variance")
+        out, moments = _image_variances(iwe[None], omit)
         ctx.save_for_backward(vox32, iwe, moments)
         ctx.meta = (plan, pad, int(omit), voxel.dtype)
         return out[0].to(voxel.dtype)
@@ -1967,38 +1914,17 @@ class _FusedVarianceVoxel(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------
 # time-aware warp at K reference times: the voxel kernels with the reference as one more dimension
 # ----------------------------------------------------------------------------------------------
-class _VoxelMultiJob(NamedTuple):
-    shifts: Tuple[float, ...]   # float32 values
-    pad: Tuple[int, int]
-    halo: Optional[int]         # the built halo of the tiled kernel (None: the general kernel, reference by reference)
-    splits: int
-
-
-def _voxel_multi_job(plan: "EventPlan", directions, pad, halo, splits, what: str) -> _VoxelMultiJob:
+def _voxel_multi_job(plan: "EventPlan", directions, pad, halo, splits, what: str) -> _KImagesJob:
     shifts = tuple(multi_reference_shifts(plan, directions))
     if plan.bins is None:
         raise ValueError('the plan holds no time bins: build it with EventPlan.build(..., emit="full", time_bin=T)')
     if not plan.binned:
         raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
     _refuse_deferred(plan, what)
-    return _VoxelMultiJob(shifts, (int(pad[0]), int(pad[1])), _voxel_halo(plan, halo), max(1, plan.resolve_splits(splits)))
+    return _KImagesJob(shifts, (int(pad[0]), int(pad[1])), _voxel_halo(plan, halo), max(1, plan.resolve_splits(splits)), "voxel")
 
 
-def _image_variances(images: torch.Tensor, omit: bool):
-    """(variances [K] f32, moments [K, 2] f64) of images [K, h, w] by one cost-kernel call."""
-    lib = _hip.require_gpu()
-    K, h, w = images.shape
-    out = torch.empty(K, dtype=torch.float32, device=images.device)
-    moments = torch.empty((K, 2), dtype=torch.float64, device=images.device)
-    nbytes = int(lib.ebos_cost_scratch_bytes(K))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
-    with _hip.on_device(images.device):
-        check(lib.ebos_image_variance_f32(ptr(images), K, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes, stream_ptr()),
-              "ebos_image_variance")
-    return out, moments
-
-
-def _launch_iwe_voxel_multi(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelMultiJob) -> torch.Tensor:
+def _launch_iwe_voxel_multi(plan: "EventPlan", vox32: torch.Tensor, job: _KImagesJob) -> torch.Tensor:
     lib = _hip.require_gpu()
     H, W = plan.image_size
     T, K, pad = int(vox32.shape[0]), len(job.shifts), job.pad
@@ -2011,7 +1937,7 @@ def _launch_iwe_voxel_multi(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelM
     return iwes
 
 
-def _launch_voxel_multi_bwd(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelMultiJob, g_images: torch.Tensor,
+def _launch_voxel_multi_bwd(plan: "EventPlan", vox32: torch.Tensor, job: _KImagesJob, g_images: torch.Tensor,
                             affine: Optional[torch.Tensor], g_lo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """d_voxel [T, 2, H, W] = sum over the references of the event backward with upstream G_k = a_k g_images[k] + c_k."""
     lib = _hip.require_gpu()
@@ -2026,50 +1952,56 @@ def _launch_voxel_multi_bwd(plan: "EventPlan", vox32: torch.Tensor, job: _VoxelM
     return d_voxel
 
 
-class _MultiRefIweVoxel(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, voxel, plan, job):
-        vox32 = _check_voxel(plan, voxel)
-        iwes = _launch_iwe_voxel_multi(plan, vox32, job)
-        ctx.save_for_backward(vox32)
-        ctx.meta = (plan, job, voxel.dtype)
-        return iwes if voxel.dtype == torch.float32 else iwes.to(voxel.dtype)
+_ROUTES = {   # route of a _KImagesJob -> (operand check, forward launcher, backward launcher)
+    "loop": (_check_flow, _launch_multiref_fwd, _launch_multiref_bwd),
+    "fused": (_check_flow, _launch_multiref_fwd, _launch_multiref_bwd),
+    "slab": (_check_flow, lambda plan, flow32, job: _launch_multiref_slab_fwd(plan, flow32, job, 0, False)[0], _launch_multiref_slab_bwd),
+    "voxel": (_check_voxel, _launch_iwe_voxel_multi, _launch_voxel_multi_bwd),
+}
+
+
+class _KImages(torch.autograd.Function):
+    """The K images of a job, differentiable with respect to its operand for any upstream [K, h, w]."""
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        (vox32,) = ctx.saved_tensors
-        plan, job, vdt = ctx.meta
-        d_voxel = _launch_voxel_multi_bwd(plan, vox32, job, g.to(torch.float32).contiguous(), None, 0)
-        return d_voxel.to(vdt), None, None
-
-
-class _MultiRefVarianceVoxel(torch.autograd.Function):
-    """mean_k var(IWE_k(voxel)): the K variances and their moments by one cost-kernel call; the event backward reads the IWEs through
-    the variances' affine maps, so no d_iwe image is made."""
-
-    @staticmethod
-    def forward(ctx, voxel, plan, job, omit):
-        vox32 = _check_voxel(plan, voxel)
-        iwes = _launch_iwe_voxel_multi(plan, vox32, job)
-        out, moments = _image_variances(iwes, omit)
-        ctx.save_for_backward(vox32, iwes, moments)
-        ctx.meta = (plan, job, int(omit), voxel.dtype)
-        return out.mean().to(voxel.dtype)
+    def forward(ctx, x, plan, job):
+        x32 = job.check(plan, x)
+        images = job.forward(plan, x32)
+        ctx.save_for_backward(x32)
+        ctx.meta = (plan, job, x.dtype)
+        return images if x.dtype == torch.float32 else images.to(x.dtype)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        lib = _hip.require_gpu()
-        vox32, iwes, moments = ctx.saved_tensors
-        plan, job, omit, vdt = ctx.meta
-        K = iwes.shape[0]
-        up = (g.to(torch.float32).reshape(1) / K).repeat(K).contiguous()
-        affine = torch.empty((K, 2), dtype=torch.float32, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_affine_f32(ptr(moments), ptr(up), K, ptr(affine), stream_ptr()), "ebos_image_variance_affine")
-        d_voxel = _launch_voxel_multi_bwd(plan, vox32, job, iwes, affine, omit)
-        return d_voxel.to(vdt), None, None, None
+        (x32,) = ctx.saved_tensors
+        plan, job, xdt = ctx.meta
+        d_x = job.backward(plan, x32, g.to(torch.float32).contiguous(), None, 0)
+        return d_x.to(xdt), None, None
+
+
+class _KImagesVariance(torch.autograd.Function):
+    """mean_k var(image_k) of a job: the K variances and their moments by one cost-kernel call; the event backward reads the images
+    through the variances' affine maps, so no d_iwe image is made."""
+
+    @staticmethod
+    def forward(ctx, x, plan, job, omit):
+        x32 = job.check(plan, x)
+        images = job.forward(plan, x32)
+        out, moments = _image_variances(images, omit)
+        ctx.save_for_backward(x32, images, moments)
+        ctx.meta = (plan, job, int(omit), x.dtype)
+        return out.mean().to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x32, images, moments = ctx.saved_tensors
+        plan, job, omit, xdt = ctx.meta
+        K = images.shape[0]
+        affine = _variance_affines(moments, (g.to(torch.float32).reshape(1) / K).repeat(K).contiguous())
+        d_x = job.backward(plan, x32, images, affine, omit)
+        return d_x.to(xdt), None, None, None
 
 
 def _eager_ok(plan: EventPlan, flow: torch.Tensor, halo) -> bool:
@@ -2217,7 +2149,7 @@ class _FusedVarianceDense(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flow, plan, pad, omit, halo, splits, cost="image_variance"):
-        lib = _hip.require_gpu()
+        _hip.require_gpu()
         fast = flow.dtype == torch.float32 and flow.is_contiguous() and flow.device == plan.device and \
             tuple(flow.shape) == (2,) + tuple(plan.image_size)
         flow32 = flow if fast else _check_flow(plan, flow)
@@ -2231,14 +2163,7 @@ class _FusedVarianceDense(torch.autograd.Function):
             return out[0] if flow.dtype == torch.float32 else out[0].to(flow.dtype)
         ctx.eager = False
         iwe = _launch_iwe_dense(plan, flow32, None, pad, halo, splits)
-        h, w = iwe.shape
-        out = torch.empty(1, dtype=torch.float32, device=plan.device)
-        moments = torch.empty((1, 2), dtype=torch.float64, device=plan.device)
-        nbytes = int(lib.ebos_cost_scratch_bytes(1))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=plan.device)
-        with _hip.on_device(plan.device):
-            check(lib.ebos_image_variance_f32(ptr(iwe), 1, h, w, int(omit), ptr(out), ptr(moments), ptr(scratch), nbytes,
-                                              stream_ptr()), "ebos_image_variance")
+        out, moments = _image_variances(iwe[None], omit)
         ctx.save_for_backward(flow32, iwe, moments)
         ctx.meta = (plan, pad, int(omit), halo, splits)
         return out[0].to(flow.dtype)

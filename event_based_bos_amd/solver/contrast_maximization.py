@@ -62,7 +62,7 @@ True and ``history`` comes from the loop's losses.  Its family is the variance c
 from __future__ import annotations
 
 import logging
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -148,6 +148,15 @@ def parse_multi_reference(block) -> Optional[dict]:
             raise ValueError(f"multi_reference.native must be true or false, got {block['native']!r}")
         out["native"] = block["native"]
     return out
+
+
+class _Warp(NamedTuple):
+    """How the solver's dense flow becomes the image(s) whose contrast it maximises (``_resolve_warp``)."""
+    operand: Callable    # flow [2, H, W] -> what the plan operators take: the flow itself, or its flow voxel [T, 2, H, W]
+    images: Callable     # (plan, operand) -> image [h, w] or images [K, h, w]: the blurred objective's operator
+    contrast: Callable   # (plan, operand, cost) -> the fused raw contrast (0-d; the mean over the references where there are several)
+    mean: bool           # do the cost kernels on ``images`` give one value per reference, to be averaged?
+    norms: Callable      # plan -> {cost: N_c}: all 1.0 where the block has no ``normalize``
 
 
 def patch_grid_shape(image_size, patch_size, sliding_window):
@@ -260,6 +269,7 @@ class ContrastMaximizationMixin(object):
             self.resident = False
             if self.multi_reference.get("native", False):
                 self._check_native_multi_reference()
+        self._warp = self._resolve_warp()
 
     def _check_native(self, block: str, variance_alone: str, before_method=None, last=None) -> None:
         """``<block>.native``: the family of the block's native loop (``time_aware_loop.TimeAwarePatchLoop`` /
@@ -296,99 +306,83 @@ class ContrastMaximizationMixin(object):
                            lambda: f"outer_padding: {self.pad} (0 only)" if self.pad != 0 else None, tile_halo)
 
     # ------------------------------------------------------------------ objective pieces
-    def _multi_reference_norms(self, plan: EventPlan) -> Dict[str, float]:
-        """N_c of the ``multi_reference`` loss: cost c of the window's zero-flow IWE (the same image at every reference time), blurred
-        like the objective's; once per plan, without gradient, 1 where the value is 0 -- or all 1 without ``normalize``."""
-        if not self.multi_reference["normalize"]:
+    def _zero_flow_norms(self, plan: EventPlan, normalize: bool, attr: str, zero_flow_iwe) -> Dict[str, float]:
+        """N_c of a loss over several reference times: cost c of the window's zero-flow IWE ``zero_flow_iwe(plan)`` (the same image at
+        every reference time), blurred like the objective's; once per plan (kept on it as ``attr``), without gradient, 1 where the
+        value is 0 -- or all 1 without ``normalize``."""
+        if not normalize:
             return {name: 1.0 for name in self.contrast_terms}
         key = (self.pad, self.blur_sigma, self.omit_boundary, tuple(self.contrast_terms))
-        cached = plan.__dict__.get("_multiref_norms")
+        cached = plan.__dict__.get(attr)
         if cached is None or cached[0] != key:
             with torch.no_grad():
-                H, W = plan.image_size
-                zero = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
-                iwe = plan.iwe_dense_multi(zero, [0.0 if plan.ref_fraction is None else float(plan.ref_fraction)],
-                                           pad=(self.pad, self.pad), halo=self.halo, fused=False)[0]
+                iwe = zero_flow_iwe(plan)
                 if self.blur_sigma > 0:
                     iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
                 vals = {name: float((ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(iwe, self.omit_boundary))
                         for name in self.contrast_terms}
-            cached = plan.__dict__["_multiref_norms"] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
+            cached = plan.__dict__[attr] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
         return cached[1]
+
+    def _zero_flow_iwe_dense(self, plan: EventPlan) -> torch.Tensor:
+        H, W = plan.image_size
+        zero = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
+        return plan.iwe_dense_multi(zero, [0.0 if plan.ref_fraction is None else float(plan.ref_fraction)],
+                                    pad=(self.pad, self.pad), halo=self.halo, fused=False)[0]
+
+    def _zero_flow_iwe_voxel(self, plan: EventPlan) -> torch.Tensor:
+        H, W = plan.image_size   # (the same image for every voxel bin, too)
+        zero = torch.zeros((self.time_aware["time_bin"], 2, H, W), dtype=torch.float32, device=plan.device)
+        return plan.iwe_voxel(zero, pad=(self.pad, self.pad), halo=self.halo)
+
+    def _multi_reference_norms(self, plan: EventPlan) -> Dict[str, float]:
+        return self._zero_flow_norms(plan, self.multi_reference["normalize"], "_multiref_norms", self._zero_flow_iwe_dense)
 
     def _time_aware_norms(self, plan: EventPlan) -> Dict[str, float]:
-        """N_c of the ``time_aware`` loss with ``directions``: cost c of the window's zero-flow IWE (the same image at every reference
-        time and for every voxel bin), blurred like the objective's; once per plan, without gradient, 1 where the value is 0 -- or all
-        1 without ``normalize``."""
-        if not self.time_aware.get("normalize", False):
-            return {name: 1.0 for name in self.contrast_terms}
-        key = (self.pad, self.blur_sigma, self.omit_boundary, tuple(self.contrast_terms))
-        cached = plan.__dict__.get("_time_aware_norms")
-        if cached is None or cached[0] != key:
-            with torch.no_grad():
-                H, W = plan.image_size
-                zero = torch.zeros((self.time_aware["time_bin"], 2, H, W), dtype=torch.float32, device=plan.device)
-                iwe = plan.iwe_voxel(zero, pad=(self.pad, self.pad), halo=self.halo)
-                if self.blur_sigma > 0:
-                    iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
-                vals = {name: float((ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(iwe, self.omit_boundary))
-                        for name in self.contrast_terms}
-            cached = plan.__dict__["_time_aware_norms"] = (key, {k: (v if v != 0.0 else 1.0) for k, v in vals.items()})
-        return cached[1]
+        return self._zero_flow_norms(plan, self.time_aware.get("normalize", False), "_time_aware_norms", self._zero_flow_iwe_voxel)
+
+    def _resolve_warp(self) -> "_Warp":
+        """The solver's warp, from ``multi_reference`` / ``time_aware`` (the geometry keys are read at call time)."""
+        kw = lambda: {"pad": (self.pad, self.pad), "halo": self.halo}   # noqa: E731
+        ta, mr = self.time_aware, self.multi_reference
+        ones = lambda plan: {name: 1.0 for name in self.contrast_terms}   # noqa: E731
+        to_voxel = None if ta is None else \
+            (lambda flow: flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0])
+        if mr is not None:
+            return _Warp(lambda flow: flow,
+                         lambda plan, x: plan.iwe_dense_multi(x, mr["directions"], fused=mr["fused"], **kw()),
+                         lambda plan, x, cost: plan.contrast_dense_multi(x, mr["directions"], cost, self.omit_boundary, fused=mr["fused"], **kw()),
+                         True, self._multi_reference_norms)
+        if ta is not None and ta.get("directions") is not None:
+            return _Warp(to_voxel,
+                         lambda plan, x: plan.iwe_voxel_multi(x, ta["directions"], **kw()),
+                         lambda plan, x, cost: plan.contrast_voxel_multi(x, ta["directions"], cost, self.omit_boundary, **kw()),
+                         True, self._time_aware_norms)
+        if ta is not None:
+            return _Warp(to_voxel,
+                         lambda plan, x: plan.iwe_voxel(x, **kw()),
+                         lambda plan, x, cost: plan.contrast_voxel(x, cost, self.omit_boundary, **kw()),
+                         False, ones)
+        return _Warp(lambda flow: flow,
+                     lambda plan, x: plan.iwe_dense(x, **kw()),
+                     lambda plan, x, cost: plan.contrast_dense(x, cost, self.omit_boundary, **kw()),
+                     False, ones)
 
     def _contrast(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
-        total = 0.0
-        if self.multi_reference is not None:
-            mr = self.multi_reference
-            norms = self._multi_reference_norms(plan)
-            if self.blur_sigma > 0:
-                iwes = plan.iwe_dense_multi(flow, mr["directions"], pad=(self.pad, self.pad), halo=self.halo, fused=mr["fused"])
-                iwes = EventImageConverter._gaussian_blur3(iwes, self.blur_sigma)
-                for name, wgt in self.contrast_terms.items():
-                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
-                    total = total + (wgt / norms[name]) * fn(iwes, self.omit_boundary).mean()
-                return total
-            for name, wgt in self.contrast_terms.items():
-                total = total + (wgt / norms[name]) * plan.contrast_dense_multi(flow, mr["directions"], name, self.omit_boundary,
-                                                                                pad=(self.pad, self.pad), halo=self.halo,
-                                                                                fused=mr["fused"])
-            return total
-        if self.time_aware is not None and self.time_aware.get("directions") is not None:
-            ta = self.time_aware
-            voxel = flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0]
-            norms = self._time_aware_norms(plan)
-            if self.blur_sigma > 0:
-                iwes = plan.iwe_voxel_multi(voxel, ta["directions"], pad=(self.pad, self.pad), halo=self.halo)
-                iwes = EventImageConverter._gaussian_blur3(iwes, self.blur_sigma)
-                for name, wgt in self.contrast_terms.items():
-                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
-                    total = total + (wgt / norms[name]) * fn(iwes, self.omit_boundary).mean()
-                return total
-            for name, wgt in self.contrast_terms.items():
-                total = total + (wgt / norms[name]) * plan.contrast_voxel_multi(voxel, ta["directions"], name, self.omit_boundary,
-                                                                                pad=(self.pad, self.pad), halo=self.halo)
-            return total
-        if self.time_aware is not None:
-            ta = self.time_aware
-            voxel = flow_voxel_batch(flow[None], ta["time_bin"], ta["scheme"], ta["t0_location"], ta["clamp"])[0]
-            if self.blur_sigma > 0:
-                iwe = EventImageConverter._gaussian_blur3(plan.iwe_voxel(voxel, pad=(self.pad, self.pad), halo=self.halo), self.blur_sigma)
-                for name, wgt in self.contrast_terms.items():
-                    fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
-                    total = total + wgt * fn(iwe, self.omit_boundary)
-                return total
-            for name, wgt in self.contrast_terms.items():
-                total = total + wgt * plan.contrast_voxel(voxel, name, self.omit_boundary, pad=(self.pad, self.pad), halo=self.halo)
-            return total
+        warp = self._warp
+        x = warp.operand(flow)
+        norms = warp.norms(plan)
         if self.blur_sigma > 0:
-            iwe = plan.iwe_dense(flow, pad=(self.pad, self.pad), halo=self.halo)
-            iwe = EventImageConverter._gaussian_blur3(iwe, self.blur_sigma)
-            for name, wgt in self.contrast_terms.items():
-                fn = ops.image_variance if name == "image_variance" else ops.gradient_magnitude
-                total = total + wgt * fn(iwe, self.omit_boundary)
-            return total
+            images = EventImageConverter._gaussian_blur3(warp.images(plan, x), self.blur_sigma)
+        total = 0.0
         for name, wgt in self.contrast_terms.items():
-            total = total + wgt * plan.contrast_dense(flow, name, self.omit_boundary, pad=(self.pad, self.pad), halo=self.halo)
+            if self.blur_sigma > 0:   # the cost kernels on the blurred image(s); the fused operators take the un-blurred ones only
+                value = (ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(images, self.omit_boundary)
+                if warp.mean:
+                    value = value.mean()
+            else:
+                value = warp.contrast(plan, x, name)
+            total = total + (wgt / norms[name]) * value   # (a warp without norms has all 1.0, and wgt / 1.0 == wgt exactly)
         return total
 
     def objective(self, plan: EventPlan, flow: torch.Tensor) -> torch.Tensor:
@@ -402,20 +396,7 @@ class ContrastMaximizationMixin(object):
     # ------------------------------------------------------------------ estimate
     def estimate(self, events, *args, **kwargs) -> np.ndarray:
         """events [n, 4] (x=row, y=col, t, p) -> flow [2, H, W] (numpy), like the reference's solvers."""
-        ev = to_gpu(events)
-        # (the objective uses unit weights: the lean build -- compact events + offsets only -- is all it reads; windows with
-        # fractional, i.e. undistorted, coordinates fall back to the full build inside)
-        # (a stream of sub-pixel rectified events is fractional window after window: once a window fell back, the lean
-        # attempt -- its kernels and its read-back, ~0.3 ms of a 100 k-event window's build -- is skipped until a full build finds
-        # integer coordinates again; either build is valid for either kind of window)
-        if self.multi_reference is not None:   # the shifted reference times read the SoA events of the full build
-            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full")
-        elif self.time_aware is not None:   # the bins travel with the SoA events of the full build
-            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
-                                   time_bin=self.time_aware["time_bin"])
-        else:
-            plan = EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
-                                   emit="full" if getattr(self, "_fractional_stream", False) else "compact")
+        plan = self._build_plan(events)
         self._fractional_stream = plan.fractional
         self.history = []
         # The optimisation loops below call loss.backward() thousands of times on graphs of one or two nodes: with the autograd
@@ -432,6 +413,22 @@ class ContrastMaximizationMixin(object):
                 raise NotImplementedError(f"motion_model {self.motion_model!r}")
         return flow.detach().cpu().numpy().astype(np.float64)
 
+    def _build_plan(self, events) -> EventPlan:
+        """The plan of one window, in the emit the solver's warp reads."""
+        ev = to_gpu(events)
+        # (the objective uses unit weights: the lean build -- compact events + offsets only -- is all it reads; windows with
+        # fractional, i.e. undistorted, coordinates fall back to the full build inside)
+        # (a stream of sub-pixel rectified events is fractional window after window: once a window fell back, the lean
+        # attempt -- its kernels and its read-back, ~0.3 ms of a 100 k-event window's build -- is skipped until a full build finds
+        # integer coordinates again; either build is valid for either kind of window)
+        if self.multi_reference is not None:   # the shifted reference times read the SoA events of the full build
+            return EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full")
+        if self.time_aware is not None:   # the bins travel with the SoA events of the full build
+            return EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
+                                   time_bin=self.time_aware["time_bin"])
+        return EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
+                               emit="full" if getattr(self, "_fractional_stream", False) else "compact")
+
     def _native_batch(self) -> bool:
         """Does ``estimate_batch`` solve several windows per launch?  The ``time_aware: {native: true}`` family with Adam."""
         return (self.time_aware is not None and bool(self.time_aware.get("native", False)) and self.opt_method == "Adam"
@@ -445,28 +442,9 @@ class ContrastMaximizationMixin(object):
         Every other configuration is the loop of ``estimate``.  Per window: ``histories[b]`` and ``patch_flows[b]``; ``loop_modes`` per
         pyramid scale; ``history`` and ``patch_flow`` hold the last window's.  A window ``estimate`` refuses is refused the same way."""
         windows = list(windows)
-        max_batch = int(max_batch)
-        if max_batch < 1:
-            raise ValueError(f"max_batch must be at least 1, got {max_batch}")
-        H, W = self.orig_image_shape
-        self.histories, self.patch_flows = [], []
-        if not windows:
-            return np.zeros((0, 2, H, W), dtype=np.float64)
-        if not self._native_batch():
-            flows = []
-            for ev in windows:
-                flows.append(self.estimate(ev))
-                self.histories.append(list(self.history))
-                self.patch_flows.append(getattr(self, "patch_flow", None))
-            return np.stack(flows).astype(np.float64)
-        max_batch = min(max_batch, _hip.CMAX_VOXEL_MAX_BATCH)
-        flows = []
-        for c0 in range(0, len(windows), max_batch):
-            plans = [EventPlan.build(to_gpu(ev), self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
-                                     time_bin=self.time_aware["time_bin"]) for ev in windows[c0:c0 + max_batch]]
-            flows.append(self._estimate_patch_flow_batch(plans))
-        self.history, self.patch_flow = self.histories[-1], self.patch_flows[-1]
-        return torch.cat(flows).detach().cpu().numpy().astype(np.float64)
+        flows = self._estimate_chunks(len(windows), max_batch, lambda b: windows[b],
+                                      lambda lo, hi: [self._build_plan(ev) for ev in windows[lo:hi]])
+        return np.zeros((0, 2) + self.orig_image_shape, dtype=np.float64) if flows is None else flows.cpu().numpy()
 
     def estimate_batch_prepared(self, prepared, frames=None, background=None, max_batch: int = 8, device_out: bool = False):
         """``estimate_batch`` on ``evaluation.PreparedWindows`` that carry their raw columns (the signature of the generative
@@ -477,33 +455,35 @@ class ContrastMaximizationMixin(object):
         ``histories``, ``patch_flows``, ``loop_modes``, ``history`` and ``patch_flow`` as ``estimate_batch`` does."""
         if getattr(prepared, "cols", None) is None or getattr(prepared, "ranges", None) is None:
             raise ValueError("estimate_batch_prepared needs windows that carry their raw columns (evaluation.window_ingest_raw_batch)")
+        ranges, dev = list(prepared.ranges), prepared.cols[2].device
+        flows = self._estimate_chunks(len(ranges), max_batch, prepared.events, lambda lo, hi: TimeAwarePlanStack.from_raw(
+            prepared.cols, ranges[lo:hi], self.orig_image_shape, self.warp_direction, self.plan_tile(), self.time_aware["time_bin"],
+            roi=prepared.roi, remove=prepared.remove, ticks_per_second=prepared.ticks_per_second))
+        if flows is None:
+            flows = torch.zeros((0, 2) + self.orig_image_shape, dtype=torch.float64, device=dev)
+        return flows.to(dev) if device_out else flows.cpu().numpy()
+
+    def _estimate_chunks(self, n: int, max_batch: int, events_of, plans_of) -> Optional[torch.Tensor]:
+        """The windows 0 .. n - 1 of ``estimate_batch`` / ``estimate_batch_prepared``: float64 [n, 2, H, W] (a host tensor from the
+        window-by-window loop, a device tensor from the batch loop), or None for no window.  ``events_of(b)``: the events of window b
+        for ``estimate``; ``plans_of(lo, hi)``: the plans, or the ready plan stack, of the chunk of windows lo .. hi - 1."""
         max_batch = int(max_batch)
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1, got {max_batch}")
-        H, W = self.orig_image_shape
-        ranges = list(prepared.ranges)
         self.histories, self.patch_flows = [], []
-        if not ranges:
-            out = torch.zeros((0, 2, H, W), dtype=torch.float64, device=prepared.cols[2].device)
-            return out if device_out else out.cpu().numpy()
+        if n == 0:
+            return None
         if not self._native_batch():
-            dev, flows = prepared.cols[2].device, []
-            for b in range(len(ranges)):
-                flows.append(self.estimate(prepared.events(b)))
+            flows = []
+            for b in range(n):
+                flows.append(self.estimate(events_of(b)))
                 self.histories.append(list(self.history))
                 self.patch_flows.append(getattr(self, "patch_flow", None))
-            out = np.stack(flows).astype(np.float64)
-            return torch.from_numpy(out).to(dev) if device_out else out
+            return torch.from_numpy(np.stack(flows).astype(np.float64))
         max_batch = min(max_batch, _hip.CMAX_VOXEL_MAX_BATCH)
-        flows = []
-        for c0 in range(0, len(ranges), max_batch):
-            stack = TimeAwarePlanStack.from_raw(prepared.cols, ranges[c0:c0 + max_batch], self.orig_image_shape, self.warp_direction,
-                                                self.plan_tile(), self.time_aware["time_bin"], roi=prepared.roi, remove=prepared.remove,
-                                                ticks_per_second=prepared.ticks_per_second)
-            flows.append(self._estimate_patch_flow_batch(stack))
+        flows = [self._estimate_patch_flow_batch(plans_of(c0, min(c0 + max_batch, n))) for c0 in range(0, n, max_batch)]
         self.history, self.patch_flow = self.histories[-1], self.patch_flows[-1]
-        out = torch.cat(flows).detach().to(torch.float64)
-        return out if device_out else out.cpu().numpy()
+        return torch.cat(flows).detach().to(torch.float64)
 
     def _estimate_patch_flow_batch(self, plans) -> torch.Tensor:
         """``_estimate_patch_flow`` for one chunk of windows through the batch loop: [B, 2, H, W] (device).  ``plans``: binned
@@ -516,23 +496,10 @@ class ContrastMaximizationMixin(object):
         self.loop_modes, per_scale = [], []
         theta = None
         for patch_size, sliding_window, n_iter in self.pyramid_scales():
-            gh, gw = patch_grid_shape((H, W), patch_size, sliding_window)
-            if theta is not None:   # every window from its own coarser scale
-                init = torch.nn.functional.interpolate(theta, size=(gh, gw), mode="bilinear", align_corners=False)
-            elif self._warm_start() is not None:
-                init = to_gpu(self._warm_start(), device=dev, dtype=torch.float32).reshape(1, 2, gh, gw).repeat(B, 1, 1, 1)
-            else:
-                init = torch.zeros((B, 2, gh, gw), dtype=torch.float32, device=dev)
             masks = [self.patch_mask(plan, patch_size, sliding_window) for plan in plans]
             mask = None if masks[0] is None else torch.stack(masks)
-            if mask is not None:
-                init = init * mask[:, None]
-            loop_cls = (time_aware_loop.TimeAwarePatchLoopBatch if self.time_aware.get("directions") is None
-                        else time_aware_loop.TimeAwareMultiReferencePatchLoopBatch)
-            loop = loop_cls(stack, patch_size, sliding_window, init, self.time_aware,
-                            self.contrast_terms["image_variance"], self.flow_terms.get("flow_norm", 0.0),
-                            self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad, self.halo, self.lr, capacity=n_iter,
-                            theta_mask=mask)
+            init = self._scale_start(theta, B, patch_size, sliding_window, mask, dev)   # (every window from its own coarser scale)
+            loop = self._native_time_aware_loop(stack, patch_size, sliding_window, init, n_iter, mask)
             loop.run(n_iter)
             self.graphed, self.fused, self.loop_mode = False, True, loop.last_run_mode
             self.loop_modes.append(loop.last_run_mode)
@@ -595,21 +562,39 @@ class ContrastMaximizationMixin(object):
             return None
         return (plan.patch_event_counts(patch_size, sliding_window) > self.event_thres).to(torch.float32)
 
+    def _scale_start(self, coarser: Optional[torch.Tensor], B: int, patch_size, sliding_window, mask: Optional[torch.Tensor],
+                     device: torch.device) -> torch.Tensor:
+        """The start [B, 2, gh, gw] of one pyramid scale for B windows: each window's patch flow of the coarser scale (``coarser``
+        [B, 2, gh', gw']) resized -- resize(x0, patch_image_size), pyramid2.py:253-255 --, at the coarsest scale the common warm
+        start or zeros; then ``mask`` [B, gh, gw] (patches that are not estimated start, and stay, at zero)."""
+        gh, gw = patch_grid_shape(self.orig_image_shape, patch_size, sliding_window)
+        if coarser is not None:
+            init = torch.nn.functional.interpolate(coarser, size=(gh, gw), mode="bilinear", align_corners=False)
+        elif self._warm_start() is not None:
+            init = to_gpu(self._warm_start(), device=device, dtype=torch.float32).reshape(1, 2, gh, gw).expand(B, 2, gh, gw).contiguous()
+        else:
+            init = torch.zeros((B, 2, gh, gw), dtype=torch.float32, device=device)
+        return init if mask is None else init * mask[:, None]
+
+    def _native_time_aware_loop(self, plans, patch_size, sliding_window, theta: torch.Tensor, capacity: int, mask: Optional[torch.Tensor]):
+        """The ``time_aware.native`` loop of one pyramid scale: of one plan, or of a ``TimeAwarePlanStack`` (the batch classes), at
+        one reference time or at the block's ``directions``."""
+        batch, multi = isinstance(plans, TimeAwarePlanStack), self.time_aware.get("directions") is not None
+        loop_cls = {(False, False): time_aware_loop.TimeAwarePatchLoop, (False, True): time_aware_loop.TimeAwareMultiReferencePatchLoop,
+                    (True, False): time_aware_loop.TimeAwarePatchLoopBatch,
+                    (True, True): time_aware_loop.TimeAwareMultiReferencePatchLoopBatch}[(batch, multi)]
+        return loop_cls(plans, patch_size, sliding_window, theta, self.time_aware, self.contrast_terms["image_variance"],
+                        self.flow_terms.get("flow_norm", 0.0), self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
+                        self.halo, self.lr, capacity=capacity, theta_mask=mask)
+
     def _estimate_patch_flow(self, plan: EventPlan) -> torch.Tensor:
         H, W = self.orig_image_shape
         self.history, self.patch_flow_per_scale, self.loop_modes = [], [], []
         theta = None
         for patch_size, sliding_window, n_iter in self.pyramid_scales():
-            gh, gw = patch_grid_shape((H, W), patch_size, sliding_window)
-            if theta is not None:  # initialise from the coarser scale: resize(x0, patch_image_size), pyramid2.py:253-255
-                init = torch.nn.functional.interpolate(theta[None], size=(gh, gw), mode="bilinear", align_corners=False)[0]
-            elif self._warm_start() is not None:
-                init = to_gpu(self._warm_start(), device=plan.device, dtype=torch.float32).reshape(2, gh, gw)
-            else:
-                init = torch.zeros((2, gh, gw), dtype=torch.float32, device=plan.device)
             mask = self.patch_mask(plan, patch_size, sliding_window)
-            if mask is not None:
-                init = init * mask
+            init = self._scale_start(None if theta is None else theta[None], 1, patch_size, sliding_window,
+                                     None if mask is None else mask[None], plan.device)[0]
             theta = self._optimise_patch_grid(plan, init.clone(), patch_size, sliding_window, n_iter, mask)
             self.patch_flow_per_scale.append(theta)
         self.patch_flow = theta
@@ -621,11 +606,7 @@ class ContrastMaximizationMixin(object):
         H, W = self.orig_image_shape
         capacity = n_iter if self.opt_method == "Adam" else 1   # (of a native block's loop: a scipy method records no losses there)
         if self.time_aware is not None and self.time_aware.get("native", False):
-            loop_cls = (time_aware_loop.TimeAwarePatchLoop if self.time_aware.get("directions") is None
-                        else time_aware_loop.TimeAwareMultiReferencePatchLoop)
-            loop = loop_cls(plan, patch_size, sliding_window, theta.detach(), self.time_aware, self.contrast_terms["image_variance"],
-                            self.flow_terms.get("flow_norm", 0.0), self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
-                            self.halo, self.lr, capacity=capacity, theta_mask=mask)
+            loop = self._native_time_aware_loop(plan, patch_size, sliding_window, theta.detach(), capacity, mask)
             return self._optimise_native(loop, theta, n_iter)
         if self.multi_reference is not None and self.multi_reference.get("native", False):
             norm = self._multi_reference_norms(plan)["image_variance"]
