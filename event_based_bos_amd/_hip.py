@@ -308,6 +308,10 @@ SIGNATURES = {
     "ebos_iwe_multiref_fits": (_I, [_I, _I, _I, _I]),
     "ebos_iwe_dense_multiref_tiled_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 8 + [C.POINTER(_F), _I, _P, _P]),
     "ebos_iwe_dense_multiref_owner_bwd_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 6 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
+    "ebos_iwe_dense_tangent_tiled_f32": (_I, [_P, _P, _P, _P, _L, _P, _P] + [_I] * 8 + [_P, _P, _P]),
+    "ebos_iwe_tangent_slab_workspace_bytes": (_Z, [_I] * 6),
+    "ebos_iwe_dense_tangent_slab_f32": (_I, [_P, _P, _P, _P, _L, _P, _P] + [_I] * 7 + [_P, _Z, _P, _P, _P]),
+    "ebos_iwe_dense_hvp_owner_bwd_f32": (_I, [_P, _P, _P, _P, _L, _P, _P] + [_I] * 6 + [_P, _P, _P, _I, _P, _P, _P]),
     "ebos_slab_multiref_config": (_I, [C.POINTER(_I), _I]),
     "ebos_iwe_slab_multiref_workspace_bytes": (_Z, [_I] * 9),
     "ebos_iwe_dense_slab_multiref_f32": (_I, [_P, _P, _P, _P, _L, _P] + [_I] * 8 + [C.POINTER(_F), _I, _P, _Z, _P, _I, _I, _P, _P, _P]),

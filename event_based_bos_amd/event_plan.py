@@ -795,6 +795,63 @@ class EventPlan:
         v = ops.gradient_magnitude(self.iwe_dense(flow, pad=pad, halo=halo, splits=splits), omit_boundary)
         return v if sign == 1.0 else v * sign
 
+    # ------------------------------------------------------------------------------------------ second order
+    def iwe_dense_jvp(self, flow: torch.Tensor, v: torch.Tensor, pad: Tuple[int, int] = (0, 0), halo="auto",
+                      splits: Optional[int] = None, with_iwe: bool = True, weight: Optional[torch.Tensor] = None):
+        """(iwe or None, tangent), float32 [H + 2 pad_h, W + 2 pad_w]: the IWE of ``flow`` [2, H, W] and its directional derivative
+        u = d IWE(flow + e v) / de at e = 0 along ``v`` [2, H, W], from ONE pass over the events
+        (``ebos_iwe_dense_tangent_tiled_f32``: a second LDS window per workgroup; ``with_iwe=False`` keeps the tangent's alone).  A
+        plain function: no autograd graph.  ``halo``: a built halo of the plan's tile is used where its windows fit the LDS, else --
+        and for ``"auto"`` -- the largest built halo of the tile whose windows fit as float64, failing that as float32
+        (``ebos_iwe_multiref_fits`` with 2 windows, 1 without the IWE); displacements beyond it take the exact spill path.
+        ``splits=None``: the slab route (``ebos_iwe_dense_tangent_slab_f32``) -- every tile stores its window(s) and a combine pass sums
+        the windows that cover a cell in tile order, so the bits repeat from call to call, and with and without the IWE, wherever the
+        windows are float64 and nothing spills.  ``splits=k``: k work items per tile on the atomic flush
+        (``ebos_iwe_dense_tangent_tiled_f32``), whose sums over overlapping windows meet in float atomics: the same images to
+        rounding.  NotImplementedError for an un-binned, lean or deferred plan, a tile without a fitting built halo and per-event
+        weights; ValueError for a ``flow`` / ``v`` that is not the plan's."""
+        flow32, v32 = _check_hvp_operands(self, flow, v, weight, "iwe_dense_jvp")
+        halo = _hvp_halo(self, halo, 2 if with_iwe else 1, "iwe_dense_jvp")
+        return _launch_tangent(self, flow32, v32, (int(pad[0]), int(pad[1])), halo, splits, bool(with_iwe))
+
+    def contrast_dense_hvp(self, flow: torch.Tensor, v: torch.Tensor, cost="image_variance", omit_boundary: bool = False,
+                           blur_sigma: float = 0.0, pad: Tuple[int, int] = (0, 0), halo="auto", state: Optional[dict] = None,
+                           splits: Optional[int] = None, weight: Optional[torch.Tensor] = None):
+        """(value, d_flow, hv, state) of the raw contrast C(flow) as ``contrast_dense`` signs it: its value (0-d), its gradient and
+        its Hessian applied to ``v`` (both [2, H, W] float32).  A plain function: no autograd graph, no double backward.
+
+        Both contrasts are quadratic in the image (blur, Sobel stencil, boundary crop and unbiased variance are linear or quadratic),
+        so the cost's Hessian applied to the tangent image u = J v is the cost's gradient map evaluated at u: with G1 = grad cost(IWE)
+        and G2 = grad cost(u), ``ebos_iwe_dense_hvp_owner_bwd_f32`` sums J^T G2 (the Gauss-Newton part), the curvature of the bilinear
+        weights against G1, and the gradient J^T G1, in one walk of every source pixel's run (no atomics: the same bits on every call
+        for the same G1, G2).  ``cost``: a name or ``{name: weight}`` -- both maps are linear in the weights, so several costs share
+        the event passes.  ``blur_sigma > 0``: the contrast of the 3-tap blurred image, ``blur^T(grad cost(blur(.)))``.
+
+        ``state`` (returned; pass it back for another ``v`` at the SAME flow and options) carries what depends on ``flow`` alone -- the
+        IWE, G1 or its affine map, value and gradient: such a call makes the tangent window only, skips the first cost pass and
+        returns the state's value and ``d_flow``.  The product from a reused state is the product without one bit for bit: the
+        tangent image comes from the slab route of ``iwe_dense_jvp`` with the state's halo (float64 windows in both calls; an event
+        beyond the halo takes the spill path's float atomics, and then the last bits may differ).  ``splits`` as in ``iwe_dense_jvp``.
+        Refusals: ``iwe_dense_jvp``'s, KeyError for an unknown cost."""
+        flow32, v32 = _check_hvp_operands(self, flow, v, weight, "contrast_dense_hvp")
+        costs = _hvp_costs(cost)
+        pad = (int(pad[0]), int(pad[1]))
+        key = (tuple(costs.items()), bool(omit_boundary), float(blur_sigma), pad)
+        if state is not None:
+            if state.get("key") != key:
+                raise ValueError("contrast_dense_hvp: state was made with other options (cost, omit_boundary, blur_sigma, pad)")
+            halo = _hvp_halo(self, state["halo"], 1, "contrast_dense_hvp")
+            _, u = _launch_tangent(self, flow32, v32, pad, halo, splits, False)
+        else:
+            halo = _hvp_halo(self, halo, 2, "contrast_dense_hvp")
+            iwe, u = _launch_tangent(self, flow32, v32, pad, halo, splits, True)
+            state = _hvp_state(iwe, costs, bool(omit_boundary), float(blur_sigma), key, halo)
+        g2, affine, g_lo = _hvp_upstreams(state, u, costs, bool(omit_boundary), float(blur_sigma))
+        d_flow, hv = _launch_hvp_owner(self, flow32, v32, pad, state["g1"], g2, affine, g_lo, state.get("d_flow") is None)
+        if d_flow is not None:
+            state["d_flow"] = d_flow
+        return state["value"], state["d_flow"], hv, state
+
     # ------------------------------------------------------------------------------------------ multi-reference contrast
     def iwe_dense_multi(self, flow: torch.Tensor, directions, pad: Tuple[int, int] = (0, 0), halo=DEFAULT_HALO,
                         splits: Optional[int] = None, fused: Optional[bool] = None) -> torch.Tensor:
@@ -1797,6 +1854,165 @@ def _launch_multiref_bwd(plan: "EventPlan", flow32: torch.Tensor, job: _KImagesJ
                                              ptr(g_images[k]), None if affine is None else ptr(affine[k]), int(g_lo), 1, ptr(d_flow),
                                              None, stream_ptr()), "ebos_iwe_dense_bwd")
     return d_flow
+
+
+# ----------------------------------------------------------------------------------------------
+# second order on the plain dense-flow warp: tangent image and Hessian-vector product
+# ----------------------------------------------------------------------------------------------
+def _check_hvp_operands(plan: EventPlan, flow: torch.Tensor, v: torch.Tensor, weight, what: str):
+    """flow and v as the contiguous float32 operands of the second-order kernels, or the operator's refusal."""
+    if not plan.binned:
+        raise NotImplementedError(f"{what} walks the runs of a binned plan: build it with a tile")
+    _refuse_deferred(plan, what)
+    if weight is not None:
+        raise NotImplementedError(f"{what}: per-event weights are not covered (the second-order kernels vote with unit weights)")
+    H, W = plan.image_size
+    for name, t in (("flow", flow), ("v", v)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (2, H, W):
+            raise ValueError(f"{what}: {name} must be a tensor [2, {H}, {W}], got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        if not t.dtype.is_floating_point:
+            raise ValueError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
+        if t.device != plan.device:
+            raise _hip.HipUnavailableError(f"{name} is on {t.device}, the event plan on {plan.device}")
+    return flow.detach().to(torch.float32).contiguous(), v.detach().to(torch.float32).contiguous()
+
+
+def canonical_runs(plan: EventPlan) -> EventPlan:
+    """The same binned full plan with the events of every source pixel's run in a canonical order: by (dt, x, y).  A plan build
+    leaves the order inside a run to its counting sort's atomic counter, and a kernel that adds in run order (the owner kernels)
+    inherits it; on the canonical plan two builds of the same window give such a kernel the same bits -- what a solver needs whose
+    iterations amplify the last bit (``TimeAwarePlanStack.canonical`` does the same for a stack).  Events that tie in all three are
+    interchangeable.  The offsets are shared, the event streams and the permutation are new tensors."""
+    from dataclasses import replace
+
+    if not plan.binned or plan.lean or plan.n == 0:
+        return plan
+    n = plan.n
+    run = torch.searchsorted(plan.key_offsets.to(torch.int64), torch.arange(n, device=plan.device), right=True)
+    order = torch.arange(n, device=plan.device)
+    for key in (plan.y[:n], plan.x[:n], plan.dt[:n], run):   # least significant first, each sort stable
+        order = order[torch.sort(key[order], stable=True)[1]]
+    out = replace(plan, **{name: getattr(plan, name)[:n][order].contiguous() for name in ("x", "y", "dt", "p", "perm", "bins")
+                           if getattr(plan, name) is not None})
+    for k in ("_frac_pending", "_parts_used", "_fullest_tile"):   # what bin() learnt about the window; the caches stay behind
+        if k in plan.__dict__:
+            out.__dict__[k] = plan.__dict__[k]
+    return out
+
+
+def _hvp_halo(plan: EventPlan, halo, windows: int, what: str) -> int:
+    """The built halo of the tangent kernel for ``windows`` LDS windows (2 with the IWE, 1 without): the requested one if it fits,
+    else a built halo of the plan's tile that does (``_multiref_job``'s rule) -- the largest whose windows are float64 before the
+    largest whose windows are float32: the tangent sums signed terms, and float32 windows are the slow ones (tile (64, 64), 2 M
+    events: two float32 windows of halo 32 take 111 us, one float64 window 20).  Displacements beyond the halo take
+    the exact spill path."""
+    lib = _hip.load_library()
+    th, tw = int(plan.tile[0]), int(plan.tile[1])
+    built_all = _hip.tiled_configs()
+    kind = {hl: int(lib.ebos_iwe_multiref_fits(th, tw, hl, windows)) for a, b, hl in built_all if (a, b) == (th, tw)}
+    fit = [hl for hl, k in kind.items() if k != 0]
+    want = None if halo is None or halo == "auto" else _max_halo(int(halo))
+    if want is not None and want in fit:
+        return want
+    if fit:
+        return max(fit, key=lambda hl: (kind[hl], hl))
+    raise NotImplementedError(f"{what}: no built halo of tile {(th, tw)} keeps {windows} window(s) in the LDS (ebos_iwe_multiref_fits); "
+                              f"the built (tile_h, tile_w, halo) are {built_all}")
+
+
+def _hvp_costs(cost) -> dict:
+    costs = {cost: 1.0} if isinstance(cost, str) else {k: float(w) for k, w in dict(cost).items()}
+    unknown = [k for k in costs if k not in ("image_variance", "gradient_magnitude")]
+    if unknown or not costs:
+        raise KeyError(f"unknown contrast cost {unknown[0] if unknown else cost!r}")
+    return costs
+
+
+def _launch_tangent(plan: EventPlan, flow32: torch.Tensor, v32: torch.Tensor, pad, halo: int, splits, with_iwe: bool):
+    """``splits=None``: the slab route (``ebos_iwe_dense_tangent_slab_f32``: one work item per tile, the tiles' windows summed in a
+    fixed order -- bits that repeat); an explicit ``splits >= 1``: the atomic flush (``ebos_iwe_dense_tangent_tiled_f32``) with that
+    many work items per tile."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    th, tw = int(plan.tile[0]), int(plan.tile[1])
+    windows = 2 if with_iwe else 1
+    images = torch.zeros((windows, H + 2 * pad[0], W + 2 * pad[1]), dtype=torch.float32, device=plan.device)
+    iwe = images[1] if with_iwe else None
+    with _hip.on_device(plan.device):
+        if splits is None:
+            cache = plan.__dict__.setdefault("_workspaces", {})
+            key = ("tangent", int(halo), windows)
+            if key not in cache:   # (every slab that is read is written first: no zero-fill)
+                cache[key] = torch.empty(int(lib.ebos_iwe_tangent_slab_workspace_bytes(H, W, th, tw, int(halo), windows)), dtype=torch.uint8,
+                                         device=plan.device)
+            ws = cache[key]
+            check(lib.ebos_iwe_dense_tangent_slab_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                      ptr(v32), H, W, th, tw, int(halo), pad[0], pad[1], ptr(ws), ws.numel(), ptr(iwe),
+                                                      ptr(images[0]), stream_ptr()), "ebos_iwe_dense_tangent_slab")
+        else:
+            check(lib.ebos_iwe_dense_tangent_tiled_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                       ptr(v32), H, W, th, tw, int(halo), max(1, plan.resolve_splits(splits)), pad[0],
+                                                       pad[1], ptr(iwe), ptr(images[0]), stream_ptr()), "ebos_iwe_dense_tangent_tiled")
+    return iwe, images[0]
+
+
+def _launch_hvp_owner(plan: EventPlan, flow32, v32, pad, g1, g2, affine, g_lo: int, want_grad: bool):
+    """-> (d_flow or None, hv), [2, H, W] each, every cell written."""
+    lib = _hip.require_gpu()
+    H, W = plan.image_size
+    hv = torch.empty((2, H, W), dtype=torch.float32, device=plan.device)
+    d_flow = torch.empty((2, H, W), dtype=torch.float32, device=plan.device) if want_grad else None
+    with _hip.on_device(plan.device):
+        check(lib.ebos_iwe_dense_hvp_owner_bwd_f32(ptr(plan.x), ptr(plan.y), ptr(plan.dt), ptr(plan.key_offsets), plan.n, ptr(flow32),
+                                                   ptr(v32), H, W, plan.tile[0], plan.tile[1], pad[0], pad[1], ptr(g1), ptr(g2),
+                                                   ptr(affine), int(g_lo), ptr(d_flow), ptr(hv), stream_ptr()),
+              "ebos_iwe_dense_hvp_owner_bwd")
+    return d_flow, hv
+
+
+def _hvp_affine_route(costs: dict, blur_sigma: float) -> bool:
+    """The variance contrast of the un-blurred image: its gradient map is an affine map of the image, folded into the owner kernel."""
+    return set(costs) == {"image_variance"} and blur_sigma == 0.0
+
+
+def _cost_value_and_grad_map(img: torch.Tensor, costs: dict, omit: bool, blur_sigma: float):
+    """(sum_c w_c C_c(blur(img)) [0-d], its gradient map with respect to img [h, w]) through the cost kernels and their ``_grad``
+    kernels, the blur pass and its backward.  The costs are quadratic in img, so the map is linear in it: evaluated at a tangent image
+    it is the cost's Hessian applied to that image."""
+    from .event_image_converter import EventImageConverter
+
+    leaf = img.detach().requires_grad_(True)
+    with torch.enable_grad():
+        x = EventImageConverter._gaussian_blur3(leaf, blur_sigma) if blur_sigma > 0 else leaf
+        value = None
+        for name, wgt in costs.items():
+            term = wgt * (ops.image_variance if name == "image_variance" else ops.gradient_magnitude)(x, omit)
+            value = term if value is None else value + term
+        (g,) = torch.autograd.grad(value, leaf)
+    return value.detach(), g.contiguous()
+
+
+def _hvp_state(iwe: torch.Tensor, costs: dict, omit: bool, blur_sigma: float, key, halo: int) -> dict:
+    """What ``contrast_dense_hvp`` keeps of a flow: the IWE, the first upstream image (G1, or the image with its affine map), the value."""
+    state = {"key": key, "halo": int(halo), "iwe": iwe, "d_flow": None}
+    if _hvp_affine_route(costs, blur_sigma):
+        wgt = costs["image_variance"]
+        out, moments = _image_variances(iwe[None], omit)
+        state["upstream"] = torch.full((1,), wgt, dtype=torch.float32, device=iwe.device)
+        state["affine1"] = _variance_affines(moments, state["upstream"])
+        state["g1"], state["value"] = iwe, wgt * out[0]
+    else:
+        state["value"], state["g1"] = _cost_value_and_grad_map(iwe, costs, omit, blur_sigma)
+    return state
+
+
+def _hvp_upstreams(state: dict, u: torch.Tensor, costs: dict, omit: bool, blur_sigma: float):
+    """-> (g2, affine (a1, c1, a2, c2) or None, g_lo): the second upstream image, the cost's gradient map at the tangent image."""
+    if _hvp_affine_route(costs, blur_sigma):
+        _, moments = _image_variances(u[None], omit)
+        affine = torch.cat([state["affine1"], _variance_affines(moments, state["upstream"])]).reshape(4).contiguous()
+        return u, affine, int(omit)
+    return _cost_value_and_grad_map(u, costs, omit, blur_sigma)[1], None, 0
 
 
 # ----------------------------------------------------------------------------------------------

@@ -416,15 +416,28 @@ class _UpsamplePatchFlow(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _hip.require_gpu()
         gh, gw, patch, slide, H, W = ctx.meta
-        g = _cuda_contig(g.float(), "grad")
-        d = torch.empty((2, gh, gw), dtype=torch.float32, device=g.device)
-        scratch = torch.empty(int(lib.ebos_upsample_bwd_scratch_bytes(gh, W)) // 4, dtype=torch.float32, device=g.device)
-        with _hip.on_device(g.device):
-            check(lib.ebos_upsample_patch_flow_bwd_f32(ptr(g), gh, gw, patch[0], patch[1], slide[0], slide[1], H, W,
-                                                       ptr(scratch), ptr(d), stream_ptr()), "ebos_upsample_patch_flow_bwd")
-        return d, None, None, None
+        return _upsample_adjoint(g, gh, gw, patch, slide, H, W), None, None, None
+
+
+def _upsample_adjoint(g: torch.Tensor, gh: int, gw: int, patch, slide, H: int, W: int) -> torch.Tensor:
+    lib = _hip.require_gpu()
+    g = _cuda_contig(g.float(), "grad")
+    d = torch.empty((2, gh, gw), dtype=torch.float32, device=g.device)
+    scratch = torch.empty(int(lib.ebos_upsample_bwd_scratch_bytes(gh, W)) // 4, dtype=torch.float32, device=g.device)
+    with _hip.on_device(g.device):
+        check(lib.ebos_upsample_patch_flow_bwd_f32(ptr(g), gh, gw, patch[0], patch[1], slide[0], slide[1], H, W,
+                                                   ptr(scratch), ptr(d), stream_ptr()), "ebos_upsample_patch_flow_bwd")
+    return d
+
+
+def upsample_patch_flow_adjoint(dense: torch.Tensor, grid_shape, patch_size, sliding_window) -> torch.Tensor:
+    """The transpose of ``upsample_patch_flow`` (a linear map): [2, H, W] -> [2, gh, gw] (f32), by its backward kernel, without an
+    autograd graph."""
+    if dense.dim() != 3 or dense.shape[0] != 2:
+        raise ValueError(f"dense flow must be [2, H, W], got {tuple(dense.shape)}")
+    return _upsample_adjoint(dense, int(grid_shape[0]), int(grid_shape[1]), (int(patch_size[0]), int(patch_size[1])),
+                             (int(sliding_window[0]), int(sliding_window[1])), int(dense.shape[1]), int(dense.shape[2]))
 
 
 def upsample_patch_flow(grid: torch.Tensor, patch_size, sliding_window, image_size) -> torch.Tensor:

@@ -12,9 +12,20 @@ objective(theta) = - contrast(IWE(warp(events, motion(theta)))) [+ weighted regu
 Everything per event runs in the fused tile-private HIP pipeline on an ``EventPlan`` built once per window.
 YAML keys read (same names as configs/hot_plate1.yaml:46-80 of the reference): warp_direction, motion_model,
 parameters, cost, cost_with_weight, outer_padding, iwe.{method, blur_sigma}, patch.{size, sliding_window, pyramid.{coarsest, finest}},
-optimizer.{method (Adam | CG | BFGS | L-BFGS-B | TNC | SLSQP | grid | random | TPE | optuna + sampler), sampler, seed, n_iter, parameters.lr,
-options, graph, fused,
+optimizer.{method (Adam | CG | BFGS | L-BFGS-B | TNC | SLSQP | Newton-CG | trust-ncg | trust-krylov | grid | random | TPE | optuna + sampler),
+sampler, seed, n_iter, parameters.lr, options, graph, fused,
 refine_iters}.
+
+``optimizer.method: Newton-CG | trust-ncg | trust-krylov`` (``SCIPY_HESSP_METHODS``; dense-flow on the plain warp only): scipy's
+second-order methods, the ``hessp`` of the reference's ``scipy_autograd.minimize`` (src/solver/scipy_autograd/scipy_minimize.py:106-107).
+Value, gradient and Hessian-vector product of the contrast come from ``EventPlan.contrast_dense_hvp`` -- explicit operators, no
+double backward --, through the patch-grid upsampling, its transpose and the event-thresholding mask; ``flow_norm`` /
+``image_gradient`` add torch's double backward of their own expressions.  Pyramid scales, masks, ``outer_padding``, ``iwe.blur_sigma``,
+both contrast costs with weights, ``optimizer.options`` and the warm start work as for the first-order scipy methods.  Such a solver
+builds its plan with ``emit="full"`` and, without an explicit ``tile``, on (64, 64); ``fused``, ``resident`` and graph capture are
+off, ``loop_mode`` reports "hessp", ``hessp_calls`` counts the products of the last estimate.  With a 2-DoF motion model,
+``time_aware`` or ``multi_reference`` the constructor raises ``NotImplementedError`` naming ``optimizer.method``.  Not covered:
+``dogleg`` / ``trust-exact`` (full Hessians) and ``trust-constr`` (the solver has no bounds or constraints to give it).
 
 ``time_aware: {time_bin, scheme: upwind | burgers, t0_location: first | middle, clamp}`` (optional, this build's; dense-flow only): the
 time-aware objective.  The dense flow is the flow at t0; ``flow_voxel_batch`` transports it into ``time_bin`` bins, every event is
@@ -71,7 +82,7 @@ from .. import _hip, costs, ops
 from ..flow_voxel import flow_voxel_batch
 from .._staging import to_gpu
 from ..event_image_converter import EventImageConverter
-from ..event_plan import EventPlan, TimeAwarePlanStack, multi_reference_fractions
+from ..event_plan import EventPlan, TimeAwarePlanStack, canonical_runs, multi_reference_fractions
 from . import fused_loop, multi_reference_loop, time_aware_loop
 from .base import SolverBase
 
@@ -79,6 +90,8 @@ logger = logging.getLogger(__name__)
 
 CONTRAST_COSTS = ("image_variance", "gradient_magnitude")
 SCIPY_METHODS = ("CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")  # first-order methods of scipy.optimize.minimize
+# second-order methods of scipy.optimize.minimize that take a Hessian-vector product (``hessp``): plain dense-flow warp only
+SCIPY_HESSP_METHODS = ("Newton-CG", "trust-ncg", "trust-krylov")
 
 
 def parse_time_aware(block) -> Optional[dict]:
@@ -213,6 +226,9 @@ class ContrastMaximizationMixin(object):
             raise ValueError("patch.pyramid needs coarsest >= finest >= 1")
         ocfg = cfg.get("optimizer") or {}
         self.opt_method = ocfg.get("method", "Adam")
+        # Newton-CG / trust-ncg / trust-krylov (module docstring): scipy with the contrast's Hessian-vector product
+        self.hessp = self.opt_method in SCIPY_HESSP_METHODS
+        self.hessp_calls = 0   # products of the last estimate
         self.n_iter = int(ocfg.get("n_iter", 100))
         self.lr = float((ocfg.get("parameters") or {}).get("lr", 0.05))
         self.scipy_options = dict(ocfg.get("options") or {})
@@ -269,6 +285,13 @@ class ContrastMaximizationMixin(object):
             self.resident = False
             if self.multi_reference.get("native", False):
                 self._check_native_multi_reference()
+        if self.hessp:
+            if self.motion_model != "dense-flow" or self.time_aware is not None or self.multi_reference is not None:
+                raise NotImplementedError(f"optimizer.method {self.opt_method!r}: the Hessian-vector product is defined for motion_model "
+                                          "'dense-flow' on the plain warp (no time_aware or multi_reference block); there, Adam or one "
+                                          f"of {SCIPY_METHODS}")
+            self.use_graph = self.fused_loop = False
+            self.resident = False
         self._warp = self._resolve_warp()
 
     def _check_native(self, block: str, variance_alone: str, before_method=None, last=None) -> None:
@@ -426,6 +449,9 @@ class ContrastMaximizationMixin(object):
         if self.time_aware is not None:   # the bins travel with the SoA events of the full build
             return EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full",
                                    time_bin=self.time_aware["time_bin"])
+        if self.hessp:   # the second-order kernels read the SoA events of the full build; the owner kernel adds in run order, and
+            # Newton's iterations amplify a last bit: every run in a canonical order, so two builds of a window give the same solve
+            return canonical_runs(EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(), emit="full"))
         return EventPlan.build(ev, self.orig_image_shape, self.warp_direction, True, tile=self.plan_tile(),
                                emit="full" if getattr(self, "_fractional_stream", False) else "compact")
 
@@ -526,7 +552,7 @@ class ContrastMaximizationMixin(object):
 
         if self.tile is not None:
             return self.tile
-        if self.multi_reference is not None:
+        if self.multi_reference is not None or self.hessp:   # (the two windows of the tangent pass fit like two references)
             return MULTI_REFERENCE_TILE
         if self.time_aware is not None and self.time_aware.get("native", False):
             # the native loop's forward is the tiled time-aware kernel: a tile it is built for with this halo, (64, 64) first
@@ -590,6 +616,7 @@ class ContrastMaximizationMixin(object):
     def _estimate_patch_flow(self, plan: EventPlan) -> torch.Tensor:
         H, W = self.orig_image_shape
         self.history, self.patch_flow_per_scale, self.loop_modes = [], [], []
+        self.hessp_calls = 0
         theta = None
         for patch_size, sliding_window, n_iter in self.pyramid_scales():
             mask = self.patch_mask(plan, patch_size, sliding_window)
@@ -615,6 +642,11 @@ class ContrastMaximizationMixin(object):
                                                                 self.flow_terms.get("image_gradient", 0.0), self.omit_boundary, self.pad,
                                                                 self.halo, self.lr, capacity=capacity, theta_mask=mask, norm=norm)
             return self._optimise_native(loop, theta, n_iter)
+        if self.hessp:
+            value_and_grad, hessp = self._hessp_objective(plan, patch_size, sliding_window, mask)
+            self.graphed, self.fused, self.loop_mode = False, False, "hessp"
+            self.loop_modes.append("hessp")
+            return self._run_scipy(None, theta.detach(), n_iter, value_and_grad=value_and_grad, hessp=hessp)
         theta = theta.requires_grad_(True)
 
         def evaluate():  # (mask: the gradient of a patch that is not estimated is zero, so it keeps its masked start)
@@ -684,16 +716,82 @@ class ContrastMaximizationMixin(object):
         self.history += loop.losses[:n_iter].cpu().tolist()
         return loop.theta
 
-    def _run_scipy(self, evaluate, theta: torch.Tensor, n_iter: int, value_and_grad=None) -> torch.Tensor:
+    def _hessp_objective(self, plan: EventPlan, patch_size, sliding_window, mask: Optional[torch.Tensor]):
+        """(value_and_grad, hessp) of one pyramid scale for the ``SCIPY_HESSP_METHODS``, without an autograd graph through the events:
+
+            loss(theta) = -sum_c w_c C_c(dense) + regularisers(dense),   dense = U (m * theta)
+            H_theta p   = m * U^T (H_dense (U (m * p)))
+
+        with U the patch-grid upsampling (linear; U^T is its backward kernel) and m the event-thresholding mask.  The contrast's
+        value, gradient and product come from ``EventPlan.contrast_dense_hvp``, whose ``state`` -- what depends on the flow alone --
+        is kept from the last ``value_and_grad`` and reused by every ``hessp`` at that theta (scipy asks for many products per outer
+        iteration); a product asked at another theta evaluates there first.  The regularisers are plain torch expressions on the
+        dense flow: their product is torch's double backward of the same expressions, on the device."""
+        H, W = self.orig_image_shape
+        grid = patch_grid_shape((H, W), patch_size, sliding_window)
+        kw = {"cost": dict(self.contrast_terms), "omit_boundary": self.omit_boundary, "blur_sigma": self.blur_sigma,
+              "pad": (self.pad, self.pad), "halo": self.halo}
+        zero = torch.zeros((2, H, W), dtype=torch.float32, device=plan.device)
+        kept = {"theta": None, "dense": None, "state": None}
+
+        def to_dense(t):
+            t = t.to(device=plan.device, dtype=torch.float32)
+            return ops.upsample_patch_flow(t if mask is None else t * mask, patch_size, sliding_window, (H, W))
+
+        def to_grid(d):
+            g = ops.upsample_patch_flow_adjoint(d, grid, patch_size, sliding_window)
+            return g if mask is None else g * mask
+
+        def regularisers(dense, v=None):
+            """(value, gradient, product with v or None) of the flow terms at ``dense``."""
+            f = dense.detach().requires_grad_(True)
+            with torch.enable_grad():
+                ones = torch.ones(f.shape[-2:], dtype=f.dtype, device=f.device)
+                r = self.flow_cost.calculate({"flow": f, "omit_boundary": self.omit_boundary, "weights": ones})
+                (g,) = torch.autograd.grad(r, f, create_graph=v is not None)
+                hv = None
+                if v is not None:   # (a term that is piecewise linear in the flow, like the total variation, has no curvature)
+                    hv = torch.autograd.grad(g, f, v, allow_unused=True)[0] if g.requires_grad else None
+                    hv = torch.zeros_like(f) if hv is None else hv
+            return r.detach(), g.detach(), hv
+
+        def value_and_grad(theta):
+            dense = to_dense(theta)
+            value, d_flow, _, state = plan.contrast_dense_hvp(dense, zero, **kw)
+            kept["theta"], kept["dense"], kept["state"] = theta.detach().clone(), dense, state
+            loss, d_dense = -value, -d_flow
+            if self.flow_cost is not None:
+                r, g, _ = regularisers(dense)
+                loss, d_dense = loss + r, d_dense + g
+            return loss, to_grid(d_dense)
+
+        def hessp(theta, p):
+            if kept["theta"] is None or not torch.equal(kept["theta"], theta):
+                value_and_grad(theta)
+            v = to_dense(p)
+            hv = -plan.contrast_dense_hvp(kept["dense"], v, state=kept["state"], **kw)[2]
+            if self.flow_cost is not None:
+                hv = hv + regularisers(kept["dense"], v)[2]
+            self.hessp_calls += 1
+            return to_grid(hv)
+
+        return value_and_grad, hessp
+
+    def _run_scipy(self, evaluate, theta: torch.Tensor, n_iter: int, value_and_grad=None, hessp=None) -> torch.Tensor:
         """Gradient-based scipy optimisers on the GPU objective, the role of the reference's
         ``scipy_autograd.minimize`` (src/solver/scipy_autograd/scipy_minimize.py:6-125): scipy drives float64 numpy
         parameters on the host; every function/gradient evaluation is one fused forward + backward on the device.
         Line searches need a differentiable start: with integer sensor coordinates the all-zero flow sits on the kink
         of the bilinear vote (every event exactly on a pixel centre), so warm-start these methods
-        (``set_previous_frame_best_estimation``) or use Adam, which does not care."""
+        (``set_previous_frame_best_estimation``) or use Adam, which does not care.  ``hessp(theta, p)``: the Hessian-vector product
+        scipy's Newton-CG / trust-region methods ask for (:106-107 of the reference's wrapper), handed on as ``hessp``."""
         import scipy.optimize as sopt
 
         shape = tuple(theta.shape)
+        second = {}
+        if hessp is not None:
+            second["hessp"] = lambda x, p: hessp(torch.from_numpy(x.reshape(shape)), torch.from_numpy(p.reshape(shape))) \
+                .double().cpu().numpy().reshape(-1)
 
         def fun(x):
             if value_and_grad is not None:  # fixed kernel pipeline, no autograd graph
@@ -709,7 +807,7 @@ class ContrastMaximizationMixin(object):
             return self.history[-1], theta.grad.detach().double().cpu().numpy().reshape(-1)
 
         x0 = theta.detach().double().cpu().numpy().reshape(-1)
-        res = sopt.minimize(fun, x0, jac=True, method=self.opt_method, options={"maxiter": int(n_iter), **self.scipy_options})
+        res = sopt.minimize(fun, x0, jac=True, method=self.opt_method, options={"maxiter": int(n_iter), **self.scipy_options}, **second)
         if not res.success:
             logger.warning(f"Unsuccessful optimization step! ({res.message})")
         self.scipy_result = res

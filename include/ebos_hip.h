@@ -1564,6 +1564,49 @@ int ebos_iwe_dense_multiref_owner_bwd_f32(const float* xs, const float* ys, cons
                                           float* d_flow, ebos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Second order on the plain dense-flow warp: the tangent image of the IWE and the Hessian-vector product of a contrast that is
+ * quadratic in the image (both shipped contrasts are), on a binned plan with its SoA events.  v [2, H, W] is the direction.
+ * An event with source pixel s, flow cell flow[:, s] and taps / fractions (fr, fc) of its warped position moves, along v, by
+ * (tx, ty) = (-dt v[0][s], -dt v[1][s]).
+ * ebos_iwe_dense_tangent_tiled_f32: u = d IWE(flow + e v) / de at e = 0, the splat of ebos_iwe_dense_multiref_tiled_f32 with the
+ *   four weights replaced by their derivatives along (tx, ty):
+ *       w00' = -(1-fc) tx - (1-fr) ty     w10' = (1-fc) tx - fr ty     w01' = -fc tx + (1-fr) ty     w11' = fc tx + fr ty
+ *   One LDS window per (tile, split) workgroup for u and, where iwe is not NULL, a second one for the IWE of the same pass; f64 windows
+ *   where ebos_iwe_multiref_fits(tile_h, tile_w, halo, iwe ? 2 : 1) is 2, f32 where it is 1, EBOS_ERR_UNSUPPORTED and no launch where
+ *   it is 0.  tangent and iwe are [h, w], h = H + 2 pad_h ...; the kernel ACCUMULATES into them (the caller zero-fills), beyond the
+ *   halo with global float atomics.
+ * ebos_iwe_dense_hvp_owner_bwd_f32: with G1 = a1 g1 + c1 and G2 = a2 g2 + c2 inside [g_lo, h - g_lo) x [g_lo, w - g_lo), 0 outside
+ *   (g1 = the cost's gradient map at the IWE, g2 = the same map at u; affine = (a1, c1, a2, c2) on the device, nullable: a = 1, c = 0),
+ *       dx(G) = (1-fc)(G10-G00) + fc(G11-G01)    dy(G) = (1-fr)(G01-G00) + fr(G11-G10)    cross = G1_00 - G1_10 - G1_01 + G1_11
+ *       hv[:, s]     = sum over the events of s of -dt (dx(G2) + cross ty,  dy(G2) + cross tx)
+ *       d_flow[:, s] = sum over the events of s of -dt (dx(G1), dy(G1))                               (nullable: not written)
+ *   The pattern of ebos_iwe_dense_multiref_owner_bwd_f32: the lane that walks a pixel's run is the only writer of its cells.  No
+ *   atomics; hv (and d_flow) [2, H, W] are OVERWRITTEN, every cell (zeros where no event lies, n == 0 included); the order of the
+ *   additions is the plan's, so two calls give the same bits.  Runs of more than 64 events are walked by the whole wave with a fixed
+ *   reduction tree.
+ * ebos_iwe_dense_tangent_slab_f32: the same images with bits that repeat.  The tangent kernel's sums over the windows of neighbouring
+ *   tiles meet in global float atomics, whose order the hardware picks: where three or more windows overlap, the last bits differ
+ *   from call to call.  Here every tile (one work item per tile) stores its window(s) to its slab of `workspace`
+ *   (ebos_iwe_tangent_slab_workspace_bytes, host only: 0 where ebos_iwe_multiref_fits is 0; no zero-fill needed) and a combine pass
+ *   adds to every image cell the slabs that cover it, in tile order, summed in f64.  Same arguments otherwise, same convention (the
+ *   caller zero-fills the images), same spill path beyond the halo -- the one part that stays atomic.  EBOS_ERR_SCRATCH for a
+ *   workspace that is too small.  The bits repeat where the windows are f64 and nothing spills.
+ * All three refuse NULL buffers and bad sizes (EBOS_ERR_INVALID_ARG) before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ebos_iwe_dense_tangent_tiled_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                     const float* flow, const float* v, int H, int W, int tile_h, int tile_w, int halo, int splits,
+                                     int pad_h, int pad_w, float* iwe, float* tangent, ebos_stream_t stream);
+size_t ebos_iwe_tangent_slab_workspace_bytes(int H, int W, int tile_h, int tile_w, int halo, int windows);
+int ebos_iwe_dense_tangent_slab_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                    const float* flow, const float* v, int H, int W, int tile_h, int tile_w, int halo, int pad_h,
+                                    int pad_w, void* workspace, size_t workspace_bytes, float* iwe, float* tangent,
+                                    ebos_stream_t stream);
+int ebos_iwe_dense_hvp_owner_bwd_f32(const float* xs, const float* ys, const float* dts, const int32_t* key_offsets, int64_t n,
+                                     const float* flow, const float* v, int H, int W, int tile_h, int tile_w, int pad_h, int pad_w,
+                                     const float* g1, const float* g2, const float* affine, int g_lo, float* d_flow, float* hv,
+                                     ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-reference contrast on the tile-private pipeline: the K-image form of ebos_iwe_dense_slab_f32 / ebos_iwe_dense_tiled_bwd_f32.
  * Events, shifts and K as above: dt_k = dt + shifts[k] is ONE rounded float32 add per event, before anything else uses it.
  * ebos_slab_multiref_config (host only): the built (tile_h, tile_w, halo) triples, as ebos_slab_config lists the single form's.
