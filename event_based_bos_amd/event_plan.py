@@ -806,9 +806,12 @@ class EventPlan:
         (``ebos_iwe_multiref_fits`` with 2 windows, 1 without the IWE); displacements beyond it take the exact spill path.
         ``splits=None``: the slab route (``ebos_iwe_dense_tangent_slab_f32``) -- every tile stores its window(s) and a combine pass sums
         the windows that cover a cell in tile order, so the bits repeat from call to call, and with and without the IWE, wherever the
-        windows are float64 and nothing spills.  ``splits=k``: k work items per tile on the atomic flush
-        (``ebos_iwe_dense_tangent_tiled_f32``), whose sums over overlapping windows meet in float atomics: the same images to
-        rounding.  NotImplementedError for an un-binned, lean or deferred plan, a tile without a fitting built halo and per-event
+        windows are float64 and nothing spills.  Float32 windows -- two windows of (64, 64, 32), (32, 64, 32) and (32, 64, 48), the
+        one window of (64, 64, 64) -- are summed by LDS float atomics in the order the hardware picks: the same images to rounding
+        (1e-6 of the float64 image per cell, like float64 windows), but 0 of 10 repeated calls repeated the first call's bits on
+        70 x 135 with 30 000 events (MI355X, tests/test_gpu_hvp_tiles.py, which runs every built triple).  ``splits=k``: k work
+        items per tile on the atomic flush (``ebos_iwe_dense_tangent_tiled_f32``), whose sums over overlapping windows meet in
+        float atomics: the same images to rounding.  NotImplementedError for an un-binned, lean or deferred plan, a tile without a fitting built halo and per-event
         weights; ValueError for a ``flow`` / ``v`` that is not the plan's."""
         flow32, v32 = _check_hvp_operands(self, flow, v, weight, "iwe_dense_jvp")
         halo = _hvp_halo(self, halo, 2 if with_iwe else 1, "iwe_dense_jvp")
@@ -829,10 +832,16 @@ class EventPlan:
 
         ``state`` (returned; pass it back for another ``v`` at the SAME flow and options) carries what depends on ``flow`` alone -- the
         IWE, G1 or its affine map, value and gradient: such a call makes the tangent window only, skips the first cost pass and
-        returns the state's value and ``d_flow``.  The product from a reused state is the product without one bit for bit: the
-        tangent image comes from the slab route of ``iwe_dense_jvp`` with the state's halo (float64 windows in both calls; an event
-        beyond the halo takes the spill path's float atomics, and then the last bits may differ).  ``splits`` as in ``iwe_dense_jvp``.
-        Refusals: ``iwe_dense_jvp``'s, KeyError for an unknown cost."""
+        returns the state's value and ``d_flow``.  The tangent image comes from the slab route of ``iwe_dense_jvp`` with the state's
+        halo.  Where that halo keeps two windows of the plan's tile as float64 -- tiles (64, 64) (halo 16 with ``"auto"``), (32, 32)
+        and (16, 64) (halo 32), ``hvp_float64_tiles()`` -- both calls run float64 windows and the product from a reused state is the
+        product without one bit for bit, as are repeated products, value and ``d_flow`` (an event beyond the halo takes the spill
+        path's float atomics, and then the last bits may differ).  On tile (32, 64), and with an explicit halo 32 on (64, 64), the
+        two windows of the first call are float32 (LDS float atomics) and the state's single window float64: every figure meets the
+        same bars, but ``d_flow`` repeated its bits in 0 of 10 calls and the tangent image with the IWE is not the tangent image
+        without it bit for bit, so ``hv`` from a reused state need not be either (MI355X, tests/test_gpu_hvp_tiles.py); the solver's
+        second-order methods refuse such a tile.  ``splits`` as in
+        ``iwe_dense_jvp``.  Refusals: ``iwe_dense_jvp``'s, KeyError for an unknown cost."""
         flow32, v32 = _check_hvp_operands(self, flow, v, weight, "contrast_dense_hvp")
         costs = _hvp_costs(cost)
         pad = (int(pad[0]), int(pad[1]))
@@ -1900,24 +1909,39 @@ def canonical_runs(plan: EventPlan) -> EventPlan:
     return out
 
 
-def _hvp_halo(plan: EventPlan, halo, windows: int, what: str) -> int:
-    """The built halo of the tangent kernel for ``windows`` LDS windows (2 with the IWE, 1 without): the requested one if it fits,
-    else a built halo of the plan's tile that does (``_multiref_job``'s rule) -- the largest whose windows are float64 before the
-    largest whose windows are float32: the tangent sums signed terms, and float32 windows are the slow ones (tile (64, 64), 2 M
-    events: two float32 windows of halo 32 take 111 us, one float64 window 20).  Displacements beyond the halo take
-    the exact spill path."""
+def hvp_tile_halo(tile, halo, windows: int, what: str) -> Tuple[int, int]:
+    """(halo, kind) of the tangent kernel on plans of ``tile`` for ``windows`` LDS windows (2 with the IWE, 1 without): the requested
+    built halo if its windows fit, else a built halo of the tile that does (``_multiref_job``'s rule) -- the largest whose windows
+    are float64 before the largest whose windows are float32: the tangent sums signed terms, and float32 windows are the slow ones
+    (tile (64, 64), 2 M events: two float32 windows of halo 32 take 111 us, one float64 window 20) and the ones whose
+    bits do not repeat.  ``kind``: ``ebos_iwe_multiref_fits`` of the choice, 2 = float64 windows, 1 = float32.  Needs the library,
+    not a GPU."""
     lib = _hip.load_library()
-    th, tw = int(plan.tile[0]), int(plan.tile[1])
+    th, tw = int(tile[0]), int(tile[1])
     built_all = _hip.tiled_configs()
     kind = {hl: int(lib.ebos_iwe_multiref_fits(th, tw, hl, windows)) for a, b, hl in built_all if (a, b) == (th, tw)}
     fit = [hl for hl, k in kind.items() if k != 0]
     want = None if halo is None or halo == "auto" else _max_halo(int(halo))
     if want is not None and want in fit:
-        return want
+        return want, kind[want]
     if fit:
-        return max(fit, key=lambda hl: (kind[hl], hl))
+        best = max(fit, key=lambda hl: (kind[hl], hl))
+        return best, kind[best]
     raise NotImplementedError(f"{what}: no built halo of tile {(th, tw)} keeps {windows} window(s) in the LDS (ebos_iwe_multiref_fits); "
                               f"the built (tile_h, tile_w, halo) are {built_all}")
+
+
+def hvp_float64_tiles() -> list:
+    """The built tiles on which ``contrast_dense_hvp`` keeps BOTH of its windows as float64 with some built halo -- where its value,
+    gradient and product repeat their bits from call to call."""
+    lib = _hip.load_library()
+    return sorted({(th, tw) for th, tw, hl in _hip.tiled_configs() if lib.ebos_iwe_multiref_fits(th, tw, hl, 2) == 2})
+
+
+def _hvp_halo(plan: EventPlan, halo, windows: int, what: str) -> int:
+    """``hvp_tile_halo`` of the plan's tile: the built halo the tangent kernel runs with.  Displacements beyond it take the exact
+    spill path."""
+    return hvp_tile_halo(plan.tile, halo, windows, what)[0]
 
 
 def _hvp_costs(cost) -> dict:

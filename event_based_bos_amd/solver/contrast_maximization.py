@@ -24,7 +24,9 @@ double backward --, through the patch-grid upsampling, its transpose and the eve
 both contrast costs with weights, ``optimizer.options`` and the warm start work as for the first-order scipy methods.  Such a solver
 builds its plan with ``emit="full"`` and, without an explicit ``tile``, on (64, 64); ``fused``, ``resident`` and graph capture are
 off, ``loop_mode`` reports "hessp", ``hessp_calls`` counts the products of the last estimate.  With a 2-DoF motion model,
-``time_aware`` or ``multi_reference`` the constructor raises ``NotImplementedError`` naming ``optimizer.method``.  Not covered:
+``time_aware`` or ``multi_reference`` the constructor raises ``NotImplementedError`` naming ``optimizer.method``; so it does for a
+``tile`` / ``halo`` whose two LDS windows are float32 (``tile: [32, 64]``, ``halo: 32`` on (64, 64)): their sums do not repeat their
+bits and two estimates of one window would differ (``_check_hessp_tile``).  Not covered:
 ``dogleg`` / ``trust-exact`` (full Hessians) and ``trust-constr`` (the solver has no bounds or constraints to give it).
 
 ``time_aware: {time_bin, scheme: upwind | burgers, t0_location: first | middle, clamp}`` (optional, this build's; dense-flow only): the
@@ -292,6 +294,7 @@ class ContrastMaximizationMixin(object):
                                           f"of {SCIPY_METHODS}")
             self.use_graph = self.fused_loop = False
             self.resident = False
+            self._check_hessp_tile()
         self._warp = self._resolve_warp()
 
     def _check_native(self, block: str, variance_alone: str, before_method=None, last=None) -> None:
@@ -314,6 +317,30 @@ class ContrastMaximizationMixin(object):
                 what = last()
         if what is not None:
             raise NotImplementedError(f"{block}.native does not cover " + what + "; drop native to run the autograd loop")
+
+    def _check_hessp_tile(self) -> None:
+        """The ``SCIPY_HESSP_METHODS`` need a loss and a gradient that repeat their bits: scipy's Newton iterations carry a last bit
+        through the kinks of the vote (**Bits**).  ``contrast_dense_hvp`` gives that where the two LDS windows of its
+        first call are float64; as float32 windows they are summed by LDS float atomics in the order the hardware picks -- on tile
+        (32, 64) the gradient repeated its bits in 0 of 10 calls and two estimates of one window ended 1.9e-6 px apart after four
+        iterations (tests/test_gpu_hvp_tiles.py).  Such a (tile, halo) is refused here, at construction, with the tiles that work; a
+        tile without a built halo raises ``hvp_tile_halo``'s NotImplementedError."""
+        from .. import _hip
+        from ..event_plan import hvp_float64_tiles, hvp_tile_halo
+
+        try:
+            _hip.load_library()
+        except _hip.HipUnavailableError:
+            return   # nothing to ask yet: the first estimate raises this error itself
+        tile = tuple(int(v) for v in self.plan_tile())
+        halo, kind = hvp_tile_halo(tile, self.halo, 2, f"optimizer.method {self.opt_method!r}")
+        if kind != 2:
+            raise NotImplementedError(
+                f"optimizer.method {self.opt_method!r} with tile {list(tile)}, halo {self.halo!r}: the IWE and the tangent image of one "
+                f"product would be float32 LDS windows (halo {halo}; ebos_iwe_multiref_fits), whose sums do not repeat their bits, "
+                "and the second-order methods amplify a last bit: two estimates of one window would differ.  Tiles whose two "
+                f"windows are float64 with halo \"auto\": {[list(t) for t in hvp_float64_tiles()]}; without a `tile` key the "
+                f"solver plans on {list(MULTI_REFERENCE_TILE)}")
 
     def _check_native_multi_reference(self) -> None:
         """``multi_reference.native``: the shared clauses, no ``outer_padding``, a (tile, halo) the K-image kernels are built for."""

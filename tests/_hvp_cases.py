@@ -116,8 +116,9 @@ def _grad_map(img, cost, omit, blur):
     return total.detach(), g
 
 
-def closed_form(ev, flow, v, cost="image_variance", omit=False, pad=0, blur=0.0, dtype=torch.float64):
-    """(value, d_flow, hv, iwe, tangent) by the formula of the kernels, event by event, in ``dtype`` on the CPU:
+def closed_form(ev, flow, v, cost="image_variance", omit=False, pad=0, blur=0.0, dtype=torch.float64, shape=None):
+    """(value, d_flow, hv, iwe, tangent) by the formula of the kernels, event by event, in ``dtype`` on the CPU (``shape``: the image
+    size of the window, (H, W) of this module unless given):
 
         s = (trunc x, trunc y);  x' = x - dt flow[0][s];  y' = y - dt flow[1][s];  (tx, ty) = (-dt v[0][s], -dt v[1][s])
         taps (R, C) = floor((x', y') + eps), fractions (fr, fc)
@@ -125,6 +126,7 @@ def closed_form(ev, flow, v, cost="image_variance", omit=False, pad=0, blur=0.0,
         G1 = grad cost(IWE),  G2 = grad cost(tangent)
         dx(G) = (1-fc)(G10-G00) + fc(G11-G01)    dy(G) = (1-fr)(G01-G00) + fr(G11-G10)    cross = G1_00 - G1_10 - G1_01 + G1_11
         hv[:, s] += -dt (dx(G2) + cross ty, dy(G2) + cross tx)        d_flow[:, s] += -dt (dx(G1), dy(G1))"""
+    H, W = shape or (M.H, M.W)
     e = torch.from_numpy(ev).to(dtype)
     fl, vv = torch.from_numpy(flow).to(dtype), torch.from_numpy(v).to(dtype)
     h, w = H + 2 * pad, W + 2 * pad

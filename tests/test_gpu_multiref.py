@@ -91,6 +91,31 @@ def test_forward_routes(ebos, case):
         assert (np.abs(warped[:, :2] - ev[:, :2]).max(1) > 9).sum() > 100
 
 
+AT_LIMIT = {"16x64x32-K2-f64": ((16, 64), 32, ("first", "last"), 2), "16x64x32-K4-f32": ((16, 64), 32, FQML, 1),
+            "32x64x48-K1-f64": ((32, 64), 48, ("middle",), 2), "32x64x48-K2-f32": ((32, 64), 48, ("first", "last"), 1)}
+
+
+@pytest.mark.parametrize("case", list(AT_LIMIT))
+def test_forward_with_the_whole_lds(ebos, case):
+    """The configurations whose K windows take exactly 160 KiB of dynamic LDS, as float64 and as float32."""
+    from event_based_bos_amd import _hip
+
+    tile, halo, directions, kind = AT_LIMIT[case]
+    K = len(directions)
+    assert _hip.load_library().ebos_iwe_multiref_fits(tile[0], tile[1], halo, K) == kind
+    assert K * (tile[0] + 2 * halo) * (tile[1] + 2 * halo) * (8 if kind == 2 else 4) == 160 * 1024
+    ev, flow = C.plain_window(), C.flow_u(6.0)
+    plan = C.plan_of(ebos, ev, "first", tile)
+    job = job_of(plan, directions, 0, halo, True)
+    assert job.halo == halo and job.fused
+    for pad in (0, 2):
+        want = C.cached(("iwes", directions, pad), lambda: C.ref_iwes(ev, flow, directions, pad).numpy())
+        got = plan.iwe_dense_multi(G(flow, torch.float32), list(directions), pad=(pad, pad), halo=halo, fused=True)
+        errs = [rel(got[k], want[k]) for k in range(K)]
+        print(f"{case} pad={pad}: IWE rel L2 {errs}")
+        assert got.shape == (K, H + 2 * pad, W + 2 * pad) and bool(torch.isfinite(got).all()) and max(errs) < 1e-4
+
+
 # ---------------------------------------------------------------------------------------------- backward
 @pytest.mark.parametrize("directions", [("last",), FML, FQML], ids=["K1", "K3", "K4"])
 @pytest.mark.parametrize("pad", [0, 2])

@@ -209,3 +209,95 @@ def test_plan_operators_refuse(op):
             _host_plan().contrast_dense_hvp(flow, flow, cost="sharpness")
         with pytest.raises(KeyError):
             _host_plan().contrast_dense_hvp(flow, flow, cost={"image_variance": 1.0, "sharpness": 1.0})
+
+
+# ---------------------------------------------------------------------------------------------- every built triple (host side)
+# (tile_h, tile_w, halo) -> (ebos_iwe_multiref_fits with 1 window, with 2): 2 = float64 windows, 1 = float32, 0 = they do not fit
+FITS_TABLE = {(64, 64, 32): (2, 1), (32, 64, 32): (2, 1), (32, 32, 32): (2, 2), (16, 64, 32): (2, 2), (64, 64, 16): (2, 2),
+              (32, 32, 16): (2, 2), (32, 32, 8): (2, 2), (64, 64, 64): (1, 0), (32, 64, 48): (2, 1)}
+# ... and the dynamic LDS of the launch, windows * (tile_h + 2 halo) * (tile_w + 2 halo) * sizeof(accumulator)
+LDS_TABLE = {(64, 64, 32): (131072, 131072), (32, 64, 32): (98304, 98304), (32, 32, 32): (73728, 147456), (16, 64, 32): (81920, 163840),
+             (64, 64, 16): (73728, 147456), (32, 32, 16): (32768, 65536), (32, 32, 8): (18432, 36864), (64, 64, 64): (147456, None),
+             (32, 64, 48): (163840, 163840)}
+
+
+def test_fits_table_of_every_built_triple(lib):
+    """Which accumulator the tangent kernel (and the multi-reference kernel, with K = windows) runs with per built triple, and the
+    LDS it asks for: three launches take the whole 160 KiB."""
+    from event_based_bos_amd import _hip
+
+    assert set(_hip.tiled_configs()) == set(FITS_TABLE)
+    at_limit = []
+    for (th, tw, hl), kinds in FITS_TABLE.items():
+        for windows, kind, lds in zip((1, 2), kinds, LDS_TABLE[(th, tw, hl)]):
+            assert lib.ebos_iwe_multiref_fits(th, tw, hl, windows) == kind, (th, tw, hl, windows)
+            if kind:
+                assert windows * (th + 2 * hl) * (tw + 2 * hl) * (8 if kind == 2 else 4) == lds <= 160 * 1024
+                at_limit += [((th, tw, hl), windows, kind)] if lds == 160 * 1024 else []
+            else:
+                assert lds is None and windows * (th + 2 * hl) * (tw + 2 * hl) * 4 > 160 * 1024
+    assert at_limit == [((16, 64, 32), 2, 2), ((32, 64, 48), 1, 2), ((32, 64, 48), 2, 1)]
+    # the multi-reference forms of the same limits: K windows
+    assert lib.ebos_iwe_multiref_fits(16, 64, 32, 4) == 1 and lib.ebos_iwe_multiref_fits(32, 64, 48, 3) == 0
+
+
+@pytest.mark.parametrize("shape", [(70, 135), (13, 21)])
+def test_tangent_slab_workspace_is_tiles_times_windows(lib, shape):
+    """``ebos_iwe_tangent_slab_workspace_bytes`` = tiles * windows * LH * LW * sizeof(accumulator), the accumulator that of the table."""
+    H_, W_ = shape
+    for (th, tw, hl), kinds in FITS_TABLE.items():
+        tiles = -(-H_ // th) * -(-W_ // tw)
+        for windows, kind in zip((1, 2), kinds):
+            want = tiles * windows * (th + 2 * hl) * (tw + 2 * hl) * {2: 8, 1: 4, 0: 0}[kind]
+            assert lib.ebos_iwe_tangent_slab_workspace_bytes(H_, W_, th, tw, hl, windows) == want, (shape, th, tw, hl, windows)
+    assert lib.ebos_iwe_tangent_slab_workspace_bytes(70, 135, 64, 64, 16, 2) == 6 * 2 * 96 * 96 * 8
+    assert lib.ebos_iwe_tangent_slab_workspace_bytes(13, 21, 32, 64, 48, 2) == 1 * 2 * 128 * 160 * 4
+
+
+def test_hvp_halo_choices_per_tile(lib):
+    """``_hvp_halo`` with "auto": the largest built halo of the tile whose windows are float64, failing that float32 -- with the IWE
+    (2 windows) / without (1); an explicit halo that fits is honoured, float32 windows included; one that does not falls back."""
+    from event_based_bos_amd import event_plan as EP
+
+    for tile, (two, one) in {(64, 64): (16, 32), (32, 64): (48, 48), (32, 32): (32, 32), (16, 64): (32, 32)}.items():
+        plan = _host_plan(tile=tile)
+        assert (EP._hvp_halo(plan, "auto", 2, "test"), EP._hvp_halo(plan, "auto", 1, "test")) == (two, one), tile
+        assert EP._hvp_halo(plan, None, 2, "test") == two
+    for windows in (1, 2):
+        with pytest.raises(NotImplementedError, match=r"no built halo of tile \(45, 80\)"):
+            EP._hvp_halo(_host_plan(tile=(45, 80)), "auto", windows, "test")
+    big = _host_plan(tile=(64, 64))
+    assert EP._hvp_halo(big, 32, 2, "test") == 32 and lib.ebos_iwe_multiref_fits(64, 64, 32, 2) == 1       # honoured as float32
+    assert EP._hvp_halo(big, 64, 1, "test") == 64 and EP._hvp_halo(big, 16, 1, "test") == 16
+    assert EP._hvp_halo(big, 64, 2, "test") == 16                                                           # does not fit: falls back
+    assert EP._hvp_halo(_host_plan(tile=(32, 64)), 32, 2, "test") == 32 and EP._hvp_halo(_host_plan(tile=(32, 32)), 8, 2, "test") == 8
+
+
+def test_per_cell_bars_hold_ten_times_over_in_float32():
+    """tests/test_gpu_hvp_tiles.py asserts every bar per cell as well, max |got - want| <= bar * max |want|.  What float32 arithmetic
+    alone does to that form -- the closed form in float32 on the CPU against the float64 yardstick, 70 x 135, 30 000 events -- must
+    sit at least ten times inside the bars (observed: IWE 2.4e-6, tangent 2.6e-6, d_flow 6.2e-6, hv 3.4e-6)."""
+    import _hvp_tile_cases as T
+
+    dev = T.float32_cpu_deviation()
+    print("float32 closed form, per cell: " + ", ".join(f"{k} {v:.2e}" for k, v in dev.items()))
+    assert max(dev["iwe"], dev["tangent"]) < 1e-5 and max(dev["d_flow"], dev["hv"]) < 1e-4
+
+
+@pytest.mark.parametrize("method", HESSP_METHODS)
+def test_solver_refuses_a_tile_with_float32_windows(lib, method):
+    """The second-order methods need bits that repeat: a (tile, halo) whose two windows fit the LDS as float32 only is refused at
+    construction, with the tiles that work (tests/test_gpu_hvp_tiles.py::test_solver_on_a_tile_with_float32_windows: what was
+    measured).  No GPU is needed to say so."""
+    from event_based_bos_amd import event_plan as EP
+
+    assert EP.hvp_float64_tiles() == [(16, 64), (32, 32), (64, 64)]
+    with pytest.raises(NotImplementedError, match=r"tile \[32, 64\].*float32.*\[16, 64\], \[32, 32\], \[64, 64\]"):
+        _solver(C.solver_config(method, tile=(32, 64)))
+    with pytest.raises(NotImplementedError, match=r"tile \[64, 64\], halo 32.*float32"):
+        _solver(C.solver_config(method, tile=(64, 64), halo=32))
+    with pytest.raises(NotImplementedError, match=r"no built halo of tile \(45, 80\)"):
+        _solver(C.solver_config(method, tile=(45, 80)))
+    for tile, halo in (((16, 64), "auto"), ((32, 32), 8), ((64, 64), 16), ((64, 64), 64)):    # (halo 64: two windows fall back to 16)
+        assert _solver(C.solver_config(method, tile=tile, halo=halo)).hessp
+    assert not _solver(C.solver_config("L-BFGS-B", tile=(32, 64))).hessp                      # the first-order methods take any tile
