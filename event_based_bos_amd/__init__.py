@@ -30,6 +30,8 @@ tub-rip/event_based_bos:
     multi-reference      one flow scored at 1 to 4 reference times from one plan: EventPlan.iwe_dense_multi / contrast_dense_multi
                          (fused="slab": the K-image slab pipeline), EventPlan.variance_multi_value_and_grad,
                          solver.multi_reference_loop.MultiReferencePatchLoop, solver block multi_reference (native: true)
+    evt3                 the camera's own EVT 3.0 .raw recordings: header, GPU decode of the word stream (events and trigger edges),
+                         host encoder; RawEventStore("cd_events.raw") goes through it
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -46,6 +48,6 @@ from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingE
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
 from .flow_voxel import flow_voxel_batch  # noqa: F401
 from .ops import time_bins, warp_voxel  # noqa: F401
-from . import costs, data_loader, evaluation, event_filters, event_voxel, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
+from . import costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

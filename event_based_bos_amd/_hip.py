@@ -325,6 +325,10 @@ SIGNATURES = {
     "ebos_iwe_voxel_multiref_owner_bwd_batch_f32": (_I, [_P] * 6 + [_I, _P] + [_I] * 7 + [C.POINTER(_F), _I, _P, _P, _I, _P, _P]),
     "ebos_cmax_voxel_multiref_solve_batch_f32": (_I, [_P, _I, _P]),
     "ebos_cmax_voxel_multiref_gradient_batch_f32": (_I, [_P, _P]),
+    "ebos_evt3_chunk_words": (_I, []),
+    "ebos_evt3_scratch_bytes": (_Z, [_L]),
+    "ebos_evt3_scan": (_I, [_P, _L, _P, _P, _P, _P, _Z, _P]),
+    "ebos_evt3_emit": (_I, [_P, _L, _P, _Z, _L, _L, _L, _L] + [_P] * 8),
 }
 
 
@@ -348,6 +352,11 @@ class EventSource(C.Structure):
     """``ebos_event_source`` of include/ebos_hip.h (same field order): the window an event filter reads."""
     _fields_ = [("kind", _I), ("layout", _I)] + [(k, _P) for k in ("events", "col", "row", "t", "pol")] + \
                [("ticks_per_second", _D), ("n", _L)]
+
+
+class Evt3State(C.Structure):
+    """``ebos_evt3_state`` of include/ebos_hip.h (same field order): the EVT 3.0 decoder's state between two words."""
+    _fields_ = [(k, C.c_int32) for k in ("has_th", "th", "tl", "y", "bx", "pol")] + [("loops", _L)]
 
 
 class VizField(C.Structure):

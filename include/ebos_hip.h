@@ -1982,6 +1982,46 @@ int ebos_plan_time_aware_raw_batch(const int16_t* col, const int16_t* row, const
                                    int32_t* key_offsets_stacked, int64_t key_stride, int32_t* counts, double* tminmax, void* scratch,
                                    size_t scratch_bytes, ebos_stream_t stream);
 
+/* ---- Prophesee EVT 3.0 recordings: the 16-bit word stream of a .raw file decoded on the device (csrc/evt3.hip) ----
+ * The reference's recordings are prophesee_0/cd_events.raw (src/data_loader/ccs.py:171); its own .raw path (:103-108, :299-317) is
+ * switched off in favour of a conversion to HDF5 (:19-20).  A word's type is its bits 15..12, v its bits 11..0:
+ *   0x8 TIME_HIGH    if the previous TIME_HIGH's value prev > v and prev - v >= 4085: loops += 1; then th = v, tl = 0
+ *   0x6 TIME_LOW     tl = v
+ *   0x0 ADDR_Y       y = v & 0x7FF
+ *   0x2 ADDR_X       one event: x = v & 0x7FF, p = v >> 11
+ *   0x3 VECT_BASE_X  bx = v & 0x7FF, pol = v >> 11
+ *   0x4 VECT_12      an event at x = bx + b, polarity pol, for every set bit b of v, ascending; then bx += 12
+ *   0x5 VECT_8       the same for bits 0..7; then bx += 8
+ *   0xA EXT_TRIGGER  one trigger record: value = v & 1, id = v >> 8
+ *   every other type is ignored
+ * An event or trigger carries the row y and the time t = (loops << 24) | (th << 12) | tl microseconds.  The state starts all zero,
+ * and every word before the first TIME_HIGH is ignored altogether: it emits nothing and sets nothing.  bx is kept modulo 2^16 (x is
+ * an int16 column, the bit pattern of bx + b).  All arithmetic is integer and there is no atomic in the data path: the output is in
+ * stream order and identical from run to run.
+ *
+ * A slab of n_words words is cut into chunks of ebos_evt3_chunk_words() words.  ebos_evt3_scan reduces every chunk to its state
+ * transformer (one workgroup per chunk) and combines them in order from *carry_in (one small launch): every chunk's incoming state
+ * and exclusive event / trigger offsets stay in `scratch`, totals[0 .. 1] = the slab's events and triggers, *carry_out = the state
+ * after the slab's last word -- all on the device; carry_in NULL = the start state, carry_out may be carry_in.  The caller reads
+ * `totals` back, allocates, and ebos_evt3_emit (one workgroup per chunk) decodes the SAME words again from that scratch into
+ *   x, y int16, t int64, p uint8 [event_capacity];  trig_t int64, trig_value, trig_id uint8 [trigger_capacity]
+ * and writes elements [0, n_events) and [0, n_triggers) only.  n_events / n_triggers are the totals as the caller read them; a
+ * capacity below them is refused (EBOS_ERR_INVALID_ARG) before anything is written, and no store ever lands at or beyond a capacity.
+ * NULL pointers (words may be NULL when n_words is 0; an output may be NULL when its capacity is 0), negative sizes, n_words beyond
+ * 2^30 and a short scratch (EBOS_ERR_SCRATCH) are refused before any HIP call.  ebos_evt3_scratch_bytes: 0 for a bad n_words. */
+typedef struct ebos_evt3_state {
+  int32_t has_th; /* a TIME_HIGH has been seen */
+  int32_t th, tl, y, bx, pol;
+  int64_t loops;
+} ebos_evt3_state;
+int ebos_evt3_chunk_words(void);
+size_t ebos_evt3_scratch_bytes(int64_t n_words);
+int ebos_evt3_scan(const uint16_t* words, int64_t n_words, const ebos_evt3_state* carry_in, ebos_evt3_state* carry_out,
+                   int64_t* totals, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_evt3_emit(const uint16_t* words, int64_t n_words, const void* scratch, size_t scratch_bytes, int64_t n_events,
+                   int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y, int64_t* t,
+                   uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

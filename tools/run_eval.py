@@ -60,9 +60,9 @@ def build_solver(ebos, cfg: dict):
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config_file")
-    ap.add_argument("--events", help=".npz of raw columns, or the reference's .hdf5 (needs h5py)")
+    ap.add_argument("--events", help=".npz of raw columns, the camera's EVT 3.0 .raw, or the reference's .hdf5 (needs h5py)")
     ap.add_argument("--frames", help="directory of image files, or a .npy / .npz stack")
-    ap.add_argument("--triggers", help="trigger_events.txt (default: next to --frames)")
+    ap.add_argument("--triggers", help="trigger_events.txt (default: next to --frames; the trigger words of a .raw --events where there is none)")
     ap.add_argument("--homography", help="homography.txt: camera -> event view")
     ap.add_argument("--height", type=int)
     ap.add_argument("--width", type=int)
@@ -93,6 +93,8 @@ def main(argv=None) -> int:
             cfg["data"]["width"] = args.width
         triggers = args.triggers or os.path.join(os.path.dirname(os.path.abspath(args.frames.rstrip("/"))), "trigger_events.txt")
         events = ebos.RawEventStore(args.events)
+        if not args.triggers and not os.path.exists(triggers) and events.triggers is not None:
+            triggers = events.triggers   # the EXT_TRIGGER words of the .raw recording itself
         frames = ebos.FrameStore(args.frames, triggers, args.homography,
                                  (cfg["data"]["height"], cfg["data"]["width"]) if args.homography else None)
     cfg = ebos.utils.propagate_config(cfg)
