@@ -30,6 +30,8 @@ tub-rip/event_based_bos:
     multi-reference      one flow scored at 1 to 4 reference times from one plan: EventPlan.iwe_dense_multi / contrast_dense_multi
                          (fused="slab": the K-image slab pipeline), EventPlan.variance_multi_value_and_grad,
                          solver.multi_reference_loop.MultiReferencePatchLoop, solver block multi_reference (native: true)
+    photometric          does a flow explain its two frames?  The reference's warp_image_forward / warp_image_torch and SSIM, and a
+                         fused per-item score (L1, RMSE, SSIM of the warped frame against the next, and of the un-warped baseline)
     evt3                 the camera's own EVT 3.0 .raw recordings: header, GPU decode of the word stream (events and trigger edges),
                          host encoder; RawEventStore("cd_events.raw") goes through it
 
@@ -48,6 +50,6 @@ from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingE
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
 from .flow_voxel import flow_voxel_batch  # noqa: F401
 from .ops import time_bins, warp_voxel  # noqa: F401
-from . import costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, poisson, solver, types, utils, visualizer  # noqa: F401
+from . import costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, photometric, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

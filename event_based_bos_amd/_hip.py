@@ -329,6 +329,14 @@ SIGNATURES = {
     "ebos_evt3_scratch_bytes": (_Z, [_L]),
     "ebos_evt3_scan": (_I, [_P, _L, _P, _P, _P, _P, _Z, _P]),
     "ebos_evt3_emit": (_I, [_P, _L, _P, _Z, _L, _L, _L, _L] + [_P] * 8),
+    "ebos_warp_image_forward_f32": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ebos_warp_image_forward_f64": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "ebos_ssim_map_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ebos_ssim_map_f64": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ebos_photometric_max_window": (_I, []),
+    "ebos_ssim_means_elems": (_Z, [_I, _I, _I, _I, _I]),
+    "ebos_photometric_scratch_bytes": (_Z, [_I, _I, _I, _I]),
+    "ebos_photometric_batch": (_I, [_I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _P, _Z, _P]),
 }
 
 
@@ -346,6 +354,7 @@ VIZ_GRAY_EVENT, VIZ_GRAY_IWE, VIZ_GRAY_CENTER = 0, 1, 2
 EVENT_VOLUME_OUT_OF_BOUNDS, EVENT_VOLUME_DEGENERATE_SPAN = 1, 2   # flags ebos_event_volume_* leaves in status[0]
 FLOW_UPWIND, FLOW_BURGERS, FLOW_SAME = 0, 1, 2
 FLOW_ROUTE_AUTO, FLOW_ROUTE_FUSED, FLOW_ROUTE_STEPS = 0, 1, 2
+IMAGE_U8, IMAGE_F32, IMAGE_F64 = 0, 1, 2   # element type codes of csrc/photometric.hip
 
 
 class EventSource(C.Structure):

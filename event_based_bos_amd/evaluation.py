@@ -19,6 +19,10 @@ a batch from the same columns (``TimeAwarePlanStack.from_raw``) and solves the b
 ``estimate`` on the windows' device events one after the other.  Any other registered solver is driven window by window through
 ``preprocess`` + ``estimate``.
 
+``run(photometric=True)`` also asks whether the flows explain the frames: per step the photometric score
+(``photometric.photometric_error_batch``) of the scaled estimate and of the frame-based flow on the two un-cropped frames, counted
+inside the ``common_params`` rectangle, into ``photometric_per_frame.txt`` and ``photometric_reference_per_frame.txt``.
+
 ``run(pictures=True)`` also draws the driver's ten pictures per step (bos_event.py:202-207) on the device, batched
 (``visualizer.render_step_batch``), and writes them under ``save_dir`` in the driver's order and under its file names.
 
@@ -34,7 +38,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _hip, event_filters, flow_error, frame_flow
+from . import _hip, event_filters, flow_error, frame_flow, photometric
 from ._hip import check, ptr, stream_ptr
 
 logger = logging.getLogger(__name__)
@@ -44,6 +48,8 @@ SUPPORTED_METHODS = ("opencv_flow", "opencv_flow_two_steps")
 TEXT_WITH_MASK = "flow_error_per_frame_with_mask.txt"
 TEXT_WITHOUT_MASK = "flow_error_per_frame_without_mask.txt"
 TEXT_TIMESTAMPS = "timestamps_per_frame.txt"
+TEXT_PHOTOMETRIC = "photometric_per_frame.txt"
+TEXT_PHOTOMETRIC_REFERENCE = "photometric_reference_per_frame.txt"
 
 
 # ------------------------------------------------------------------------------------------------ the plan (host)
@@ -290,6 +296,8 @@ class EvaluationResult(object):
     poisson: Optional[list] = None         # on request: per step (P of the scaled estimate, P of the reference flow) device tensors
     files: dict = field(default_factory=dict)
     pictures: Optional[list] = None        # with pictures=True: per step {name: uint8 numpy picture} as written
+    photometric: Optional[list] = None             # with photometric=True: per step the photometric score of the scaled estimate ...
+    photometric_reference: Optional[list] = None   # ... and of the frame-based flow ({column of photometric.COLUMNS: np.float64})
 
     @property
     def statistics(self) -> dict:
@@ -381,15 +389,22 @@ class RecordingEvaluator(object):
         return save_line(self.solver, i_frame, d, name, self.save_dir)
 
     # ------------------------------------------------------------------ run
-    def run(self, max_batch: int = 8, poisson: bool = False, keep_flows: bool = False, pictures: bool = False) -> EvaluationResult:
-        """``pictures``: also render the driver's ten pictures of every step (``visualizer.render_step_batch``: one more
+    def run(self, max_batch: int = 8, poisson: bool = False, keep_flows: bool = False, pictures: bool = False,
+            photometric: bool = False) -> EvaluationResult:
+        """``photometric``: also score, per step, the scaled estimate ``est * gt_time_scale / period`` (the scaling of the pictures)
+        and the frame-based flow against the two un-cropped frames with ``photometric.photometric_error_batch`` (two calls of two
+        launches per batch, ``roi`` = the ``common_params`` rectangle; the tables come back in the batch's one read-back) ->
+        ``result.photometric`` / ``result.photometric_reference`` and two more text files.  Off: nothing changes.
+
+        ``pictures``: also render the driver's ten pictures of every step (``visualizer.render_step_batch``: one more
         ``window_ingest_raw_batch`` call for the unfiltered events between the two frames, then a fixed number of launches per
         batch) and write them, ``pred_flow<i>.npy`` and ``color_wheel.png`` under ``save_dir`` (default: the solver's
         visualizer's directory, else the working directory) as the reference names them.  Needs PIL.  Off: nothing changes."""
         if int(max_batch) != max_batch or max_batch < 1:
             raise ValueError(f"max_batch {max_batch!r} < 1")
         plan = plan_evaluation(self.config, self.events, self.frames)
-        result = EvaluationResult(flows=[] if keep_flows else None, poisson=[] if poisson else None, pictures=[] if pictures else None)
+        result = EvaluationResult(flows=[] if keep_flows else None, poisson=[] if poisson else None, pictures=[] if pictures else None,
+                                  photometric=[] if photometric else None, photometric_reference=[] if photometric else None)
         self._picture_writer = None
         if pictures:
             from .visualizer import Visualizer
@@ -462,7 +477,10 @@ class RecordingEvaluator(object):
         roi = (slice(None), slice(None), slice(c["xmin"], c["xmax"]), slice(c["ymin"], c["ymax"]))
         plain, _ = flow_error.flow_error_batch(gt[roi], est[roi])
         masked, _ = flow_error.flow_error_batch(gt[roi], est[roi], event_mask=mask[roi[0], roi[2], roi[3]][:, None])
-        small = torch.cat([plain[:, :8], masked[:, :8], period.reshape(-1, 1).to(plain.device)], dim=1).cpu().numpy()   # the batch's one read-back
+        columns = [plain[:, :8], masked[:, :8], period.reshape(-1, 1).to(plain.device)]
+        if result.photometric is not None:
+            columns += self._photometric(steps, full, k1, k2, est, gt, period)
+        small = torch.cat(columns, dim=1).cpu().numpy()   # the batch's one read-back
         if poisson:
             from .poisson import poisson_reconstruct_batch
 
@@ -481,10 +499,31 @@ class RecordingEvaluator(object):
             result.errors_with_mask.append(e1)
             result.timestamps.append(ts)
             result.batch_time_scales.append(float(small[b, 16]))
+            if result.photometric is not None:
+                n = len(photometric.COLUMNS)
+                p0 = {k: np.float64(small[b, 17 + j]) for j, k in enumerate(photometric.COLUMNS)}
+                p1 = {k: np.float64(small[b, 17 + n + j]) for j, k in enumerate(photometric.COLUMNS)}
+                result.files[TEXT_PHOTOMETRIC] = self._write(s.i_frame, p0, TEXT_PHOTOMETRIC)
+                result.files[TEXT_PHOTOMETRIC_REFERENCE] = self._write(s.i_frame, p1, TEXT_PHOTOMETRIC_REFERENCE)
+                result.photometric.append(p0)
+                result.photometric_reference.append(p1)
             if result.flows is not None:
                 result.flows.append((est[b], gt[b]))
             if result.poisson is not None:
                 result.poisson.append((p_est[b], p_gt[b]))
+
+    def _photometric(self, steps, full, k1, k2, est, gt, period) -> List[torch.Tensor]:
+        """The photometric tables [B, 7] of the scaled estimate and of the frame-based flow on the un-cropped frames of the batch."""
+        c = self.common
+        roi = (c["xmin"], c["xmax"], c["ymin"], c["ymax"])
+        frame1, frame2 = full[k1], full[k2]
+        scale = torch.tensor([s.gt_time_scale for s in steps], dtype=torch.float64, device=est.device) / period.to(est.device)
+        pred = est.double() * scale[:, None, None, None]
+        tables = []
+        for flow in (pred, gt):
+            as_flow = (lambda f: f) if frame1.dtype == torch.uint8 else (lambda f: f.to(flow.dtype))
+            tables.append(photometric.photometric_error_batch(as_flow(frame1), as_flow(frame2), flow, roi=roi)[0].to(est.device))
+        return tables
 
     def _solve_sequential(self, steps, gt, full, k1, full0):
         """A solver without a prepared path: ``preprocess`` + ``estimate`` per window, as the driver calls them."""

@@ -9,7 +9,9 @@ its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does,
 ``standardize_image_center`` from ``poisson``, as src/utils/__init__.py:34,54 does, and ``bos_optical_flow`` and
 ``pad_to_same_resolution`` from ``frame_flow``, as src/utils/__init__.py:34-42 does, and the two time-resolved event representations,
 ``create_event_voxel`` and ``generate_discretized_event_volume``, from ``event_voxel``, as src/utils/__init__.py:4,7 does, and the
-time-aware flow (``construct_dense_flow_voxel_*`` and the functions around it) from ``flow_voxel``, as src/utils/__init__.py:19-33 does.
+time-aware flow (``construct_dense_flow_voxel_*`` and the functions around it) from ``flow_voxel``, as src/utils/__init__.py:19-33 does,
+and the frame warps ``warp_image_forward`` / ``warp_image_torch`` and ``SSIM`` / ``ssim`` from ``photometric``, as
+src/utils/__init__.py:40-41,54 does.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -76,3 +78,4 @@ from .flow_voxel import (construct_dense_flow_voxel_numpy, construct_dense_flow_
                          convert_flow_per_bin_to_flow_per_sec, flow_voxel_batch, inviscid_burger_flow_to_voxel_numpy,
                          inviscid_burger_flow_to_voxel_torch, propagate_flow_to_voxel_numpy, propagate_flow_to_voxel_torch,
                          truncate_voxel_flow_numpy, upwind_flow_to_voxel_numpy, upwind_flow_to_voxel_torch)
+from .photometric import SSIM, ssim, warp_image_forward, warp_image_torch  # noqa: E402,F401

@@ -2022,6 +2022,52 @@ int ebos_evt3_emit(const uint16_t* words, int64_t n_words, const void* scratch, 
                    int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y, int64_t* t,
                    uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream);
 
+/* ---- photometric check of a flow: frame warp, SSIM and the fused per-item score (csrc/photometric.hip) ----
+ * Element type codes of images, shifts and flows. */
+#define EBOS_IMAGE_U8 0
+#define EBOS_IMAGE_F32 1
+#define EBOS_IMAGE_F64 2
+/* The reference's warp_image_forward / warp_image_torch (src/utils/frame_utils.py:56-115) for B items: out[b] (H x W, the compute
+ * type) = images[b] sampled at x - flow, bilinear, zeros outside, through the reference's chain -- the float32 base grid
+ * i / ((size - 1) / 2) - 1, the displacement subtracted in its own type, grid_sample's align_corners=True un-normalisation, four
+ * taps.  images: contiguous H x W planes of image_dtype (EBOS_IMAGE_U8 or the compute type), item b at element offset
+ * b * image_sb (0: one image for all items).  Exactly one of flows ([B, 2, H, W], rows first, contiguous, the compute type) and
+ * shifts ([B, 2] of shift_dtype: EBOS_IMAGE_F32 or the compute type; shift / ((size - 1) / 2) is formed in the shift's type and
+ * subtracted from the grid in float32, as warp_image_torch's 0-dim shift is)
+ * is given.  Refused before any launch (EBOS_ERR_INVALID_ARG): B outside 1 .. 65535, H or W below 2, H W >= 2^31, a NULL buffer,
+ * a dtype code that is not built.  One launch. */
+int ebos_warp_image_forward_f32(const void* images, int image_dtype, int64_t image_sb, const float* flows, const void* shifts,
+                                int shift_dtype, int B, int H, int W, float* out, ebos_stream_t stream);
+int ebos_warp_image_forward_f64(const void* images, int image_dtype, int64_t image_sb, const double* flows, const void* shifts,
+                                int shift_dtype, int B, int H, int W, double* out, ebos_stream_t stream);
+/* The reference's SSIM map (src/utils/stat_utils.py:228-243) of the B C image pairs img1[n], img2[n] (contiguous [B, C, H, W]):
+ * the five moments E[x], E[y], E[x x], E[y y], E[x y] under taps (window_size x window_size of the compute type, made by the host
+ * as create_window makes them), zero padding of window_size / 2, C1 = 0.01^2, C2 = 0.03^2.  out: [B, C, H, W].  means: NULL, or
+ * ebos_ssim_means_elems(dtype, B, C, H, W) float64 (0: bad arguments): the mean of every map, of every item's C maps and of all maps --
+ * the first B C + B + 1 values; the rest is scratch -- each the exact float64 sum rounded once, then divided (the map kernel leaves a
+ * sum per tile; two more small launches).
+ * Refused before any launch: B C outside 1 .. 65535, H or W below 2, H W >= 2^31, an even or non-positive window_size, a NULL
+ * buffer (EBOS_ERR_INVALID_ARG); a window_size above ebos_photometric_max_window() (EBOS_ERR_UNSUPPORTED). */
+int ebos_ssim_map_f32(const float* img1, const float* img2, const float* taps, int window_size, int B, int C, int H, int W, float* out,
+                      double* means, ebos_stream_t stream);
+int ebos_ssim_map_f64(const double* img1, const double* img2, const double* taps, int window_size, int B, int C, int H, int W, double* out,
+                      double* means, ebos_stream_t stream);
+int ebos_photometric_max_window(void);
+size_t ebos_ssim_means_elems(int dtype, int B, int C, int H, int W);
+/* The fused score of B items.  w = warp_image_forward(frame1[b], flow[b]) over the whole image.  A pixel is COUNTED when it lies in
+ * rows [xmin, xmax) x columns [ymin, ymax) (has_roi), mask[b] is non-zero there (mask not NULL), both flow components are finite
+ * and all four bilinear taps lie inside the image.  out [B, 7] float64:
+ *   L1 = mean |w - frame2|, RMSE = sqrt(mean (w - frame2)^2), SSIM = mean of the SSIM map of (w, frame2)   over the counted pixels,
+ *   L1_0, RMSE_0, SSIM_0 = the same with w = frame1,  n_points = the count (0: the other six are NaN).
+ * dtype: the type of flow [B, 2, H, W] and taps, and the compute type (EBOS_IMAGE_F32 / _F64); frame_dtype: EBOS_IMAGE_U8 or dtype.
+ * frame1: item b at element offset b * frame1_sb (0: shared); frame2 [B, H, W]; mask uint8, item b at b * mask_sb.  Two launches,
+ * no atomics, no host synchronisation; the same bits on every run and wherever an item stands in the batch.  scratch:
+ * ebos_photometric_scratch_bytes(dtype, B, H, W) bytes (0: bad arguments; EBOS_ERR_SCRATCH when short).  Refusals as above. */
+size_t ebos_photometric_scratch_bytes(int dtype, int B, int H, int W);
+int ebos_photometric_batch(int dtype, int frame_dtype, int B, int H, int W, const void* frame1, int64_t frame1_sb, const void* frame2,
+                           const void* flow, const void* taps, int window_size, int has_roi, int xmin, int xmax, int ymin, int ymax,
+                           const uint8_t* mask, int64_t mask_sb, double* out, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 
     python tools/run_eval.py --config_file tests/golden/config_hot_plate1.json --events recording.npz --frames frames/ \
         --triggers trigger_events.txt [--homography homography.txt] [--max-batch 8] [--height H --width W] [--out out/]
-    python tools/run_eval.py --synthetic [--n-iter 60] [--pictures]
+    python tools/run_eval.py --synthetic [--n-iter 60] [--pictures] [--photometric]
     python tools/run_eval.py --synthetic --config_file configs/cmax_time_aware_eval.yaml [--n-iter 60]
 
 ``--config_file`` is a JSON (or, where PyYAML is installed, YAML) file with the reference's keys; a file with an "input" section
@@ -18,6 +18,8 @@ import json
 import os
 import sys
 import tempfile
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -70,6 +72,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default=None, help="directory of the three text files (default: a temporary directory)")
     ap.add_argument("--poisson", action="store_true")
     ap.add_argument("--pictures", action="store_true", help="also write the driver's ten pictures per step under --out (needs PIL)")
+    ap.add_argument("--photometric", action="store_true",
+                    help="also score the estimate and the frame-based flow against the frames (L1, RMSE, SSIM): two more text files")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n-iter", type=int, default=60, help="--synthetic: Adam iterations")
     args = ap.parse_args(argv)
@@ -100,10 +104,15 @@ def main(argv=None) -> int:
     cfg = ebos.utils.propagate_config(cfg)
     solv = build_solver(ebos, cfg)
     result = RecordingEvaluator(cfg, events, frames, solv, save_dir=out).run(max_batch=args.max_batch, poisson=args.poisson,
-                                                                              pictures=args.pictures)
+                                                                              pictures=args.pictures, photometric=args.photometric)
     print(f"{len(result.steps)} steps evaluated, {len(result.skipped)} skipped; text files in {out}")
     if args.pictures:
         print(f"  {sum(f.endswith('.png') for f in os.listdir(out))} pictures and {sum(f.endswith('.npy') for f in os.listdir(out))} flows written")
+    if args.photometric:
+        for name, dicts in (("estimate", result.photometric), ("frame-based", result.photometric_reference)):
+            for k in ("L1", "SSIM"):
+                v, v0 = np.array([d[k] for d in dicts]), np.array([d[k + "_0"] for d in dicts])
+                print(f"  photometric   {name:11s} {k:4s} mean {np.nanmean(v):.6g}  (un-warped {np.nanmean(v0):.6g})")
     for name, stats in result.statistics.items():
         for k, s in stats.items():
             print(f"  {name:13s} {k:5s} mean {s['mean']:.6g}  std {s['std']:.6g}  min {s['min']:.6g}  max {s['max']:.6g}  n {s['n_data']}")
