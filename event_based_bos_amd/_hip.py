@@ -23,6 +23,7 @@ PROFILE_SLAB_ACCUMULATE, PROFILE_TILED_BWD, PROFILE_SLAB_COMBINE, PROFILE_GRADMA
 ABI_VERSION = 2
 GML_NO_POLARITY, GML_EVENT_WEIGHTS = 1, 2   # flags of ebos_gml_objective_f64 / ebos_gml_solve_scale_f64
 GML_VELOCITY = 4                            # ebos_gml_dep_*: the direct-velocity model
+EKLT_ROUTE_AUTO, EKLT_ROUTE_PATCH, EKLT_ROUTE_ROI = 0, 1, 2   # ebos_eklt_sweep_batch_f64
 
 
 
@@ -246,6 +247,11 @@ SIGNATURES = {
     "ebos_gml_dep_select_batch": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _D, _P, _P, _P, _Z, _Z, _P]),
     "ebos_gml_dep_init_batch_f64": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "ebos_gml_dep_solve_batch_f64": (_I, [_I] * 11 + [_P, _P, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _D, _P, _L, _P, _P, _Z, _Z, _P]),
+    "ebos_eklt_sweep_fits": (_I, [_I, _I, _I]),
+    "ebos_eklt_sweep_halo": (_I, [_P, _I]),
+    "ebos_eklt_sweep_scratch_bytes": (_Z, [_I, _I, _I, _I]),
+    "ebos_eklt_sweep_batch_f64": (_I, [_I, _I, _I, _P, _P, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _D, _I, _P, _P, _P, _P, _Z, _P]),
+    "ebos_eklt_patch_flow_batch_f64": (_I, [_I] * 7 + [_P, _P, _I, _P, _P, _P]),
     "ebos_warp_perspective": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
     "ebos_window_ingest_scratch_bytes": (_Z, [_I] * 8),
     "ebos_window_ingest_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 12 + [_P] * 6 + [_Z, _P]),

@@ -5,6 +5,7 @@ from .contrast_maximization import (ContrastMaximization, ContrastMaximizationMi
                                     register_into)
 from .generative import GenerativePatchPyramid, make_generative_class, register_generative_into
 from .generative_dependent import GenerativePatchDependent, make_dependent_class, register_dependent_into
+from .eklt_sweep import GenerativeGlobal, GenerativePatchIndependent, register_eklt_into
 from .window_pipeline import WindowPipeline
 
 collections = {
@@ -12,4 +13,6 @@ collections = {
     "cmax": ContrastMaximization,
     "generative_patch_pyramid": GenerativePatchPyramid,
     "generative_patch_dependent": GenerativePatchDependent,
+    "generative_patch_independent": GenerativePatchIndependent,
+    "generative_global": GenerativeGlobal,
 }

@@ -1205,6 +1205,45 @@ int ebos_gml_dep_solve_batch_f64(int n_windows, int H, int W, int patch, int sli
                                  size_t scratch_stride, size_t scratch_bytes, ebos_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * The sampled EKLT solvers, patch_eklt and generative_max_likelihood (src/solver/patch_eklt.py:101-136,
+ * generative_max_likelihood.py:489-529), as a sweep in float64 (csrc/eklt_sweep.hip): every box is scored under every hypothesis
+ *   P0 = v_x T_p(gx) + v_y T_p(gy) on the box (|P0| with EBOS_GML_NO_POLARITY, * we[box] with EBOS_GML_EVENT_WEIGHTS),
+ *   P = P0 / (|P0|_F + 1e-4),  Q = q[box] / |q[box]|_F,  cost = w_diff_norm max_c sum_r |P - Q|,
+ * T_p = cv2.warpPerspective of the whole image by the translation (p_x rows, p_y columns), INTER_LINEAR, BORDER_CONSTANT 0, in the
+ * classic path: the source coordinate rounded to 1/32 pixel (half to even), the four float32 table weights, the sum in double.
+ * gx, gy, q, we: the planes of ebos_gml_prepare_batch_f64 ([B, H, W]; gx, gy with grad_stride 0 = one model image; q holds the
+ * event weights already, and any positive scale of it gives the same Q).
+ * boxes [P, 4] (device int32): rows [r0, r1), columns [c0, c1), each inside the image and at most ph x pw; sel [B, P] (device
+ * int32, NULL = all): 0 = do not evaluate.  A box that breaks these bounds, or whose |q[box]|_F is 0 or NaN, is not evaluated.
+ * hyp [K, 4] (HOST float64): v_x, v_y, p_x, p_y per hypothesis; the entry derives the integer shift and the table weights once per
+ * call.  cost [B, P, K] (NULL: not stored): written for every evaluated box, untouched elsewhere.  best_cost / best_index [B, P]:
+ * the row minimum, the lowest index on a tie; a NaN cost never wins; +inf / -1 where no hypothesis won or the box is not
+ * evaluated.  No atomics; a cost depends on its box and hypothesis alone, so results are bit-reproducible and do not depend on
+ * the window's place in a batch or on how a table is cut into calls.
+ * Routes: EBOS_EKLT_ROUTE_PATCH holds a box with a halo of ebos_eklt_sweep_halo(hyp, K) = max |integer shift| + 1 pixels in LDS --
+ * 8 B x (2 (ph + 2 halo)(pw + 2 halo) + 2 ph pw) <= 160 KiB - 4 KiB, which ebos_eklt_sweep_fits reports -- and evaluates one
+ * hypothesis per thread; EBOS_EKLT_ROUTE_ROI reads global memory with one workgroup per (hypothesis, box) (at most 65535 boxes),
+ * for boxes up to the full image; EBOS_EKLT_ROUTE_AUTO takes the patch route where it fits.  The two routes sum in different
+ * orders.  Scratch: ebos_eklt_sweep_scratch_bytes (route AUTO: enough for either).
+ * ebos_eklt_patch_flow_batch_f64: grid [B, 2, gh, gw] = the winner's (v_x, v_y) of hyp [K, 4] (DEVICE float64; 0 where best_index
+ * is -1), and flow [B, 2, H, W] = interpolate_dense_flow_from_patch_numpy of it (patch_eklt.py:138-171: edge pad
+ * int(patch / 2 // slide) + 1 cells, bilinear x slide with half-pixel centres, centre crop).
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_EKLT_ROUTE_AUTO 0
+#define EBOS_EKLT_ROUTE_PATCH 1
+#define EBOS_EKLT_ROUTE_ROI 2
+
+int ebos_eklt_sweep_fits(int ph, int pw, int halo);
+int ebos_eklt_sweep_halo(const double* hyp, int n_hyp);
+size_t ebos_eklt_sweep_scratch_bytes(int n_windows, int n_boxes, int n_hyp, int route);
+int ebos_eklt_sweep_batch_f64(int n_windows, int H, int W, const double* gx, const double* gy, int64_t grad_stride, const double* q,
+                              const double* we, const int* boxes, int n_boxes, int ph, int pw, const int* sel, const double* hyp,
+                              int n_hyp, int flags, double w_diff_norm, int route, double* cost, double* best_cost, int* best_index,
+                              void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_eklt_patch_flow_batch_f64(int n_windows, int H, int W, int patch, int slide, int gh, int gw, const int* best_index,
+                                   const double* hyp, int n_hyp, double* grid, double* flow, ebos_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Perspective warp of camera frames into the event view: cv2.warpPerspective(src, M, (W, H), flags, BORDER_CONSTANT, border_value)
  * as the reference's co-capture loader applies it to every frame (src/data_loader/ccs.py:373-396), for B frames in one launch,
  * with the driver's validate_image crop (bos_event.py:25-39) fused in.  The arithmetic is OpenCV's classic fixed-point path

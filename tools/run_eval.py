@@ -5,6 +5,7 @@
         --triggers trigger_events.txt [--homography homography.txt] [--max-batch 8] [--height H --width W] [--out out/]
     python tools/run_eval.py --synthetic [--n-iter 60] [--pictures] [--photometric]
     python tools/run_eval.py --synthetic --config_file configs/cmax_time_aware_eval.yaml [--n-iter 60]
+    python tools/run_eval.py --synthetic --config_file configs/eklt_patch_sweep.yaml --n-iter 64   # the sampled patch_eklt: 64 hypotheses
 
 ``--config_file`` is a JSON (or, where PyYAML is installed, YAML) file with the reference's keys; a file with an "input" section
 (tests/golden/config_hot_plate1.json) is read from there and propagated.  ``--synthetic`` builds a small recording in a temporary
@@ -23,7 +24,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SOLVERS = {"patch_eklt_pyramid2": "generative_patch_pyramid", "patch_eklt_dependent": "generative_patch_dependent"}
+SOLVERS = {"patch_eklt_pyramid2": "generative_patch_pyramid", "patch_eklt_dependent": "generative_patch_dependent",
+           "patch_eklt": "generative_patch_independent", "generative_max_likelihood": "generative_global"}
 
 
 def load_config(path: str) -> dict:

@@ -6,6 +6,8 @@ BOS scene with a known displacement field.
     python tools/run_gml.py --size 128 160 --n_iter 120 --json out.json
     python tools/run_gml.py --config_file tests/golden/config_hot_plate1.json # the REFERENCE's configs/hot_plate1.yaml, as it is
     python tools/run_gml.py --method patch_eklt_dependent                     # the single-scale solver, the YAML's patch_eklt block
+    python tools/run_gml.py --method patch_eklt --n_iter 800                  # the sampled solvers: n_iter hypotheses per patch
+    python tools/run_gml.py --method generative_max_likelihood --n_iter 800   #   ... or for the one ROI (solver/eklt_sweep.py)
     python tools/run_gml.py --batch 8                                         # 8 windows of the scene through estimate_batch
 
 The scene: a textured frame L, a potential phi (two Gaussian bumps) and its gradient d = grad phi as the displacement; events are
@@ -42,12 +44,20 @@ def scene(H, W, n_events, seed=0):
     return frame, ev, d
 
 
+SWEEPS = ("patch_eklt", "generative_max_likelihood")
+
+
 def default_config(H, W, n_iter, method="patch_eklt_pyramid2"):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from _gml_cases import YAML_COST, YAML_GML
     cfg = {"method": method, "filter": {"filters": [], "parameters": {"xmin": 0, "xmax": H, "ymin": 0, "ymax": W}},
            "cost_with_weight": dict(YAML_COST), "optimizer": {"method": "Adam", "n_iter": n_iter}, "generative_ml": dict(YAML_GML)}
-    if method == "patch_eklt_dependent":
+    if method in SWEEPS:   # the reference YAML's optuna block: the angle model, a translation within 0.4 px
+        cfg["cost_with_weight"] = {"diff_norm": 1.0}
+        cfg["optimizer"] = {"method": "optuna", "sampler": "random", "n_iter": n_iter,
+                            "parameters": {"angle": {"min": 0, "max": 6.2832}, "p_x": {"min": -0.4, "max": 0.4}, "p_y": {"min": -0.4, "max": 0.4}}}
+        cfg["generative_ml"].update({"angle_model": True, "poisson_model": False})
+    if method in ("patch_eklt_dependent", "patch_eklt"):
         cfg["patch_eklt"] = {"patch_size": 4, "sliding_window": 2, "do_event_thresholding": False, "event_thres": 8}
     return cfg
 
@@ -59,7 +69,7 @@ def main():
     ap.add_argument("--events", type=int, default=0, help="events in the window (default 2 per pixel)")
     ap.add_argument("--config_file", default=None, help="a reference config (JSON with a 'propagated' section, or a solver dict)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent"),
+    ap.add_argument("--method", default="patch_eklt_pyramid2", choices=("patch_eklt_pyramid2", "patch_eklt_dependent") + SWEEPS,
                     help="the solver when no --config_file is given")
     ap.add_argument("--batch", type=int, default=0, metavar="B",
                     help="also solve B windows of the scene (different event seeds and counts) with estimate_batch: per-window time "
@@ -85,6 +95,7 @@ def main():
     reg = types.SimpleNamespace(SolverBase=ebos.solver.SolverBase, collections={})
     ebos.solver.register_generative_into(reg)          # method patch_eklt_pyramid2, no override
     ebos.solver.register_dependent_into(reg)           # method patch_eklt_dependent
+    ebos.solver.register_eklt_into(reg)                # methods patch_eklt, generative_max_likelihood
     solv = reg.collections[method]((H, W), (H, W), {}, solver_cfg)
     np.random.seed(args.seed)
     solv.estimate(events, frame=frame, background=frame)   # warm-up (code objects, allocations)
@@ -103,7 +114,8 @@ def main():
     err = calculate_flow_error_numpy(d[None], flow[None], m[None, None].astype(np.float64))
     n_it = len(h["loss"])
     res = {"method": method, "size": [H, W], "roi": [xmin, xmax, ymin, ymax], "iterations": n_it, "events": int(len(events)),
-           "loss_first": float(h["loss"][0]), "loss_last": float(h["loss"][-1]), "window_ms": 1e3 * t_window,
+           "loss_first": float(h["loss"][0]) if n_it else None, "loss_last": float(h["loss"][-1]) if n_it else None,
+           "window_ms": 1e3 * t_window,
            "ms_per_iteration": 1e3 * t_window / max(n_it, 1), "cosine_roi": cos,
            "EPE": float(err["EPE"]), "AE": float(err["AE"])}
     if args.batch > 0:
@@ -120,6 +132,10 @@ def main():
                     "batch_ms_per_iteration": 1e3 * t_batch / args.batch / max(n_it, 1),
                     "batch_vs_sequential": t_window / (t_batch / args.batch),
                     "batch_window0_bit_identical": bool(np.array_equal(flows[0], flow))})
+    if method in SWEEPS:   # no iterations: hypotheses, and the winners' costs
+        sel = solv.estimate_indices
+        res.update({"hypotheses": int(solver_cfg["optimizer"]["n_iter"]), "boxes": int(solv.n_patch), "boxes_scored": int(len(sel)),
+                    "best_value_mean": float(np.mean(solv.best_values[sel])) if len(sel) else None})
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:
