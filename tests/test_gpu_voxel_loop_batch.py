@@ -22,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _voxel_loop_cases as C  # noqa: E402
 from _voxel_loop_cases import G, H, N, PATCH, R, T5, W, rel  # noqa: E402
+from _voxel_launch import P, S, ok, owner_batch, stack_of, tiled_batch  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -56,20 +57,6 @@ def lib(ebos):
     from event_based_bos_amd import _hip
 
     return _hip.require_gpu()
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
-
-
-def S():
-    from event_based_bos_amd._hip import stream_ptr
-
-    return stream_ptr()
-
-
-def ok(rc, lib):
-    assert rc == 0, lib.ebos_last_error()
 
 
 def guarded(shape, dtype=torch.float32, fill=float("nan"), guard=4096):
@@ -119,11 +106,6 @@ def stage_windows():
     return C.cached("batch_stage_windows", lambda: three_windows(stage_voxels(), seed=41))
 
 
-def stack_of(ebos, windows, T=T5):
-    plans = [C.plan_of(ebos, ev, T=T) for ev in windows]
-    return plans, ebos.EventPlan.stack_time_aware(plans)
-
-
 # ---------------------------------------------------------------------------------------------- 1. deterministic stages, bit for bit
 @pytest.mark.parametrize("shape", [(H, W), (H, 72)])            # scalar stores, and the 16-byte path (W % 4 == 0)
 def test_upsample_forward_batch_is_the_single_call(lib, shape):
@@ -163,12 +145,6 @@ def test_regularisers_batch_is_the_single_call(lib, shape):
         ok(lib.ebos_flow_regularisers_f32(P(flows[b]), h, w, 0.1, 0.2, P(d_one), P(p_one), None, 0, 0, None, None, S()), lib)
         assert torch.equal(outs[0][0][b], d_one) and torch.equal(outs[0][1][b], p_one), b
         assert float(p_one.sum()) > 0.0
-
-
-def owner_batch(lib, stack, voxels, g_images, affine, T, pad, g_lo, out):
-    ok(lib.ebos_iwe_voxel_owner_bwd_batch_f32(P(stack.x), P(stack.y), P(stack.dt), P(stack.bins), P(stack.key_offsets), stack.ns_array(),
-                                              len(stack), P(voxels), T, H, W, stack.tile[0], stack.tile[1], pad, pad, P(g_images), P(affine),
-                                              g_lo, P(out), S()), lib)
 
 
 def owner_inputs(T, pad, seed=7):
@@ -255,11 +231,6 @@ def iwe_refs(windows, voxels):
 
 def stage_iwe_refs():
     return C.cached("batch_stage_iwe", lambda: iwe_refs(stage_windows(), stage_voxels()))
-
-
-def tiled_batch(lib, stack, voxels, halo, out, pad=0, splits=1):
-    ok(lib.ebos_iwe_voxel_tiled_batch_f32(P(stack.x), P(stack.y), P(stack.dt), P(stack.bins), P(stack.key_offsets), stack.ns_array(), len(stack),
-                                          P(voxels), T5, H, W, stack.tile[0], stack.tile[1], halo, splits, pad, pad, P(out), S()), lib)
 
 
 @pytest.mark.parametrize("halo,splits", [(HALO, 1), (HALO, 3), (8, 1), (24, 1)])     # (32, 32, 24) is no built configuration: the fall-back

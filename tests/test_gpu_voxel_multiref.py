@@ -16,11 +16,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _voxel_multiref_cases as M  # noqa: E402
 from _voxel_multiref_cases import FML, FQML, G, H, N, R, T5, W, rel  # noqa: E402
+from _voxel_launch import GUARD, P, S, c_shifts, forward, guarded, guards_untouched, ok, owner_backward  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
 DIRECTIONS = {1: ("last",), 3: FML, 4: FQML}
-GUARD = 4096
 
 
 @pytest.fixture(scope="module")
@@ -37,67 +37,6 @@ def lib(ebos):
     from event_based_bos_amd import _hip
 
     return _hip.require_gpu()
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
-
-
-def S():
-    from event_based_bos_amd._hip import stream_ptr
-
-    return stream_ptr()
-
-
-def ok(rc, lib):
-    assert rc == 0, lib.ebos_last_error()
-
-
-def guarded(values=None, shape=None, fill=float("nan")):
-    """(whole buffer, the view in its middle): GUARD cells of ``fill`` in front and behind; the middle holds ``values`` (or ``fill``)."""
-    shape = tuple(values.shape) if values is not None else tuple(shape)
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), fill, dtype=torch.float32, device=M.dev())
-    view = buf[GUARD:GUARD + n].view(*shape)
-    if values is not None:
-        view.copy_(values)
-    return buf, view
-
-
-def guards_untouched(buf):
-    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
-
-
-def c_shifts(plan, directions):
-    from event_based_bos_amd.event_plan import multi_reference_shifts
-
-    sh = multi_reference_shifts(plan, directions)
-    return (ctypes.c_float * len(sh))(*sh), len(sh)
-
-
-def forward(lib, plan, voxel, directions, halo, pad, splits=1):
-    """The single-window C entry on a NaN-guarded voxel and a zero-filled output between NaN guard cells."""
-    T = voxel.shape[0]
-    sh, K = c_shifts(plan, directions)
-    vbuf, vox = guarded(values=voxel)
-    obuf, iwes = guarded(shape=(K, H + 2 * pad, W + 2 * pad))
-    iwes.zero_()                                                   # (the entry point accumulates: the caller zero-fills once)
-    ok(lib.ebos_iwe_voxel_multiref_tiled_f32(P(plan.x), P(plan.y), P(plan.dt), P(plan.bins), P(plan.key_offsets), plan.n, P(vox), T, H, W,
-                                             plan.tile[0], plan.tile[1], halo, splits, pad, pad, sh, K, P(iwes), S()), lib)
-    torch.cuda.synchronize()
-    assert guards_untouched(obuf) and guards_untouched(vbuf) and bool(torch.isfinite(iwes).all())
-    return iwes
-
-
-def owner_backward(lib, plan, voxel, directions, g_images, affine, g_lo, pad):
-    """The single-window C entry into a d_voxel whose every byte is 0xFF (every float a NaN: a cell that is not written shows)."""
-    T = voxel.shape[0]
-    sh, K = c_shifts(plan, directions)
-    out = torch.empty((T, 2, H, W), dtype=torch.float32, device=M.dev())
-    out.view(torch.uint8).fill_(0xFF)
-    ok(lib.ebos_iwe_voxel_multiref_owner_bwd_f32(P(plan.x), P(plan.y), P(plan.dt), P(plan.bins), P(plan.key_offsets), plan.n, P(voxel), T, H,
-                                                 W, plan.tile[0], plan.tile[1], pad, pad, sh, K, P(g_images), P(affine), g_lo, P(out), S()), lib)
-    return out
 
 
 def fixed_upstream(K, pad, seed=7):
