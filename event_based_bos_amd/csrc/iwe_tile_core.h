@@ -115,9 +115,105 @@ struct TileRange {
   int part;                  // which part of its tile this workgroup is (0 when tiles are not split)
   int32_t beg, end;          // FMT_XY: this workgroup's slice of the tile's events (plan order)
   int32_t g_first, g_last;   // groups of 4 this workgroup reads (g_first > g_last: nothing to do)
-  int32_t tile_groups;       // groups of the WHOLE tile (0: an empty tile -- the kernels' set-up has short cuts for it; set by tile_range only)
+  int32_t tile_groups;       // groups of the WHOLE tile (0: an empty tile -- the kernels' set-up has short cuts for it; set by tile_head / tile_range only)
+  int32_t tile;              // ty * tiles_x + tx (-1: an unused work item of an adaptive plan); set by tile_head only
+  int32_t g_tile;            // FMT_COMPACT: first group of the WHOLE tile; set by tile_head only
 };
 
+// A work item's range comes in three pieces, so that a kernel can order them around its first event loads:
+//   tile_head    which tile, part and slab, and the groups to read -- ALL the first event loads need.  Compact format: one dependent
+//                trip (the grp_off pair) behind the kernel arguments, and no division where the tiles are not split; adaptive plans
+//                read item_tile / item_part together, then part_off and grp_off together.
+//   tile_bounds  beg / end, the plan indices behind the groups (compact format: two more loads of key_offsets, which the lean loop
+//                wants at its checksum only: issued behind the event loads they share a trip with them instead of standing in front).
+//                The (x, y, dt) format's groups ARE plan indices: tile_head has set them.
+//   tile_coords  (ty, tx): a run-time division, wanted by the flow base and the slab's place in the image, not by the event loads.
+// The single-window accumulate pass (accumulate_tile) takes the pieces; tile_range, below, is the whole range at once for the
+// kernels whose set-up reads all of it up front or a window ahead (backward, batched persistent, resident).
+// under_loads: work that needs nothing of the range (the LDS clear), run once the head's last loads are ISSUED and before their
+// values are touched -- the loaded words pass through an opaque register behind it, so that the arithmetic on them, and with it the
+// wait for them, cannot be placed in front.  Not run for an unused work item.
+struct NothingUnder {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <int FMT, typename Under = NothingUnder>
+__device__ __forceinline__ TileRange tile_head(const int32_t* __restrict__ key_offsets, const EvPtrs& ev, int tile_px, int splits,
+                                               Under&& under_loads = Under{}) {
+  constexpr bool kUnder = !std::is_same<typename std::decay<Under>::type, NothingUnder>::value;
+  TileRange r;
+  r.ty = r.tx = -1;
+  r.beg = r.end = 0;
+  int tile, part = 0;
+  int32_t a, b;  // compact format: the tile's groups [a, b) from grp_off; (x, y, dt) format: its plan indices [a, b) from key_offsets
+  auto load_ab = [&]() {
+    a = FMT == FMT_COMPACT ? ev.grp_off[tile] : key_offsets[tile * tile_px];
+    b = FMT == FMT_COMPACT ? ev.grp_off[tile + 1] : key_offsets[(tile + 1) * tile_px];
+  };
+  auto hold = [](int32_t& v) {  // (a uniform word, whichever kind of load brought it, through an opaque scalar register)
+    v = __builtin_amdgcn_readfirstlane(v);
+    asm volatile("" : "+s"(v));
+  };
+  if (splits == 0) {  // adaptive: this workgroup is one work item of the plan's part table
+    tile = ev.item_tile[blockIdx.x];
+    part = ev.item_part[blockIdx.x];
+    if (tile < 0) {  // unused item
+      r.slab = r.part = r.g_first = r.tile_groups = r.g_tile = 0;
+      r.g_last = -1;
+      r.tile = -1;
+      return r;
+    }
+    int32_t s0 = ev.part_off[tile], s1 = ev.part_off[tile + 1];  // the tile's slabs [s0, s1): one trip for the four loads
+    load_ab();
+    under_loads();
+    if constexpr (kUnder) hold(a), hold(b), hold(s0), hold(s1);
+    splits = s1 - s0;
+    r.slab = s0 + part;
+  } else {
+    if (splits == 1) {  // (uniform) whole tiles: no division in front of the first loads
+      tile = blockIdx.x;
+    } else {
+      tile = blockIdx.x / splits;
+      part = blockIdx.x - tile * splits;
+    }
+    load_ab();
+    under_loads();
+    if constexpr (kUnder) hold(a), hold(b);
+    r.slab = blockIdx.x;
+  }
+  r.tile = tile;
+  r.part = part;
+  int32_t chunk = b - a;
+  if (splits != 1) chunk = (chunk + splits - 1) / splits;
+  if (FMT == FMT_COMPACT) {
+    const int32_t gb = min(b, a + part * chunk), ge = min(b, gb + chunk);
+    r.g_first = gb;
+    r.g_last = ge - 1;
+    r.tile_groups = b - a;
+    r.g_tile = a;
+  } else {
+    chunk = (chunk + kWave - 1) & ~(kWave - 1);
+    r.beg = min(b, a + part * chunk);
+    r.end = min(b, r.beg + chunk);
+    r.g_first = r.beg >> 2;
+    r.g_last = r.beg < r.end ? (r.end - 1) >> 2 : r.g_first - 1;
+    r.tile_groups = (b - a + 3) >> 2;
+    r.g_tile = 0;
+  }
+  return r;
+}
+template <int FMT>
+__device__ __forceinline__ void tile_bounds(TileRange& r, const int32_t* __restrict__ key_offsets, int tile_px) {
+  if (FMT == FMT_COMPACT && r.tile >= 0) {
+    r.beg = key_offsets[r.tile * tile_px] + 4 * (r.g_first - r.g_tile);  // plan index of the first slot
+    r.end = key_offsets[(r.tile + 1) * tile_px];
+  }
+}
+__device__ __forceinline__ void tile_coords(TileRange& r, int tiles_x) {
+  if (r.tile >= 0) {
+    r.ty = r.tile / tiles_x;
+    r.tx = r.tile - r.ty * tiles_x;
+  }
+}
 template <int FMT>
 __device__ __forceinline__ TileRange tile_range(const int32_t* __restrict__ key_offsets, const EvPtrs& ev, int tile_px,
                                                 int tiles_x, int splits) {
@@ -1325,20 +1421,31 @@ __device__ __forceinline__ void accumulate_tile(const EvPtrs& ev, const int32_t*
   __shared__ TileShared sh;
   EBOS_STAMP(0);
   static_assert(kCells % 2 == 0, "LDS image is cleared 16 bytes per lane");
-  // (dense field: the clear comes first -- it needs nothing, and the dependent loads of tile_range fly over it; run-time
-  // windows: the tile's flow values, which bound its displacements, are requested before the clear and awaited after it)
+  // (dense field: the clear needs nothing -- it runs under the last loads of the tile's head, which are issued in front of it and
+  // awaited behind it; run-time windows: the tile's flow values, which bound its displacements, are requested before the clear
+  // and awaited after it)
   constexpr bool kBoundFromFlow = DYN && !GRID && !UNIFORM;
-  if (!GRID && !kBoundFromFlow)
-    for (int i = threadIdx.x; i < kCells / 2; i += kBlock)  // all-zero bits = 0 in both modes
-      reinterpret_cast<double2*>(s_acc)[i] = make_double2(0.0, 0.0);
-  const TileRange tr = tile_range<FMT>(key_offsets, ev, TH * TW, tiles_x, splits);
-  if (tr.ty < 0) return;  // unused work item of an adaptive plan: its slab is never read
+  auto clear_under_head = [&]() {
+    if (!GRID && !kBoundFromFlow)
+      for (int i = threadIdx.x; i < kCells / 2; i += kBlock)  // all-zero bits = 0 in both modes
+        reinterpret_cast<double2*>(s_acc)[i] = make_double2(0.0, 0.0);
+  };
+  // The lean loop reads beg / end at its checksum only, and nothing in front of the first event loads needs (ty, tx): the head
+  // alone stands before those loads; the key_offsets pair is requested behind them (one trip for both) and the division follows.
+  // Every other loop reads beg / end in its set-up: the whole range at once, as tile_range gives it.
+  constexpr bool kLeanPre = FMT == FMT_COMPACT && !HAS_W && MODE == ACC_FX && !FRAC;
+  TileRange tr = tile_head<FMT>(key_offsets, ev, TH * TW, splits, clear_under_head);
+  if (tr.tile < 0) return;  // unused work item of an adaptive plan: its slab is never read (nor its LDS cleared)
+  if (!kLeanPre) {
+    tile_coords(tr, tiles_x);
+    tile_bounds<FMT>(tr, key_offsets, TH * TW);
+  }
   // An EMPTY tile (the static background of a schlieren recording: most tiles of a crowded window) owes the combine pass a slab of
   // zeros under the smallest window and nothing else: no LDS image, no tile flow (2.2 us), no event loop, no checksum -- 5 us of a
   // work item that a second round of work items (one workgroup per CU) used to pay in full.
   if (tr.tile_groups == 0 && !ZERO) {
     const Win<TH, TW, HALO, DYN> win{DYN ? halo_for(0.0f, 1, HALO) : HALO, DYN ? halo_for(0.0f, 4, HALO) : HALO};
-    if (DYN && halo_tab != nullptr && threadIdx.x == 0) halo_tab[tr.ty * tiles_x + tr.tx] = win_pack(win.hr, win.hc);
+    if (DYN && halo_tab != nullptr && threadIdx.x == 0) halo_tab[tr.tile] = win_pack(win.hr, win.hc);
     float4* out0 = reinterpret_cast<float4*>(slabs + (int64_t)tr.slab * ((TH + 2 * HALO) * kLWmax));
     const int n4 = win.LH() * win.LW() / 4;
 #ifndef EBOS_PLAIN_SLABS
@@ -1351,12 +1458,14 @@ __device__ __forceinline__ void accumulate_tile(const EvPtrs& ev, const int32_t*
   }
   // the lean loop's first two chunks per wave, requested here: they arrive under the rest of the set-up and its barrier instead of
   // a round trip after it (the persistent batched kernel requests them a whole window ahead)
-  constexpr bool kLeanPre = FMT == FMT_COMPACT && !HAS_W && MODE == ACC_FX && !FRAC;
   CRaw pre[2];
   if (kLeanPre) {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     pre[0] = load_craw(tr.g_first + wave * kWave + lane, tr, ev);
     pre[1] = load_craw(tr.g_first + (wave + kBlock / kWave) * kWave + lane, tr, ev);
+    __builtin_amdgcn_sched_barrier(0);  // (the four loads above are ISSUED before anything below is: neither moves across)
+    tile_bounds<FMT>(tr, key_offsets, TH * TW);
+    tile_coords(tr, tiles_x);
   }
   float mu = 0.0f, mv = 0.0f;
   if (kBoundFromFlow) {
@@ -1714,7 +1823,8 @@ iwe_slab_combine_kernel(const float* __restrict__ slabs, float* spill, int tiles
 // many moment partials at 1280x720.  Needs w, pad_w, HALO, TW multiples of 4 (the scalar kernel covers the rest).
 constexpr int kCombineRows = 4;
 
-template <int TH, int TW, int HALO, bool DYN>
+// WT: the IWE quads leave write-through (the single-window kernel); the batched form keeps plain stores
+template <int TH, int TW, int HALO, bool DYN, bool WT = false>
 __device__ __forceinline__ void combine4_block(const float* __restrict__ slabs, float* spill, int tiles_y, int tiles_x, int splits, int H,
                                                int W, int pad_h, int pad_w, float* __restrict__ iwe, int g_lo,
                                                double* __restrict__ partials, const int32_t* __restrict__ part_off,
@@ -1852,7 +1962,17 @@ __device__ __forceinline__ void combine4_block(const float* __restrict__ slabs, 
       if (exact) vd[0] += (double)s4.x, vd[1] += (double)s4.y, vd[2] += (double)s4.z, vd[3] += (double)s4.w;
       *reinterpret_cast<float4*>(spill + gi) = make_float4(0.f, 0.f, 0.f, 0.f);  // keep the spill image zero
     }
-    *reinterpret_cast<float4*>(iwe + gi) = v;
+#ifndef EBOS_PLAIN_SLABS
+    if constexpr (WT) {
+      // The IWE leaves write-through, like the slabs: 3.7 MB at 1280x720 do not sit dirty in the L2s until the end-of-kernel
+      // release writes them back in one burst in front of the next launch.  (Descriptor on this workgroup's first row -- uniform
+      // --, the quad's place in the workgroup's rows as the 32-bit offset: no image size can overflow it.)
+      const __amdgpu_buffer_rsrc_t iwe_rsrc =
+          slab_rsrc(iwe + (int64_t)blockIdx.y * kCombineRows * w, (unsigned)(kCombineRows * w) * (unsigned)sizeof(float));
+      slab_store4(iwe_rsrc, (unsigned)(ty_ * w + C) * 4u, v);
+    } else
+#endif
+      *reinterpret_cast<float4*>(iwe + gi) = v;
   }
   if (partials != nullptr) {
     double s = 0.0, ss = 0.0;
@@ -1878,8 +1998,8 @@ iwe_slab_combine4_kernel(const float* __restrict__ slabs, float* spill, int tile
                          int W, int pad_h, int pad_w, float* __restrict__ iwe, int g_lo, double* __restrict__ partials,
                          const int32_t* __restrict__ part_off, const unsigned* __restrict__ spill_epoch, unsigned epoch,
                          const unsigned* __restrict__ halo_tab, FinalizeIn fin) {
-  combine4_block<TH, TW, HALO, DYN>(slabs, spill, tiles_y, tiles_x, splits, H, W, pad_h, pad_w, iwe, g_lo, partials, part_off,
-                                    spill_epoch, epoch, halo_tab, fin);
+  combine4_block<TH, TW, HALO, DYN, true>(slabs, spill, tiles_y, tiles_x, splits, H, W, pad_h, pad_w, iwe, g_lo, partials, part_off,
+                                          spill_epoch, epoch, halo_tab, fin);
 }
 
 template <int TH, int TW, int HALO, bool DYN = false>
