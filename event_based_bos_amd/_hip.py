@@ -6,6 +6,7 @@ missing, every compute entry point raises ``HipUnavailableError`` -- loudly, at 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -583,26 +584,24 @@ def suffix(dtype: torch.dtype) -> str:
     raise TypeError(f"event_based_bos_amd kernels exist for float32 and float64 tensors, got {dtype}")
 
 
-def slab_configs():
-    lib = load_library()
-    n = lib.ebos_slab_config(None, 0)
+@functools.lru_cache(maxsize=None)
+def _configs(entry_name: str):
+    """The (tile_h, tile_w, halo) triples one ``ebos_*_config`` entry reports, in the library's order; read once per entry."""
+    entry = getattr(load_library(), entry_name)
+    n = entry(None, 0)
     buf = (C.c_int * (3 * n))()
-    lib.ebos_slab_config(buf, n)
-    return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
+    entry(buf, n)
+    return tuple((buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n))
+
+
+def slab_configs():
+    return list(_configs("ebos_slab_config"))
 
 
 def slab_multiref_configs():
     """The (tile_h, tile_w, halo) triples the multi-reference slab kernels are built for (``ebos_slab_multiref_config``)."""
-    lib = load_library()
-    n = lib.ebos_slab_multiref_config(None, 0)
-    buf = (C.c_int * (3 * n))()
-    lib.ebos_slab_multiref_config(buf, n)
-    return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
+    return list(_configs("ebos_slab_multiref_config"))
 
 
 def tiled_configs():
-    lib = load_library()
-    n = lib.ebos_tiled_config(None, 0)
-    buf = (C.c_int * (3 * n))()
-    lib.ebos_tiled_config(buf, n)
-    return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n)]
+    return list(_configs("ebos_tiled_config"))

@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "tile_configs.h"
 
 namespace ebos {
 namespace {
@@ -40,12 +41,7 @@ struct MultiRef {
 bool has_reg(const ebos_cmax_voxel_batch_problem* q) { return q->w_flow_norm != 0.0f || q->w_image_gradient != 0.0f; }
 
 bool tiled_forward(const ebos_cmax_voxel_batch_problem* q) {
-  if (q->halo <= 0) return false;
-  int cfg[3 * 64];
-  const int n = ebos_tiled_config(cfg, 64);
-  for (int i = 0; i < n && i < 64; ++i)
-    if (cfg[3 * i] == q->tile_h && cfg[3 * i + 1] == q->tile_w && cfg[3 * i + 2] == q->halo) return true;
-  return false;
+  return q->halo > 0 && config_ok(kTiledConfigs, q->tile_h, q->tile_w, q->halo);
 }
 
 // `who`: the entry point the caller used, in front of every refusal

@@ -15,6 +15,7 @@
 //                             atomic unit wants).  Taps beyond the halo go straight to global atomics,
 //                             so any flow magnitude stays correct.
 // All kernels evaluate the warp in source-pixel-relative coordinates (warped_taps of warp_footprint.h).
+#include "tile_configs.h"
 #include "warp_footprint.h"
 
 namespace ebos {
@@ -148,13 +149,6 @@ iwe_dense_tiled_kernel(const float* __restrict__ xs, const float* __restrict__ y
     if (R >= 0 && R < h && C >= 0 && C < w) atomic_add(&iwe[(int64_t)R * w + C], v);
   }
 }
-
-struct TiledConfig {
-  int th, tw, halo;
-};
-constexpr TiledConfig kTiledConfigs[] = {{64, 64, 32}, {32, 64, 32}, {32, 32, 32}, {64, 64, 16}, {32, 32, 16},
-                                         {32, 32, 8},  {64, 64, 64}, {32, 64, 48}, {16, 64, 32}};
-constexpr int kNumTiledConfigs = sizeof(kTiledConfigs) / sizeof(kTiledConfigs[0]);
 
 template <int TH, int TW, int HALO>
 int launch_tiled(const float* xs, const float* ys, const float* dts, const float* weight, const int32_t* key_offsets,
@@ -330,13 +324,7 @@ int ebos_iwe_dense_f32(const float* x, const float* y, const float* dt, const fl
 }
 
 int ebos_tiled_config(int* out, int cap) {
-  using namespace ebos;
-  for (int i = 0; i < kNumTiledConfigs && i < cap && out != nullptr; ++i) {
-    out[3 * i] = kTiledConfigs[i].th;
-    out[3 * i + 1] = kTiledConfigs[i].tw;
-    out[3 * i + 2] = kTiledConfigs[i].halo;
-  }
-  return kNumTiledConfigs;
+  return ebos::copy_configs(ebos::kTiledConfigs, out, cap);
 }
 
 int ebos_iwe_dense_tiled_f32(const float* xs, const float* ys, const float* dts, const float* weight,
@@ -350,20 +338,9 @@ int ebos_iwe_dense_tiled_f32(const float* xs, const float* ys, const float* dts,
                "ebos_iwe_dense_tiled: bad sizes (splits=%d)", splits);
   if (n == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_TILED_CASE(TH, TW, HL)                                                                             \
-  if (tile_h == TH && tile_w == TW && halo == HL)                                                              \
-    rc = launch_tiled<TH, TW, HL>(xs, ys, dts, weight, key_offsets, flow, H, W, splits, pad_h, pad_w, iwe, s);
-  EBOS_TILED_CASE(64, 64, 32)
-  EBOS_TILED_CASE(32, 64, 32)
-  EBOS_TILED_CASE(32, 32, 32)
-  EBOS_TILED_CASE(16, 64, 32)
-  EBOS_TILED_CASE(64, 64, 16)
-  EBOS_TILED_CASE(32, 32, 16)
-  EBOS_TILED_CASE(32, 32, 8)
-  EBOS_TILED_CASE(64, 64, 64)
-  EBOS_TILED_CASE(32, 64, 48)
-#undef EBOS_TILED_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return launch_tiled<t.th, t.tw, t.halo>(xs, ys, dts, weight, key_offsets, flow, H, W, splits, pad_h, pad_w, iwe, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     set_error("ebos_iwe_dense_tiled: no kernel built for tile %dx%d halo %d (see ebos_tiled_config)", tile_h, tile_w, halo);
     return rc;

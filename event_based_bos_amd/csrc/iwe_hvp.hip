@@ -22,6 +22,7 @@
 //            every call.
 #include <cmath>
 
+#include "tile_configs.h"
 #include "warp_footprint.h"
 
 namespace ebos {
@@ -259,23 +260,12 @@ int tangent_entry(const char* who, const float* xs, const float* ys, const float
   }
   if (n == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_TANGENT_CASE(TH, TW, HL)                                                                                                 \
-  if (tile_h == TH && tile_w == TW && halo == HL)                                                                                    \
-    rc = iwe ? launch_tangent<TH, TW, HL, true>(fits, xs, ys, dts, key_offsets, (int32_t)n, flow, v, H, W, splits, pad_h, pad_w, iwe, \
-                                                tangent, slab, s)                                                                    \
-             : launch_tangent<TH, TW, HL, false>(fits, xs, ys, dts, key_offsets, (int32_t)n, flow, v, H, W, splits, pad_h, pad_w,     \
-                                                 nullptr, tangent, slab, s);
-  EBOS_TANGENT_CASE(64, 64, 32)
-  EBOS_TANGENT_CASE(32, 64, 32)
-  EBOS_TANGENT_CASE(32, 32, 32)
-  EBOS_TANGENT_CASE(16, 64, 32)
-  EBOS_TANGENT_CASE(64, 64, 16)
-  EBOS_TANGENT_CASE(32, 32, 16)
-  EBOS_TANGENT_CASE(32, 32, 8)
-  EBOS_TANGENT_CASE(64, 64, 64)
-  EBOS_TANGENT_CASE(32, 64, 48)
-#undef EBOS_TANGENT_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return iwe ? launch_tangent<t.th, t.tw, t.halo, true>(fits, xs, ys, dts, key_offsets, (int32_t)n, flow, v, H, W, splits, pad_h, pad_w,
+                                                          iwe, tangent, slab, s)
+               : launch_tangent<t.th, t.tw, t.halo, false>(fits, xs, ys, dts, key_offsets, (int32_t)n, flow, v, H, W, splits, pad_h, pad_w,
+                                                           nullptr, tangent, slab, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     set_error("%s: no kernel built for tile %dx%d halo %d (see ebos_tiled_config)", who, tile_h, tile_w, halo);
     return rc;

@@ -13,6 +13,7 @@
 //            cell written, the same bits on every call
 #include <cmath>
 
+#include "tile_configs.h"
 #include "warp_footprint.h"
 
 namespace ebos {
@@ -135,14 +136,6 @@ int fits_cells(size_t cells, int K) {
   if (cells * K * sizeof(double) <= kLdsBytes) return 2;
   if (cells * K * sizeof(float) <= kLdsBytes) return 1;
   return 0;
-}
-
-bool is_tiled_config(int th, int tw, int halo) {
-  int cfg[3 * 32];
-  const int n = ebos_tiled_config(cfg, 32);
-  for (int i = 0; i < n && i < 32; ++i)
-    if (cfg[3 * i] == th && cfg[3 * i + 1] == tw && cfg[3 * i + 2] == halo) return true;
-  return false;
 }
 
 template <int TH, int TW, int HALO, typename ACC>
@@ -344,7 +337,7 @@ extern "C" {
 
 int ebos_iwe_multiref_fits(int tile_h, int tile_w, int halo, int K) {
   using namespace ebos;
-  if (tile_h <= 0 || tile_w <= 0 || halo < 0 || !is_tiled_config(tile_h, tile_w, halo)) return 0;
+  if (tile_h <= 0 || tile_w <= 0 || halo < 0 || !config_ok(kTiledConfigs, tile_h, tile_w, halo)) return 0;
   return fits_cells((size_t)(tile_h + 2 * halo) * (tile_w + 2 * halo), K);
 }
 
@@ -367,20 +360,9 @@ int ebos_iwe_dense_multiref_tiled_f32(const float* xs, const float* ys, const fl
   }
   if (n == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_MULTIREF_CASE(TH, TW, HL)                                                                                          \
-  if (tile_h == TH && tile_w == TW && halo == HL)                                                                              \
-    rc = launch_multiref<TH, TW, HL>(xs, ys, dts, key_offsets, (int32_t)n, flow, H, W, splits, pad_h, pad_w, sh, K, iwes, s);
-  EBOS_MULTIREF_CASE(64, 64, 32)
-  EBOS_MULTIREF_CASE(32, 64, 32)
-  EBOS_MULTIREF_CASE(32, 32, 32)
-  EBOS_MULTIREF_CASE(16, 64, 32)
-  EBOS_MULTIREF_CASE(64, 64, 16)
-  EBOS_MULTIREF_CASE(32, 32, 16)
-  EBOS_MULTIREF_CASE(32, 32, 8)
-  EBOS_MULTIREF_CASE(64, 64, 64)
-  EBOS_MULTIREF_CASE(32, 64, 48)
-#undef EBOS_MULTIREF_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return launch_multiref<t.th, t.tw, t.halo>(xs, ys, dts, key_offsets, (int32_t)n, flow, H, W, splits, pad_h, pad_w, sh, K, iwes, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     set_error("ebos_iwe_dense_multiref_tiled: no kernel built for tile %dx%d halo %d (see ebos_tiled_config)", tile_h, tile_w, halo);
     return rc;

@@ -33,16 +33,6 @@ struct RefScalars {  // one float per reference, by value in the kernel argument
   __device__ __forceinline__ float of(int k) const { return k == 0 ? at[0] : k == 1 ? at[1] : k == 2 ? at[2] : at[3]; }
 };
 
-// the built (tile, halo) triples
-constexpr SlabConfig kMultirefConfigs[] = {{32, 32, 8}, {32, 32, 32}, {64, 64, 16}, {64, 64, 32}};
-constexpr int kNumMultirefConfigs = sizeof(kMultirefConfigs) / sizeof(kMultirefConfigs[0]);
-
-bool multiref_config_ok(int th, int tw, int halo) {
-  for (int i = 0; i < kNumMultirefConfigs; ++i)
-    if (kMultirefConfigs[i].th == th && kMultirefConfigs[i].tw == tw && kMultirefConfigs[i].halo == halo) return true;
-  return false;
-}
-
 // ---- forward ------------------------------------------------------------------------------------
 // workspace k = the single form's workspace (slab_layout) at ws + k * ws_stride: slabs, spill image, partials, SpillEpoch word,
 // counters -- every section's contract is the single form's, per reference
@@ -389,7 +379,7 @@ int check_triple(const char* who, int tile_h, int tile_w, int halo, int splits) 
     set_error("%s: run-time halo windows (EBOS_HALO_AUTO) are not built for the multi-reference kernels: pass a built halo", who);
     return EBOS_ERR_UNSUPPORTED;
   }
-  if (!multiref_config_ok(tile_h, tile_w, halo)) {
+  if (!config_ok(kMultirefSlabConfigs, tile_h, tile_w, halo)) {
     set_error("%s: no kernel built for tile %dx%d halo %d (see ebos_slab_multiref_config)", who, tile_h, tile_w, halo);
     return EBOS_ERR_UNSUPPORTED;
   }
@@ -399,27 +389,13 @@ int check_triple(const char* who, int tile_h, int tile_w, int halo, int splits) 
 }  // namespace
 }  // namespace ebos
 
-#define EBOS_MULTIREF_SLAB_DISPATCH(CALL)                                   \
-  if (tile_h == 32 && tile_w == 32 && halo == 8) { rc = CALL(32, 32, 8); }  \
-  else if (tile_h == 32 && tile_w == 32 && halo == 32) { rc = CALL(32, 32, 32); } \
-  else if (tile_h == 64 && tile_w == 64 && halo == 16) { rc = CALL(64, 64, 16); } \
-  else if (tile_h == 64 && tile_w == 64 && halo == 32) { rc = CALL(64, 64, 32); }
-
 extern "C" {
 
-int ebos_slab_multiref_config(int* out, int cap) {
-  using namespace ebos;
-  for (int i = 0; i < kNumMultirefConfigs && i < cap && out != nullptr; ++i) {
-    out[3 * i] = kMultirefConfigs[i].th;
-    out[3 * i + 1] = kMultirefConfigs[i].tw;
-    out[3 * i + 2] = kMultirefConfigs[i].halo;
-  }
-  return kNumMultirefConfigs;
-}
+int ebos_slab_multiref_config(int* out, int cap) { return ebos::copy_configs(ebos::kMultirefSlabConfigs, out, cap); }
 
 size_t ebos_iwe_slab_multiref_workspace_bytes(int K, int H, int W, int tile_h, int tile_w, int halo, int splits, int pad_h, int pad_w) {
   using namespace ebos;
-  if (K < 1 || K > kMaxRef || H <= 0 || W <= 0 || splits < 1 || pad_h < 0 || pad_w < 0 || !multiref_config_ok(tile_h, tile_w, halo)) return 0;
+  if (K < 1 || K > kMaxRef || H <= 0 || W <= 0 || splits < 1 || pad_h < 0 || pad_w < 0 || !config_ok(kMultirefSlabConfigs, tile_h, tile_w, halo)) return 0;
   return (size_t)K * slab_layout(H, W, tile_h, tile_w, halo, splits, pad_h, pad_w).total;  // K workspaces of the single form, back to back
 }
 
@@ -444,16 +420,11 @@ int ebos_iwe_dense_slab_multiref_f32(const float* xs, const float* ys, const flo
     return EBOS_ERR_SCRATCH;
   }
   const EvPtrs evp{xs, ys, dts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  static const int acc_mode = [] {  // EBOS_SLAB_ACC=f64 forces the f64 accumulator, as in the single form
-    const char* e = getenv("EBOS_SLAB_ACC");
-    return (e && e[0] == 'f') ? (int)ACC_F64 : (int)ACC_FX;
-  }();
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_CALL(TH, TW, HL)                                                                                                        \
-  launch_multiref_slab_fwd<TH, TW, HL>(evp, key_offsets, flow, H, W, splits, pad_h, pad_w, sh, K, reinterpret_cast<char*>(workspace), \
-                                       iwes, want_variance, omit_boundary, variances, moments, acc_mode, as_stream(stream))
-  EBOS_MULTIREF_SLAB_DISPATCH(EBOS_CALL)
-#undef EBOS_CALL
+  const int rc = dispatch_multiref_slab(tile_h, tile_w, halo, [&](auto t) {
+    return launch_multiref_slab_fwd<t.th, t.tw, t.halo>(evp, key_offsets, flow, H, W, splits, pad_h, pad_w, sh, K,
+                                                        reinterpret_cast<char*>(workspace), iwes, want_variance, omit_boundary, variances,
+                                                        moments, slab_acc_mode(), as_stream(stream));  // (EBOS_SLAB_ACC, as in the single form)
+  });
   if (rc != EBOS_OK) return rc;
   EBOS_CHECK_LAUNCH("ebos_iwe_dense_slab_multiref");
   return EBOS_OK;
@@ -476,12 +447,10 @@ int ebos_iwe_dense_tiled_multiref_bwd_f32(const float* xs, const float* ys, cons
   if (int rc = check_triple(who, tile_h, tile_w, halo, 1)) return rc;
   const int64_t n_keys = (int64_t)((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w) * tile_h * tile_w;
   EBOS_REQUIRE(n_keys < INT32_MAX && (int64_t)H * W < INT32_MAX, "%s: a %dx%d image is more than a plan can hold", who, H, W);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_CALL(TH, TW, HL)                                                                                                      \
-  launch_multiref_tiled_bwd<TH, TW, HL>(xs, ys, dts, key_offsets, (int32_t)n, flow, H, W, pad_h, pad_w, sh, sc, K, g_images, affine, g_lo, \
-                                        var_moments, upstream, addend, d_flow, as_stream(stream))
-  EBOS_MULTIREF_SLAB_DISPATCH(EBOS_CALL)
-#undef EBOS_CALL
+  const int rc = dispatch_multiref_slab(tile_h, tile_w, halo, [&](auto t) {
+    return launch_multiref_tiled_bwd<t.th, t.tw, t.halo>(xs, ys, dts, key_offsets, (int32_t)n, flow, H, W, pad_h, pad_w, sh, sc, K, g_images,
+                                                         affine, g_lo, var_moments, upstream, addend, d_flow, as_stream(stream));
+  });
   if (rc != EBOS_OK) return rc;
   EBOS_CHECK_LAUNCH("ebos_iwe_dense_tiled_multiref_bwd");
   return EBOS_OK;

@@ -3230,17 +3230,6 @@ bwd_parts_combine_kernel(const float* __restrict__ parts, const int32_t* __restr
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-struct SlabConfig {
-  int th, tw, halo;
-};
-// f64 tile + halo must fit 160 KiB (forward); backward needs 16 TH TW + 4 LH LW bytes
-// {45, 80, 32} cuts 720 x 1280 into exactly 16 x 16 = 256 tiles: one workgroup per CU of an MI355X
-// smaller halos for windows whose displacements are small (BOS flows are typically a few pixels): slabs, LDS clear / decode and
-// the backward kernel's upstream tile all shrink with (TH + 2 halo)(TW + 2 halo); taps beyond the halo stay correct (spill)
-constexpr SlabConfig kSlabConfigs[] = {{64, 64, 32}, {45, 80, 32}, {32, 64, 32}, {32, 32, 32}, {64, 64, 16},
-                                       {45, 80, 16}, {32, 32, 16}, {32, 32, 8}};
-constexpr int kNumSlabConfigs = sizeof(kSlabConfigs) / sizeof(kSlabConfigs[0]);
-
 struct SlabLayout {
   int tiles_y, tiles_x, nblk, h, w, combine_blocks;
   size_t slab_cells;   // per workgroup

@@ -83,16 +83,23 @@ int order_after(hipStream_t later, hipStream_t earlier, const char* what) {
   return EBOS_OK;
 }
 
-const SlabOps* slab_ops_64x64x32();
-const SlabOps* slab_ops_45x80x32();
-const SlabOps* slab_ops_32x64x32();
-const SlabOps* slab_ops_32x32x32();
-const SlabOps* slab_ops_64x64x16();
-const SlabOps* slab_ops_45x80x16();
-const SlabOps* slab_ops_32x32x16();
-const SlabOps* slab_ops_32x32x8();
+// EBOS_SLAB_ACC=f64 forces the f64 accumulator (debug / A-B runs); read once per process
+int slab_acc_mode() {
+  static const int mode = [] {
+    const char* e = getenv("EBOS_SLAB_ACC");
+    return (e && e[0] == 'f') ? (int)ACC_F64 : (int)ACC_FX;
+  }();
+  return mode;
+}
+
+// the per-triple units' tables (EBOS_DEFINE_SLAB_OPS), named from the list of built triples
+#define EBOS_SLAB_OPS_DECLARE(TH, TW, HL) const SlabOps* slab_ops_##TH##x##TW##x##HL();
+EBOS_SLAB_CONFIGS(EBOS_SLAB_OPS_DECLARE)
+#undef EBOS_SLAB_OPS_DECLARE
 const SlabOps* slab_ops(int th, int tw, int halo) {
-  static const SlabOps* const all[] = {slab_ops_64x64x32(), slab_ops_45x80x32(), slab_ops_32x64x32(), slab_ops_32x32x32(), slab_ops_64x64x16(), slab_ops_45x80x16(), slab_ops_32x32x16(), slab_ops_32x32x8()};
+#define EBOS_SLAB_OPS_GET(TH, TW, HL) slab_ops_##TH##x##TW##x##HL(),
+  static const SlabOps* const all[] = {EBOS_SLAB_CONFIGS(EBOS_SLAB_OPS_GET)};
+#undef EBOS_SLAB_OPS_GET
   for (const SlabOps* o : all)
     if (o->th == th && o->tw == tw && o->halo == halo) return o;
   return nullptr;
@@ -100,36 +107,14 @@ const SlabOps* slab_ops(int th, int tw, int halo) {
 
 namespace {
 
-bool slab_config_ok(int th, int tw, int halo) {
-  for (int i = 0; i < kNumSlabConfigs; ++i)
-    if (kSlabConfigs[i].th == th && kSlabConfigs[i].tw == tw && kSlabConfigs[i].halo == halo) return true;
-  return false;
-}
+bool slab_config_ok(int th, int tw, int halo) { return config_ok(kSlabConfigs, th, tw, halo); }
 
 }  // namespace
 }  // namespace ebos
 
-#define EBOS_SLAB_DISPATCH(CALL)                                             \
-  if (tile_h == 64 && tile_w == 64 && halo == 32) { rc = CALL(64, 64, 32); } \
-  else if (tile_h == 45 && tile_w == 80 && halo == 32) { rc = CALL(45, 80, 32); } \
-  else if (tile_h == 32 && tile_w == 64 && halo == 32) { rc = CALL(32, 64, 32); } \
-  else if (tile_h == 32 && tile_w == 32 && halo == 32) { rc = CALL(32, 32, 32); } \
-  else if (tile_h == 64 && tile_w == 64 && halo == 16) { rc = CALL(64, 64, 16); } \
-  else if (tile_h == 45 && tile_w == 80 && halo == 16) { rc = CALL(45, 80, 16); } \
-  else if (tile_h == 32 && tile_w == 32 && halo == 16) { rc = CALL(32, 32, 16); } \
-  else if (tile_h == 32 && tile_w == 32 && halo == 8) { rc = CALL(32, 32, 8); }
-
 extern "C" {
 
-int ebos_slab_config(int* out, int cap) {
-  using namespace ebos;
-  for (int i = 0; i < kNumSlabConfigs && i < cap && out != nullptr; ++i) {
-    out[3 * i] = kSlabConfigs[i].th;
-    out[3 * i + 1] = kSlabConfigs[i].tw;
-    out[3 * i + 2] = kSlabConfigs[i].halo;
-  }
-  return kNumSlabConfigs;
-}
+int ebos_slab_config(int* out, int cap) { return ebos::copy_configs(ebos::kSlabConfigs, out, cap); }
 
 int ebos_halo_auto(int max_halo, double dt_bound) {
   if (max_halo <= 0 || max_halo > 255 || !(dt_bound >= 0.0) || dt_bound > 4096.0) return max_halo;  // (no auto: the built halo itself)
@@ -194,13 +179,9 @@ static int iwe_slab_entry(const ebos::GridSrc* grid_src, const float* xs, const 
   const int n_tiles_ = ((H + tile_h - 1) / tile_h) * ((W + tile_w - 1) / tile_w);
   const EvPtrs evp{xs, ys, dts, weight, grp_offsets, cpix, cdt, part_table, part_table ? part_table + n_tiles_ + 1 : nullptr,
                    part_table ? part_table + n_tiles_ + 1 + kAdaptiveItemsPerTile * n_tiles_ : nullptr, cfx, cfy};
-  static const int acc_mode = [] {  // EBOS_SLAB_ACC=f64 forces the f64 accumulator (debug / A-B runs)
-    const char* e = getenv("EBOS_SLAB_ACC");
-    return (e && e[0] == 'f') ? (int)ACC_F64 : (int)ACC_FX;
-  }();
   int rc = EBOS_ERR_UNSUPPORTED;
   rc = slab_ops(tile_h, tile_w, halo)->fwd(evp, key_offsets, flow, false, H, W, splits, pad_h, pad_w, ws, iwe, want_variance, omit_boundary,
-                                           out_variance, moments, acc_mode, s, grid_src, ha);
+                                           out_variance, moments, slab_acc_mode(), s, grid_src, ha);
   if (rc != EBOS_OK) return rc;
   EBOS_CHECK_LAUNCH("ebos_iwe_dense_slab");
   return EBOS_OK;
@@ -220,16 +201,12 @@ int ebos_iwe_dense_slab_f32(const float* xs, const float* ys, const float* dts, 
 int ebos_patch_fused_supported(int tile_h, int tile_w, int halo_arg, int slide_h, int slide_w) {
   using namespace ebos;
   const int halo = decode_halo(halo_arg).halo;
-  int rc = 0;
-#define EBOS_CALL(TH, TW, HL) \
-  ((grid_fwd_fits<TH, TW, HL>() && grid_bwd_fits<TH, TW, HL>() && (TH + 2 * kBwdApron) / slide_h + 3 <= kGridCells && \
-    (TW + 2 * kBwdApron) / slide_w + 3 <= kGridCells)                                                                   \
-       ? 1                                                                                                              \
-       : 0)
   if (slide_h <= 0 || slide_w <= 0) return 0;
-  EBOS_SLAB_DISPATCH(EBOS_CALL)
-#undef EBOS_CALL
-  return rc;
+  const int rc = dispatch_slab(tile_h, tile_w, halo, [&](auto t) {
+    constexpr bool fits = grid_fwd_fits<t.th, t.tw, t.halo>() && grid_bwd_fits<t.th, t.tw, t.halo>();
+    return (fits && (t.th + 2 * kBwdApron) / slide_h + 3 <= kGridCells && (t.tw + 2 * kBwdApron) / slide_w + 3 <= kGridCells) ? 1 : 0;
+  });
+  return rc == 1 ? 1 : 0;  // (no built triple: 0)
 }
 
 int ebos_iwe_patch_slab_f32(const int32_t* grp_offsets, const uint16_t* cpix, const float* cdt, const int32_t* key_offsets,

@@ -4,12 +4,14 @@
 // to compile, the long pole of the build.
 #pragma once
 #include "iwe_tile_core.h"
+#include "tile_configs.h"
 
 namespace ebos {
 
 // (shared host state: defined once, in iwe_tiled.hip)
 unsigned next_spill_epoch();                                                   // a number of its own for every forward call (never 0)
 int order_after(hipStream_t later, hipStream_t earlier, const char* what);    // `later` waits for everything enqueued on `earlier`
+int slab_acc_mode();                                                           // ACC_FX, or ACC_F64 where EBOS_SLAB_ACC=f64 is set
 
 struct SlabOps {  // the launchers of one built configuration
   int th, tw, halo;
@@ -24,7 +26,7 @@ struct SlabOps {  // the launchers of one built configuration
              const GridSrc* grid_src, int adaptive, float s_norm, float s_tv, double* reg_partials, MomentsIn mj, const HaloArg& ha,
              bool finalize_uniform);
 };
-// the built configurations' tables (kSlabConfigs, iwe_tile_core.h); nullptr: not built
+// the built configurations' tables (EBOS_SLAB_CONFIGS, tile_configs.h); nullptr: not built
 const SlabOps* slab_ops(int th, int tw, int halo);
 
 #ifdef EBOS_SLAB_OPS_UNIT  // a configuration's translation unit: the templates and EBOS_DEFINE_SLAB_OPS

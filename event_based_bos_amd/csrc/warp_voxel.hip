@@ -14,6 +14,7 @@
 //
 // Every kernel reads a bin as min(bins[i], T - 1): a bins array that was made for another T cannot index outside the voxel.
 // Dead and padding slots never gather.
+#include "tile_configs.h"
 #include "warp_voxel_core.h"
 
 namespace ebos {
@@ -555,20 +556,9 @@ int ebos_iwe_voxel_tiled_f32(const float* xs, const float* ys, const float* dts,
                "ebos_iwe_voxel_tiled: bad sizes (splits=%d)", splits);
   if (n == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_VOXEL_TILED_CASE(TH, TW, HL)                                                                            \
-  if (tile_h == TH && tile_w == TW && halo == HL)                                                                    \
-    rc = launch_voxel_tiled<TH, TW, HL>(xs, ys, dts, weight, bins, key_offsets, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
-  EBOS_VOXEL_TILED_CASE(64, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 32, 32)
-  EBOS_VOXEL_TILED_CASE(16, 64, 32)
-  EBOS_VOXEL_TILED_CASE(64, 64, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 8)
-  EBOS_VOXEL_TILED_CASE(64, 64, 64)
-  EBOS_VOXEL_TILED_CASE(32, 64, 48)
-#undef EBOS_VOXEL_TILED_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return launch_voxel_tiled<t.th, t.tw, t.halo>(xs, ys, dts, weight, bins, key_offsets, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     set_error("ebos_iwe_voxel_tiled: no kernel built for tile %dx%d halo %d (see ebos_tiled_config)", tile_h, tile_w, halo);
     return rc;
@@ -597,20 +587,9 @@ int ebos_iwe_voxel_tiled_batch_f32(const float* xs, const float* ys, const float
   EBOS_REQUIRE((xs && ys && dts && bins) || total == 0, "ebos_iwe_voxel_tiled_batch: NULL event buffer");
   if (total == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_VOXEL_TILED_CASE(TH, TW, HL)                         \
-  if (tile_h == TH && tile_w == TW && halo == HL)                 \
-    rc = launch_voxel_tiled_batch<TH, TW, HL>(xs, ys, dts, bins, key_offsets, B, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
-  EBOS_VOXEL_TILED_CASE(64, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 32, 32)
-  EBOS_VOXEL_TILED_CASE(16, 64, 32)
-  EBOS_VOXEL_TILED_CASE(64, 64, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 8)
-  EBOS_VOXEL_TILED_CASE(64, 64, 64)
-  EBOS_VOXEL_TILED_CASE(32, 64, 48)
-#undef EBOS_VOXEL_TILED_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return launch_voxel_tiled_batch<t.th, t.tw, t.halo>(xs, ys, dts, bins, key_offsets, B, voxel, T, H, W, splits, pad_h, pad_w, iwe, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     // (tile, halo) is no built configuration: the general kernel, window by window (any event order, global float atomics)
     const int64_t cells = (int64_t)T * 2 * H * W, img = (int64_t)(H + 2 * pad_h) * (W + 2 * pad_w);

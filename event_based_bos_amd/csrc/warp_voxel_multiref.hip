@@ -13,6 +13,7 @@
 // The bin of an event does not depend on the reference; bins are read as min(bins[i], T - 1).
 #include <cmath>
 
+#include "tile_configs.h"
 #include "warp_voxel_core.h"
 
 namespace ebos {
@@ -256,20 +257,9 @@ int multiref_tiled_batch(const char* who, const float* xs, const float* ys, cons
   EBOS_REQUIRE((xs && ys && dts && bins) || total == 0, "%s: NULL event buffer", who);
   if (total == 0) return EBOS_OK;
   hipStream_t s = as_stream(stream);
-  int rc = EBOS_ERR_UNSUPPORTED;
-#define EBOS_VOXEL_TILED_CASE(TH, TW, HL)         \
-  if (tile_h == TH && tile_w == TW && halo == HL) \
-    rc = launch_multiref_tiled_batch<TH, TW, HL>(xs, ys, dts, bins, key_offsets, B, voxel, T, H, W, splits, pad_h, pad_w, sh, K, iwes, s);
-  EBOS_VOXEL_TILED_CASE(64, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 64, 32)
-  EBOS_VOXEL_TILED_CASE(32, 32, 32)
-  EBOS_VOXEL_TILED_CASE(16, 64, 32)
-  EBOS_VOXEL_TILED_CASE(64, 64, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 16)
-  EBOS_VOXEL_TILED_CASE(32, 32, 8)
-  EBOS_VOXEL_TILED_CASE(64, 64, 64)
-  EBOS_VOXEL_TILED_CASE(32, 64, 48)
-#undef EBOS_VOXEL_TILED_CASE
+  const int rc = dispatch_tiled(tile_h, tile_w, halo, [&](auto t) {
+    return launch_multiref_tiled_batch<t.th, t.tw, t.halo>(xs, ys, dts, bins, key_offsets, B, voxel, T, H, W, splits, pad_h, pad_w, sh, K, iwes, s);
+  });
   if (rc == EBOS_ERR_UNSUPPORTED) {
     // (tile, halo) is no built configuration: the general kernel, window by window and reference by reference
     const int64_t cells = (int64_t)T * 2 * H * W, img = (int64_t)(H + 2 * pad_h) * (W + 2 * pad_w);

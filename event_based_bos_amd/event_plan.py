@@ -1307,18 +1307,13 @@ def _check_out(out: Optional[torch.Tensor], shape, device: torch.device) -> None
         raise ValueError(f"out must be a contiguous float32 tensor of shape {tuple(shape)} on {device}")
 
 
-_SLAB_CONFIGS = None
-
-
 def _slab_ok(plan: EventPlan, halo) -> bool:
-    global _SLAB_CONFIGS
     if not plan.binned or halo is None:
         return False
-    if _SLAB_CONFIGS is None:
-        _SLAB_CONFIGS = set(_hip.slab_configs())
+    built = _hip.slab_configs()
     if halo == "auto":
-        return any((th, tw) == tuple(plan.tile) for th, tw, _ in _SLAB_CONFIGS)
-    return (plan.tile[0], plan.tile[1], _max_halo(int(halo))) in _SLAB_CONFIGS
+        return any((th, tw) == tuple(plan.tile) for th, tw, _ in built)
+    return (plan.tile[0], plan.tile[1], _max_halo(int(halo))) in built
 
 
 def _refuse_deferred(plan: EventPlan, what: str) -> None:
@@ -2042,18 +2037,12 @@ def _hvp_upstreams(state: dict, u: torch.Tensor, costs: dict, omit: bool, blur_s
 # ----------------------------------------------------------------------------------------------
 # time-aware warp on a plan: the flow of an event's own time bin
 # ----------------------------------------------------------------------------------------------
-_TILED_CONFIGS = None
-
-
 def _voxel_halo(plan: EventPlan, halo) -> Optional[int]:
     """The built halo the tiled voxel kernel runs with, or None for the general kernel: ``"auto"`` is the default built halo."""
-    global _TILED_CONFIGS
     if halo is None or not plan.binned:
         return None
     halo = DEFAULT_HALO if halo == "auto" else _max_halo(int(halo))
-    if _TILED_CONFIGS is None:
-        _TILED_CONFIGS = set(_hip.tiled_configs())
-    return halo if (plan.tile[0], plan.tile[1], halo) in _TILED_CONFIGS else None
+    return halo if (plan.tile[0], plan.tile[1], halo) in _hip.tiled_configs() else None
 
 
 def _check_voxel(plan: EventPlan, voxel: torch.Tensor) -> torch.Tensor:

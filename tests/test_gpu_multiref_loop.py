@@ -68,8 +68,19 @@ def test_forward_has_the_bits_of_the_single_form(ebos, directions, halo, plan_di
     assert torch.equal(got, iwes)
 
 
+# every triple of the multi-reference slab family (ebos_slab_multiref_config), with the splits the test runs it at
+VECTOR_COMBINE_CASES = {"tile32-halo8": ((32, 32), 8, 2), "tile64-halo16": ((64, 64), 16, 1), "tile32-halo32": ((32, 32), 32, 2),
+                        "tile64-halo32": ((64, 64), 32, 1)}
+
+
+def test_the_vector_combine_sweep_is_the_built_set(ebos):
+    from event_based_bos_amd import _hip
+
+    assert sorted(t + (hl,) for t, hl, _ in VECTOR_COMBINE_CASES.values()) == sorted(_hip.slab_multiref_configs())
+
+
 @pytest.mark.parametrize("pad", [0, 4])
-@pytest.mark.parametrize("tile,halo,splits", [((32, 32), 8, 2), ((64, 64), 16, 1)], ids=["tile32-halo8", "tile64-halo16"])
+@pytest.mark.parametrize("tile,halo,splits", list(VECTOR_COMBINE_CASES.values()), ids=list(VECTOR_COMBINE_CASES))
 def test_forward_vector_combine_has_the_bits_of_the_single_form(ebos, tile, halo, splits, pad):
     """Image and padding widths that are multiples of 4 take the combine pass that handles four pixels per thread (37 x 70 never
     does): a 37 x 72 window of its own, 8 000 events, |flow| <= 6 px and references inside the window, so nothing leaves halo 8."""
