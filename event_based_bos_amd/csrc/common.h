@@ -169,6 +169,21 @@ __device__ __forceinline__ void block_sum2(T& a, T& b, T* red) {
   b = rb;
 }
 
+// Block-level odd-even merge-split of `len` elements that one workgroup sorts at most 2 * chunk of at a time: chunks c and c + 1 are
+// sorted together (the smaller half back to c), pairs of alternating parity, as many phases as there are chunks -- which leaves the
+// whole sorted, in place, without scratch (the last chunk may be short: it stands for one padded with +inf).  sort_span(first
+// element, count <= 2 * chunk, halves_sorted) sorts that span ascending; block-uniform arguments.  The first phase also sorts a last
+// chunk that has no partner, so from the second phase on both chunks of a span stand sorted (halves_sorted: the first `chunk`
+// elements and the rest -- a merge is enough; a sorter may ignore it).  (event_plan.hip: hot runs of the full build; plan_lean.hip: a
+// run beyond the bin sort's staging area.)
+template <typename SortSpan>
+__device__ __forceinline__ void odd_even_merge_split(int len, int chunk, SortSpan&& sort_span) {
+  const int m = (len + chunk - 1) / chunk;
+  for (int c = 0; c < m; c += 2) sort_span(c * chunk, min(2 * chunk, len - c * chunk), false);
+  for (int phase = 1; phase < m; ++phase)
+    for (int c = phase & 1; c + 1 < m; c += 2) sort_span(c * chunk, min(2 * chunk, len - c * chunk), true);
+}
+
 // hardware float atomics (no CAS loop): global_atomic_add_f32 / _f64, ds_add_f32 / _f64
 __device__ __forceinline__ void atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }
 __device__ __forceinline__ void atomic_add(double* p, double v) { unsafeAtomicAdd(p, v); }

@@ -442,10 +442,7 @@ compact_canon_hot_kernel(const int32_t* __restrict__ key_offsets, int tile_px, c
     if (len <= kCanonHot) {
       sort_span(o0, len);
     } else {
-      constexpr int kChunk = kCanonHot / 2;
-      const int m = (len + kChunk - 1) / kChunk;
-      for (int phase = 0; phase < m; ++phase)
-        for (int c = phase & 1; c + 1 < m; c += 2) sort_span(o0 + (int64_t)c * kChunk, min(2 * kChunk, len - c * kChunk));
+      odd_even_merge_split(len, kCanonHot / 2, [&](int first, int count, bool) { sort_span(o0 + first, count); });
     }
   }
 }

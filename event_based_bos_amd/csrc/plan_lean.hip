@@ -642,6 +642,54 @@ __device__ __forceinline__ void lean_gather(const LeanScratch& sc, const LeanGeo
   }
 }
 
+// (uniform) v[0, L) in LDS, ascending by sort_key, by the whole workgroup of kSortBlock threads: a bitonic network with every
+// comparator ascending -- the first stage of a merge pairs i with its mirror image in the block, the others i with i + stride --, so
+// the virtual +inf beyond the run's end never moves: any length, in place.  Behind a barrier; ends with one.  halves_sorted: the
+// first n2 / 2 elements (n2: the power of two that holds L) and the rest stand sorted already -- the last merge is the whole sort.
+__device__ __forceinline__ void lds_sort_ascending(float* v, int L, bool halves_sorted = false) {
+  int n2 = 1;
+  while (n2 < L) n2 <<= 1;
+  for (int size = halves_sorted ? max(n2, 2) : 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < n2 / 2; t += kSortBlock) {
+        const int blk = t / stride, off = t - blk * stride, lo = blk * 2 * stride + off;
+        const int hi = stride == (size >> 1) ? blk * 2 * stride + (2 * stride - 1 - off) : lo + stride;
+        if (hi < L) {
+          const float x = v[lo], y = v[hi];
+          if (sort_key(x) > sort_key(y)) v[lo] = y, v[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// (uniform) run[0, m) in MEMORY, ascending by sort_key, by the whole workgroup through `lds` (lds_floats of it, free): one load, sort
+// and store when the run fits, odd-even merge-split when it does not -- over chunks of the largest power of two of which the LDS
+// holds a pair: a span of two sorted chunks is then the two halves of the network's last merge, one stage of ~15 steps instead of the
+// ~120 of a sort.  The workgroup reads what other waves of it stored -- the caller's stores to the run included --: a
+// workgroup-scope fence and a barrier between the stores and the loads.  Out of line: a stuck pixel's route, kept off the registers
+// of the kernel around it.
+__device__ __noinline__ void sort_run_through_lds(float* run, int m, float* lds, int lds_floats) {
+  auto sort_span = [&](int first, int count, bool halves_sorted) {
+    for (int i = threadIdx.x; i < count; i += kSortBlock) lds[i] = run[first + i];
+    __syncthreads();
+    lds_sort_ascending(lds, count, halves_sorted);
+    for (int i = threadIdx.x; i < count; i += kSortBlock) run[first + i] = lds[i];
+    __threadfence_block();
+    __syncthreads();
+  };
+  __threadfence_block();
+  __syncthreads();
+  if (m <= lds_floats) {
+    sort_span(0, m, false);
+  } else {
+    int chunk = 1;
+    while (4 * chunk <= lds_floats) chunk <<= 1;   // (2 x chunk <= lds_floats < 4 x chunk)
+    odd_even_merge_split(m, chunk, sort_span);
+  }
+}
+
 // one workgroup per bin: counting sort of the bin's segment by pixel -> key_offsets of the band, cpix / cdt at their final slots
 // (a workgroup of ONE window's grid: blockIdx.x in lean_bin_sort_kernel and in lean_bin_sort_batch_kernel, whose blockIdx.y is the
 // window -- the placement below is the same in both)
@@ -753,7 +801,10 @@ __device__ __forceinline__ void lean_bin_sort_body(const LeanGeom& g, const Lean
   // run leaves in ascending dt (equal dt: equal slots whatever their order): an event takes the slot of its RANK in its run, counted
   // over the run in LDS (O(run) reads per event); a hot pixel (a run beyond kLeanCanon) is first sorted in place by the whole
   // workgroup, a bitonic network.  A staged bin is ranked where it stands; an overfull one is gathered again in chunks of whole
-  // pixels (a run that does not fit the staging area on its own keeps its order of arrival).
+  // pixels.  A run that does not fit the staging area on its own (a stuck pixel: tens of thousands of events) goes to its slots of
+  // the segment first and is sorted THERE by the same network, through the staging area: in one load when its dt alone fit, by
+  // odd-even merge-split over pairs of half-sized chunks (as compact_canon_hot_kernel, event_plan.hip) when they do not -- runs of
+  // any length leave in the canonical order.
   if (!staged) {   // an overfull bin re-stages chunks of whole pixels in the WHOLE staging area (both buffers: 2 x sort_cap events)
     s_dt = a_dt;
     s_px = a_px;
@@ -776,7 +827,7 @@ __device__ __forceinline__ void lean_bin_sort_body(const LeanGeom& g, const Lean
       }
       p_hi = lo;
     }
-    // (one run larger than the staging area on its own: straight to its slots of the segment, in the order it arrives)
+    // (one run larger than the staging area on its own: straight to its slots of the segment, and sorted there)
     const bool direct = p_hi == p_lo;
     if (direct) p_hi = p_lo + 1;
     const int c1 = p_hi < n_pix ? s_cnt[p_hi] : len, m = c1 - c0;
@@ -799,6 +850,10 @@ __device__ __forceinline__ void lean_bin_sort_body(const LeanGeom& g, const Lean
       if (wide) for_each_staged(std::false_type{}, load8, keep);
       else for_each_staged(std::false_type{}, load4, keep);
       if (direct) {
+        // The run stands in its slots in the order the cursor's atomics arrived; every slot carries the same pixel, so only its dt
+        // move: through the staging area (free here: 3 floats per event of one staging buffer; sort_cap counts both, 2 x an even
+        // number), sorted, stored again
+        sort_run_through_lds(cdt + out0 + c0, m, s_dt, sort_cap / 2 * 3);
         p_lo = p_hi;
         continue;
       }
@@ -815,25 +870,10 @@ __device__ __forceinline__ void lean_bin_sort_body(const LeanGeom& g, const Lean
     // sorts they were 5 us of a workgroup's 30: a store's way to memory, waited for with nothing else to do)
     for (int i = threadIdx.x; i < m; i += kSortBlock) cpix[out0 + c0 + i] = s_px[i];
     const int n_hot = min(s_nhot, kHotList);
-    for (int h = 0; h < n_hot; ++h) {   // (uniform) a hot pixel: bitonic network with every comparator ascending -- the first stage of
-      const int pi = s_hot[h];          // a merge pairs i with its mirror image in the block, the others i with i + stride --, so the
-      const int rb = s_cnt[pi] - c0, L = run_end(pi) - c0 - rb;   // virtual +inf beyond the run's end never moves: any length, in place
-      float* v = s_dt + rb;
-      int n2 = 1;
-      while (n2 < L) n2 <<= 1;
-      for (int size = 2; size <= n2; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-          for (int t = threadIdx.x; t < n2 / 2; t += kSortBlock) {
-            const int blk = t / stride, off = t - blk * stride, lo = blk * 2 * stride + off;
-            const int hi = stride == (size >> 1) ? blk * 2 * stride + (2 * stride - 1 - off) : lo + stride;
-            if (hi < L) {
-              const float x = v[lo], y = v[hi];
-              if (sort_key(x) > sort_key(y)) v[lo] = y, v[hi] = x;
-            }
-          }
-          __syncthreads();
-        }
-      }
+    for (int h = 0; h < n_hot; ++h) {   // (uniform) a hot pixel: sorted where it stands
+      const int pi = s_hot[h];
+      const int rb = s_cnt[pi] - c0, L = run_end(pi) - c0 - rb;
+      lds_sort_ascending(s_dt + rb, L);
     }
     EBOS_LSTAMP(1, 6);
     // Runs of up to 16 events -- nearly every pixel of a window that is not clustered -- are SORTED by sixteen lanes each, a bitonic

@@ -254,7 +254,7 @@ int ebos_plan_facts(const int32_t* key_offsets, int H, int W, int tile_h, int ti
  * the SoA arrays and the permutation that only per-event weights and fractional source coordinates need.  The window is read
  * ONCE: every chunk of it is counting-sorted by (tile, row band) inside LDS and staged as a coalesced stream, one workgroup per
  * band then gathers its runs, sorts them by source pixel in LDS and puts every pixel's events in ascending dt (two builds of one
- * window hold identical arrays); no global atomics per event, no scattered writes.  Outputs exactly what ebos_bin_events_f32 +
+ * window hold identical arrays, whatever the length of a pixel's run); no global atomics per event, no scattered writes.  Outputs exactly what ebos_bin_events_f32 +
  * ebos_plan_compact_f32 produce:
  *     key_offsets [n_keys + 1], grp_offsets [tiles + 1], cpix / cdt [capacity_slots >= n + 3 tiles + 4]
  * (the order of the events inside one source pixel is unspecified in both), plus

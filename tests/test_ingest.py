@@ -406,8 +406,8 @@ def test_plan_facts_read_back(emit):
 def test_lean_build_of_dense_windows_gathers_overfull_bins_in_chunks(case):
     """Windows beyond ~10 k events per tile leave the bins LARGER than the bin sort's LDS staging on purpose (fewer, longer (chunk, bin)
     runs: the stage kernel's table and the gather were what the build cost): an overfull bin is gathered once for its histogram and once
-    per chunk of whole pixels.  Same arrays from two builds, every run in ascending dt, the events of the full build; a single run larger
-    than the whole staging area (a pixel firing 30 000 times) is written in the order it arrives -- same events, order unspecified."""
+    per chunk of whole pixels.  Same arrays from two builds, every run in ascending dt, the events of the full build -- also for a single run larger
+    than the whole staging area (a pixel firing 30 000 times), which is written to its slots and sorted there."""
     import event_based_bos_amd as ebos
 
     H, W, tile = 128, 128, (64, 64)
@@ -433,15 +433,8 @@ def test_lean_build_of_dense_windows_gathers_overfull_bins_in_chunks(case):
         want = fdt[a:b][np.lexsort((fdt[a:b], runs))]
         np.testing.assert_array_equal(cpx[a:b], fpx[a:b])
         np.testing.assert_array_equal(cpx2[a:b], fpx[a:b])
-        if case == "one_run_beyond_the_staging_area":
-            giant = np.diff(offs) >= 30_000
-            keep = ~giant[runs]
-            np.testing.assert_array_equal(cdt[a:b][keep], want[keep])
-            np.testing.assert_array_equal(cdt2[a:b][keep], want[keep])
-            np.testing.assert_array_equal(cdt[a:b][np.lexsort((cdt[a:b], runs))], want)
-        else:
-            np.testing.assert_array_equal(cdt[a:b], want)
-            np.testing.assert_array_equal(cdt2[a:b], want)
+        np.testing.assert_array_equal(cdt[a:b], want)
+        np.testing.assert_array_equal(cdt2[a:b], want)
 
 
 @pytest.mark.gpu
