@@ -79,7 +79,9 @@ variance_finalize_kernel(const double* __restrict__ partials, int nparts, int64_
   ss = block_sum(ss, red);
   if (threadIdx.x == 0) {
     const double mean = m > 0 ? s / (double)m : 0.0;
-    const double var = (ss - s * mean) / (double)(m - 1);  // unbiased (torch.var default); m <= 1 -> nan/inf like torch
+    // unbiased (torch.var default).  m <= 1 -> nan like torch, said outright: the formula gives -0 for an empty region (0 / -1),
+    // and 0 / 0 for one pixel only if ss - s * mean is not contracted into an fma (the residual of the rounded square: +-inf)
+    const double var = m > 1 ? (ss - s * mean) / (double)(m - 1) : __builtin_nan("");
     out[k] = (T)var;
     if (moments) {
       moments[2 * k] = mean;
@@ -170,7 +172,8 @@ gradmag_grad_kernel(const T* __restrict__ images, int h, int w, Region rg, const
   const int64_t hw = (int64_t)h * w;
   const T* img = images + k * hw;
   T* d = d_images + k * hw;
-  const double scale = 2.0 * (double)upstream[k] / (double)rg.count() * 0.125;
+  // (an empty region: the mean is nan and no pixel takes part in it -- a zero gradient like torch's, not inf * 0)
+  const double scale = rg.count() > 0 ? 2.0 * (double)upstream[k] / (double)rg.count() * 0.125 : 0.0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) {
     const int pr = (int)(i / w), pc = (int)(i % w);
     double acc = 0.0;
