@@ -34,6 +34,8 @@ tub-rip/event_based_bos:
                          fused per-item score (L1, RMSE, SSIM of the warped frame against the next, and of the un-warped baseline)
     evt3                 the camera's own EVT 3.0 .raw recordings: header, GPU decode of the word stream (events and trigger edges),
                          host encoder; RawEventStore("cd_events.raw") goes through it
+    calibration          lens calibration: CameraCalibration (K, D), its rectification map, rectified sub-pixel events from raw
+                         columns, the reference's undistort_events; frame_warp.undistort_image rectifies (and warps) frames in one resample
 
 All arithmetic of the path runs in hand-written HIP kernels reached through the C ABI of
 libebos_hip.so (include/ebos_hip.h).  There is no CPU fallback: without the library or a GPU the
@@ -44,12 +46,13 @@ from .warp import MotionModelKeyError, Warp  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
 from .event_plan import EventPlan, SlabBatch, TimeAwarePlanStack  # noqa: F401
 from .data_loader import FrameStore, RawEventStore  # noqa: F401
-from .frame_warp import validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
+from .frame_warp import undistort_image, undistort_image_batch, validate_image, warp_perspective, warp_perspective_batch  # noqa: F401
+from .calibration import CameraCalibration, rectify_events_raw, undistort_events  # noqa: F401
 from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingEvaluator, plan_evaluation,  # noqa: F401
                          window_ingest_raw_batch)
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
 from .flow_voxel import flow_voxel_batch  # noqa: F401
 from .ops import time_bins, warp_voxel  # noqa: F401
-from . import costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, photometric, poisson, solver, types, utils, visualizer  # noqa: F401
+from . import calibration, costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, photometric, poisson, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

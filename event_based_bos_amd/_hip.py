@@ -254,6 +254,13 @@ SIGNATURES = {
     "ebos_eklt_sweep_batch_f64": (_I, [_I, _I, _I, _P, _P, _L, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _D, _I, _P, _P, _P, _P, _Z, _P]),
     "ebos_eklt_patch_flow_batch_f64": (_I, [_I] * 7 + [_P, _P, _I, _P, _P, _P]),
     "ebos_warp_perspective": (_I, [_I, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
+    "ebos_rectify_map_f64": (_I, [_P, _I, _I, _I, _P, _P]),
+    "ebos_rectify_scratch_bytes": (_Z, [_L]),
+    "ebos_rectify_events_raw": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ebos_undistort_events_f32": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ebos_undistort_events_f64": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ebos_undistort_image_u8": (_I, [_I, _I, _I, _P, _L, _L, _P, _P, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
+    "ebos_undistort_image_f32": (_I, [_I, _I, _I, _P, _L, _L, _P, _P, _I, _I, _D, _I, _I, _I, _I, _P, _L, _L, _P]),
     "ebos_window_ingest_scratch_bytes": (_Z, [_I] * 8),
     "ebos_window_ingest_raw_batch": (_I, [_P, _P, _P, _I, _P, _L, _D, _P, _I, _L] + [_I] * 12 + [_P] * 6 + [_Z, _P]),
     "ebos_viz_reduce_f64": (_I, [_I, _I, _I, _P, _I, _D, _P, _P]),

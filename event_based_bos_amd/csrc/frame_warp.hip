@@ -16,6 +16,8 @@
 
 #pragma clang fp contract(off)
 
+#include "remap_sample.h"
+
 namespace ebos {
 namespace {
 
@@ -23,8 +25,6 @@ constexpr int kPix = 4;          // adjacent output pixels per lane
 constexpr int kBlockX = 64;      // lanes along a row: one wave covers 256 adjacent pixels
 constexpr int kBlockY = 4;
 constexpr int kMaxMats = 32;     // per-frame matrices travel as kernel arguments: frames per launch when they differ
-constexpr int kInterBits = 5;
-constexpr int kInterTab = 1 << kInterBits;
 
 template <int N>
 struct WarpMats {
@@ -43,46 +43,6 @@ struct WarpArgs {
 };
 
 template <typename T>
-struct Px;
-template <>
-struct Px<uint8_t> {
-  using vec = uint32_t;
-  static __device__ __forceinline__ uint8_t border(double v) {
-    const double r = rint(v);
-    return (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-  }
-  static __device__ __forceinline__ uint8_t blend(uint8_t s00, uint8_t s01, uint8_t s10, uint8_t s11, int fx, int fy) {
-    // the 32 x 32 table of the restatement in closed form: 32768 (1 - fy / 32)(1 - fx / 32) = 32 (32 - fy)(32 - fx), ...
-    const int ax = kInterTab - fx, ay = kInterTab - fy;
-    const int acc = (int)s00 * (32 * ay * ax) + (int)s01 * (32 * ay * fx) + (int)s10 * (32 * fy * ax) + (int)s11 * (32 * fy * fx);
-    return (uint8_t)((acc + (1 << 14)) >> 15);
-  }
-  static __device__ __forceinline__ vec pack(const uint8_t* v) {
-    return (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-  }
-};
-template <>
-struct Px<float> {
-  using vec = float4;
-  static __device__ __forceinline__ float border(double v) { return (float)v; }
-  static __device__ __forceinline__ float blend(float s00, float s01, float s10, float s11, int fx, int fy) {
-    const float step = 1.0f / kInterTab;
-    const float bx = (float)fx * step, by = (float)fy * step;
-    const float ax = 1.0f - bx, ay = 1.0f - by;
-    return ((s00 * (ay * ax) + s01 * (ay * bx)) + s10 * (by * ax)) + s11 * (by * bx);
-  }
-  static __device__ __forceinline__ vec pack(const float* v) { return make_float4(v[0], v[1], v[2], v[3]); }
-};
-
-// (fmin / fmax return the other operand for a NaN, as numpy's fmin / fmax do in the restatement: a NaN coordinate -- inf * 0 where
-// 32 / W overflows -- becomes INT_MAX in both, which is outside every source)
-__device__ __forceinline__ int round_clamped(double v) {
-  v = fmax(-2147483648.0, fmin(2147483647.0, v));
-  return (int)rint(v);
-}
-__device__ __forceinline__ int sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
-
-template <typename T>
 __device__ __forceinline__ T warp_pixel(const T* __restrict__ src, int64_t sr, int Hs, int Ws, const double* m, int bw, int x, double m1y,
                                         double m4y, double m7y, bool nearest, T cval) {
   const int xb = (x / bw) * bw;
@@ -94,21 +54,7 @@ __device__ __forceinline__ T warp_pixel(const T* __restrict__ src, int64_t sr, i
   const double s = Wd != 0.0 ? (nearest ? 1.0 : (double)kInterTab) / Wd : 0.0;
   const int X = round_clamped((X0 + m[0] * x1) * s);
   const int Y = round_clamped((Y0 + m[3] * x1) * s);
-  if (nearest) {
-    const int sx = sat16(X), sy = sat16(Y);
-    return ((unsigned)sx < (unsigned)Ws && (unsigned)sy < (unsigned)Hs) ? src[(int64_t)sy * sr + sx] : cval;
-  }
-  const int sx = sat16(X >> kInterBits), sy = sat16(Y >> kInterBits);
-  const int fx = X & (kInterTab - 1), fy = Y & (kInterTab - 1);
-  const bool c0 = (unsigned)sx < (unsigned)Ws, c1 = (unsigned)(sx + 1) < (unsigned)Ws;
-  const bool r0 = (unsigned)sy < (unsigned)Hs, r1 = (unsigned)(sy + 1) < (unsigned)Hs;
-  if (!((c0 || c1) && (r0 || r1))) return cval;
-  const T* p = src + (int64_t)sy * sr + sx;
-  const T s00 = (r0 && c0) ? p[0] : cval;
-  const T s01 = (r0 && c1) ? p[1] : cval;
-  const T s10 = (r1 && c0) ? p[sr] : cval;
-  const T s11 = (r1 && c1) ? p[sr + 1] : cval;
-  return Px<T>::blend(s00, s01, s10, s11, fx, fy);
+  return sample_tap<T>(src, sr, Hs, Ws, X, Y, nearest, cval);
 }
 
 template <typename T, bool VEC, int NM>
@@ -138,25 +84,6 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void warp_perspective_kernel(Warp
   } else {
     for (int k = 0; col + k < a.w; ++k) out[k] = warp_pixel<T>(src, a.src_sr, a.Hs, a.Ws, m, a.bw, x + k, m1y, m4y, m7y, nearest, cval);
   }
-}
-
-// closed-form inverse: cofactors times ONE reciprocal of the determinant (false: singular or not finite)
-bool invert3x3(const double* s, double* t) {
-  const double det = s[0] * (s[4] * s[8] - s[5] * s[7]) - s[1] * (s[3] * s[8] - s[5] * s[6]) + s[2] * (s[3] * s[7] - s[4] * s[6]);
-  if (det == 0.0 || !isfinite(det)) return false;
-  const double d = 1.0 / det;
-  t[0] = (s[4] * s[8] - s[5] * s[7]) * d;
-  t[1] = (s[2] * s[7] - s[1] * s[8]) * d;
-  t[2] = (s[1] * s[5] - s[2] * s[4]) * d;
-  t[3] = (s[5] * s[6] - s[3] * s[8]) * d;
-  t[4] = (s[0] * s[8] - s[2] * s[6]) * d;
-  t[5] = (s[2] * s[3] - s[0] * s[5]) * d;
-  t[6] = (s[3] * s[7] - s[4] * s[6]) * d;
-  t[7] = (s[1] * s[6] - s[0] * s[7]) * d;
-  t[8] = (s[0] * s[4] - s[1] * s[3]) * d;
-  for (int i = 0; i < 9; ++i)
-    if (!isfinite(t[i])) return false;
-  return true;
 }
 
 // one matrix of the call as the kernel takes it: checked, inverted unless the caller's is the inverse map already

@@ -14,6 +14,10 @@ expands it with the same fp64 time arithmetic.
     events = store.load_event(i0, i1)                    # reference format, for any reference-style caller
     plan = store.plan(i0, i1, (720, 1280), "first")      # fast path: raw columns -> device -> EventPlan
 
+With ``calibration=`` (a ``calibration.CameraCalibration``, or the ``{"K", "D"}`` dict ``load_calib`` returns) the store answers the
+reference loaders' ``load_calib`` / ``undistort`` and hands out rectified sub-pixel windows: ``load_event(.., rectify=True)``,
+``plan(.., rectify=True)``.
+
 Index helpers follow the reference loader: ``index_to_time`` (:319-330), ``time_to_index`` = searchsorted - 1 (:343-356).
 
 ``FrameStore`` is the frame half (:36-47, :136-156, :332-343, :359-396): the camera frames, their trigger timestamps and the
@@ -42,11 +46,28 @@ logger = logging.getLogger(__name__)
 COLUMNS = (("x", np.int16), ("y", np.int16), ("t", np.int32), ("p", np.bool_))
 
 
+def _as_calibration(calibration, sensor_size):
+    """None, a ``CameraCalibration``, or the {"K", "D"[, "new_K"]} dict ``load_calib`` returns (then ``sensor_size`` is required)."""
+    if calibration is None:
+        return None
+    from .calibration import CameraCalibration
+
+    if isinstance(calibration, CameraCalibration):
+        return calibration
+    if isinstance(calibration, dict):
+        if calibration.get("K") is not None and calibration.get("D") is not None and sensor_size is None \
+                and calibration.get("sensor_size") is None:
+            raise ValueError("sensor_size (height, width) is required with a calibration given as a dict")
+        return CameraCalibration.from_dict(calibration, sensor_size)
+    raise ValueError(f"calibration must be a CameraCalibration or a dict with K and D, got {type(calibration).__name__}")
+
+
 class RawEventStore(object):
     NAME = "RAW_COLUMNS"
     TICKS_PER_SECOND = 1e6  # microsecond timestamps, src/data_loader/ccs.py:295
 
-    def __init__(self, source: Union[str, Dict[str, np.ndarray]], sensor_size: Optional[Tuple[int, int]] = None):
+    def __init__(self, source: Union[str, Dict[str, np.ndarray]], sensor_size: Optional[Tuple[int, int]] = None, calibration=None):
+        self.calibration = _as_calibration(calibration, sensor_size)   # None: no calibration, as the reference's loaders answer
         self.header = None            # a .raw source: the parsed header (evt3.RawHeader)
         self.triggers = None          # a .raw source: int64 [n, 3] = (t, id, value), the "old" layout of read_trigger_timestamps
         self.dropped_outside = 0      # a .raw source: events outside the header's geometry, removed
@@ -129,9 +150,13 @@ class RawEventStore(object):
             logger.error(e)
             raise IndexError(e)
 
-    def load_event(self, start_index: int, end_index: int, *args, **kwargs) -> np.ndarray:
-        """float64 [n, 4] = (row, col, t in seconds, p), as src/data_loader/ccs.py:247-297."""
+    def load_event(self, start_index: int, end_index: int, *args, rectify: bool = False, **kwargs) -> np.ndarray:
+        """float64 [n, 4] = (row, col, t in seconds, p), as src/data_loader/ccs.py:247-297.  ``rectify=True`` (needs a calibration
+        and a GPU): the window's events at their rectified sub-pixel positions, ``calibration.rectify_events_raw`` -- events that
+        leave the sensor's image are dropped, so the array may be shorter; ``t`` and ``p`` are unchanged bit for bit."""
         self._check(start_index, end_index)
+        if rectify:
+            return self._rectified(start_index, end_index, "cuda").cpu().numpy()
         n = end_index - start_index
         events = np.zeros((n, 4), dtype=np.float64)
         sl = slice(start_index, end_index)
@@ -169,8 +194,49 @@ class RawEventStore(object):
         cols = (torch.from_numpy(self.event_data[k][sl].view(np.uint8) if k == "p" else self.event_data[k][sl]) for k in "xytp")
         return tuple(c.pin_memory().to(dev, non_blocking=True) for c in cols)
 
+    # ------------------------------------------------------------------ calibration (reference: ccs.py:427-451)
+    def load_calib(self) -> dict:
+        """{"K": camera matrix, "D": distortion coefficients}; both None without a calibration, as the reference's loaders answer."""
+        if self.calibration is None:
+            return {"K": None, "D": None}
+        return self.calibration.as_dict()
+
+    def undistort(self, event_batch):
+        """``utils.undistort_events`` with the store's own rectification map (integer positions, the reference's semantics).
+        Without a calibration: ``NotImplementedError``, as the reference's loaders raise."""
+        if self.calibration is None:
+            logger.error("Not supported!")
+            raise NotImplementedError("the store has no calibration: pass calibration= (a CameraCalibration or a {'K', 'D'} dict)")
+        from .calibration import undistort_events
+
+        dev = event_batch.device if isinstance(event_batch, torch.Tensor) and event_batch.is_cuda else None
+        rmap = self.calibration.rectify_map(dev)
+        H, W = self.calibration.sensor_size
+        return undistort_events(event_batch, rmap[..., 1], rmap[..., 0], H, W)
+
+    def _rectified(self, start_index: int, end_index: int, device, dtype=torch.float64) -> torch.Tensor:
+        if self.calibration is None:
+            raise ValueError("rectify=True needs a calibration: pass calibration= (a CameraCalibration or a {'K', 'D'} dict)")
+        from .calibration import rectify_events_raw
+
+        _hip.require_gpu()
+        col, row, t, pol = self.load_raw(start_index, end_index, device)
+        events, outside_sensor, outside_image = rectify_events_raw(col, row, t, pol, self.calibration, self.TICKS_PER_SECOND, dtype)
+        if outside_sensor or outside_image:
+            logger.info(f"events {start_index} .. {end_index}: {outside_sensor} outside the sensor, {outside_image} rectified to outside "
+                        "the image, dropped")
+        return events
+
     def plan(self, start_index: int, end_index: int, image_size: Tuple[int, int], direction="first",
-             normalize_t: bool = True, tile="auto", device="cuda", deferred: bool = False, emit: str = "full") -> EventPlan:
+             normalize_t: bool = True, tile="auto", device="cuda", deferred: bool = False, emit: str = "full",
+             rectify: bool = False) -> EventPlan:
+        """``rectify=True``: ``EventPlan.build`` -- the full build, which is what fractional windows take -- on the window's rectified
+        events (``calibration.rectify_events_raw``); ``deferred`` and ``emit`` other than "full" are refused."""
+        if rectify:
+            if deferred or emit != "full":
+                raise ValueError("rectify=True takes the full plan build: the lean and deferred builds are integer-only")
+            self._check(start_index, end_index)
+            return EventPlan.build(self._rectified(start_index, end_index, device), image_size, direction, normalize_t, tile)
         col, row, t, pol = self.load_raw(start_index, end_index, device)
         return EventPlan.build_raw(col, row, t, pol, image_size, direction, normalize_t, tile, self.TICKS_PER_SECOND,
                                    deferred=deferred, emit=emit)
@@ -301,9 +367,15 @@ class FrameStore(object):
         timestamps ... the trigger file (either text format) or an array, see ``read_trigger_timestamps``; seconds = stamps / 1e6.
         homography ... None (frames are returned as they are), a text file (``np.loadtxt``) or a 3 x 3 array: camera -> event view.
         sensor_size ... (height, width) of the event sensor: the size warped frames have.  Required with a homography.
+        calibration ... None, or the ``CameraCalibration`` of the FRAME camera (its ``sensor_size`` is the raw frames' size): frames
+            are then rectified, and warped where a homography (rectified frame -> event view) is set, in one resample
+            (``frame_warp.undistort_image``).  Without one nothing changes.
     """
     def __init__(self, frames, timestamps, homography=None, sensor_size: Optional[Tuple[int, int]] = None,
-                 timestamp_layout: str = "auto"):
+                 timestamp_layout: str = "auto", calibration=None):
+        if calibration is not None and not hasattr(calibration, "camera_array"):
+            raise ValueError("calibration must be a CameraCalibration of the frame camera (its sensor_size is the raw frames' size)")
+        self.calibration = calibration
         self._files, self._stack = None, None
         if isinstance(frames, (str, os.PathLike)):
             frames = str(frames)
@@ -383,7 +455,10 @@ class FrameStore(object):
 
         index = self._check_index(index)
         image, timestamp = self._raw(index), self.timestamps[index]
-        if self.warp_frame:
+        if self.calibration is not None:
+            image = frame_warp.undistort_image(image, self.calibration, self.homography,
+                                               (self._WIDTH, self._HEIGHT) if self.warp_frame else None)
+        elif self.warp_frame:
             image = frame_warp.warp_perspective(image, self.homography, (self._WIDTH, self._HEIGHT))
         return image, timestamp
 
@@ -423,6 +498,9 @@ class FrameStore(object):
             host = torch.from_numpy(np.stack([first] + [self._raw(i) for i in idx[1:]]))
         raw = host.to(dev, non_blocking=True)
         ts = self.timestamps[idx]
+        if self.calibration is not None:
+            return frame_warp.undistort_image_batch(raw, self.calibration, self.homography, (W, H) if self.warp_frame else None,
+                                                    roi=rect), ts
         if not self.warp_frame:
             return raw[:, rect[0]:rect[1], rect[2]:rect[3]], ts
         return frame_warp.warp_perspective_batch(raw, self.homography, (W, H), roi=rect), ts

@@ -208,6 +208,85 @@ def warp_perspective(src, M, dsize, flags: int = INTER_LINEAR, border_value: flo
     return out[0].cpu().numpy() if numpy_out else out[0]
 
 
+def _check_calib(calib, Hs: int, Ws: int):
+    from .calibration import CameraCalibration
+
+    if not isinstance(calib, CameraCalibration):
+        raise ValueError(f"calib must be a CameraCalibration, got {type(calib).__name__}")
+    if calib.sensor_size != (Hs, Ws):
+        raise ValueError(f"the calibration belongs to a {calib.sensor_size[0]} x {calib.sensor_size[1]} sensor, the frames are {Hs} x {Ws}")
+    return calib
+
+
+def _validate_undistort(srcs, ndim, calib, homography, dsize, roi, border_value):
+    _check_frames(srcs, "image" if ndim == 2 else "images", ndim)
+    Hs, Ws = int(srcs.shape[-2]), int(srcs.shape[-1])
+    _check_calib(calib, Hs, Ws)
+    m = None if homography is None else _check_matrix(homography, None, 0)
+    W, H = (Ws, Hs) if dsize is None else _check_dsize(dsize)
+    rect = _check_roi(roi, H, W)
+    try:
+        border_value = float(border_value)
+        ok = np.isfinite(border_value)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"border_value must be one finite number, got {border_value!r}")
+    return m, W, H, rect, border_value
+
+
+def _launch_undistort(srcs: torch.Tensor, calib, m: Optional[np.ndarray], H: int, W: int, border_value: float, rect: tuple,
+                      out: torch.Tensor) -> None:
+    lib = _hip.require_gpu()
+    B, Hs, Ws = (int(v) for v in srcs.shape)
+    dev = srcs.device
+    cam = calib.camera_array()
+    fn = lib.ebos_undistort_image_u8 if srcs.dtype == torch.uint8 else lib.ebos_undistort_image_f32
+    with _hip.on_device(dev):
+        check(fn(B, Hs, Ws, srcs.data_ptr(), srcs.stride(0) if B > 1 else 0, srcs.stride(1), cam.ctypes.data_as(C.c_void_p),
+                 None if m is None else m.ctypes.data_as(C.c_void_p), H, W, float(border_value), *rect, out.data_ptr(),
+                 out.stride(0) if B > 1 else 0, out.stride(1), stream_ptr(dev)), "ebos_undistort_image")
+
+
+def undistort_image_batch(images, calib, homography=None, dsize=None, roi: Optional[Roi] = None, border_value: float = 0,
+                          out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """Every frame of ``images`` [B, Hs, Ws] (uint8 / float32, numpy or torch) rectified in one launch, without a host
+    synchronisation: see ``undistort_image``.  ``out``: an optional device [B, h, w] view with a unit column stride to write into.
+    Returns a device [B, h, w] tensor; a frame's bits do not depend on the batch it is in."""
+    m, W, H, rect, border_value = _validate_undistort(images, 3, calib, homography, dsize, roi, border_value)
+    B, h, w = int(images.shape[0]), rect[1] - rect[0], rect[3] - rect[2]
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and tuple(out.shape) == (B, h, w) and out.dtype == _dtype_of(images)
+                and out.stride(2) == 1 and out.stride(1) >= w and out.stride(0) >= 0):
+            raise ValueError(f"out must be a device [{B}, {h}, {w}] tensor of {images.dtype} with a unit column stride")
+        device = out.device
+    dev = images.device if isinstance(images, torch.Tensor) and images.is_cuda else (torch.device(device) if device is not None else None)
+    sv = _upload(images, dev)
+    if out is None:
+        out = torch.empty((B, h, w), dtype=sv.dtype, device=sv.device)
+    elif out.device != sv.device:
+        raise ValueError(f"out is on {out.device}, the frames on {sv.device}")
+    _launch_undistort(sv, calib, m, H, W, border_value, rect, out)
+    return out
+
+
+def undistort_image(image, calib, homography=None, dsize=None, roi: Optional[Roi] = None, border_value: float = 0):
+    """One [Hs, Ws] uint8 / float32 frame of the camera ``calib`` (a ``CameraCalibration`` whose ``sensor_size`` is the frame's)
+    rectified -- ``cv2.undistort(image, K, D, None, new_K)`` -- and, where ``homography`` (3 x 3, rectified frame -> destination, as
+    ``cv2.warpPerspective`` takes it) is given, warped into the destination ``dsize`` = (W, H) (default: the frame's own size) IN
+    THE SAME RESAMPLE: an output pixel takes its ideal position (through the inverse homography), is normalised by ``new_K``, pushed
+    through the lens model and sampled there with the fixed-point bilinear arithmetic of ``warp_perspective`` (constant border).
+    One resample is not two: the result is not ``warp_perspective(undistort(image))`` pixel for pixel, it is sharper.  Where
+    every coefficient of ``D`` is zero and ``new_K`` is ``K`` the result is ``warp_perspective``'s bit for bit.  ``roi`` as there.
+    numpy in -> numpy out; a tensor in -> a device tensor.  Restated by tests/_rectify_ref.py; not checked against OpenCV."""
+    m, W, H, rect, border_value = _validate_undistort(image, 2, calib, homography, dsize, roi, border_value)
+    numpy_out = not isinstance(image, torch.Tensor)
+    sv = _upload(image[None], image.device if not numpy_out and image.is_cuda else None)
+    out = torch.empty((1, rect[1] - rect[0], rect[3] - rect[2]), dtype=sv.dtype, device=sv.device)
+    _launch_undistort(sv, calib, m, H, W, border_value, rect, out)
+    return out[0].cpu().numpy() if numpy_out else out[0]
+
+
 def check_even_crop(h: int, w: int, roi) -> None:
     """The driver refuses a crop with an odd number of rows or columns (its later stages halve the frame): so does this."""
     if h % 2:

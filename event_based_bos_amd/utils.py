@@ -11,7 +11,8 @@ its flow-error metrics from ``flow_error``, as src/utils/__init__.py:20-21 does,
 ``create_event_voxel`` and ``generate_discretized_event_volume``, from ``event_voxel``, as src/utils/__init__.py:4,7 does, and the
 time-aware flow (``construct_dense_flow_voxel_*`` and the functions around it) from ``flow_voxel``, as src/utils/__init__.py:19-33 does,
 and the frame warps ``warp_image_forward`` / ``warp_image_torch`` and ``SSIM`` / ``ssim`` from ``photometric``, as
-src/utils/__init__.py:40-41,54 does.
+src/utils/__init__.py:40-41,54 does, and ``undistort_events`` (src/utils/event_utils.py:242-266) from ``calibration``, with the fused
+frame rectification ``undistort_image`` / ``undistort_image_batch`` of ``frame_warp`` beside it.
 
 ``propagate_config`` is the driver's config plumbing for this path (reference: src/utils/config_utils.py:42-88): the
 solver reads its region of interest from keys that only exist after that propagation.
@@ -79,3 +80,5 @@ from .flow_voxel import (construct_dense_flow_voxel_numpy, construct_dense_flow_
                          inviscid_burger_flow_to_voxel_torch, propagate_flow_to_voxel_numpy, propagate_flow_to_voxel_torch,
                          truncate_voxel_flow_numpy, upwind_flow_to_voxel_numpy, upwind_flow_to_voxel_torch)
 from .photometric import SSIM, ssim, warp_image_forward, warp_image_torch  # noqa: E402,F401
+from .calibration import undistort_events  # noqa: E402,F401
+from .frame_warp import undistort_image, undistort_image_batch  # noqa: E402,F401

@@ -1275,6 +1275,59 @@ int ebos_warp_perspective(int dtype, int B, int Hs, int Ws, const void* src, int
                           int64_t m_stride, int H, int W, int flags, double border_value, int xmin, int xmax, int ymin, int ymax,
                           void* out, int64_t out_sb, int64_t out_sr, ebos_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Lens calibration (csrc/rectify.hip): from a camera matrix K and OpenCV-order distortion coefficients D to rectified sub-pixel
+ * events and rectified frames (reference: src/utils/event_utils.py:242-266 undistort_events, the loaders' load_calib / undistort,
+ * src/solver/base.py:363-378 undistort_image).  tests/_rectify_ref.py restates every kernel in numpy with the same operation order.
+ *
+ * camera: 16 HOST doubles (fx, fy, cx, cy of K; fx', fy', cx', cy' of new_K; k1, k2, p1, p2, k3, k4, k5, k6), all finite, focal
+ * lengths non-zero.  cx / fx belong to the column axis (sensor x), cy / fy to the row axis.  Forward model, ideal normalised (x, y)
+ * -> sensor pixel (u, v), every operation rounded on its own:
+ *   r2 = x x + y y;  rad = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2);  a = (2 x) y
+ *   dx = p1 a + p2 (r2 + 2 (x x));  dy = p1 (r2 + 2 (y y)) + p2 a;  u = fx (x rad + dx) + cx;  v = fy (y rad + dy) + cy
+ *
+ *   ebos_rectify_map_f64      map [H, W, 2] float64 (16-byte aligned) = the rectified (row', col') of every sensor pixel: from
+ *                             x0 = (col - cx) / fx, y0 = (row - cy) / fy exactly `iterations` (1 .. 1000) steps
+ *                             x = (x0 - dx(x, y)) / rad(x, y), y = (y0 - dy(x, y)) / rad(x, y) starting at (x0, y0), then
+ *                             (fy' y + cy', fx' x + cx').  One thread per pixel, plain stores.
+ *   ebos_rectify_events_raw   raw columns (col / row int16, t int32 or int64 ticks, pol uint8) + that map -> events_out [m, 4] =
+ *                             (row', col', ticks / ticks_per_second, pol != 0) float64 or float32 (out_is_f32), in stream order.
+ *                             Dropped: an event whose pixel is outside the H x W sensor (the map is not read for it; counted in
+ *                             counts[1]), and one whose rectified position, in the output's type, is not inside 0 <= row' < H_out,
+ *                             0 <= col' < W_out.  counts: device int32 [2] = (m, dropped outside the sensor); the second kind of
+ *                             drop is n - m - counts[1].  events_out holds n rows (16-byte aligned); rows past m are not written.
+ *   ebos_undistort_events_*   the reference's undistort_events on events [n, 4]: k = int32(map_y[int32(x), int32(y)]),
+ *                             l = int32(map_x[..]) (truncation toward zero; negative indices count from the end, as numpy's),
+ *                             columns 0 and 1 replaced by k and l, rows with 0 <= k < h and 0 <= l < w kept in order.  map_x /
+ *                             map_y: float64 [map_h, map_w].  counts: device int32 [2] = (m, events whose index numpy refuses).
+ *   ebos_undistort_image_*    B frames [Hs, Ws] (uint8 or float32) rectified in one launch: output pixel (row r, column c) takes its
+ *                             ideal position (c, r) -- M^-1 (c, r, 1) where M (HOST, 3 x 3, frame -> destination, may be NULL) is
+ *                             given: the perspective kernel's coordinate walk --, normalises it by new_K, applies the forward model
+ *                             and samples the source at (u, v) as ebos_warp_perspective's INTER_LINEAR does (rint(32 u), 5 fraction
+ *                             bits, 15-bit weights or float products, constant border).  Where every coefficient is zero and new_K
+ *                             equals K the lens step is skipped and the result is ebos_warp_perspective's bit for bit.  Rectangle,
+ *                             strides and limits as there.
+ * Events compact through a keep flag, the device-wide exclusive scan the plan build and ebos_filter_compact use, and a scatter;
+ * scratch: ebos_rectify_scratch_bytes(n) bytes; n <= EBOS_RECTIFY_MAX_EVENTS.  No host synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+#define EBOS_RECTIFY_MAX_EVENTS 2147000000LL
+
+int ebos_rectify_map_f64(const double* camera, int iterations, int H, int W, double* map, ebos_stream_t stream);
+size_t ebos_rectify_scratch_bytes(int64_t n);
+int ebos_rectify_events_raw(const int16_t* col, const int16_t* row, const void* t, int t_is_int64, const uint8_t* pol, int64_t n,
+                            double ticks_per_second, const double* map, int H, int W, int H_out, int W_out, int out_is_f32,
+                            void* events_out, int32_t* counts, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_undistort_events_f32(const float* events, int64_t n, const double* map_x, const double* map_y, int map_h, int map_w, int h, int w,
+                              float* events_out, int32_t* counts, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_undistort_events_f64(const double* events, int64_t n, const double* map_x, const double* map_y, int map_h, int map_w, int h, int w,
+                              double* events_out, int32_t* counts, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_undistort_image_u8(int B, int Hs, int Ws, const uint8_t* src, int64_t src_sb, int64_t src_sr, const double* camera,
+                            const double* M, int H, int W, double border_value, int xmin, int xmax, int ymin, int ymax, uint8_t* out,
+                            int64_t out_sb, int64_t out_sr, ebos_stream_t stream);
+int ebos_undistort_image_f32(int B, int Hs, int Ws, const float* src, int64_t src_sb, int64_t src_sr, const double* camera, const double* M,
+                             int H, int W, double border_value, int xmin, int xmax, int ymin, int ymax, float* out, int64_t out_sb,
+                             int64_t out_sr, ebos_stream_t stream);
+
 /* ---- several solver windows' event side in one launch, from the raw sensor columns (csrc/window_ingest.hip) -----------------
  * col / row int16, t int32 (t_is_64 = 0) or int64 ticks, pol uint8: device columns of n_total events (RawEventStore.load_raw).
  * ranges: device int64 [B, 2], window b = events [begin, end) of the columns; ranges may overlap or be empty and are clamped to

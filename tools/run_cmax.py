@@ -9,6 +9,7 @@ on a synthetic window (the recorded CCS sequences are not distributable).
     python tools/run_cmax.py --config_file tests/golden/config_hot_plate1.json --height 260 --width 346   # BASELINE configs[0] size
     python tools/run_cmax.py --flow-error     # + EPE / NPE / AE against the synthetic scene's dense truth in the ROI
     python tools/run_cmax.py --poisson OUT.npz   # + the Poisson integration (and its uint8 picture) of the estimate and the truth
+    python tools/run_cmax.py --calib CAMERA.json # rectify the window first: a JSON file with "K", "D" and an optional "new_K"
 
 With the reference's file: 720x1280 and the region of interest rows 0:720, cols 320:960 as declared (:5-6, :23-26), motion model
 2d-translation, Adam, n_iter 600, blur_sigma 3 (:46-70) are taken from it; ``solver.method`` (the release ships no CMax solver,
@@ -96,6 +97,22 @@ def poisson_outputs(flow, truth, path):
             "abs_max_truth": float(np.abs(P[1]).max())}
 
 
+def rectify_window(events, shape, path):
+    """The window as a calibrated sensor delivers it -- int16 pixel columns, microsecond ticks -- rectified on the GPU with the camera
+    of ``path`` (JSON: "K" 3 x 3, "D" 4 / 5 / 8 coefficients, optional "new_K"): ``calibration.rectify_events_raw``.  The events come
+    back at sub-pixel positions, so the solve takes the fractional route; events that leave the image are dropped."""
+    import torch
+    with open(path) as f:
+        cam = json.load(f)
+    calib = ebos.CameraCalibration(cam["K"], cam["D"], shape, new_K=cam.get("new_K"))
+    col, row = (torch.from_numpy(np.floor(events[:, k]).astype(np.int16)).cuda() for k in (1, 0))
+    t = torch.from_numpy(np.rint(events[:, 2] * 1e6).astype(np.int64)).cuda()
+    pol = torch.from_numpy(events[:, 3].astype(np.uint8)).cuda()
+    out, outside_sensor, outside_image = ebos.rectify_events_raw(col, row, t, pol, calib)
+    return out.cpu().numpy(), {"file": os.path.basename(path), "coefficients": int(calib.D.size), "outside_sensor": outside_sensor,
+                               "outside_image": outside_image}
+
+
 def load_config(path):
     if path.endswith(".json"):  # fixture made from the reference's YAML by tests/golden/make_golden.py --config
         return json.load(open(path))["input"]
@@ -113,6 +130,8 @@ def main():
     ap.add_argument("--n-iter", type=int, default=None, help="override solver.optimizer.n_iter")
     ap.add_argument("--fractional", action="store_true", help="keep the synthetic events' sub-pixel coordinates (events rectified with a sub-pixel map) "
                                                             "instead of rounding them to the sensor's integer pixels")
+    ap.add_argument("--calib", default=None, metavar="FILE.json", help="camera calibration {K, D[, new_K]}: the window is rectified on the GPU "
+                                                                       "(sub-pixel positions) before the solve")
     ap.add_argument("--flow-error", action="store_true", help="also report EPE / NPE / AE in the ROI against the scene's dense truth, "
                                                             "without and with the event mask (SolverBase.calculate_flow_error)")
     ap.add_argument("--poisson", default=None, metavar="OUT.npz", help="save the Poisson integration of the estimate and of the scene's "
@@ -141,6 +160,9 @@ def main():
     if args.n_iter is not None:
         scfg.setdefault("optimizer", {})["n_iter"] = args.n_iter
     events, shape = synthetic_window(cfg)
+    calib_info = None
+    if args.calib:
+        events, calib_info = rectify_window(events, shape, args.calib)
     crop_shape = (d["crop_height"], d["crop_width"])
     solver = ebos.solver.collections[scfg["method"]](shape, crop_shape, calibration_parameter=None, solver_config=scfg,
                                                      visualize_module=None)
@@ -164,6 +186,8 @@ def main():
     extra = {"flow_error": flow_errors(solver, flow, dense_truth(d), events, cp)} if args.flow_error else {}
     if args.poisson:
         extra["poisson"] = poisson_outputs(flow, dense_truth(d), args.poisson)
+    if calib_info is not None:
+        extra["calibration"] = calib_info
     print(json.dumps({"config_file": os.path.relpath(args.config_file, ROOT), "overrides": overrides, "events_in": n_in,
                       "events": int(len(events)), "image": list(shape), "crop": list(crop_shape), "roi": [cp[k] for k in ("xmin", "xmax", "ymin", "ymax")],
                       "motion_model": solver.motion_model, "optimizer": solver.opt_method, "blur_sigma": solver.blur_sigma,
