@@ -101,6 +101,8 @@ _WARP_VOXEL_BWD = [_P, _P, _I, _D, _I, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P]
 _W2_BWD = [_P, _P, _I, _D, _I, _P, _P, _L, _P, _P]
 _SPLAT = [_P, _P, _D, _I, _D, _L, _L, _I, _I, _I, _I, _P, _P]
 _SPLAT_BWD = [_P, _P, _D, _D, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P]
+_SPLAT_INDEX = [_P, _I, _D, _L, _L, _I, _I, _I, _I, _P, _Z, _P]
+_SPLAT_ORDERED = [_P, _P, _D, _I, _D, _L, _L, _I, _I, _I, _I, _P, _Z, _P, _P]
 _SOA = [_P, _P, _I, _D, _I, _L, _P, _P, _P, _P, _P]
 _VAR = [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]
 _VAR_GRAD = [_P, _I, _I, _I, _I, _P, _P, _P, _P]
@@ -128,6 +130,11 @@ SIGNATURES = {
     "ebos_splat_f64": (_I, _SPLAT),
     "ebos_splat_bwd_f32": (_I, _SPLAT_BWD),
     "ebos_splat_bwd_f64": (_I, _SPLAT_BWD),
+    "ebos_splat_index_bytes": (_Z, [_L, _L, _I, _I, _I]),
+    "ebos_splat_index_build_f32": (_I, _SPLAT_INDEX),
+    "ebos_splat_index_build_f64": (_I, _SPLAT_INDEX),
+    "ebos_splat_ordered_f32": (_I, _SPLAT_ORDERED),
+    "ebos_splat_ordered_f64": (_I, _SPLAT_ORDERED),
     "ebos_events_to_soa_f32": (_I, _SOA),
     "ebos_events_to_soa_f64": (_I, _SOA),
     "ebos_raw_time_range": (_I, [_P, _I, _L, _D, _P, _P, _P]),

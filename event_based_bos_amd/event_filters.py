@@ -81,8 +81,11 @@ class _Window(object):
 class _Chain(object):
     """Keep masks of successive filters over ONE window, on the device; ``compact`` ends it."""
 
-    def __init__(self, win: _Window, image_shape):
+    def __init__(self, win: _Window, image_shape, vote: str = "atomic"):
         self.lib = _hip.require_gpu()
+        if vote not in ("atomic", "ordered"):
+            raise ValueError(f"vote must be 'atomic' or 'ordered', got {vote!r}")
+        self.vote = vote   # how the hot-pixel filter's image of fractional events is accumulated (ops.splat's routes)
         self.win, self.H, self.W = win, int(image_shape[0]), int(image_shape[1])
         self.mask: Optional[torch.Tensor] = None
         self.n_dev: Optional[torch.Tensor] = None   # events in the chain's current output (device int32); None: all win.n
@@ -121,14 +124,19 @@ class _Chain(object):
                 self.compact_in_place()
                 if self.win.n < MIN_EVENTS:
                     return
-            iwe = torch.zeros((self.H, self.W), dtype=torch.float64, device=self.win.device)
             ev = self.win.events
             if ev.dtype != torch.float64 or self.win.layout != 0x24:
                 ic = [self.win.layout & 3, (self.win.layout >> 2) & 3, self.win.layout >> 4 & 3]
                 ev = torch.stack([ev[:, ic[0]], ev[:, ic[1]], ev[:, ic[2]], ev[:, ic[2]]], dim=1).to(torch.float64).contiguous()
-            with _hip.on_device(self.win.device):
-                check(self.lib.ebos_splat_f64(ptr(ev), None, 1.0, _hip.SPLAT_BILINEAR, 1e-8, 1, self.win.n, self.H, self.W, 0, 0,
-                                              ptr(iwe), stream_ptr()), "ebos_splat_f64")
+            if self.vote == "ordered":
+                from . import ops
+
+                iwe = ops.splat(ev[None, :self.win.n], (self.H, self.W), (0, 0), 1.0, _hip.SPLAT_BILINEAR, 1e-8, route="ordered")[0]
+            else:
+                iwe = torch.zeros((self.H, self.W), dtype=torch.float64, device=self.win.device)
+                with _hip.on_device(self.win.device):
+                    check(self.lib.ebos_splat_f64(ptr(ev), None, 1.0, _hip.SPLAT_BILINEAR, 1e-8, 1, self.win.n, self.H, self.W, 0, 0,
+                                                  ptr(iwe), stream_ptr()), "ebos_splat_f64")
         mask, n_out = self._outputs()
         src = self.win.source()
         with _hip.on_device(self.win.device):
@@ -221,10 +229,12 @@ def continuous_background_activity_filter(events: NUMPY_TORCH, image_shape: tupl
     return _like_input(out, events), m_ret
 
 
-def hot_pixel_filter(events: NUMPY_TORCH, image_shape: tuple, hot_pixel: int = 10, index_convention: Optional[dict] = None) -> NUMPY_TORCH:
-    """src/utils/event_filters.py:100-128: drops the events of pixels whose sigma = 0 image of events is > ``hot_pixel``."""
+def hot_pixel_filter(events: NUMPY_TORCH, image_shape: tuple, hot_pixel: int = 10, index_convention: Optional[dict] = None,
+                     vote: str = "atomic") -> NUMPY_TORCH:
+    """src/utils/event_filters.py:100-128: drops the events of pixels whose sigma = 0 image of events is > ``hot_pixel``.
+    ``vote``: the route of that image for fractional coordinates ("atomic", or "ordered": the same image bit for bit every time)."""
     ev = _device_events(events)
-    chain = _Chain(_Window(events=ev, layout=_layout(index_convention)), image_shape)
+    chain = _Chain(_Window(events=ev, layout=_layout(index_convention)), image_shape, vote)
     chain.hot(hot_pixel)
     return _like_input(chain.compact().events, events)
 
@@ -247,6 +257,7 @@ class EventFilter(object):
             self.filters = ["CROP"] + self.filters
         self.index_convention = filter_config.get("index_convention", DEFAULT_INDEX_CONVENTION)
         self.continuous_update = bool(self.filter_params.get("BAF_continuous_update", False))
+        self.vote = str(self.filter_params.get("HOT_vote", "atomic"))   # the hot-pixel image's route: "atomic" | "ordered"
         self.time_map: Optional[torch.Tensor] = None
         self.setup()
 
@@ -291,7 +302,7 @@ class EventFilter(object):
 
     def _run(self, win: _Window, names: Sequence[str]) -> _Window:
         p = self.filter_params
-        chain = _Chain(win, self.image_shape)
+        chain = _Chain(win, self.image_shape, self.vote)
         for name in names:
             if name == "BAF":
                 m = chain.baf(p["BAF_dt"], p["BAF_ksize"], p["BAF_num_support_event"], self.time_map)

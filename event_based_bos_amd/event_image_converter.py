@@ -68,9 +68,14 @@ class EventImageConverter(object):
         image_size (tuple) ... (H, W)
         outer_padding (int or tuple) ... padding added on every side so that warped events that leave the
             sensor still land in the image.
+        vote (str) ... "atomic" (default): float atomics on the image.  "ordered": every accumulation goes through a sorted index
+            and a fixed summation order (``ops.SplatIndex``) and repeats bit for bit; the fused provenance path is the same for both.
     """
 
-    def __init__(self, image_size: tuple, outer_padding: Union[int, Tuple[int, int]] = 0):
+    def __init__(self, image_size: tuple, outer_padding: Union[int, Tuple[int, int]] = 0, vote: str = "atomic"):
+        if vote not in ops.SPLAT_ROUTES:
+            raise ValueError(f"vote must be one of {ops.SPLAT_ROUTES}, got {vote!r}")
+        self.vote = vote
         if isinstance(outer_padding, (int, float)):
             self.outer_padding = (int(outer_padding), int(outer_padding))
         else:
@@ -87,8 +92,8 @@ class EventImageConverter(object):
         self.image_size = tuple(s + p for s, p in zip(self.image_size, self.outer_padding))
 
     # ------------------------------------------------------------------ core accumulation
-    def _accumulate(self, events, weight, mode: int, eps: float, out_dtype: Optional[torch.dtype]) -> torch.Tensor:
-        """-> GPU tensor [b, h, w] ([1, 2, h, w] for polarity)."""
+    def _accumulate(self, events, weight, mode: int, eps: float, out_dtype: Optional[torch.dtype], index=None) -> torch.Tensor:
+        """-> GPU tensor [b, h, w] ([1, 2, h, w] for polarity).  ``index``: the ``ops.SplatIndex`` of these events (ordered vote)."""
         ev = to_gpu(events, dtype=out_dtype)
         if ev.dim() == 2:
             ev = ev[None]
@@ -104,7 +109,15 @@ class EventImageConverter(object):
         if mode == _hip.SPLAT_POLARITY:
             # boolean-mask indexing in the reference flattens the batch axis (:356-362)
             ev = ev.reshape(1, -1, 4)
-        return ops.splat(ev, self.image_size, self.outer_padding, wt, mode, eps)
+        if index is not None:
+            return index.vote(wt, mode)
+        return ops.splat(ev, self.image_size, self.outer_padding, wt, mode, eps, route=self.vote)
+
+    def _index_of(self, ev: torch.Tensor, eps: float):
+        """One index for several bilinear votes of the same events (ordered vote), else None."""
+        if self.vote != "ordered":
+            return None
+        return ops.SplatIndex.build(ev if ev.dim() == 3 else ev[None], self.image_size, self.outer_padding, eps)
 
     def _finish(self, img: torch.Tensor, kind: str):
         return back(img.squeeze(), kind)
@@ -224,8 +237,9 @@ class EventImageConverter(object):
             assert is_numpy(values)
             ev = to_gpu(events, dtype=torch.float64)
             val = to_gpu(values, device=ev.device, dtype=torch.float64)
-            num = self._accumulate(ev, val - base, _hip.SPLAT_BILINEAR, EPS_NUMPY, torch.float64).squeeze()
-            den = self._accumulate(ev, 1.0, _hip.SPLAT_BILINEAR, EPS_NUMPY, torch.float64).squeeze()
+            index = self._index_of(ev, EPS_NUMPY)
+            num = self._accumulate(ev, val - base, _hip.SPLAT_BILINEAR, EPS_NUMPY, torch.float64, index).squeeze()
+            den = self._accumulate(ev, 1.0, _hip.SPLAT_BILINEAR, EPS_NUMPY, torch.float64, index).squeeze()
             out = num / (den + 1e-2) + base
             if sigma > 0:
                 out = self._gaussian_filter(out, sigma)
@@ -235,8 +249,9 @@ class EventImageConverter(object):
             kind = kind_of(events)
             ev = to_gpu(events)
             val = to_gpu(values, device=ev.device, dtype=ev.dtype)
-            num = self._accumulate(ev, val - base, _hip.SPLAT_BILINEAR, EPS_TENSOR, None).squeeze()
-            den = self._accumulate(ev, 1.0, _hip.SPLAT_BILINEAR, EPS_TENSOR, None).squeeze()
+            index = self._index_of(ev, EPS_TENSOR)
+            num = self._accumulate(ev, val - base, _hip.SPLAT_BILINEAR, EPS_TENSOR, None, index).squeeze()
+            den = self._accumulate(ev, 1.0, _hip.SPLAT_BILINEAR, EPS_TENSOR, None, index).squeeze()
             out = torch.divide(num, den + 1e-2) + base
             if out.dim() == 2:
                 out = out[None, None, ...]

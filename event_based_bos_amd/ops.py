@@ -291,12 +291,105 @@ class _Splat(torch.autograd.Function):
         return d_events, d_weight, None, None, None, None, None, None, None
 
 
+class _SplatOrdered(torch.autograd.Function):
+    """The ordered route (csrc/splat_ordered.hip): the forward gathers through a ``SplatIndex`` workspace; the backward is
+    ``_Splat``'s -- the same order-free gather kernel on the same saved inputs."""
+
+    @staticmethod
+    def forward(ctx, events, weight, weight_scalar, mode, eps, h, w, pad_h, pad_w, workspace):
+        lib = _hip.require_gpu()
+        b, n, _ = events.shape
+        if weight is not None:
+            weight = _cuda_contig(weight.to(events.dtype), "weight")
+        shape = (b, 2, h, w) if mode == _hip.SPLAT_POLARITY else (b, h, w)
+        image = torch.empty(shape, dtype=events.dtype, device=events.device)   # every pixel is written by its owner
+        with _hip.on_device(events.device):
+            fn = getattr(lib, "ebos_splat_ordered_" + suffix(events.dtype))
+            check(fn(ptr(events), ptr(weight), float(weight_scalar), mode, float(eps), b, n, h, w, pad_h, pad_w,
+                     ptr(workspace), workspace.numel(), ptr(image), stream_ptr()), "ebos_splat_ordered")
+        ctx.save_for_backward(events, weight if weight is not None else torch.empty(0))
+        ctx.meta = (weight is not None, float(weight_scalar), mode, float(eps), h, w, pad_h, pad_w)
+        return image
+
+    @staticmethod
+    def backward(ctx, g):
+        return _Splat.backward(ctx, g) + (None,)
+
+
+class SplatIndex:
+    """The sorted index of a window's events by destination cell, for the ordered route of the vote: built once
+    (``SplatIndex.build``), voted any number of times with different weights (``vote``).  Images of this route are a pure
+    function of their inputs, bit for bit -- no atomics; the summation order is stated in include/ebos_hip.h.
+
+    ``offsets`` int32 [keys + 1] and ``indices`` int32 [b * n] are views of the workspace: ``indices[offsets[k]:offsets[k + 1]]``
+    are the events (``row * n + e``) whose top-left tap is cell ``k`` of the extended grid, ascending."""
+
+    def __init__(self, events, h, w, pad, eps, polarity, workspace):
+        self.events, self.h, self.w, self.pad, self.eps, self.polarity, self.workspace = events, h, w, pad, eps, polarity, workspace
+
+    @classmethod
+    def build(cls, events: torch.Tensor, image_size: Tuple[int, int], pad: Tuple[int, int] = (0, 0), eps: float = 1e-6,
+              polarity: bool = False) -> "SplatIndex":
+        """events [b, n, 4]; ``image_size`` is the PADDED size.  ``polarity``: an index for ``SPLAT_POLARITY`` votes (two planes
+        per batch row); otherwise it serves ``SPLAT_BILINEAR`` and ``SPLAT_COUNT``."""
+        if events.dim() != 3 or events.shape[-1] != 4:
+            raise ValueError(f"SplatIndex.build expects events [b,n,4], got {tuple(events.shape)}")
+        lib = _hip.require_gpu()
+        events = _cuda_contig(events, "events")
+        b, n, _ = events.shape
+        h, w, pad = int(image_size[0]), int(image_size[1]), (int(pad[0]), int(pad[1]))
+        mode = _hip.SPLAT_POLARITY if polarity else _hip.SPLAT_BILINEAR
+        nbytes = int(lib.ebos_splat_index_bytes(b, n, h, w, mode))
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=events.device)
+        with _hip.on_device(events.device):
+            fn = getattr(lib, "ebos_splat_index_build_" + suffix(events.dtype))
+            # (sizes the library refuses have nbytes == 0 and are refused here with its message)
+            check(fn(ptr(events), mode, float(eps), b, n, h, w, pad[0], pad[1], ptr(workspace), nbytes, stream_ptr()),
+                  "ebos_splat_index_build")
+        return cls(events, h, w, pad, float(eps), bool(polarity), workspace)
+
+    @property
+    def keys(self) -> int:
+        return self.events.shape[0] * (2 if self.polarity else 1) * (self.h + 1) * (self.w + 1)
+
+    @property
+    def offsets(self) -> torch.Tensor:
+        return self.workspace[:4 * (self.keys + 1)].view(_INT32)
+
+    @property
+    def indices(self) -> torch.Tensor:
+        start = (4 * (self.keys + 1) + 255) // 256 * 256
+        return self.workspace[start:start + 4 * self.events.shape[0] * self.events.shape[1]].view(_INT32)
+
+    def vote(self, weight=1.0, mode: Optional[int] = None) -> torch.Tensor:
+        """-> image [b, h, w] ([b, 2, h, w] for a polarity index); ``weight`` a number, a 0-d tensor or a tensor [b, n];
+        ``mode`` defaults to the one the index was built for.  Differentiable like ``splat``."""
+        mode = (_hip.SPLAT_POLARITY if self.polarity else _hip.SPLAT_BILINEAR) if mode is None else int(mode)
+        if mode not in (_hip.SPLAT_BILINEAR, _hip.SPLAT_COUNT, _hip.SPLAT_POLARITY) or (mode == _hip.SPLAT_POLARITY) != self.polarity:
+            raise ValueError(f"SplatIndex.vote: mode {mode} does not go with an index built with polarity={self.polarity}")
+        ev = self.events
+        args = (mode, self.eps, self.h, self.w, self.pad[0], self.pad[1], self.workspace)
+        if isinstance(weight, torch.Tensor) and weight.dim() > 0:
+            return _SplatOrdered.apply(ev, weight.reshape(ev.shape[0], ev.shape[1]), 1.0, *args)
+        if isinstance(weight, torch.Tensor):  # 0-d tensor weight: differentiable by scaling the unit-weight image, as in splat
+            return _SplatOrdered.apply(ev, None, 1.0, *args) * weight.to(ev.device)
+        return _SplatOrdered.apply(ev, None, float(weight), *args)
+
+
+SPLAT_ROUTES = ("atomic", "ordered")
+
+
 def splat(events: torch.Tensor, image_size: Tuple[int, int], pad: Tuple[int, int] = (0, 0),
-          weight=1.0, mode: int = _hip.SPLAT_BILINEAR, eps: float = 1e-6) -> torch.Tensor:
+          weight=1.0, mode: int = _hip.SPLAT_BILINEAR, eps: float = 1e-6, route: str = "atomic") -> torch.Tensor:
     """events [b, n, 4] -> image [b, h, w] ([b, 2, h, w] for polarity); ``image_size`` is the
-    PADDED size.  src/event_image_converter.py:407-620."""
+    PADDED size.  src/event_image_converter.py:407-620.  ``route``: "atomic" (float atomics on the image, the default) or
+    "ordered" (a ``SplatIndex`` built and voted once: bit-identical repeats)."""
+    if route not in SPLAT_ROUTES:
+        raise ValueError(f"splat: route must be one of {SPLAT_ROUTES}, got {route!r}")
     if events.dim() != 3 or events.shape[-1] != 4:
         raise ValueError(f"splat expects events [b,n,4], got {tuple(events.shape)}")
+    if route == "ordered":
+        return SplatIndex.build(events, image_size, pad, eps, polarity=int(mode) == _hip.SPLAT_POLARITY).vote(weight, int(mode))
     h, w = int(image_size[0]), int(image_size[1])
     if isinstance(weight, torch.Tensor) and weight.dim() > 0:
         wt, ws = weight.reshape(events.shape[0], events.shape[1]), 1.0

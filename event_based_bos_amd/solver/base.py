@@ -45,8 +45,9 @@ class SolverBase(object):
         self.sequential_video_list: list = []
         self.evaluation_text_list: list = []
         self.pad = int(self.slv_config.get("outer_padding", 0))
-        self.orig_imager = event_image_converter.EventImageConverter(self.orig_image_shape, outer_padding=self.pad)
-        self.crop_imager = event_image_converter.EventImageConverter(self.crop_image_shape, outer_padding=self.pad)
+        self.vote = str((self.slv_config.get("iwe") or {}).get("vote", "atomic"))   # iwe: {vote: ordered}: bit-identical repeats
+        self.orig_imager = event_image_converter.EventImageConverter(self.orig_image_shape, outer_padding=self.pad, vote=self.vote)
+        self.crop_imager = event_image_converter.EventImageConverter(self.crop_image_shape, outer_padding=self.pad, vote=self.vote)
         self.orig_warper = warp.Warp(self.orig_image_shape, normalize_t=True, calib_param=calibration_parameter)
         self.crop_warper = warp.Warp(self.crop_image_shape, normalize_t=True, calib_param=calibration_parameter)
         self.warp_direction = self.slv_config.get("warp_direction", "first")
@@ -55,7 +56,7 @@ class SolverBase(object):
         self.filter_set = self._filter_from_config(self.orig_image_shape, self.slv_config)
         self.previous_best = None
         self.iwe_visualize_max_scale = self.slv_config.get("max_scale", 50)
-        self._viz_imager = event_image_converter.EventImageConverter(self.orig_image_shape)   # (the reference's orig_imager: no padding)
+        self._viz_imager = event_image_converter.EventImageConverter(self.orig_image_shape, vote=self.vote)   # (the reference's orig_imager: no padding)
 
     @staticmethod
     def _filter_from_config(image_shape, cfg: dict) -> Optional[event_filters.EventFilter]:

@@ -160,7 +160,7 @@ class EkltSweepMixin(GenerativeMixin):
         self._gml_velocity = False
         self._gml_n_dim = len(parameter_keys(gml))
         self._gml_frame = None
-        self._gml_imager = EventImageConverter((H, W))
+        self._gml_imager = EventImageConverter((H, W), vote=str((cfg.get("iwe") or {}).get("vote", "atomic")))
         self.cost_func = _History(cost.keys())
         self.iter_cnt = 0
         self.histories = []

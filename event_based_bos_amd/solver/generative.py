@@ -140,7 +140,7 @@ class GenerativeMixin(object):
         roi = (max(0, min(xmin, H)), max(0, min(xmax, H)), max(0, min(ymin, W)), max(0, min(ymax, W)))
         self._gml_roi = roi
         self._gml_frame = None
-        self._gml_imager = EventImageConverter((H, W))
+        self._gml_imager = EventImageConverter((H, W), vote=str((cfg.get("iwe") or {}).get("vote", "atomic")))
         self.cost_func = _History(cost.keys())
         self.params_per_scale = {}
         self.iter_cnt = 0

@@ -167,6 +167,48 @@ int ebos_splat_bwd_f64(const double* events, const double* weight, double weight
                        double* d_events, double* d_weight, ebos_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The ordered route of the same accumulation (csrc/splat_ordered.hip): a sorted index of the events by destination
+ * cell, then one owner per pixel that sums its addends in a fixed order and writes the pixel with a plain store.  No
+ * atomics on the image and no float atomics anywhere: the image is a pure function of the inputs, bit for bit -- call
+ * after call, and for a batch row alone or inside any batch.  events, weight, mode, eps, sizes and padding mean what they
+ * mean for ebos_splat_*; every tap is computed exactly as there.  ebos_splat_* stays the default route.
+ *
+ * Index.  Event i = row * n + e.  Its top-left tap (R, C) lies in the extended grid R in [-1, h-1], C in [-1, w-1], or
+ * the event is dropped (none of its four taps is inside the image, or a coordinate is NaN, +-Inf or beyond 2^30).
+ *     key = ((row * planes + plane) * (h + 1) + R + 1) * (w + 1) + C + 1        keys = b * planes * (h + 1) * (w + 1)
+ * with planes = 2, plane = (p > 0 ? 0 : 1) for EBOS_SPLAT_POLARITY and planes = 1, plane = 0 otherwise.  The workspace
+ * (ebos_splat_index_bytes bytes; 0 for sizes that are refused) starts with
+ *     int32 offsets[keys + 1]     at byte 0
+ *     int32 indices[b * n]        at the next multiple of 256 bytes
+ * indices[offsets[k] .. offsets[k+1]) are the events of key k, ascending; the dropped events stand behind
+ * offsets[keys].  The rest of the workspace is scratch of the build (a stable radix sort; the grouping does not depend on
+ * the order in which anything executes).  An index serves any number of ebos_splat_ordered_* calls on the same events,
+ * mode, eps, sizes and padding, with any weights.  b <= 65535; b * n and keys must stay below 2^31 (EBOS_ERR_INVALID_ARG).
+ *
+ * Summation order.  The addend list of pixel (row, plane, r, c) is the events of the cells (r-1, c-1), (r-1, c),
+ * (r, c-1), (r, c) in this order, each cell in ascending event index; an event's addend is its tap on (r, c),
+ *     fr fc wv,   fr (1-fc) wv,   (1-fr) fc wv,   (1-fr)(1-fc) wv          for the four cells,
+ * evaluated in the element type as (x * y) * wv, every operation rounded on its own; wv = weight[i] or weight_scalar;
+ * EBOS_SPLAT_COUNT adds 1 per addend.
+ *   - a list of at most 256 addends:  s = +0, then s = s + addend in list order;
+ *   - a longer list:  p[l] = +0, then p[l] = p[l] + addend[j] for j = l, l + 64, l + 128, ... ascending, l = 0 .. 63;
+ *     then for off = 32, 16, 8, 4, 2, 1:  p[l] = p[l] + p[l + off] for l < off;  s = p[0].
+ * Every pixel of image [b, h, w] ([b, 2, h, w] for polarity) is overwritten (+0 without addends): the caller need not
+ * zero it.  The backward of this route is ebos_splat_bwd_*.
+ * ---------------------------------------------------------------------------------------- */
+size_t ebos_splat_index_bytes(int64_t b, int64_t n, int h, int w, int mode);
+int ebos_splat_index_build_f32(const float* events, int mode, double eps, int64_t b, int64_t n, int h, int w,
+                               int pad_h, int pad_w, void* index, size_t index_bytes, ebos_stream_t stream);
+int ebos_splat_index_build_f64(const double* events, int mode, double eps, int64_t b, int64_t n, int h, int w,
+                               int pad_h, int pad_w, void* index, size_t index_bytes, ebos_stream_t stream);
+int ebos_splat_ordered_f32(const float* events, const float* weight, double weight_scalar, int mode, double eps,
+                           int64_t b, int64_t n, int h, int w, int pad_h, int pad_w, const void* index,
+                           size_t index_bytes, float* image, ebos_stream_t stream);
+int ebos_splat_ordered_f64(const double* events, const double* weight, double weight_scalar, int mode, double eps,
+                           int64_t b, int64_t n, int h, int w, int pad_h, int pad_w, const void* index,
+                           size_t index_bytes, double* image, ebos_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Event plan: the device-resident, iteration-invariant form of one event window used by the
  * fused hot path.  (x, y, t, p) of every event are constant across solver iterations and flow
  * hypotheses: only the motion changes, so this is built once per window.
