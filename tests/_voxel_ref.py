@@ -5,13 +5,28 @@ arrays the reference itself produced, exactly: both add the votes of a voxel seq
 
 Besides the grid, both functions return per voxel the number of contributions ``k`` and the sum of their magnitudes ``sabs``
 (float64): two summation orders of the same k addends differ by at most ``2 k u sabs`` (``error_bound``; every partial sum is
-bounded by sabs and each of the k - 1 additions of either order rounds once, relative u).
+bounded by sabs and each of the k - 1 additions of either order rounds once, relative u).  ``within_bound`` is that check, shared
+by the GPU tests.
 """
+import math
+
 import numpy as np
 
 
 def error_bound(k, sabs, u=2.0 ** -53):
     return 2.0 * k * u * sabs
+
+
+def within_bound(got, ref, u=2.0 ** -53):
+    """``got`` (a numpy array or a torch tensor on any device) against ``ref`` = (grid, k, sabs) of a restatement below."""
+    want, k, sabs = ref
+    got = got.detach().cpu().numpy() if hasattr(got, "detach") else got
+    assert got.shape == want.shape and got.dtype == want.dtype
+    err, bound = np.abs(got.astype(np.float64) - want.astype(np.float64)), error_bound(k, sabs, u)
+    worst = (err / np.where(bound > 0, bound, 1.0)).max()
+    print(f"max |gpu - ref| {err.max():.3e}, worst share of the bound {worst:.3f}, {int((k == 0).sum())} voxels without a vote")
+    assert (got[k == 0] == 0).all()
+    assert (err <= bound).all(), (float(err.max()), int((err > bound).sum()))
 
 
 def create_event_voxel(x, y, pol, time, voxel_shape, normalize=False):
@@ -48,6 +63,33 @@ def normalize_voxel(grid):
             std = grid[mask].std(ddof=1) if mask.sum() > 1 else np.nan
         grid[mask] = (grid[mask] - mean) / std if std > 0 else grid[mask] - mean
     return grid
+
+
+def normalize_exact(grid):
+    """``normalize_voxel`` with the moments summed exactly: the mean from ``math.fsum`` (one rounding, and one more in the
+    division), m2 as ``math.fsum`` of the squared deviations from that mean, std = sqrt(m2 / (k - 1)), then the reference's map.
+    What the normaliser is held to where the order of a plain sum would matter: 10^5 voxels, or a mean far from zero."""
+    grid = np.array(grid, dtype=np.float64)
+    mask = grid != 0
+    v = grid[mask]
+    if v.size == 0:
+        return grid
+    mean = math.fsum(v) / v.size
+    d = v - mean
+    std = math.sqrt(math.fsum(d * d) / (v.size - 1)) if v.size > 1 else math.nan
+    grid[mask] = d / std if std > 0 else d
+    return grid
+
+
+def normalize_bound(grid, u=2.0 ** -53):
+    """The per-voxel bar of the GPU normaliser against ``normalize_exact``: 64 u max|v| / std.  A lane's Welford pass folds at most
+    6 voxels and 8 + 8 Chan merges follow (a workgroup's tree, then the tree over the partials); each of those ~22 steps rounds
+    once, relative u, a quantity no larger than max|v|; the subtraction and the division of the map add two; doubled, 64.  The
+    error of the mean is what this measures: it shifts every voxel by (error / std)."""
+    v = np.asarray(grid, dtype=np.float64)
+    v = v[v != 0]
+    d = v - math.fsum(v) / v.size
+    return 64.0 * u * np.abs(v).max() / math.sqrt(math.fsum(d * d) / (v.size - 1))
 
 
 def generate_discretized_event_volume(events, vol_size):

@@ -4,8 +4,9 @@ tests/test_voxel.py pins to the reference's own arrays.
 The kernels compute every addend of a voxel as the reference does (fp contract off, the reference's order of operations), so the
 addends are bit-equal and only their order of summation differs: per voxel |gpu - ref| <= 2 k u sum|w| (k addends, u = 2^-53, or
 2^-24 for the float32 volume), and a voxel nothing votes into is exactly 0.  All cases are a 12 x 16 sensor with about 2000 events
-(eight workgroups of events, four partials in the normaliser); nothing here depends on a larger size -- the indices are 64-bit
-throughout, and a grid beyond 2^31 voxels would need 16 GiB.
+(eight workgroups of events, four partials in the normaliser).  The paths that only run at real sizes -- the stride loops of the
+normaliser and of the volume's range kernel, the ROI scans beyond their first step, one long window among short ones -- are in
+tests/test_gpu_voxel_sizes.py.  (The indices are 64-bit throughout; a grid beyond 2^31 voxels would need 16 GiB.)
 """
 import os
 import sys
@@ -39,15 +40,7 @@ def ref_case(c):
     return _cache[c]
 
 
-def within_bound(got, ref, u=2.0 ** -53):
-    want, k, sabs = ref
-    got = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else got
-    assert got.shape == want.shape and got.dtype == want.dtype
-    err, bound = np.abs(got.astype(np.float64) - want.astype(np.float64)), R.error_bound(k, sabs, u)
-    worst = (err / np.where(bound > 0, bound, 1.0)).max()
-    print(f"max |gpu - ref| {err.max():.3e}, worst share of the bound {worst:.3f}, {int((k == 0).sum())} voxels without a vote")
-    assert (got[k == 0] == 0).all()
-    assert (err <= bound).all(), (float(err.max()), int((err > bound).sum()))
+within_bound = R.within_bound
 
 
 def recording():
