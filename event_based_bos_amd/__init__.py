@@ -33,7 +33,9 @@ tub-rip/event_based_bos:
     photometric          does a flow explain its two frames?  The reference's warp_image_forward / warp_image_torch and SSIM, and a
                          fused per-item score (L1, RMSE, SSIM of the warped frame against the next, and of the un-warped baseline)
     evt3                 the camera's own EVT 3.0 .raw recordings: header, GPU decode of the word stream (events and trigger edges),
-                         host encoder; RawEventStore("cd_events.raw") goes through it
+                         host encoder
+    recordings           every Prophesee format: EVT 2.0, EVT 2.1, EVT 3.0 .raw and .dat files, decoded on the GPU (decode_recording),
+                         host encoders and file writers; RawEventStore("cd_events.raw") / RawEventStore("x_td.dat") go through it
     calibration          lens calibration: CameraCalibration (K, D), its rectification map, rectified sub-pixel events from raw
                          columns, the reference's undistort_events; frame_warp.undistort_image rectifies (and warps) frames in one resample
 
@@ -53,6 +55,6 @@ from .evaluation import (EvalStep, EvaluationResult, PreparedWindows, RecordingE
 from .event_voxel import create_event_voxel, event_voxel_batch, generate_discretized_event_volume  # noqa: F401
 from .flow_voxel import flow_voxel_batch  # noqa: F401
 from .ops import time_bins, warp_voxel  # noqa: F401
-from . import calibration, costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, photometric, poisson, solver, types, utils, visualizer  # noqa: F401
+from . import calibration, costs, data_loader, evaluation, event_filters, event_voxel, evt3, flow_error, flow_voxel, frame_flow, frame_warp, fusion, ops, photometric, poisson, recordings, solver, types, utils, visualizer  # noqa: F401
 
 __version__ = "0.1.0"

@@ -350,6 +350,12 @@ SIGNATURES = {
     "ebos_evt3_scratch_bytes": (_Z, [_L]),
     "ebos_evt3_scan": (_I, [_P, _L, _P, _P, _P, _P, _Z, _P]),
     "ebos_evt3_emit": (_I, [_P, _L, _P, _Z, _L, _L, _L, _L] + [_P] * 8),
+    "ebos_evt2_chunk_words": (_I, [_I]),
+    "ebos_evt2_scratch_bytes": (_Z, [_L, _I]),
+    "ebos_evt2_scan": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "ebos_evt2_emit": (_I, [_P, _L, _I, _I, _P, _Z, _L, _L, _L, _L] + [_P] * 8),
+    "ebos_evt21_route": (_I, [_I]),
+    "ebos_dat_decode": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _P]),
     "ebos_warp_image_forward_f32": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ebos_warp_image_forward_f64": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ebos_ssim_map_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
@@ -387,6 +393,11 @@ class EventSource(C.Structure):
 class Evt3State(C.Structure):
     """``ebos_evt3_state`` of include/ebos_hip.h (same field order): the EVT 3.0 decoder's state between two words."""
     _fields_ = [(k, C.c_int32) for k in ("has_th", "th", "tl", "y", "bx", "pol")] + [("loops", _L)]
+
+
+class Evt2State(C.Structure):
+    """``ebos_evt2_state`` of include/ebos_hip.h (same field order): the EVT 2.0 / 2.1 decoder's state between two words."""
+    _fields_ = [("has_th", C.c_int32), ("th", C.c_int32), ("loops", _L)]
 
 
 class VizField(C.Structure):

@@ -30,7 +30,7 @@ SOURCES = ["errors.cpp", "warp_kernels.hip", "splat_kernels.hip", "event_plan.hi
            "cmax_resident_45x80_2dof.hip", "cmax_resident_32x32_2dof.hip", "cmax_resident_32x64_2dof.hip",
            "event_filters.hip", "flow_error.hip", "poisson.hip", "gml.hip", "farneback.hip", "frame_warp.hip", "window_ingest.hip", "visualize.hip",
            "event_voxel.hip", "flow_voxel.hip", "flow_voxel_grad.hip", "warp_voxel.hip", "warp_voxel_multiref.hip", "cmax_voxel.hip",
-           "plan_time_aware.hip", "iwe_multiref.hip", "iwe_multiref_slab.hip", "cmax_multiref.hip", "iwe_hvp.hip", "evt3.hip", "photometric.hip",
+           "plan_time_aware.hip", "iwe_multiref.hip", "iwe_multiref_slab.hip", "cmax_multiref.hip", "iwe_hvp.hip", "evt3.hip", "evt2.hip", "photometric.hip",
            "eklt_sweep.hip", "rectify.hip", "splat_ordered.hip"]
 
 # -munsafe-fp-atomics: hardware global_atomic_add_f32/f64 and ds_add_f32 instead of CAS loops.

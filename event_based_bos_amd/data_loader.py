@@ -5,8 +5,8 @@ The reference reads CCS recordings from HDF5 (``raw_events/{x: int16, y: int16, 
 src/data_loader/ccs.py:57-66) and hands every window to the solver as a float64 ``[n, 4]`` array
 ``(row = y, col = x, t / 1e6, p)`` (:289-297).  ``h5py`` is not part of this image, so the store keeps the same
 four columns in an uncompressed ``.npz`` (keys ``raw_events_x/y/t/p``; an ``.hdf5`` path is read directly where ``h5py`` exists,
-``_hdf5.py``; the camera's own EVT 3.0 ``cd_events.raw``, ccs.py:171, is decoded on the GPU, ``evt3.py``, and brings its trigger
-edges along as ``store.triggers``) -- and, more to the point, it can hand a
+``_hdf5.py``; the camera's own ``cd_events.raw``, ccs.py:171 -- EVT 2.0, 2.1 or 3.0 -- and ``.dat`` files are decoded on the GPU,
+``recordings.py``, and a ``.raw`` file brings its trigger edges along as ``store.triggers``) -- and, more to the point, it can hand a
 window to the GPU *as raw columns* (9 B/event instead of 32 B/event over PCIe), where ``EventPlan.build_raw``
 expands it with the same fp64 time arithmetic.
 
@@ -66,15 +66,16 @@ class RawEventStore(object):
     NAME = "RAW_COLUMNS"
     TICKS_PER_SECOND = 1e6  # microsecond timestamps, src/data_loader/ccs.py:295
 
-    def __init__(self, source: Union[str, Dict[str, np.ndarray]], sensor_size: Optional[Tuple[int, int]] = None, calibration=None):
+    def __init__(self, source: Union[str, Dict[str, np.ndarray]], sensor_size: Optional[Tuple[int, int]] = None, calibration=None,
+                 half_swapped: Optional[bool] = None):
         self.calibration = _as_calibration(calibration, sensor_size)   # None: no calibration, as the reference's loaders answer
-        self.header = None            # a .raw source: the parsed header (evt3.RawHeader)
-        self.triggers = None          # a .raw source: int64 [n, 3] = (t, id, value), the "old" layout of read_trigger_timestamps
-        self.dropped_outside = 0      # a .raw source: events outside the header's geometry, removed
+        self.header = None            # a .raw / .dat source: the parsed header (evt3.RawHeader)
+        self.triggers = None          # a .raw / .dat source: int64 [n, 3] = (t, id, value), the "old" layout of read_trigger_timestamps
+        self.dropped_outside = 0      # a .raw / .dat source: events outside the header's geometry, removed
         if isinstance(source, dict):
             data = source
-        elif str(source).lower().endswith(".raw"):   # the camera's own EVT 3.0 recording, decoded on the GPU (evt3.py)
-            data = self._read_raw(str(source), sensor_size)
+        elif str(source).lower().endswith((".raw", ".dat")):   # the camera's own recording, decoded on the GPU (recordings.py)
+            data = self._read_raw(str(source), sensor_size, half_swapped)
         elif str(source).lower().endswith((".hdf5", ".h5")):   # the reference's own recordings, read as its h5py_loader does (needs h5py)
             from ._hdf5 import read_raw_events
 
@@ -96,13 +97,14 @@ class RawEventStore(object):
         self._time_cache = None
         self._pinned = None
 
-    def _read_raw(self, path: str, sensor_size: Optional[Tuple[int, int]]) -> Dict[str, np.ndarray]:
-        """The columns of a Prophesee EVT 3.0 ``.raw`` file (``evt3.decode_raw_file``: decoded on the GPU), narrowed as ``save``
-        narrows them; the trigger edges of the same pass go to ``self.triggers``.  Events outside the geometry are removed here, on
-        the host: the downstream kernels index by pixel."""
-        from .evt3 import decode_raw_file
+    def _read_raw(self, path: str, sensor_size: Optional[Tuple[int, int]], half_swapped: Optional[bool] = None) -> Dict[str, np.ndarray]:
+        """The columns of a Prophesee ``.raw`` (EVT 2.0, 2.1, 3.0) or ``.dat`` file (``recordings.decode_recording``: decoded on the
+        GPU), narrowed as ``save`` narrows them; the trigger edges of the same pass go to ``self.triggers`` (none in a DAT file).
+        ``half_swapped``: the word order of an EVT 2.1 file, None = what its header says.  Events outside the geometry are removed
+        here, on the host: the downstream kernels index by pixel."""
+        from .recordings import decode_recording
 
-        x, y, t, p, self.triggers, self.header = decode_raw_file(path, sensor_size=sensor_size)
+        x, y, t, p, self.triggers, self.header = decode_recording(path, sensor_size=sensor_size, half_swapped=half_swapped)
         outside = (x.view(np.uint16) >= self.header.width) | (y.view(np.uint16) >= self.header.height)
         self.dropped_outside = int(outside.sum())
         if self.dropped_outside:

@@ -2156,6 +2156,57 @@ int ebos_evt3_emit(const uint16_t* words, int64_t n_words, const void* scratch, 
                    int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y, int64_t* t,
                    uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream);
 
+/* ---- Prophesee EVT 2.0, EVT 2.1 and DAT recordings decoded on the device (csrc/evt2.hip; the state algebra: csrc/evt2_core.h) ----
+ * The other formats Prophesee cameras and tools write.  The rules are written from the format documentation, not checked against
+ * OpenEB.
+ * EVT 2.0: little-endian uint32 words, type = w >> 28:
+ *   0x8 EVT_TIME_HIGH  v = w & 0x0FFFFFFF; if the previous TIME_HIGH's value prev > v and prev - v >= 2^28 - 11: loops += 1; then th = v
+ *   0x0 CD_OFF, 0x1 CD_ON  one event: p = type, ts = (w >> 22) & 0x3F, x = (w >> 11) & 0x7FF, y = w & 0x7FF
+ *   0xA EXT_TRIGGER    one trigger record: ts = (w >> 22) & 0x3F, id = (w >> 8) & 0x1F, value = w & 1
+ *   every other type is ignored (0xE OTHERS and 0xF CONTINUED included)
+ * EVT 2.1: little-endian uint64 words, type = w >> 60:
+ *   0x8 EVT_TIME_HIGH  v = (w >> 32) & 0x0FFFFFFF, the same loop rule
+ *   0x0 EVT_NEG, 0x1 EVT_POS  p = type, ts = (w >> 54) & 0x3F, bx = (w >> 43) & 0x7FF, y = (w >> 32) & 0x7FF, valid = w & 0xFFFFFFFF:
+ *                      an event at x = bx + b for every set bit b of valid, ascending (x is the int16 bit pattern: bx + 31 reaches 2078)
+ *   0xA EXT_TRIGGER    ts = (w >> 54) & 0x3F, id = (w >> 40) & 0x1F, value = (w >> 32) & 1
+ *   every other type is ignored
+ *   half_swapped != 0: the legacy order, the two 32-bit halves of every word exchanged in the file; undone as the words are loaded.
+ * In both, an event or trigger carries t = (loops << 34) | (th << 6) | ts microseconds; the state starts all zero and every word
+ * before the first TIME_HIGH is ignored altogether.  Integer arithmetic only, no atomic in the data path: stream order, the same
+ * bytes every run.
+ *
+ * The protocol is that of ebos_evt3_scan / ebos_evt3_emit above, with word_bytes = 4 (EVT 2.0) or 8 (EVT 2.1): n_words counts
+ * words of that size (at most 2^30), a slab is cut into chunks of ebos_evt2_chunk_words(word_bytes) words (0: bad word_bytes),
+ * ebos_evt2_scan leaves every chunk's record, incoming state and exclusive offsets in `scratch`
+ * (ebos_evt2_scratch_bytes(n_words, word_bytes) bytes; 0: bad arguments), totals[0 .. 1] = the slab's events and triggers (64-bit)
+ * and *carry_out (carry_in NULL = the start state; carry_out may be carry_in), and ebos_evt2_emit decodes the SAME words again into
+ * elements [0, n_events) and [0, n_triggers) of the seven columns of ebos_evt3_emit.  Refused before any HIP call
+ * (EBOS_ERR_INVALID_ARG): a word_bytes other than 4 or 8, NULL pointers (words may be NULL when n_words is 0; an output when its
+ * capacity is 0), words not aligned to word_bytes, negative sizes, n_words beyond 2^30, a capacity below the totals; a short
+ * scratch: EBOS_ERR_SCRATCH.  No store lands at or beyond a capacity.
+ * ebos_evt21_route: how the EVT 2.1 emit pass turns vector words into events -- 0: the build's choice, 1: every lane walks the bits
+ * of its own words into the LDS stage, 2: every output slot searches its word in the per-word offsets and takes the rank-th set
+ * bit of its mask.  The same bytes either way.  Returns the previous value (-1: a bad route, nothing changed). */
+typedef struct ebos_evt2_state {
+  int32_t has_th; /* a TIME_HIGH has been seen */
+  int32_t th;
+  int64_t loops;
+} ebos_evt2_state;
+int ebos_evt2_chunk_words(int word_bytes);
+size_t ebos_evt2_scratch_bytes(int64_t n_words, int word_bytes);
+int ebos_evt2_scan(const void* words, int64_t n_words, int word_bytes /* 4 | 8 */, int half_swapped, const ebos_evt2_state* carry_in,
+                   ebos_evt2_state* carry_out, int64_t* totals, void* scratch, size_t scratch_bytes, ebos_stream_t stream);
+int ebos_evt2_emit(const void* words, int64_t n_words, int word_bytes, int half_swapped, const void* scratch, size_t scratch_bytes,
+                   int64_t n_events, int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y,
+                   int64_t* t, uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream);
+int ebos_evt21_route(int route);
+/* DAT: n_records records of two little-endian uint32 (ts, data), 8-byte aligned.  version 2: x = data & 0x3FFF, y = (data >> 14) &
+ * 0x3FFF, p = (data >> 28) & 1; version 1: x = data & 0x1FF, y = (data >> 9) & 0xFF, p = (data >> 17) & 1; t = ts as it stands (no
+ * wrap is counted).  Writes elements [0, n_records) of x, y int16, t int64, p uint8 [capacity]; one launch.  Refused before any HIP
+ * call: n_records outside [0, 2^30], a version other than 1 or 2, capacity below n_records, NULL or misaligned pointers. */
+int ebos_dat_decode(const void* records, int64_t n_records, int version, int16_t* x, int16_t* y, int64_t* t, uint8_t* p, int64_t capacity,
+                    ebos_stream_t stream);
+
 /* ---- photometric check of a flow: frame warp, SSIM and the fused per-item score (csrc/photometric.hip) ----
  * Element type codes of images, shifts and flows. */
 #define EBOS_IMAGE_U8 0

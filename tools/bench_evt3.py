@@ -32,8 +32,8 @@ COPY_RATE = 6.29e12   # B/s, the measured device-to-device copy rate
 H, W = 720, 1280
 
 
-def block(n_events: int, seed: int = 0):
-    """One repetition: about ``n_events`` events in bursts over [0, 2^24) us, a trigger edge every 10 ms."""
+def block_columns(n_events: int, seed: int = 0):
+    """One repetition as columns: about ``n_events`` events (x, y, t, p) in bursts over [0, 2^24) us, and a trigger edge every 10 ms."""
     rng = np.random.default_rng(seed)
     n_bursts = max(n_events * 2 // 13, 2)
     lens = rng.integers(1, 13, size=n_bursts)
@@ -50,7 +50,13 @@ def block(n_events: int, seed: int = 0):
     stamps = np.arange(5000, 1 << 24, 10_000)
     triggers = np.stack([np.repeat(stamps, 2) + np.tile([0, 100], len(stamps)), np.zeros(2 * len(stamps), np.int64),
                          np.tile([1, 0], len(stamps))], 1)
-    return evt3.encode_evt3(x, y, bt[owner], p, triggers), len(owner), len(triggers)
+    return x, y, bt[owner], p, triggers
+
+
+def block(n_events: int, seed: int = 0):
+    """One repetition as EVT 3.0 words, its events and its trigger records."""
+    x, y, t, p, triggers = block_columns(n_events, seed)
+    return evt3.encode_evt3(x, y, t, p, triggers), len(t), len(triggers)
 
 
 def device_times(words: np.ndarray, reps: int, slab_words: int):
