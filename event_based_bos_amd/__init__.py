@@ -36,6 +36,7 @@ tub-rip/event_based_bos:
                          host encoder
     recordings           every Prophesee format: EVT 2.0, EVT 2.1, EVT 3.0 .raw and .dat files, decoded on the GPU (decode_recording),
                          host encoders and file writers; RawEventStore("cd_events.raw") / RawEventStore("x_td.dat") go through it
+                         (both stand on _word_stream: the .raw header, one slab decode, one file loop)
     calibration          lens calibration: CameraCalibration (K, D), its rectification map, rectified sub-pixel events from raw
                          columns, the reference's undistort_events; frame_warp.undistort_image rectifies (and warps) frames in one resample
 

@@ -354,7 +354,6 @@ SIGNATURES = {
     "ebos_evt2_scratch_bytes": (_Z, [_L, _I]),
     "ebos_evt2_scan": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ebos_evt2_emit": (_I, [_P, _L, _I, _I, _P, _Z, _L, _L, _L, _L] + [_P] * 8),
-    "ebos_evt21_route": (_I, [_I]),
     "ebos_dat_decode": (_I, [_P, _L, _I, _P, _P, _P, _P, _L, _P]),
     "ebos_warp_image_forward_f32": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ebos_warp_image_forward_f64": (_I, [_P, _I, _L, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -1,5 +1,6 @@
 // evt2.hip -- Prophesee EVT 2.0 and EVT 2.1 word streams and DAT records decoded on the device.  The formats and the entry
-// points: include/ebos_hip.h; the state algebra: evt2_core.h.
+// points: include/ebos_hip.h; the state algebra: evt2_core.h; the scans, the stage and the entries' argument checks, shared with
+// evt3.hip: word_scan.h; the body of the scan pass, shared as text: word_scan_body.h.
 //
 // EVT 2.0 / 2.1 carry everything but the time base in the word that emits; the time base (has_th, th, loops) is set by TIME_HIGH
 // words.  What a stretch of words does to it, and how much the stretch emits, is a small record that composes (evt2::Xf), so the
@@ -11,11 +12,13 @@
 //               slots come from prefix counts over the wave plus the wave offsets;
 //                 EVT 2.0  a compaction, 0 or 1 event a word: ballots; the chunk's events are staged in LDS and stored to their final
 //                          places by the whole workgroup, consecutive lanes on consecutive elements;
-//                 EVT 2.1  an expansion, 0 to 32 events a word: two routes (ebos_evt21_route), see evt21_emit_kernel.
+//                 EVT 2.1  an expansion, 0 to 32 events a word: a lane walks the set bits of its own words into the stage, see
+//                          evt21_emit_kernel.
 // Integer arithmetic only, no atomics: stream order, the same bytes every run.  Every store is guarded by the caller's totals.
 // DAT is fixed records: one streaming kernel.
 #include "common.h"
 #include "evt2_core.h"
+#include "word_scan.h"
 
 namespace ebos {
 namespace {
@@ -24,12 +27,8 @@ using evt2::Time;
 using evt2::Word;
 using evt2::Xf;
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kScanBlock = 1024;  // the one workgroup of the scan pass
-constexpr int kStage = 2048;      // events the emit pass stages in LDS at a time (13 B each)
-constexpr int64_t kMaxWords = (int64_t)1 << 30;
-constexpr int kRouteAuto = 0, kRouteWalk = 1, kRouteSearch = 2;
+constexpr int kStage = 2048;  // events the emit pass stages in LDS at a time (13 B each)
+using In = ChunkIn<ebos_evt2_state>;
 
 // words per thread: two 16-byte loads of consecutive words
 template <int kWordBytes>
@@ -54,12 +53,6 @@ constexpr int chunk_of() {
 }
 static_assert(chunk_of<4>() <= kStage, "an EVT 2.0 chunk's events fit one stage");
 
-struct ChunkIn {
-  ebos_evt2_state s;  // the state before the chunk's first word
-  long long ev, tr;   // events / triggers of the slab before the chunk
-};
-static_assert(sizeof(Xf) % 8 == 0 && sizeof(ChunkIn) % 8 == 0, "scratch arrays of 8-byte aligned records");
-
 // what a thread's words are to the workgroup scan of the EVT 2.1 emit pass: the time record and the raw event count
 struct Lane {
   Time t;
@@ -68,8 +61,6 @@ struct Lane {
 __device__ __forceinline__ Lane then(const Lane& u, const Lane& v) { return Lane{evt2::then(u.t, v.t), u.ev + v.ev}; }
 using evt2::then;
 
-template <typename T>
-__device__ __forceinline__ T identity_of();
 template <>
 __device__ __forceinline__ Time identity_of<Time>() {
   return evt2::time_identity();
@@ -95,51 +86,6 @@ __device__ __forceinline__ Xf exchange(const Xf& x, F f) {
 template <typename F>
 __device__ __forceinline__ Lane exchange(const Lane& x, F f) {
   return Lane{exchange(x.t, f), f(x.ev)};
-}
-template <typename T>
-__device__ __forceinline__ T shfl_up_rec(const T& x, int off) {
-  return exchange(x, [off](auto v) { return __shfl_up(v, off, kWave); });
-}
-template <typename T>
-__device__ __forceinline__ T shfl_rec(const T& x, int lane) {
-  return exchange(x, [lane](auto v) { return __shfl(v, lane, kWave); });
-}
-
-// inclusive scan of one record per lane over the wave, in lane order
-template <typename T>
-__device__ __forceinline__ T wave_scan_inclusive(const T& mine) {
-  const int lane = threadIdx.x & (kWave - 1);
-  T inc = mine;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const T o = shfl_up_rec(inc, off);
-    if (lane >= off) inc = then(o, inc);
-  }
-  return inc;
-}
-
-// Exclusive scan of one record per thread over the workgroup, in thread order; `total` = all of them.  waves: kWaves records of LDS.
-// One barrier: the caller may put values of its own next to the records before it and read them after it (`publish`, lane 63 only).
-template <typename T, typename Publish>
-__device__ __forceinline__ T block_scan_exclusive(const T& mine, T* waves, T& total, Publish publish) {
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const T inc = wave_scan_inclusive(mine);
-  if (lane == kWave - 1) {
-    waves[wid] = inc;
-    publish(wid);
-  }
-  __syncthreads();
-  T exc = shfl_up_rec(inc, 1);
-  if (lane == 0) exc = identity_of<T>();
-  T pre = identity_of<T>();
-  total = identity_of<T>();
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const T t = waves[w];
-    if (w < wid) pre = then(pre, t);
-    total = then(total, t);
-  }
-  return then(pre, exc);
 }
 
 // the thread's words: word k of thread t of chunk c is word c * kChunk + t * kPerThread + k; past the slab's end: an ignored type
@@ -192,71 +138,10 @@ __global__ __launch_bounds__(kBlock) void evt2_summary_kernel(const void* __rest
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-// One workgroup.  A wave owns a contiguous run of tiles of 64 chunks and walks it twice with one chunk per lane (consecutive lanes
-// read and write consecutive records): first for the run's total, then, with the totals of the waves before it, for every chunk's
-// incoming state and offsets.
 __global__ __launch_bounds__(kScanBlock) void evt2_scan_kernel(const Xf* __restrict__ sums, int64_t n_chunks, const ebos_evt2_state* carry_in,
-                                                               ebos_evt2_state* carry_out, int64_t* totals, ChunkIn* __restrict__ cin) {
-  constexpr int kScanWaves = kScanBlock / kWave;
-  __shared__ Xf waves[kScanWaves];
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  ebos_evt2_state s = ebos_evt2_state{0, 0, 0};
-  if (carry_in) s = *carry_in;
-  const int64_t tiles = (n_chunks + kWave - 1) / kWave, per = (tiles + kScanWaves - 1) / kScanWaves;
-  const int64_t first = (int64_t)wid * per;
-  const int64_t lo = first < tiles ? first : tiles, hi = lo + per < tiles ? lo + per : tiles;
-  Xf run = evt2::identity();
-  for (int64_t tile = lo; tile < hi; ++tile) {
-    const int64_t c = tile * kWave + lane;
-    const Xf inc = wave_scan_inclusive(c < n_chunks ? sums[c] : evt2::identity());
-    run = then(run, shfl_rec(inc, kWave - 1));
-  }
-  if (lane == 0) waves[wid] = run;
-  __syncthreads();  // (every thread has read *carry_in before one writes *carry_out)
-  Xf pre = evt2::identity();
-  for (int w = 0; w < wid; ++w) pre = then(pre, waves[w]);
-  long long ev = 0, tr = 0;
-  evt2::apply(s, pre, ev, tr);
-  for (int64_t tile = lo; tile < hi; ++tile) {
-    const int64_t c = tile * kWave + lane;
-    const Xf inc = wave_scan_inclusive(c < n_chunks ? sums[c] : evt2::identity());
-    Xf exc = shfl_up_rec(inc, 1);
-    if (lane == 0) exc = evt2::identity();
-    ChunkIn in;
-    in.s = s;
-    in.ev = ev;
-    in.tr = tr;
-    evt2::apply(in.s, exc, in.ev, in.tr);
-    if (c < n_chunks) cin[c] = in;
-    evt2::apply(s, shfl_rec(inc, kWave - 1), ev, tr);
-  }
-  if (threadIdx.x == kScanBlock - 1) {  // (the last wave's tiles are the slab's last ones, or none: s, ev, tr are the slab's)
-    *carry_out = s;
-    totals[0] = ev;
-    totals[1] = tr;
-  }
-}
-
-// The emit pass's stage.  A thread's events are consecutive in the output but few, so stores straight from the threads would touch
-// a cache line per lane: the chunk's events go through LDS instead, kStage at a time, and the workgroup copies a full stage out
-// with consecutive lanes on consecutive elements.
-struct Stage {
-  int64_t t[kStage];
-  int16_t x[kStage];
-  int16_t y[kStage];
-  uint8_t p[kStage];
-};
-__device__ __forceinline__ void store_stage(const Stage& stage, int count, long long first, long long n_events, int16_t* __restrict__ x,
-                                            int16_t* __restrict__ y, int64_t* __restrict__ t, uint8_t* __restrict__ p) {
-  for (int i = threadIdx.x; i < count; i += kBlock) {
-    const long long g = first + i;
-    if (g < n_events) {
-      x[g] = stage.x[i];
-      y[g] = stage.y[i];
-      t[g] = stage.t[i];
-      p[g] = stage.p[i];
-    }
-  }
+                                                               ebos_evt2_state* carry_out, int64_t* totals, In* __restrict__ cin) {
+  using State = ebos_evt2_state;
+#include "word_scan_body.h"
 }
 
 // Raw counts and offsets count every event and trigger word, also those before the stream's first TIME_HIGH.  Those are dropped --
@@ -264,7 +149,7 @@ __device__ __forceinline__ void store_stage(const Stage& stage, int count, long 
 struct Dropped {
   int ev, tr;
 };
-__device__ __forceinline__ Dropped dropped_of(const ChunkIn& in, const Xf& sum) {
+__device__ __forceinline__ Dropped dropped_of(const In& in, const Xf& sum) {
   return in.s.has_th ? Dropped{0, 0} : Dropped{(int)sum.ev_a, (int)sum.tr_a};
 }
 
@@ -283,14 +168,14 @@ __device__ __forceinline__ void ballot_counts(const bool (&flag)[P], int& before
 }
 
 __global__ __launch_bounds__(kBlock) void evt2_emit_kernel(const void* __restrict__ words, int64_t n_words, int aligned16,
-                                                           const Xf* __restrict__ sums, const ChunkIn* __restrict__ cin, long long n_events,
+                                                           const Xf* __restrict__ sums, const In* __restrict__ cin, long long n_events,
                                                            long long n_triggers, int16_t* __restrict__ x, int16_t* __restrict__ y,
                                                            int64_t* __restrict__ t, uint8_t* __restrict__ p, int64_t* __restrict__ trig_t,
                                                            uint8_t* __restrict__ trig_value, uint8_t* __restrict__ trig_id) {
   constexpr int P = Format<4>::kPerThread;
   __shared__ Time wave_time[kWaves];
   __shared__ int wave_ev[kWaves], wave_tr[kWaves];
-  __shared__ Stage stage;
+  __shared__ Stage<kStage> stage;
   uint32_t w[P];
   load_words<4>(words, n_words, aligned16, 0, w);
   // the time record of the thread's own words; its event and trigger words, counted over the wave by ballots
@@ -319,7 +204,7 @@ __global__ __launch_bounds__(kBlock) void evt2_emit_kernel(const void* __restric
       tr += wave_tr[v];
     }
   }
-  const ChunkIn in = cin[blockIdx.x];
+  const In in = cin[blockIdx.x];
   const Xf sum = sums[blockIdx.x];
   const Dropped drop = dropped_of(in, sum);
   const int n_ev = (int)(sum.ev_a + sum.ev_b) - drop.ev;  // the chunk's own event count (the same in every thread)
@@ -355,36 +240,17 @@ __global__ __launch_bounds__(kBlock) void evt2_emit_kernel(const void* __restric
   store_stage(stage, n_ev < kStage ? n_ev : kStage, in.ev, n_events, x, y, t, p);
 }
 
-// position of the r-th (from 0) set bit of m, which has more than r set bits
-__device__ __forceinline__ int select_bit(uint32_t m, int r) {
-  int pos = 0;
-#pragma unroll
-  for (int width = 16; width >= 1; width >>= 1) {
-    const int c = __popc(m & ((1u << width) - 1u));
-    if (r >= c) {
-      r -= c;
-      m >>= width;
-      pos += width;
-    }
-  }
-  return pos;
-}
-
 // EVT 2.1: a word fires 0 to 32 events, a chunk up to 32 kChunk.  Every thread knows the offset of each of its words' first event
-// (the workgroup scan of the raw counts) and the word's time.  Two routes from there:
-//   kRouteWalk    a lane walks the set bits of its own words into the LDS stage, kStage events a round (a word outside the round
-//                 is skipped whole), and the workgroup stores the stage;
-//   kRouteSearch  the words, their times and their offsets go to LDS once; every output slot finds its word by a binary search
-//                 in the offsets, takes the rank-th set bit of the word's mask and is stored straight from the thread: consecutive
-//                 lanes hold consecutive slots, and no round needs a barrier.
-template <int kRoute>
+// (the workgroup scan of the raw counts) and the word's time; from there a lane walks the set bits of its own words into the LDS
+// stage, kStage events a round (a word outside the round is skipped whole), and the workgroup stores the stage.  (A search of every
+// output slot for its word was measured against this walk and lost on both kinds of stream: DESIGN 4.36.)
 __global__ __launch_bounds__(kBlock) void evt21_emit_kernel(const void* __restrict__ words, int64_t n_words, int aligned16, int half_swapped,
-                                                            const Xf* __restrict__ sums, const ChunkIn* __restrict__ cin,
+                                                            const Xf* __restrict__ sums, const In* __restrict__ cin,
                                                             long long n_events, long long n_triggers, int16_t* __restrict__ x,
                                                             int16_t* __restrict__ y, int64_t* __restrict__ t, uint8_t* __restrict__ p,
                                                             int64_t* __restrict__ trig_t, uint8_t* __restrict__ trig_value,
                                                             uint8_t* __restrict__ trig_id) {
-  constexpr int P = Format<8>::kPerThread, kChunk = chunk_of<8>();
+  constexpr int P = Format<8>::kPerThread;
   __shared__ Lane wave_lane[kWaves];
   __shared__ int wave_tr[kWaves];
   uint64_t w[P];
@@ -409,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void evt21_emit_kernel(const void* __restri
   for (int v = 0; v < kWaves; ++v) {
     if (v < wid) tr += wave_tr[v];
   }
-  const ChunkIn in = cin[blockIdx.x];
+  const In in = cin[blockIdx.x];
   const Xf sum = sums[blockIdx.x];
   const Dropped drop = dropped_of(in, sum);
   const int n_ev = (int)(sum.ev_a + sum.ev_b) - drop.ev;  // at most 32 kChunk
@@ -438,65 +304,31 @@ __global__ __launch_bounds__(kBlock) void evt21_emit_kernel(const void* __restri
       ++tr;
     }
   }
-  if constexpr (kRoute == kRouteWalk) {
-    __shared__ Stage stage;
-    for (int lo = 0; lo < n_ev; lo += kStage) {
-#pragma unroll
-      for (int k = 0; k < P; ++k) {
-        if (count[k] == 0 || off[k] >= lo + kStage || off[k] + count[k] <= lo) continue;
-        const int16_t ey = (int16_t)((w[k] >> 32) & 0x7FFull);
-        const int bx = (int)((w[k] >> 43) & 0x7FFull);
-        const uint8_t ep = (uint8_t)(w[k] >> 60);
-        uint32_t m = (uint32_t)w[k];
-        int e = off[k] - lo;
-        while (m) {
-          const int b = __builtin_ctz(m);
-          m &= m - 1;
-          if ((unsigned)e < (unsigned)kStage) {
-            stage.x[e] = (int16_t)(bx + b);
-            stage.y[e] = ey;
-            stage.t[e] = time[k];
-            stage.p[e] = ep;
-          }
-          ++e;
-        }
-      }
-      __syncthreads();
-      store_stage(stage, n_ev - lo < kStage ? n_ev - lo : kStage, in.ev + lo, n_events, x, y, t, p);
-      __syncthreads();
-    }
-  } else {
-    __shared__ int word_off[kChunk + 1];
-    __shared__ uint64_t word_bits[kChunk];
-    __shared__ int64_t word_time[kChunk];
+  __shared__ Stage<kStage> stage;
+  for (int lo = 0; lo < n_ev; lo += kStage) {
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-      const int i = threadIdx.x * P + k;
-      // (a word that fires nothing keeps its offset: the search never lands on it)
-      word_off[i] = off[k] < 0 ? 0 : off[k];
-      word_bits[i] = count[k] ? w[k] : 0ull;
-      word_time[i] = time[k];
+      if (count[k] == 0 || off[k] >= lo + kStage || off[k] + count[k] <= lo) continue;
+      const int16_t ey = (int16_t)((w[k] >> 32) & 0x7FFull);
+      const int bx = (int)((w[k] >> 43) & 0x7FFull);
+      const uint8_t ep = (uint8_t)(w[k] >> 60);
+      uint32_t m = (uint32_t)w[k];
+      int e = off[k] - lo;
+      while (m) {
+        const int b = __builtin_ctz(m);
+        m &= m - 1;
+        if ((unsigned)e < (unsigned)kStage) {
+          stage.x[e] = (int16_t)(bx + b);
+          stage.y[e] = ey;
+          stage.t[e] = time[k];
+          stage.p[e] = ep;
+        }
+        ++e;
+      }
     }
-    if (threadIdx.x == 0) word_off[kChunk] = n_ev;
     __syncthreads();
-    for (int e = threadIdx.x; e < n_ev; e += kBlock) {
-      // the last word whose offset is <= e: every word after it that shares its offset fires nothing
-      int lo = 0, hi = kChunk;  // word_off[lo] <= e < word_off[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (word_off[mid] <= e) lo = mid;
-        else hi = mid;
-      }
-      const uint64_t u = word_bits[lo];
-      const int b = select_bit((uint32_t)u, e - word_off[lo]);
-      const long long g = in.ev + e;
-      if (g < n_events) {
-        x[g] = (int16_t)((int)((u >> 43) & 0x7FFull) + b);
-        y[g] = (int16_t)((u >> 32) & 0x7FFull);
-        t[g] = word_time[lo];
-        p[g] = (uint8_t)(u >> 60);
-      }
-    }
+    store_stage(stage, n_ev - lo < kStage ? n_ev - lo : kStage, in.ev + lo, n_events, x, y, t, p);
+    __syncthreads();
   }
 }
 
@@ -536,15 +368,6 @@ __global__ __launch_bounds__(kBlock) void dat_decode_kernel(const uint2* __restr
 }
 
 inline int chunk_words(int word_bytes) { return word_bytes == 4 ? chunk_of<4>() : chunk_of<8>(); }
-inline int64_t chunks_of(int64_t n_words, int word_bytes) { return (n_words + chunk_words(word_bytes) - 1) / chunk_words(word_bytes); }
-inline size_t scratch_need(int64_t n_words, int word_bytes) {
-  const int64_t c = chunks_of(n_words, word_bytes) > 0 ? chunks_of(n_words, word_bytes) : 1;
-  return (size_t)c * (sizeof(Xf) + sizeof(ChunkIn));
-}
-
-int g_route = kRouteAuto;
-// the build's choice: the walk, the faster route on a dense-vector stream and on one bit per word alike
-inline int route_of() { return g_route == kRouteAuto ? kRouteWalk : g_route; }
 
 }  // namespace
 }  // namespace ebos
@@ -555,31 +378,17 @@ extern "C" int ebos_evt2_chunk_words(int word_bytes) { return word_bytes == 4 ||
 
 extern "C" size_t ebos_evt2_scratch_bytes(int64_t n_words, int word_bytes) {
   if ((word_bytes != 4 && word_bytes != 8) || n_words < 0 || n_words > kMaxWords) return 0;
-  return scratch_need(n_words, word_bytes);
-}
-
-extern "C" int ebos_evt21_route(int route) {
-  if (route != kRouteAuto && route != kRouteWalk && route != kRouteSearch) return -1;
-  const int before = g_route;
-  g_route = route;
-  return before;
+  return scratch_need<Xf, ebos_evt2_state>(n_words, chunk_words(word_bytes));
 }
 
 extern "C" int ebos_evt2_scan(const void* words, int64_t n_words, int word_bytes, int half_swapped, const ebos_evt2_state* carry_in,
                               ebos_evt2_state* carry_out, int64_t* totals, void* scratch, size_t scratch_bytes, ebos_stream_t stream) {
   EBOS_REQUIRE(word_bytes == 4 || word_bytes == 8, "ebos_evt2_scan: word_bytes %d is neither 4 (EVT 2.0) nor 8 (EVT 2.1)", word_bytes);
-  EBOS_REQUIRE(n_words >= 0 && n_words <= kMaxWords, "ebos_evt2_scan: n_words %lld outside [0, 2^30]", (long long)n_words);
-  EBOS_REQUIRE(words || n_words == 0, "ebos_evt2_scan: words is NULL");
-  EBOS_REQUIRE(((uintptr_t)words & (uintptr_t)(word_bytes - 1)) == 0, "ebos_evt2_scan: words is not %d-byte aligned", word_bytes);
-  EBOS_REQUIRE(carry_out && totals && scratch, "ebos_evt2_scan: NULL carry_out / totals / scratch");
-  EBOS_REQUIRE(((uintptr_t)scratch & 7) == 0, "ebos_evt2_scan: scratch is not 8-byte aligned");
-  if (scratch_bytes < scratch_need(n_words, word_bytes)) {
-    set_error("ebos_evt2_scan: scratch too small (%zu < %zu)", scratch_bytes, scratch_need(n_words, word_bytes));
-    return EBOS_ERR_SCRATCH;
-  }
-  const int64_t n_chunks = chunks_of(n_words, word_bytes);
-  Xf* sums = static_cast<Xf*>(scratch);
-  ChunkIn* cin = reinterpret_cast<ChunkIn*>(sums + (n_chunks > 0 ? n_chunks : 1));
+  if (const int e = check_scan_args<Xf, ebos_evt2_state>("ebos_evt2_scan", words, n_words, word_bytes, chunk_words(word_bytes), carry_out,
+                                                         totals, scratch, scratch_bytes))
+    return e;
+  const int64_t n_chunks = chunks_of(n_words, chunk_words(word_bytes));
+  const auto [sums, cin] = split_scratch<Xf, ebos_evt2_state>(scratch, n_chunks);
   hipStream_t s = as_stream(stream);
   const int aligned16 = (int)(((uintptr_t)words & 15) == 0);
   if (n_chunks > 0) {
@@ -599,42 +408,23 @@ extern "C" int ebos_evt2_emit(const void* words, int64_t n_words, int word_bytes
                               int64_t n_events, int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y,
                               int64_t* t, uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream) {
   EBOS_REQUIRE(word_bytes == 4 || word_bytes == 8, "ebos_evt2_emit: word_bytes %d is neither 4 (EVT 2.0) nor 8 (EVT 2.1)", word_bytes);
-  EBOS_REQUIRE(n_words >= 0 && n_words <= kMaxWords, "ebos_evt2_emit: n_words %lld outside [0, 2^30]", (long long)n_words);
-  EBOS_REQUIRE(words || n_words == 0, "ebos_evt2_emit: words is NULL");
-  EBOS_REQUIRE(((uintptr_t)words & (uintptr_t)(word_bytes - 1)) == 0, "ebos_evt2_emit: words is not %d-byte aligned", word_bytes);
-  EBOS_REQUIRE(scratch && ((uintptr_t)scratch & 7) == 0, "ebos_evt2_emit: scratch is NULL or not 8-byte aligned");
-  EBOS_REQUIRE(n_events >= 0 && n_triggers >= 0 && event_capacity >= 0 && trigger_capacity >= 0,
-               "ebos_evt2_emit: negative totals or capacities");
-  EBOS_REQUIRE(event_capacity >= n_events, "ebos_evt2_emit: event capacity %lld below the slab's %lld events",
-               (long long)event_capacity, (long long)n_events);
-  EBOS_REQUIRE(trigger_capacity >= n_triggers, "ebos_evt2_emit: trigger capacity %lld below the slab's %lld triggers",
-               (long long)trigger_capacity, (long long)n_triggers);
-  EBOS_REQUIRE(event_capacity == 0 || (x && y && t && p), "ebos_evt2_emit: NULL event column");
-  EBOS_REQUIRE(trigger_capacity == 0 || (trig_t && trig_value && trig_id), "ebos_evt2_emit: NULL trigger column");
-  EBOS_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 1) == 0 && (((uintptr_t)t | (uintptr_t)trig_t) & 7) == 0,
-               "ebos_evt2_emit: misaligned output column");
-  if (scratch_bytes < scratch_need(n_words, word_bytes)) {
-    set_error("ebos_evt2_emit: scratch too small (%zu < %zu)", scratch_bytes, scratch_need(n_words, word_bytes));
-    return EBOS_ERR_SCRATCH;
-  }
-  const int64_t n_chunks = chunks_of(n_words, word_bytes);
+  if (const int e = check_emit_args<Xf, ebos_evt2_state>("ebos_evt2_emit", words, n_words, word_bytes, chunk_words(word_bytes), scratch,
+                                                         scratch_bytes, n_events, n_triggers, event_capacity, trigger_capacity, x, y, t, p,
+                                                         trig_t, trig_value, trig_id))
+    return e;
+  const int64_t n_chunks = chunks_of(n_words, chunk_words(word_bytes));
   if (n_chunks == 0) return EBOS_OK;
-  const Xf* sums = static_cast<const Xf*>(scratch);
-  const ChunkIn* cin = reinterpret_cast<const ChunkIn*>(sums + n_chunks);
+  const auto [sums, cin] = split_scratch<Xf, ebos_evt2_state>(scratch, n_chunks);
   const int aligned16 = (int)(((uintptr_t)words & 15) == 0);
   const dim3 grid((unsigned)n_chunks), block(kBlock);
   hipStream_t s = as_stream(stream);
   // (stores are guarded by the totals the caller read, not by the larger capacities: nothing past them is touched)
-  if (word_bytes == 4) {
+  if (word_bytes == 4)
     hipLaunchKernelGGL(evt2_emit_kernel, grid, block, 0, s, words, n_words, aligned16, sums, cin, (long long)n_events, (long long)n_triggers,
                        x, y, t, p, trig_t, trig_value, trig_id);
-  } else if (route_of() == kRouteWalk) {
-    hipLaunchKernelGGL(evt21_emit_kernel<kRouteWalk>, grid, block, 0, s, words, n_words, aligned16, half_swapped ? 1 : 0, sums, cin,
+  else
+    hipLaunchKernelGGL(evt21_emit_kernel, grid, block, 0, s, words, n_words, aligned16, half_swapped ? 1 : 0, sums, cin,
                        (long long)n_events, (long long)n_triggers, x, y, t, p, trig_t, trig_value, trig_id);
-  } else {
-    hipLaunchKernelGGL(evt21_emit_kernel<kRouteSearch>, grid, block, 0, s, words, n_words, aligned16, half_swapped ? 1 : 0, sums, cin,
-                       (long long)n_events, (long long)n_triggers, x, y, t, p, trig_t, trig_value, trig_id);
-  }
   EBOS_CHECK_LAUNCH("ebos_evt2_emit");
   return EBOS_OK;
 }

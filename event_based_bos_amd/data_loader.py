@@ -69,7 +69,7 @@ class RawEventStore(object):
     def __init__(self, source: Union[str, Dict[str, np.ndarray]], sensor_size: Optional[Tuple[int, int]] = None, calibration=None,
                  half_swapped: Optional[bool] = None):
         self.calibration = _as_calibration(calibration, sensor_size)   # None: no calibration, as the reference's loaders answer
-        self.header = None            # a .raw / .dat source: the parsed header (evt3.RawHeader)
+        self.header = None            # a .raw / .dat source: the parsed header (recordings.RawHeader)
         self.triggers = None          # a .raw / .dat source: int64 [n, 3] = (t, id, value), the "old" layout of read_trigger_timestamps
         self.dropped_outside = 0      # a .raw / .dat source: events outside the header's geometry, removed
         if isinstance(source, dict):

@@ -13,97 +13,38 @@ camera file was at hand: the decoder is checked against a restatement of the rul
 """
 from __future__ import annotations
 
-import ctypes as C
-import logging
-import os
-import re
-from collections import namedtuple
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from . import _hip
-
-logger = logging.getLogger(__name__)
+from . import _hip, _word_stream as _ws
+from ._word_stream import RawHeader, read_raw_header   # noqa: F401  (public here)
 
 TIME_HIGH, TIME_LOW, ADDR_Y, ADDR_X, VECT_BASE_X, VECT_12, VECT_8, EXT_TRIGGER = 0x8, 0x6, 0x0, 0x2, 0x3, 0x4, 0x5, 0xA
 _TH_STEP = 8   # the encoder's consecutive TIME_HIGH words differ by at most this many ticks of 4096 us
 
-RawHeader = namedtuple("RawHeader", "format width height payload_offset fields")
-Evt3Slab = namedtuple("Evt3Slab", "x y t p trigger_t trigger_value trigger_id carry")
+_FORMAT = _ws.WORDS["EVT3"]
+Evt3Slab = _ws.Slab
 
 
-# ---------------------------------------------------------------------------------------------------- header
-def read_raw_header(path: str) -> RawHeader:
-    """The ASCII header of a ``.raw`` file: while the next byte is ``%``, a line through the next newline; ``% end`` ends the header
-    even if more ``%`` lines follow.  ``format`` is "EVT3" (``% evt 3.0`` or ``% format EVT3[;height=H;width=W]``) or the name of
-    the format the file declares (None: none declared); the geometry comes from the format line's ``height=`` / ``width=`` or from
-    ``% geometry WxH`` (None: none declared).  ``fields``: the raw ``key -> value`` strings."""
-    fields: Dict[str, str] = {}
-    with open(path, "rb") as f:
-        offset = 0
-        while True:
-            c = f.read(1)
-            if c != b"%":
-                break
-            line = c + f.readline()
-            offset += len(line)
-            f.seek(offset)
-            text = line[1:].decode("ascii", "replace").strip()
-            if text == "end":
-                break
-            key, _, value = text.partition(" ")
-            if key:
-                fields[key] = value.strip()
-    fmt, width, height = None, None, None
-    if "evt" in fields:
-        fmt = {"3.0": "EVT3", "2.0": "EVT2", "2.1": "EVT21"}.get(fields["evt"], "evt " + fields["evt"])
-    if "format" in fields:
-        parts = fields["format"].split(";")
-        fmt = parts[0].strip().upper()
-        for part in parts[1:]:
-            k, _, v = part.partition("=")
-            if k.strip() == "height" and v.strip().isdigit():
-                height = int(v)
-            elif k.strip() == "width" and v.strip().isdigit():
-                width = int(v)
-    if (width is None or height is None) and "geometry" in fields:
-        m = re.fullmatch(r"(\d+)\s*[xX]\s*(\d+)", fields["geometry"])
-        if m:
-            width, height = int(m.group(1)), int(m.group(2))
-    return RawHeader(fmt, width, height, offset, fields)
+# ---------------------------------------------------------------------------------------------------- files
+_HINTS = ("`% evt 3.0` or `% format EVT3`", "EVT3 (EVT 3.0)", " (`% geometry WxH` or `% format EVT3;height=H;width=W`)")
+_ODD_TAIL = "the payload has an odd length ({n_bytes} bytes); the last byte is dropped"
 
 
-def _checked_header(path: str, sensor_size: Optional[Tuple[int, int]]) -> RawHeader:
-    header = read_raw_header(path)
-    if header.format != "EVT3":
-        if header.format is None:
-            raise ValueError(f"{path}: the header declares no format (`% evt 3.0` or `% format EVT3`)")
-        raise NotImplementedError(f"{path}: format {header.format} is not decoded here, only EVT3 (EVT 3.0)")
-    if sensor_size is not None:
-        header = header._replace(height=int(sensor_size[0]), width=int(sensor_size[1]))
-    if header.width is None or header.height is None:
-        raise ValueError(f"{path}: the header holds no geometry (`% geometry WxH` or `% format EVT3;height=H;width=W`); "
-                         f"pass sensor_size=(H, W)")
-    return header
+def _checked_header(path: str, sensor_size: Optional[Tuple[int, int]], slab_words: int = 1) -> RawHeader:
+    return _ws.checked_header(path, read_raw_header(path), ("EVT3",), _HINTS, sensor_size, slab_words)
 
 
 def raw_word_count(path: str, header: RawHeader) -> int:
     """The 16-bit words after the header; an odd trailing byte is dropped with a warning."""
-    n_bytes = max(0, os.path.getsize(path) - header.payload_offset)
-    if n_bytes % 2:
-        logger.warning(f"{path}: the payload has an odd length ({n_bytes} bytes); the last byte is dropped")
-    return n_bytes // 2
+    return _ws.payload_items(path, header, 2, "words", _ODD_TAIL)
 
 
 def write_raw_file(path: str, words, width: int, height: int) -> None:
     """A ``.raw`` file of ``words`` (uint16) under the header current cameras write (``% format EVT3;height=H;width=W``, ``% end``)."""
-    words = np.ascontiguousarray(np.asarray(words, dtype="<u2"))
-    with open(path, "wb") as f:
-        f.write(f"% camera_integrator_name Prophesee\n% evt 3.0\n% format EVT3;height={int(height)};width={int(width)}\n"
-                f"% geometry {int(width)}x{int(height)}\n% end\n".encode("ascii"))
-        f.write(words.tobytes())
+    _ws.write_raw_file(path, words, width, height, "EVT3")
 
 
 # ---------------------------------------------------------------------------------------------------- encoder (host)
@@ -113,27 +54,13 @@ def encode_evt3(x, y, t, p, triggers=None, vectorize: bool = True) -> np.ndarray
     that consecutive ones never differ by more than 8 ticks -- starting from 0, so the decoder counts every wrap of the 24-bit time
     --; TIME_LOW and ADDR_Y come on change; runs of equal (t, y, p) with ascending x less than 12 apart are packed into VECT_BASE_X +
     VECT_12 words (a VECT_8 for a last group that fits) where ``vectorize`` allows, every other event is an ADDR_X."""
-    x, y, p = (np.asarray(a).astype(np.int64).ravel() for a in (x, y, p))
-    t = np.asarray(t).astype(np.int64).ravel()
+    x, y, t, p = _ws.columns(x, y, t, p)
+    trig = _ws.trigger_rows(triggers, 4, "EVT3")
     n = len(t)
-    if not (len(x) == len(y) == len(p) == n):
-        raise ValueError("x, y, t, p must be of equal length")
-    trig = np.zeros((0, 3), np.int64) if triggers is None else np.asarray(triggers, dtype=np.int64).reshape(-1, 3)
-    m = len(trig)
     if n and (x.min() < 0 or x.max() > 0x7FF or y.min() < 0 or y.max() > 0x7FF):
         raise ValueError("EVT3 addresses are 11 bits: 0 <= x, y < 2048")
-    if m and (trig[:, 1].min() < 0 or trig[:, 1].max() > 15):
-        raise ValueError("EVT3 trigger ids are 4 bits")
-    for name, col in (("t", t), ("trigger t", trig[:, 0])):
-        if len(col) and (col[0] < 0 or np.any(np.diff(col) < 0)):
-            raise ValueError(f"{name} must be non-negative and non-decreasing")
-    # the merged items: trigger j sits after the events with t <= its time
-    total = n + m
-    trig_pos = np.searchsorted(t, trig[:, 0], side="right") + np.arange(m)
-    is_trig = np.zeros(total, bool)
-    is_trig[trig_pos] = True
-    it = np.empty(total, np.int64)
-    it[is_trig], it[~is_trig] = trig[:, 0], t
+    is_trig, it = _ws.merge(t, trig)
+    total = n + len(trig)
     if total == 0:
         return np.zeros(0, np.uint16)
     ev_pos = np.nonzero(~is_trig)[0]
@@ -155,10 +82,10 @@ def encode_evt3(x, y, t, p, triggers=None, vectorize: bool = True) -> np.ndarray
     main = np.zeros(total, np.int64)
     vec = np.zeros(total, np.int64)
     main[is_trig] = (EXT_TRIGGER << 12) | (trig[:, 1] << 8) | (trig[:, 2] & 1)
-    main[ev_pos] = (ADDR_X << 12) | ((p != 0).astype(np.int64) << 11) | x
+    main[ev_pos] = (ADDR_X << 12) | (p << 11) | x
     if n and vectorize:
         cont = np.zeros(n, bool)
-        cont[1:] = ((t[1:] == t[:-1]) & (y[1:] == y[:-1]) & ((p[1:] != 0) == (p[:-1] != 0)) & (x[1:] > x[:-1]) & (x[1:] - x[:-1] < 12) &
+        cont[1:] = ((t[1:] == t[:-1]) & (y[1:] == y[:-1]) & (p[1:] == p[:-1]) & (x[1:] > x[:-1]) & (x[1:] - x[:-1] < 12) &
                     (ev_pos[1:] == ev_pos[:-1] + 1))
         run = np.cumsum(~cont) - 1
         run_start = np.nonzero(~cont)[0]
@@ -175,7 +102,7 @@ def encode_evt3(x, y, t, p, triggers=None, vectorize: bool = True) -> np.ndarray
         kind = np.where(last_group & (mask < 256), VECT_8, VECT_12)
         starts_run = in_vec & ~cont
         c_main[ev_pos[in_vec & cont]] = False
-        main[ev_pos[starts_run]] = (VECT_BASE_X << 12) | ((p[starts_run] != 0).astype(np.int64) << 11) | x[starts_run]
+        main[ev_pos[starts_run]] = (VECT_BASE_X << 12) | (p[starts_run] << 11) | x[starts_run]
         c_vec[ev_pos[gstart]] = True
         vec[ev_pos[gstart]] = (kind << 12) | mask
     counts = n_th + c_tl + c_y + c_main + c_vec
@@ -204,19 +131,17 @@ def encode_evt3(x, y, t, p, triggers=None, vectorize: bool = True) -> np.ndarray
 # ---------------------------------------------------------------------------------------------------- decode (device)
 def chunk_words() -> int:
     """Words per chunk of the decode (``ebos_evt3_chunk_words``): where the seams between workgroups lie."""
-    return int(_hip.load_library().ebos_evt3_chunk_words())
+    return _ws.chunk_words(_FORMAT)
 
 
 def new_carry(device="cuda", state: Optional[dict] = None) -> torch.Tensor:
     """A decoder state on the device (``ebos_evt3_state`` as 32 bytes): the start state, or ``state``'s fields."""
-    s = _hip.Evt3State(**(state or {}))
-    return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(device)
+    return _ws.new_carry(_FORMAT, device, state)
 
 
 def carry_to_dict(carry: torch.Tensor) -> dict:
     """The fields of a device decoder state (one read-back)."""
-    s = _hip.Evt3State.from_buffer_copy(carry.cpu().numpy().tobytes())
-    return {k: int(getattr(s, k)) for k, _ in _hip.Evt3State._fields_}
+    return _ws.carry_to_dict(_FORMAT, carry)
 
 
 def _device_words(words, device) -> torch.Tensor:
@@ -227,33 +152,18 @@ def _device_words(words, device) -> torch.Tensor:
     arr = np.ascontiguousarray(np.asarray(words))
     if arr.dtype != np.uint16 or arr.ndim != 1:
         raise TypeError(f"EVT3 words are a 1-D uint16 array, got {arr.dtype} {arr.shape}")
-    return torch.from_numpy(arr.view(np.int16)).to(device)
+    return torch.from_numpy(arr.view(_FORMAT.np_signed)).to(device)
 
 
 def evt3_scan(words: torch.Tensor, carry: Optional[torch.Tensor] = None):
     """Passes 1 and 2 on a device tensor of words: (scratch, totals int64 [2] on the device, the carry-out).  No synchronisation."""
-    lib = _hip.require_gpu()
-    dev = words.device
-    n = words.numel()
-    with _hip.on_device(dev):
-        scratch = torch.empty(int(lib.ebos_evt3_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-        totals = torch.empty(2, dtype=torch.int64, device=dev)
-        carry_out = torch.empty(C.sizeof(_hip.Evt3State), dtype=torch.uint8, device=dev)
-        _hip.check(lib.ebos_evt3_scan(_hip.ptr(words) if n else None, n, _hip.ptr(carry), _hip.ptr(carry_out), _hip.ptr(totals),
-                                      _hip.ptr(scratch), scratch.numel(), _hip.stream_ptr(dev)), "ebos_evt3_scan")
-    return scratch, totals, carry_out
+    return _ws.scan(_FORMAT, words, carry)
 
 
 def evt3_emit(words: torch.Tensor, scratch: torch.Tensor, n_events: int, n_triggers: int, x, y, t, p, trigger_t, trigger_value,
               trigger_id) -> None:
     """Pass 3 into the caller's columns (their lengths are the capacities); ``scratch`` is what ``evt3_scan`` left for these words."""
-    lib = _hip.require_gpu()
-    n = words.numel()
-    with _hip.on_device(words.device):
-        _hip.check(lib.ebos_evt3_emit(_hip.ptr(words) if n else None, n, _hip.ptr(scratch), scratch.numel(), int(n_events), int(n_triggers),
-                                      min(c.numel() for c in (x, y, t, p)), min(c.numel() for c in (trigger_t, trigger_value, trigger_id)),
-                                      _hip.ptr(x), _hip.ptr(y), _hip.ptr(t), _hip.ptr(p), _hip.ptr(trigger_t), _hip.ptr(trigger_value),
-                                      _hip.ptr(trigger_id), _hip.stream_ptr(words.device)), "ebos_evt3_emit")
+    _ws.emit(_FORMAT, words, scratch, n_events, n_triggers, x, y, t, p, trigger_t, trigger_value, trigger_id)
 
 
 def decode_evt3(words, carry: Optional[torch.Tensor] = None, device="cuda") -> Evt3Slab:
@@ -261,37 +171,12 @@ def decode_evt3(words, carry: Optional[torch.Tensor] = None, device="cuda") -> E
     columns x, y int16, t int64 (microseconds), p uint8, the triggers' t int64, value and id uint8, and the carry after the slab's
     last word, on the device.  One host read-back, of the two totals that size the columns."""
     _hip.require_gpu()
-    w = _device_words(words, device)
-    scratch, totals, carry_out = evt3_scan(w, carry)
-    n_ev, n_tr = (int(v) for v in totals.tolist())
-    dev = w.device
-    cols = [torch.empty(n_ev, dtype=d, device=dev) for d in (torch.int16, torch.int16, torch.int64, torch.uint8)]
-    trig = [torch.empty(n_tr, dtype=d, device=dev) for d in (torch.int64, torch.uint8, torch.uint8)]
-    evt3_emit(w, scratch, n_ev, n_tr, *cols, *trig)
-    return Evt3Slab(*cols, *trig, carry_out)
+    return _ws.decode_slab(_FORMAT, _device_words(words, device), carry)
 
 
 def decode_raw_file(path: str, slab_words: int = 1 << 26, sensor_size: Optional[Tuple[int, int]] = None, device="cuda"):
     """A ``.raw`` file decoded slab by slab, the carry staying on the device between slabs: host columns (x int16, y int16, t int64,
     p uint8), the triggers as int64 [n, 3] = (t, id, value), and the header (with ``sensor_size`` in the place of a missing
     geometry).  An odd trailing byte is dropped with a warning."""
-    header = _checked_header(path, sensor_size)
-    if slab_words < 1 or slab_words > (1 << 30):
-        raise ValueError(f"slab_words must lie in [1, 2^30], got {slab_words}")
-    _hip.require_gpu()
-    n_words = raw_word_count(path, header)
-    carry = None
-    cols, trigs = [[] for _ in range(4)], []
-    with open(path, "rb") as f:
-        f.seek(header.payload_offset)
-        for lo in range(0, n_words, int(slab_words)):
-            words = np.fromfile(f, dtype="<u2", count=min(int(slab_words), n_words - lo)).astype(np.uint16, copy=False)
-            slab = decode_evt3(words, carry, device)
-            carry = slab.carry
-            for k in range(4):
-                cols[k].append(slab[k].cpu().numpy())
-            trigs.append(torch.stack([slab.trigger_t, slab.trigger_id.to(torch.int64), slab.trigger_value.to(torch.int64)], 1).cpu().numpy())
-    dtypes = (np.int16, np.int16, np.int64, np.uint8)
-    x, y, t, p = (np.concatenate(c) if c else np.zeros(0, d) for c, d in zip(cols, dtypes))
-    triggers = np.concatenate(trigs) if trigs else np.zeros((0, 3), np.int64)
-    return x, y, t, p, triggers, header
+    header = _checked_header(path, sensor_size, slab_words)
+    return _ws.decode_file(path, header, slab_words, lambda words, carry: decode_evt3(words, carry, device), 2, tail=_ODD_TAIL)

@@ -2183,10 +2183,7 @@ int ebos_evt3_emit(const uint16_t* words, int64_t n_words, const void* scratch, 
  * elements [0, n_events) and [0, n_triggers) of the seven columns of ebos_evt3_emit.  Refused before any HIP call
  * (EBOS_ERR_INVALID_ARG): a word_bytes other than 4 or 8, NULL pointers (words may be NULL when n_words is 0; an output when its
  * capacity is 0), words not aligned to word_bytes, negative sizes, n_words beyond 2^30, a capacity below the totals; a short
- * scratch: EBOS_ERR_SCRATCH.  No store lands at or beyond a capacity.
- * ebos_evt21_route: how the EVT 2.1 emit pass turns vector words into events -- 0: the build's choice, 1: every lane walks the bits
- * of its own words into the LDS stage, 2: every output slot searches its word in the per-word offsets and takes the rank-th set
- * bit of its mask.  The same bytes either way.  Returns the previous value (-1: a bad route, nothing changed). */
+ * scratch: EBOS_ERR_SCRATCH.  No store lands at or beyond a capacity. */
 typedef struct ebos_evt2_state {
   int32_t has_th; /* a TIME_HIGH has been seen */
   int32_t th;
@@ -2199,7 +2196,6 @@ int ebos_evt2_scan(const void* words, int64_t n_words, int word_bytes /* 4 | 8 *
 int ebos_evt2_emit(const void* words, int64_t n_words, int word_bytes, int half_swapped, const void* scratch, size_t scratch_bytes,
                    int64_t n_events, int64_t n_triggers, int64_t event_capacity, int64_t trigger_capacity, int16_t* x, int16_t* y,
                    int64_t* t, uint8_t* p, int64_t* trig_t, uint8_t* trig_value, uint8_t* trig_id, ebos_stream_t stream);
-int ebos_evt21_route(int route);
 /* DAT: n_records records of two little-endian uint32 (ts, data), 8-byte aligned.  version 2: x = data & 0x3FFF, y = (data >> 14) &
  * 0x3FFF, p = (data >> 28) & 1; version 1: x = data & 0x1FF, y = (data >> 9) & 0xFF, p = (data >> 17) & 1; t = ts as it stands (no
  * wrap is counted).  Writes elements [0, n_records) of x, y int16, t int64, p uint8 [capacity]; one launch.  Refused before any HIP

@@ -245,3 +245,27 @@ def test_events_outside_the_geometry_are_dropped(raw_recording, tmp_path):
     evt3.write_raw_file(late, evt3.encode_evt3(c["x"][:2000], c["y"][:2000], t, c["p"][:2000]), W, H)
     store = RawEventStore(late)
     assert store.event_data["t"].dtype == np.int64 and np.array_equal(store.event_data["t"], t)
+
+
+@pytest.mark.parametrize("chunks", [70, 1093])
+def test_scan_pass_beyond_one_wave_and_one_tile(C, chunks):
+    """The scan pass gives wave w the tiles [w per, (w + 1) per) of 64 chunks, per = ceil(tiles / 16): a second wave has work from 65
+    chunks, a wave walks a second tile from 1025.  The oracle is the encoder's input (the encoder is held to the restatement on the
+    CPU), over two wraps of the 24-bit time so that the loop count crosses the waves."""
+    from event_based_bos_amd import evt3
+
+    rng = np.random.default_rng(chunks)
+    n = chunks * C
+    t = np.sort(rng.integers(0, 40_000_001, size=n))
+    t[0], t[-1] = 0, 40_000_000
+    x, y, p = rng.integers(0, 2048, size=n), rng.integers(0, 2048, size=n), rng.integers(0, 2, size=n)
+    triggers = np.stack([np.sort(rng.integers(0, 40_000_001, size=300)), rng.integers(0, 16, size=300), rng.integers(0, 2, size=300)], 1)
+    words = evt3.encode_evt3(x, y, t, p, triggers, vectorize=False)
+    n_chunks = -(-len(words) // C)
+    assert n_chunks > (64 if chunks == 70 else 1088) and n_chunks % 64 != 0
+    s = evt3.decode_evt3(words)
+    for got, want in zip((s.x, s.y, s.t, s.p, s.trigger_t, s.trigger_id, s.trigger_value), (x, y, t, p, *triggers.T)):
+        assert got.shape == want.shape and np.array_equal(got.cpu().numpy(), want)
+    last = max(int(t[-1]), int(triggers[-1, 0]))
+    state = evt3.carry_to_dict(s.carry)
+    assert (state["has_th"], state["loops"], state["th"]) == (1, last >> 24, (last >> 12) & 0xFFF) and state["loops"] == 2

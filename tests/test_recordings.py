@@ -305,9 +305,6 @@ def test_c_entries_refuse_before_any_hip_call(lib):
     assert lib.ebos_dat_decode(p, 5, 2, p + 1, p, p, p, 5, None) == -1 and b"misaligned" in lib.ebos_last_error()
     assert lib.ebos_dat_decode(p, 5, 2, p, p, p + 4, p, 5, None) == -1 and b"misaligned" in lib.ebos_last_error()
     assert lib.ebos_dat_decode(None, 0, 2, None, None, None, None, 0, None) == 0          # nothing to do: no launch
-    # the route of the EVT 2.1 emit pass: a bad value changes nothing
-    before = lib.ebos_evt21_route(2)
-    assert lib.ebos_evt21_route(7) == -1 and lib.ebos_evt21_route(before) == 2 and lib.ebos_evt21_route(before) == before
 
 
 def test_state_struct_layout_matches_the_ctypes_mirror(tmp_path):
@@ -343,8 +340,8 @@ def test_the_unit_is_part_of_the_build():
     from event_based_bos_amd.build import SOURCES
 
     assert "evt2.hip" in SOURCES and "evt3.hip" in SOURCES and _hip.ABI_VERSION == 2
-    assert {"ebos_evt2_chunk_words", "ebos_evt2_scratch_bytes", "ebos_evt2_scan", "ebos_evt2_emit", "ebos_evt21_route",
-            "ebos_dat_decode"} <= set(_hip.SIGNATURES)
+    assert {"ebos_evt2_chunk_words", "ebos_evt2_scratch_bytes", "ebos_evt2_scan", "ebos_evt2_emit", "ebos_dat_decode"} <= set(_hip.SIGNATURES)
+    assert "ebos_evt21_route" not in _hip.SIGNATURES              # one emit pass for EVT 2.1, no switch
     assert ebos.recordings.decode_recording and ebos.recordings.FORMATS == ("EVT2", "EVT21", "EVT3", "DAT")
 
 

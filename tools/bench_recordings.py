@@ -6,7 +6,7 @@ The stream: that tool's block of bursts (1 to 12 events on one row at one micros
 encoder once and repeated; the decoded times repeat with every copy.  ``evt21-sparse`` is the same block with one event a word
 (``vectorize=False``), ``evt21`` packs the bursts into vector words.  Reported, one JSON line per format:
   scan_ms / emit_ms     device events around ebos_evt2_scan (the summary and the scan kernel) and ebos_evt2_emit, slab by slab, median;
-                        DAT has no scan pass.  EVT 2.1: ``routes`` holds the emit time of both routes, emit_ms is the build's choice
+                        DAT has no scan pass
   kernels               the kernels' average times, where --kernel-stats names the CSV of a `rocprofv3 --kernel-trace --stats
                         --output-format csv` run of this tool (a run of its own: --device-only --reps 5), or a CSV of the same
                         columns with one row per kernel and grid (profiles/recordings_kernel_stats.csv)
@@ -37,7 +37,6 @@ from bench_evt3 import H, W, block_columns  # noqa: E402
 
 FORMATS = ("evt2", "evt21", "evt21-sparse", "dat")
 KERNELS = ("evt2_summary_kernel", "evt2_scan_kernel", "evt2_emit_kernel", "evt21_emit_kernel", "dat_decode_kernel")
-ROUTES = {"walk": 1, "search": 2}
 
 
 def copy_rate(n_bytes: int = 1 << 30, reps: int = 5) -> float:
@@ -129,7 +128,7 @@ def kernel_stats(path: str):
             name = row.get("Name", "")
             for k in KERNELS:
                 if k in name:
-                    key = k + ("<search>" if k == "evt21_emit_kernel" and ("Li2E" in name or "<2>" in name) else "")
+                    key = k
                     if row.get("GridX"):     # (one row per grid: the slabs of a stream differ in length)
                         key += " grid " + row["GridX"]
                     out[key] = {"calls": int(row["Calls"]), "average_ms": float(row["AverageNs"]) / 1e6}
@@ -147,17 +146,7 @@ def run(fmt: str, a, rate: float) -> dict:
     else:
         n_items, item_bytes = len(stream), stream.dtype.itemsize
         r["chunk_words"] = recordings.chunk_words("EVT2" if fmt == "evt2" else "EVT21")
-        if fmt == "evt2":
-            scan_ms, emit_ms, n_ev, n_tr = words_times(stream, a.reps, a.slab_words)
-        else:
-            r["routes"] = {}
-            for name, route in ROUTES.items():
-                before = recordings.set_evt21_route(route)
-                try:
-                    scan_ms, r["routes"][name], n_ev, n_tr = words_times(stream, a.reps, a.slab_words)
-                finally:
-                    recordings.set_evt21_route(before)
-            scan_ms, emit_ms, n_ev, n_tr = words_times(stream, a.reps, a.slab_words)
+        scan_ms, emit_ms, n_ev, n_tr = words_times(stream, a.reps, a.slab_words)
     assert (n_ev, n_tr) == (copies * ev_block, copies * tr_block), "the decode lost or invented events"
     must = item_bytes * n_items + 13 * n_ev + 10 * n_tr
     seconds = (scan_ms + emit_ms) * 1e-3
